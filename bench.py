@@ -13,9 +13,15 @@ itself (fresh child processes, before this one has made any HIP call).  `--seque
 sequences of different lengths (the 11 KITTI odometry sequences, scaled by --seq-scale) handed out longest-first to
 whichever rank is free, value = sum of frames / wall time.
 
-Prints ONE JSON line (rank 0).  `cpu_baseline` times the same step with the CPU restatement (oracle/:
-front-end, matchers, pose optimisation; PyTorch-CPU ASDNet run per level like the reference) and, when
-oracle/_ref is present, the reference's own g2o for LocalBA -- as a reported baseline, never the product.
+Prints ONE JSON line (rank 0).  A plain run sets up, warms up, times the K steps (`--steps`) and prints the line: the
+headline, `steady_state` and the ASDNet figures the timed window itself collects (`roofline`, `asdnet_layers`).
+`--full` adds the passes of their own the headline does not need -- the variants (`lane_variant`,
+`one_submission_variant`, `local_map_sweep`, `do_mapping_variant`, `h2d_variant`) and `cpu_baseline`, which times the
+same step with the CPU restatement (oracle/: front-end, matchers, pose optimisation; PyTorch-CPU ASDNet run per level
+like the reference) and, when oracle/_ref is present, the reference's own g2o for LocalBA -- as a reported baseline,
+never the product.  `--dump-outputs DIR` writes what the last timed step returned (its statistics: keypoints, matches of
+both stages, inliers, LocalBA chi2 on a keyframe) as DIR/<name>.npy; the inputs are seeded, so two builds compare output
+for output.
 """
 import argparse
 import json
@@ -730,6 +736,14 @@ def run_steps_python(be, wl, t0, n, last, prefetch_beyond=False):
     return last, stats
 
 
+def dump_outputs(out_dir, stats):
+    """--dump-outputs: what the last timed step returned to its caller (asd_track_stats, or the same dict from the Python loop), one
+    float64 array of one element per field"""
+    os.makedirs(out_dir, exist_ok=True)
+    for k, v in stats.items():
+        np.save(os.path.join(out_dir, f"{k}.npy"), np.array([v], np.float64))
+
+
 def selftest_dist(args):
     """CPU-only rehearsal of the N>1 control plane (gloo): rendezvous, barrier, max-over-ranks, aggregation."""
     d = Dist(args.gpus)
@@ -902,6 +916,8 @@ def run_euroc_stereo(args, pkg, dist, rank, world, device):
     dt = time.perf_counter() - t0
     tmax = dist.max(dt)
     total = dist.sum(float(args.steps))
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, stats)
     if be.native is not None:
         be.native.lib.asd_track_drain(be.native.h)
         be.native.close()
@@ -946,14 +962,14 @@ def run_sequences(args, pkg, dist, rank, world, device):
     replay(cams[0], args.warmup)                       # untimed: code objects, clocks, allocations
     be.hip.sync(); device_sync(device); dist.barrier()
     t0 = time.perf_counter()
-    mine, frames = [], 0
+    mine, frames, stats = [], 0, {}
     while True:
         k = dist.next_ticket("sequence")
         if k >= len(seqs):
             break
         q = seqs[k]
         ts = time.perf_counter()
-        replay(q["cam"], q["frames"])
+        stats = replay(q["cam"], q["frames"])
         mine.append({"seq": q["name"], "frames": q["frames"], "s": round(time.perf_counter() - ts, 4)})
         frames += q["frames"]
     be.hip.sync(); device_sync(device)
@@ -963,6 +979,8 @@ def run_sequences(args, pkg, dist, rank, world, device):
     tmax = dist.max(dt)
     total = dist.sum(float(frames))
     reports = dist.gather_json({"rank": rank, "device": device, "busy_s": round(busy, 4), "sequences": mine})
+    if args.dump_outputs and rank == 0:   # the last frame of the last sequence this rank replayed
+        dump_outputs(args.dump_outputs, stats)
     be.close()
     if rank == 0:
         assert int(total) == sum(q["frames"] for q in seqs), "a sequence was lost or run twice"
@@ -985,7 +1003,12 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=300)
     ap.add_argument("--warmup", type=int, default=45)
-    ap.add_argument("--cpu-frames", type=int, default=15, help="frames of the CPU baseline sample (0 = skip)")
+    ap.add_argument("--cpu-frames", type=int, default=15, help="--full: frames of the CPU baseline sample (0 = skip)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the passes the headline does not need: the variants (N = 1 only, each can be skipped with its --no-* "
+                         "switch) and the CPU baselines")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write the statistics the last timed step returned as DIR/<name>.npy (float64)")
     ap.add_argument("--selftest-dist", action="store_true")
     ap.add_argument("--sequences", type=int, default=0,
                     help="BASELINE configs[4]: this many independent sequences (11 = KITTI odometry 00-10) in a shared "
@@ -1081,8 +1104,11 @@ def main():
     last, stats = run_steps(be, wl, prime + args.warmup, args.steps, last, prefetch_beyond=True)
     be.hip.sync(); device_sync(device); dist.barrier()
     dt = time.perf_counter() - t0
+    be.hip.profile_enable(False)   # the per-layer ASDNet figures below cover the timed window only
     tmax = dist.max(dt)
     frames_total = dist.sum(float(args.steps))
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, stats)
     n_kf = kf_in(prime + args.warmup, args.steps)
     steady = None
     if tm0 is not None:
@@ -1097,11 +1123,11 @@ def main():
                   "what": "tracking (window time minus the time inside asd_local_ba) per frame + one LocalBA / kf_interval, from separately "
                           "accumulated host timers of this rank; `value` is K / window time with the window placed to hold ceil(K / kf_interval) LocalBAs"}
 
+    # --full only: the variants and the CPU baselines below are passes of their own after the timed window, each an extra key.
     # The optional lane (asd_local_ba_submit): the same K frames once more with LocalBA running beside the next frames' tracking.  It
     # changes the data dependency (frames t+1.. read the pre-BA map), so it is reported as an extra key and never as `value`.
     lane_variant = None
-    if world == 1 and not args.lane_ba and not args.no_lane_variant:
-        be.hip.profile_enable(False)
+    if args.full and world == 1 and not args.lane_ba and not args.no_lane_variant:
         be.async_ba = True
         if be.native is not None:
             be.native.lib.asd_track_set_async_ba(be.native.h, 1)
@@ -1159,8 +1185,7 @@ def main():
     # is gone, so the local map must be known before the frame is tracked.  The stand-in map allows that; the reference's Tracking does
     # not in general (include/asd_slam.h).  An extra key, never `value`.
     one_submission_variant = None
-    if world == 1 and be.native is not None and not be.chain and not args.no_one_submission_variant:
-        be.hip.profile_enable(False)
+    if args.full and world == 1 and be.native is not None and not be.chain and not args.no_one_submission_variant:
         be.native.lib.asd_track_drain(be.native.h)
         be.native.lib.asd_track_set_chain(be.native.h, 1)
         tl = prime + args.warmup + 3 * args.steps + 8 * KF_INTERVAL
@@ -1185,8 +1210,7 @@ def main():
     # Larger local maps (Tracking.cc:881-905 collects every map point of up to 80 local keyframes): the headline form with 2 / 4 / 8 candidates
     # per point of the last frame = 4 k / 8 k / 16 k local-map candidates per frame.  Extra key; `value` keeps the 4 k stand-in.
     local_map_sweep = None
-    if world == 1 and be.native is not None and not args.no_local_map_sweep:
-        be.hip.profile_enable(False)
+    if args.full and world == 1 and be.native is not None and not args.no_local_map_sweep:
         local_map_sweep = {"what": "the headline's two-call form with k candidates per point of the last frame in the stand-in local map (k x 2000 candidates per frame; "
                                    "the claim replay runs over the map points that have a candidate list, in chunks of 4096)", "runs": []}
         nsw = max(2 * KF_INTERVAL, args.steps // 2)
@@ -1211,7 +1235,7 @@ def main():
     # Fuse calls, distinctive descriptors) as the library's three batched submissions at every keyframe: reference order
     # (LocalMapping.cc:59-113).  An extra key: the metric -- and `value` -- is tracking + LocalBA.
     do_mapping_variant = None
-    if world == 1 and be.native is not None and not args.no_do_mapping_variant:
+    if args.full and world == 1 and be.native is not None and not args.no_do_mapping_variant:
         import ctypes as C
         D, dm_keep, dm_n = build_do_mapping_inputs(pkg, be.hip)
         be.native.lib.asd_track_set_do_mapping(be.native.h, C.byref(D), dm_n)
@@ -1241,7 +1265,7 @@ def main():
     # half's stream copies it, 467 KB per frame over PCIe) -- how kitti.cc:116-155 hands images to the tracker.  An extra key: `value`
     # keeps its definition (inputs resident in HBM when the timed region starts).
     h2d_variant = None
-    if world == 1 and be.native is not None and not args.no_h2d_variant:
+    if args.full and world == 1 and be.native is not None and not args.no_h2d_variant:
         be.native.lib.asd_track_drain(be.native.h)   # its read-ahead submissions go back to the library before another handle runs
         nh = NativeHost(pkg, be, wl, pipeline=not args.no_pipeline, frames_on_host=True)
         keep_native, be.native = be.native, nh
@@ -1320,7 +1344,7 @@ def main():
             out["do_mapping_variant"] = do_mapping_variant
         if steady is not None:
             out["steady_state"] = steady
-        if args.cpu_frames > 0 and world == 1:   # reported baseline: rank 0 at N = 1 only
+        if args.full and args.cpu_frames > 0 and world == 1:   # reported baseline: rank 0 at N = 1 only
             cb = CpuBackend(pkg, wl)
             nf = args.cpu_frames
             cl, _ = run_steps(cb, wl, 0, 1, None)        # one untimed frame (torch warm-up, page-in)

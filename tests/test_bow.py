@@ -242,19 +242,23 @@ def test_oracle_bow_assembly_equals_reference_classes(oracle):
 
 
 def test_reference_dbow2_live_when_built(oracle, oracle_mod):
-    """where oracle/_ref/libdbow2_ref.so exists (build container, GPU box): the same comparison live on fresh inputs"""
-    if not oracle_mod.RefDBoW2.available():
-        pytest.skip("oracle/_ref/libdbow2_ref.so not built")
-    ref = oracle_mod.RefDBoW2()
-    rng = np.random.default_rng(77)
-    for n in (0, 5, 1500):
-        word = rng.integers(0, 400, n).astype(np.int32)
-        node = (word // 13).astype(np.int32)
-        weight = np.where(rng.uniform(size=n) < 0.1, 0.0, rng.uniform(0.1, 5.0, n))
+    """the same comparison on fresh inputs, every scoring: against the reference classes' results stored in
+    tests/golden/live_golden.npz (tests/golden/make_live_golden.py) and, where oracle/_ref/libdbow2_ref.so exists (build
+    container, GPU box), against the reference classes live"""
+    from tests.golden.make_live_golden import BOW_KEYS, bow_inputs
+    G = np.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "live_golden.npz"))
+    ref = oracle_mod.RefDBoW2() if oracle_mod.RefDBoW2.available() else None
+    for n, word, weight, node in bow_inputs():
+        for k, v in (("word", word), ("weight", weight), ("node", node)):
+            np.testing.assert_array_equal(v, G[f"bow_n{n}_in_{k}"])
         for weighting in range(4):
             for scoring in range(6):
                 a = oracle.bow_assemble(word, weight, node, weighting, scoring)
-                b = ref.assemble(word, weight, node, weighting, scoring)
-                for x, y in zip(a[0] + a[1], b[0] + b[1]):
-                    np.testing.assert_array_equal(x.view(np.uint64) if x.dtype == np.float64 else x,
-                                                  y.view(np.uint64) if y.dtype == np.float64 else y)
+                refs = [tuple(G[f"bow_n{n}_w{weighting}_s{scoring}_{key}"] for key in BOW_KEYS)]
+                if ref is not None:
+                    b = ref.assemble(word, weight, node, weighting, scoring)
+                    refs.append(b[0] + b[1])
+                for r in refs:
+                    for x, y in zip(a[0] + a[1], r, strict=True):
+                        np.testing.assert_array_equal(x.view(np.uint64) if x.dtype == np.float64 else x,
+                                                      y.view(np.uint64) if y.dtype == np.float64 else y)

@@ -81,17 +81,22 @@ def test_oracle_pose_optimization_matches_g2o(oracle, golden):
 
 
 def test_oracle_vs_live_reference_nominal(oracle, synth):
-    """SURVEY 8(d) nominal problem (E ~ 29k) against the reference g2o itself, when oracle/_ref is built."""
+    """SURVEY 8(d) nominal problem (E ~ 29k) against the reference g2o: its results stored in tests/golden/live_golden.npz
+    (tests/golden/make_live_golden.py) and, when oracle/_ref is built, the reference g2o itself."""
     from oracle import pyoracle
-    if not pyoracle.RefG2O.available():
-        pytest.skip("oracle/_ref/libg2o_ref.so not built (needs /root/reference)")
-    ref = pyoracle.RefG2O()
+    from tests.golden.make_live_golden import BA_KEYS, problem_digest
+    G = np.load(os.path.join(GOLDEN, "live_golden.npz"))
     prob = synth.ba_problem()
-    r, o = ref.local_ba(prob), oracle.local_ba(prob)
-    np.testing.assert_allclose(o["poses"], r["poses"], atol=1e-9, rtol=0)
-    np.testing.assert_allclose(o["points"], r["points"], atol=1e-7, rtol=0)
-    np.testing.assert_array_equal(o["edge_outlier1"], r["edge_outlier1"])
-    assert (o["iters_first"], o["iters_second"]) == (r["iters_first"], r["iters_second"])
+    assert problem_digest(prob) == str(G["nominal_in_sha256"]), "the seeded generator no longer makes the stored problem"
+    refs = [{k: G["nominal_out_" + k] for k in BA_KEYS}]
+    if pyoracle.RefG2O.available():
+        refs.append(pyoracle.RefG2O().local_ba(prob))
+    o = oracle.local_ba(prob)
+    for r in refs:
+        np.testing.assert_allclose(o["poses"], r["poses"], atol=1e-9, rtol=0)
+        np.testing.assert_allclose(o["points"], r["points"], atol=1e-7, rtol=0)
+        np.testing.assert_array_equal(o["edge_outlier1"], r["edge_outlier1"])
+        assert (o["iters_first"], o["iters_second"]) == (r["iters_first"], r["iters_second"])
 
 
 def test_pose_conversion_roundtrip(oracle, synth):

@@ -1,6 +1,6 @@
 set -e
 O=gpurun_out/r4b; mkdir -p $O
-python3 bench.py > $O/bench.json 2> $O/bench.err || { tail -5 $O/bench.err; exit 1; }
+python3 bench.py --full > $O/bench.json 2> $O/bench.err || { tail -5 $O/bench.err; exit 1; }
 python3 - <<'PY'
 import json
 d=json.loads(open('gpurun_out/r4b/bench.json').read().strip().splitlines()[-1])

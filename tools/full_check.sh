@@ -4,7 +4,7 @@ O=gpurun_out/r5a; mkdir -p $O
 timeout -k 10 1000 python -m pytest tests -m gpu -q --durations=5 > $O/tests.log 2>&1 || { tail -40 $O/tests.log; exit 1; }
 tail -3 $O/tests.log
 python3 -c "import __graft_entry__ as g; g.smoke()" 2>&1 | tail -3
-timeout -k 10 400 python3 bench.py > $O/bench.json 2> $O/bench.err
+timeout -k 10 400 python3 bench.py --full > $O/bench.json 2> $O/bench.err
 python3 - <<'PY'
 import json
 d=json.loads(open('gpurun_out/r5a/bench.json').read().strip().splitlines()[-1])

@@ -3,7 +3,7 @@
 # with `|| echo`; its cause -- the CU-masked stream, profiles/r03_teardown_diagnostics.txt -- is gone).
 set -e
 O=gpurun_out/r05p; mkdir -p $O
-python3 bench.py > $O/bench.json 2> $O/bench.err
+python3 bench.py --full > $O/bench.json 2> $O/bench.err
 cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof -o bench -- python3 bench.py --cpu-frames 0 --no-lane-variant --no-h2d-variant --no-do-mapping-variant --no-one-submission-variant --no-local-map-sweep > $O/bench_prof.log 2>&1
 test -s $O/prof/bench_kernel_stats.csv
@@ -17,7 +17,7 @@ ASD_TIMING=1 python3 bench.py --chain --cpu-frames 0 --no-lane-variant --no-h2d-
 grep -E "track_frame (resolve|device)" $O/chain_clock.err | tail -3 > $O/chain_clock.txt
 # BASELINE configs[3] (stereo) through the C++ host, the driver's K = 20 / W = 5 command, the per-keyframe stage
 python3 bench.py --workload euroc-stereo --steps 300 --warmup 45 > $O/bench_euroc_stereo.json 2> $O/bench_euroc_stereo.err
-python3 bench.py --steps 20 --warmup 5 --cpu-frames 0 > $O/bench_k20.json 2> $O/bench_k20.err
+python3 bench.py --full --steps 20 --warmup 5 --cpu-frames 0 > $O/bench_k20.json 2> $O/bench_k20.err
 python3 tools/kf_times.py --reps 12 > $O/kf_ops.json 2> $O/kf_ops.err
 python3 bench.py --sequences 11 --seq-scale 0.05 > $O/sequences_1gpu.json 2> $O/sequences_1gpu.err
 find $O/prof -name "*kernel_trace.csv" -delete
