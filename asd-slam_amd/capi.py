@@ -98,6 +98,20 @@ def load_library():
     return C.CDLL(path)
 
 
+def undistort_map(K, dist, w, h):
+    """asd_undistort_map: the map pair cv::undistort builds (host only, no context) -> (xy int16 [h, w, 2], frac uint16 [h, w]).
+    K = (fx, fy, cx, cy), dist = (k1, k2, p1, p2) or None, both passed as float32 like the reference's CV_32F mK / mDistCoef."""
+    lib = load_library()
+    Kf = _c(K, np.float32)
+    df = None if dist is None else _c(dist, np.float32)
+    xy = np.empty((h, w, 2), np.int16)
+    frac = np.empty((h, w), np.uint16)
+    rc = lib.asd_undistort_map(_p(Kf), _p(df), int(w), int(h), _p(xy), _p(frac))
+    if rc != 0:
+        raise AsdError(rc, "asd_undistort_map: invalid arguments")
+    return xy, frac
+
+
 class AsdHip:
     """One asd_ctx (= one HIP device + stream)."""
 
@@ -260,6 +274,26 @@ class AsdHip:
     def extract_hold(self, on=True):
         """asd_extract_hold: no further ASDNet forward of the read-ahead extractor is enqueued while on (a wait on a held submission ends it)"""
         self._chk(self.lib.asd_extract_hold(self.ctx, int(on)))
+
+    def set_undistortion(self, K, dist, w, h):
+        """asd_set_undistortion: every extraction from now on runs on cv::undistort(image, K, dist); dist None / zeros clears it"""
+        Kf = None if K is None else _c(K, np.float32)
+        df = None if dist is None else _c(dist, np.float32)
+        self._chk(self.lib.asd_set_undistortion(self.ctx, _p(Kf), _p(df), int(w), int(h)))
+
+    def undistort(self, image, device_resident=False, w=None, h=None, stride=None):
+        """asd_undistort on the context's map: a host array (or, device_resident=True, a device pointer with w, h, stride) -> u8 [h, w]"""
+        if device_resident:
+            src = image
+        else:
+            image = np.asarray(image)
+            assert image.dtype == np.uint8 and image.ndim == 2 and image.strides[1] == 1
+            h, w = image.shape
+            stride = image.strides[0]
+            src = C.c_void_p(image.ctypes.data)
+        out = np.empty((h, w), np.uint8)
+        self._chk(self.lib.asd_undistort(self.ctx, src, int(device_resident), int(w), int(h), int(stride), _p(out), int(w)))
+        return out
 
     def profile_enable(self, on=True):
         self._chk(self.lib.asd_profile_enable(self.ctx, int(on)))

@@ -151,6 +151,7 @@ int asd_ctx_destroy(asd_ctx* ctx) {
   frontend_async_shutdown(ctx);
   asdnet_free(ctx);
   frontend_free(ctx);
+  undistort_free(ctx);
   matcher_free(ctx);
   ba_free(ctx);
   mapping_free(ctx);

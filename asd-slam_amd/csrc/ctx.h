@@ -245,6 +245,15 @@ struct AsdFrameSlot {
   hipEvent_t ev_staged = nullptr;  // recorded behind the slot's H2D copies: h_stage may be rewritten once it has completed
 };
 
+// cv::undistort's map pair of asd_set_undistortion in HBM (undistort.hip): per pixel (x, y) as short2 and the 10-bit fraction as
+// uint16, rows of mpitch pixels (a multiple of 4: one 16-B and one 8-B load per four pixels); d_io = asd_undistort's own staging
+struct UndistortMap {
+  int w = 0, h = 0, mpitch = 0;
+  short2* d_xy = nullptr;
+  uint16_t* d_frac = nullptr;
+  uint8_t* d_io = nullptr;
+};
+
 struct asd_ctx {
   asd_config cfg{};
   hipStream_t stream = nullptr;
@@ -298,6 +307,7 @@ struct asd_ctx {
 
   // ---- front-end (state private to frontend.hip)
   struct FrontendState* fe = nullptr;
+  UndistortMap* und = nullptr;   // set: every extraction's level 0 is the undistorted image (k_undistort instead of k_copy_image)
   int last_n = 0;   // keypoints of the last asd_extract (descriptors in d_desc)
 
   // ---- frames
@@ -368,6 +378,13 @@ void frontend_async_shutdown(asd_ctx* ctx);
 // true while submissions of asd_extract_submit have not been waited for: the worker thread owns the shared pyramid / score /
 // blur buffers and the ASDNet activations then, and the synchronous entry points that use them must refuse to run
 bool asd_extractor_busy(asd_ctx* ctx, const char* who);
+// the caller's image into a pitched device buffer on `st`, the way level 0 is filled without a map: device and page-locked host
+// memory by k_copy_image, pageable host memory by hipMemcpy2DAsync
+int frontend_image_to_device(asd_ctx* ctx, const uint8_t* image, bool on_device, int width, int height, int stride, uint8_t* dst,
+                             int pitch, hipStream_t st);
+// undistort.hip
+int undistort_launch(asd_ctx* ctx, const UndistortMap& U, hipStream_t st, const uint8_t* src, int stride, uint8_t* dst, int pitch);
+void undistort_free(asd_ctx* ctx);
 // true (+ error message) while an asd_track_* call armed with asd_track_async has not been finished: its upload / result blocks,
 // the matcher's candidate buffers and the pose solver's staging are in use
 bool asd_track_busy(asd_ctx* ctx, const char* who);

@@ -448,6 +448,9 @@ struct FrontendState {
   std::vector<float> raw_x[ASD_MAX_LEVELS], raw_y[ASD_MAX_LEVELS], raw_r[ASD_MAX_LEVELS];
   std::vector<int> sel[ASD_MAX_LEVELS];
   LevelPool* pool = nullptr;
+  // host images while an undistortion map is set: k_undistort's source in device memory (allocated at the first such extraction)
+  uint8_t* d_stage = nullptr;
+  int stage_pitch = 0;
   ExtractSlot slot0;  // buffers of the synchronous asd_extract (aliases ctx->d_patches / d_desc and the arrays above)
 };
 
@@ -476,6 +479,7 @@ static int fe_alloc(asd_ctx* ctx, FrontendState** out) {
     ncell_max += (lw / 30 + 2) * (lh / 30 + 2);
   }
   fe->buf_bytes = bytes + 4096;
+  fe->stage_pitch = (W + kPitchAlign - 1) / kPitchAlign * kPitchAlign;
   ASD_HIP_CHECK(ctx, hipMalloc(&fe->d_pyr, fe->buf_bytes));
   ASD_HIP_CHECK(ctx, hipMalloc(&fe->d_blur, fe->buf_bytes));
   ASD_HIP_CHECK(ctx, hipMalloc(&fe->d_score, fe->buf_bytes));
@@ -508,7 +512,7 @@ static void fe_free(FrontendState* fe) {
   if (!fe) return;
   void* dev[] = {fe->d_pyr, fe->d_blur, fe->d_score, fe->d_xofs, fe->d_ialpha, fe->d_yofs, fe->d_ibeta, fe->d_cells,
                  fe->d_cell_count, fe->d_cell_off, fe->d_level_cell_start, fe->d_level_start,
-                 fe->d_kps, fe->d_angles};
+                 fe->d_kps, fe->d_angles, fe->d_stage};
   for (void* p : dev) if (p) (void)hipFree(p);
   void* host[] = {fe->h_corners, fe->h_level_start, fe->h_kps, fe->h_angles, fe->h_desc};
   for (void* p : host) if (p) (void)hipHostFree(p);
@@ -680,6 +684,28 @@ static void slot_free(ExtractSlot& S) {
   S = ExtractSlot();
 }
 
+// device memory and page-locked host memory go through the copy kernel; pageable host memory (asd_extract with an ordinary buffer)
+// needs the runtime's staging copy
+int frontend_image_to_device(asd_ctx* ctx, const uint8_t* image, bool on_device, int width, int height, int stride, uint8_t* dst,
+                             int pitch, hipStream_t st) {
+  bool by_kernel = on_device;
+  const uint8_t* src_dev = image;
+  if (!by_kernel) {
+    hipPointerAttribute_t at{};
+    by_kernel = hipPointerGetAttributes(&at, image) == hipSuccess && at.type == hipMemoryTypeHost && at.devicePointer != nullptr;
+    if (!by_kernel) (void)hipGetLastError();   // (an unregistered pointer is reported as an error: not ours)
+    // the device-side address of the mapping: equal to the host address for hipHostMalloc memory, not necessarily for hipHostRegister'ed memory
+    else src_dev = static_cast<const uint8_t*>(at.devicePointer) + (image - static_cast<const uint8_t*>(at.hostPointer ? at.hostPointer : image));
+  }
+  if (by_kernel) {
+    hipLaunchKernelGGL(k_copy_image, dim3((width + 1023) / 1024, height), dim3(256), 0, st, src_dev, stride, width, height, dst, pitch);
+    ASD_HIP_CHECK(ctx, hipGetLastError());
+  } else {
+    ASD_HIP_CHECK(ctx, hipMemcpy2DAsync(dst, pitch, image, stride, width, height, hipMemcpyHostToDevice, st));
+  }
+  return ASD_OK;
+}
+
 // E1-E5: pyramid, FAST, quadtree, orientation, blur, patch gather.  Fills kps (angle still 0) and leaves the
 // patches + angles in the slot; records S.ev_front on `st` after the last kernel.  Blocks the calling host
 // thread twice (corner counts, corner list) but never waits for anything outside `st`.
@@ -702,24 +728,19 @@ static int extract_front(asd_ctx* ctx, FrontendState* fe, const ExtractJob& J, E
   const auto t_start = now();
   ASD_HIP_CHECK(ctx, hipEventRecord(S.ev_begin, st));
   // E1 pyramid
-  {
-    // device memory and page-locked host memory go through the copy kernel; pageable host memory (asd_extract with an ordinary buffer)
-    // needs the runtime's staging copy
-    bool by_kernel = J.on_device;
-    const uint8_t* src_dev = J.image;
-    if (!by_kernel) {
-      hipPointerAttribute_t at{};
-      by_kernel = hipPointerGetAttributes(&at, J.image) == hipSuccess && at.type == hipMemoryTypeHost && at.devicePointer != nullptr;
-      if (!by_kernel) (void)hipGetLastError();   // (an unregistered pointer is reported as an error: not ours)
-      // the device-side address of the mapping: equal to the host address for hipHostMalloc memory, not necessarily for hipHostRegister'ed memory
-      else src_dev = static_cast<const uint8_t*>(at.devicePointer) + (J.image - static_cast<const uint8_t*>(at.hostPointer ? at.hostPointer : J.image));
+  if (!ctx->und) {
+    if ((rc = frontend_image_to_device(ctx, J.image, J.on_device, width, height, stride, fe->d_pyr + P.lv[0].off, P.lv[0].pitch, st)) != ASD_OK) return rc;
+  } else {
+    // cv::undistort (Tracking.cc:104,125) as level 0: k_undistort gathers from device memory only -- a device-resident image in
+    // place, a host image after the copy above into this front-end state's staging buffer (never single bytes over PCIe)
+    const uint8_t* src = J.image;
+    int src_stride = stride;
+    if (!J.on_device) {
+      if (!fe->d_stage) ASD_HIP_CHECK(ctx, hipMalloc(&fe->d_stage, (size_t)fe->stage_pitch * ctx->cfg.max_height));
+      if ((rc = frontend_image_to_device(ctx, J.image, false, width, height, stride, fe->d_stage, fe->stage_pitch, st)) != ASD_OK) return rc;
+      src = fe->d_stage; src_stride = fe->stage_pitch;
     }
-    if (by_kernel) {
-      hipLaunchKernelGGL(k_copy_image, dim3((width + 1023) / 1024, height), dim3(256), 0, st, src_dev, stride, width, height, fe->d_pyr + P.lv[0].off, P.lv[0].pitch);
-      ASD_HIP_CHECK(ctx, hipGetLastError());
-    } else {
-      ASD_HIP_CHECK(ctx, hipMemcpy2DAsync(fe->d_pyr + P.lv[0].off, P.lv[0].pitch, J.image, stride, width, height, hipMemcpyHostToDevice, st));
-    }
+    if ((rc = undistort_launch(ctx, *ctx->und, st, src, src_stride, fe->d_pyr + P.lv[0].off, P.lv[0].pitch)) != ASD_OK) return rc;
   }
   for (int l = 1; l < nl; ++l) {
     const LevelDev &Sl = P.lv[l - 1], &D = P.lv[l];
@@ -837,6 +858,10 @@ static int extract_check(asd_ctx* ctx, const uint8_t* image, int32_t width, int3
   if (!ctx || !image || stride < width) return ASD_ERR_INVALID;
   if (width > ctx->cfg.max_width || height > ctx->cfg.max_height) { ctx->set_error("image %dx%d exceeds ctx capacity %dx%d", width, height, ctx->cfg.max_width, ctx->cfg.max_height); return ASD_ERR_CAPACITY; }
   if (!ctx->weights_loaded) { ctx->set_error("asd_load_weights has not been called"); return ASD_ERR_NO_WEIGHTS; }
+  if (ctx->und && (width != ctx->und->w || height != ctx->und->h)) {
+    ctx->set_error("image %dx%d, the undistortion map (asd_set_undistortion) is %dx%d", width, height, ctx->und->w, ctx->und->h);
+    return ASD_ERR_INVALID;
+  }
   return ASD_OK;
 }
 

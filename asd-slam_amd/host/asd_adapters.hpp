@@ -62,6 +62,12 @@ class Context {
   Context& operator=(const Context&) = delete;
   asd_ctx* get() const { return ctx_; }
   const char* error() const { return asd_last_error(ctx_); }
+  // Tracking's constructor (Tracking.cc:59-72): mK = (fx, fy, cx, cy), mDistCoef = (k1, k2, p1, p2).  Replaces the per-frame
+  // cv::undistort(im, mImGray, mK, mDistCoef) of Tracking.cc:104,125: the raw image goes to ExtractDesc / asd_extract_submit and
+  // the Frame still gets distCoefZero.  Zero coefficients set no map.
+  void SetUndistortion(const float K[4], const float distCoef[4], int width, int height) {
+    if (asd_set_undistortion(ctx_, K, distCoef, width, height) != ASD_OK) throw std::runtime_error(error());
+  }
  private:
   asd_ctx* ctx_ = nullptr;
 };

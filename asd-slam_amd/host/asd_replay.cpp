@@ -212,6 +212,12 @@ int main(int argc, char** argv) {
   if (asd_ctx_create(&cfg, &ctx) != ASD_OK || !ctx) { fprintf(stderr, "asd_ctx_create failed: no usable HIP device (there is no CPU fallback)\n"); return 1; }
   auto fail = [&](const char* what) { fprintf(stderr, "%s: %s\n", what, asd_last_error(ctx)); asd_ctx_destroy(ctx); return 1; };
   if (asd_load_weights(ctx, cw, bm, bv, 1e-5f) != ASD_OK) return fail("asd_load_weights");
+  {   // Tracking::GrabImageMonocular undistorts every image with mK / mDistCoef (CV_32F) before the Frame is built (Tracking.cc:104);
+      // zero coefficients set no map
+    const float K32[4] = {(float)cam.fx, (float)cam.fy, (float)cam.cx, (float)cam.cy};
+    const float D32[4] = {(float)cam.distort[0], (float)cam.distort[1], (float)cam.distort[2], (float)cam.distort[3]};
+    if (asd_set_undistortion(ctx, K32, D32, W, H) != ASD_OK) return fail("asd_set_undistortion");
+  }
 
   if (a.chain) {
     const int rc = run_chain(a, ctx, files, nframes, W, H, cam, img[0]);

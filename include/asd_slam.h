@@ -154,6 +154,28 @@ int asd_get_level_image(asd_ctx* ctx, int32_t level, int32_t blurred, uint8_t* o
 int asd_get_raw_corners(asd_ctx* ctx, int32_t level, int32_t capacity, float* x, float* y,
                         float* response, int32_t* n_out);
 
+/* ---- undistortion in front of the extractor (Tracking.cc:104,125) -------------------
+ * Tracking::GrabImageMonocular and Tracking::Loc call cv::undistort(im, mImGray, mK, mDistCoef) on every image
+ * and build the Frame with distCoefZero.  K = (fx, fy, cx, cy) and dist = (k1, k2, p1, p2) as the CV_32F mK /
+ * mDistCoef hold them (Tracking.cc:59-72).
+ * asd_undistort_map writes the map pair OpenCV 3.2.0's cv::undistort builds internally (newCameraMatrix empty:
+ * initUndistortRectifyMap in stripes of min(max(1, 4096 / width), height) rows, CV_16SC2 + CV_16UC1):
+ * xy[height][width][2] = integer source (x, y), frac[height][width] = (y fraction) * 32 + (x fraction), in 1/32 px.
+ * Host only: needs no context and no device.  dist == NULL means zero coefficients. */
+int asd_undistort_map(const float K[4], const float dist[4], int32_t width, int32_t height, int16_t* xy, uint16_t* frac);
+/* Builds that map once and keeps it in HBM: from then on every extraction (asd_extract, asd_extract_device,
+ * asd_extract_submit; device, pinned and pageable sources) runs on the undistorted image -- remap INTER_LINEAR,
+ * BORDER_CONSTANT 0, integer-exact, as level 0 of the pyramid (asd_get_level_image(0, 0) returns it) -- and an
+ * extraction of another size returns ASD_ERR_INVALID.  dist == NULL or four zero coefficients clear the map (no extra
+ * launch).  ASD_ERR_CAPACITY above max_width / max_height; ASD_ERR_INVALID while submissions of asd_extract_submit are
+ * outstanding. */
+int asd_set_undistortion(asd_ctx* ctx, const float K[4], const float dist[4], int32_t width, int32_t height);
+/* cv::undistort itself on the context's map, result into host memory dst (row stride dst_stride): for callers that
+ * need the image (a viewer, the right image of a stereo pair).  src is a device pointer if device_resident != 0, else
+ * host memory (pinned or pageable).  ASD_ERR_INVALID without a map or for another size. */
+int asd_undistort(asd_ctx* ctx, const uint8_t* src, int32_t device_resident, int32_t width, int32_t height, int32_t stride,
+                  uint8_t* dst, int32_t dst_stride);
+
 /* ---- frames, grid (G1) and matchers (M0-M2, M4 init, M5) ----------------------------- */
 /* A frame slot keeps what the reference keeps in Frame: undistorted keypoints
  * (mvKeysUn), descriptors (mDescriptors) and the 64x48 grid (Frame.cc:123-138), all
