@@ -516,6 +516,13 @@ class AsdHip:
         bad = self.lib.asd_debug_level_sweep(self.ctx, C.c_float(lo), C.c_float(hi), C.byref(n))
         return bad, n.value
 
+    def local_ba_forms(self):
+        """[2, 5] int32 per round of the last LocalBA: (dense solve 0 solve_lds / 1 chol_lds / 2 chol / -1 none,
+        structure 0 device / 1 host, nPf, nLa, Ea) -- asd_debug_local_ba_forms"""
+        out = np.empty((2, 5), np.int32)
+        self._chk(self.lib.asd_debug_local_ba_forms(self.ctx, _p(out)))
+        return out
+
     def match_project_keyframe(self, slot_cur, n_cur, valid, Xw, min_dist, max_dist, desc, kf_angle, occupied, Tcw, K, th, orb_dist,
                                check_ori=True):
         a = [_c(valid, np.uint8), _c(Xw, np.float32), _c(min_dist, np.float32), _c(max_dist, np.float32), _c(desc, np.float32),

@@ -2057,6 +2057,7 @@ struct BaState {
   char* h_po = nullptr;         // pinned staging of asd_pose_optimize
   size_t h_po_cap = 0;
   struct BaLane* lane = nullptr;   // asd_local_ba_submit / _wait: the optional LocalBA lane (own thread, stream and events)
+  int forms[2][5] = {{-1, -1, -1, -1, -1}, {-1, -1, -1, -1, -1}};   // asd_debug_local_ba_forms: per round of the last LocalBA
 };
 
 // OPTIONAL lane, not the reference's order.  This fork of ORB-SLAM2 has no mapping thread: Tracking::CreateNewKeyFrame calls
@@ -2335,6 +2336,10 @@ int local_ba_impl(asd_ctx* ctx, BaState* s, asd_ba_problem* pr, asd_ba_result* r
   int rc;
   const auto t_enter = std::chrono::steady_clock::now();
 #define ENS(buf, bytes) if ((rc = s->buf.ensure(ctx, (bytes))) != ASD_OK) return rc
+  // the reduced pose system has n = 6 nPf rows, nPf <= the number of free poses: A and Apack are sized by that, not by P
+  int F = 0;
+  for (int p = 0; p < P; ++p) F += !pr->fixed[p];
+  F = std::max(F, 1);
   ENS(pose, (size_t)P * sizeof(Pose7)); ENS(pose_bak, (size_t)P * sizeof(Pose7));
   ENS(pts, (size_t)L * 24); ENS(pts_bak, (size_t)L * 24);
   ENS(e_pt, (size_t)E * 4); ENS(e_ps, (size_t)E * 4); ENS(obs, (size_t)E * 16); ENS(info, (size_t)E * 8);
@@ -2342,7 +2347,7 @@ int local_ba_impl(asd_ctx* ctx, BaState* s, asd_ba_problem* pr, asd_ba_result* r
   ENS(pose_of_h, (size_t)P * 4); ENS(pt_of_h, (size_t)L * 4); ENS(pt_start, (size_t)(L + 1) * 4);
   ENS(ps_start, (size_t)(P + 1) * 4); ENS(ps_edges, (size_t)E * 4);
   ENS(Bk, (size_t)E * 18 * 8); ENS(Hc, (size_t)E * 27 * 8); ENS(Hl, (size_t)E * 9 * 8); ENS(Hpp, (size_t)P * 27 * 8); ENS(Hll, (size_t)L * 9 * 8); ENS(Dinv, (size_t)L * 6 * 8);
-  ENS(db, (size_t)L * 3 * 8); ENS(x, ((size_t)6 * P + 3 * L) * 8); ENS(A, (size_t)36 * P * P * 8); ENS(Apack, (size_t)18 * P * (P + 1) * 8); ENS(bs, (size_t)6 * P * 8);
+  ENS(db, (size_t)L * 3 * 8); ENS(x, ((size_t)6 * P + 3 * L) * 8); ENS(A, (size_t)36 * F * F * 8); ENS(Apack, (size_t)18 * F * (F + 1) * 8); ENS(bs, (size_t)6 * P * 8);
   ENS(misc, 64); ENS(chi2, (size_t)E * 8); ENS(dpos, (size_t)E); ENS(lvl, (size_t)E); ENS(out1, (size_t)E); ENS(HppPart, (size_t)P * kPoseSplit * 27 * 8);
   const int nblk_e = (E + 255) / 256, nblk_l = (L + 255) / 256, nblk_p = (P + 255) / 256;
   const size_t npartial = (size_t)nblk_e + nblk_l + nblk_p + 8;
@@ -2404,6 +2409,7 @@ int local_ba_impl(asd_ctx* ctx, BaState* s, asd_ba_problem* pr, asd_ba_result* r
   d.tickets = reinterpret_cast<int*>(reinterpret_cast<char*>(d.lm_log) + sizeof(LmLog) * kLmLogCap);
   ASD_HIP_CHECK(ctx, hipMemsetAsync(d.tickets, 0, sizeof(int) * ((size_t)P + 2), st));
 
+  for (auto& f : s->forms) for (int& v : f) v = -1;
   const auto t_uploaded = std::chrono::steady_clock::now();
   std::vector<uint8_t> level(E, 0);
   std::vector<int> act, pose_h(P), pt_h(L), pose_of_h, pt_of_h, pt_start, ps_start, ps_edges, ps_hv, blk_i, blk_j, pair_start, ph_of_k, cursor,
@@ -2418,6 +2424,7 @@ int local_ba_impl(asd_ctx* ctx, BaState* s, asd_ba_problem* pr, asd_ba_result* r
   // lost all its edges gets a zero step, and x + 0.0 == x, so every sum equals the sum over the compacted lists g2o would build --
   // without the second host pass over the edges and its uploads (0.45 ms per LocalBA).
   int nPf = 0, nLa = 0, Ea = 0, nblk = 0;
+  int struct_form = -1;   // 0 = built on the device, 1 = on the host (in round 0; round 1 reuses it)
   size_t n_pairs_total = 0;
   SchurBlocks sb{};
   std::chrono::steady_clock::time_point t_prep;
@@ -2427,9 +2434,9 @@ int local_ba_impl(asd_ctx* ctx, BaState* s, asd_ba_problem* pr, asd_ba_result* r
     int r2;
     int n_free_max = 0;
     for (int p = 0; p < P; ++p) n_free_max += !pr->fixed[p];
-    static const bool struct_host = getenv("ASD_BA_STRUCT") && !strcmp(getenv("ASD_BA_STRUCT"), "host");
-    // a landmark observed twice by one pose (nothing forbids it, the host loop and the general branch of k_ba_struct_pairs handle it)
-    // has more pairs than the device tables are sized for -- E (F + 1) / 2 assumes at most one edge per (landmark, free pose): such a
+    const bool struct_host = ctx->ba_struct_host;   // per context (a process-wide latch made the first call decide for every context)
+    // a landmark observed twice by one pose (nothing forbids it; the host loop gives its diagonal block both cross terms, the general
+    // branch of k_ba_struct_pairs does not) has more pairs than the device tables are sized for -- E (F + 1) / 2 assumes at most one edge per (landmark, free pose): such a
     // problem takes the host-built structure instead of writing past the pair list
     bool dup_edges = false;
     if (round_idx == 0 && !struct_host && E > 0 && P <= kStructMaxP && n_free_max <= kStructMaxFree) {
@@ -2560,7 +2567,7 @@ int local_ba_impl(asd_ctx* ctx, BaState* s, asd_ba_problem* pr, asd_ba_result* r
       while (a < s1 && ph_of_k[a] < 0) ++a;  // fixed poses sort first
       for (; a < s1; ++a) {
         const int ro = row_off[ph_of_k[a]];
-        for (int b = a; b < s1; ++b) ++pair_start[ro + ph_of_k[b] + 1];
+        for (int b = a; b < s1; ++b) pair_start[ro + ph_of_k[b] + 1] += 1 + (b != a && ph_of_k[b] == ph_of_k[a]);
       }
     }
     for (int q = 0; q < nblk_all; ++q) pair_start[q + 1] += pair_start[q];
@@ -2603,7 +2610,12 @@ int local_ba_impl(asd_ctx* ctx, BaState* s, asd_ba_problem* pr, asd_ba_result* r
         while (a < s1 && ph_of_k[a] < 0) ++a;
         for (; a < s1; ++a) {
           const int ro = row_off[ph_of_k[a]];
-          for (int b = a; b < s1; ++b) { const int o = cursor[ro + ph_of_k[b]]++; pp[o] = make_int2(a, b); ph_[o] = h; }
+          for (int b = a; b < s1; ++b) {
+            const int o = cursor[ro + ph_of_k[b]]++; pp[o] = make_int2(a, b); ph_[o] = h;
+            // two edges of one pose (a duplicate observation): k_ba_schur adds Y_a B_b^T for a pair, and the diagonal block needs
+            // both cross terms, Y_a B_b^T + Y_b B_a^T -- the transposed block of an off-diagonal pair is written from the same sum
+            if (b != a && ph_of_k[b] == ph_of_k[a]) { const int o2 = cursor[ro + ph_of_k[b]]++; pp[o2] = make_int2(b, a); ph_[o2] = h; }
+          }
         }
       }
     }
@@ -2618,6 +2630,12 @@ int local_ba_impl(asd_ctx* ctx, BaState* s, asd_ba_problem* pr, asd_ba_result* r
                      reinterpret_cast<const int2*>(db + o_pairs), reinterpret_cast<const int*>(db + o_pair_h)};
     d.Ea = Ea; d.nPf = nPf; d.nLa = nLa;
     }   // round_idx == 0
+    if (round_idx == 0) struct_form = struct_dev ? 0 : 1;
+    {
+      int* f = s->forms[round_idx];
+      f[0] = Ea == 0 || nPf == 0 ? -1 : nPf <= kSolveMaxBlocks ? 0 : nPf <= 32 ? 1 : 2;   // the dense solve enqueue_block picks
+      f[1] = struct_form; f[2] = nPf; f[3] = nLa; f[4] = Ea;
+    }
     t_prep = std::chrono::steady_clock::now();
     *iters_out = 0;
     *chi_out = 0;
@@ -2839,6 +2857,14 @@ int asd_local_ba_wait(asd_ctx* ctx) {
   ln->done = false;
   ctx->ms_ba = ln->ms;
   return ln->rc;
+}
+
+int32_t asd_debug_local_ba_forms(const asd_ctx* ctx, int32_t out[2][5]) {
+  if (!ctx || !out) return ASD_ERR_INVALID;
+  const BaState* s = static_cast<const BaState*>(ctx->ba);
+  for (int r = 0; r < 2; ++r)
+    for (int k = 0; k < 5; ++k) out[r][k] = s ? s->forms[r][k] : -1;
+  return ASD_OK;
 }
 
 int asd_local_ba_poll(asd_ctx* ctx) {

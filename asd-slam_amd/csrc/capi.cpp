@@ -116,6 +116,7 @@ int asd_ctx_create(const asd_config* cfg, asd_ctx** out) {
   // ASD_ASDNET_SPLIT_LAYERS=<mask> picks layers (bit 0 = conv2 ... bit 4 = conv6, bit 5 = fc)
   c->net_split = 0x3f;
   if (const char* e = getenv("ASD_MATCH_REPLAY")) c->match_replay_host = !strcmp(e, "host");   // matcher.hip, k_resolve
+  if (const char* e = getenv("ASD_BA_STRUCT")) c->ba_struct_host = !strcmp(e, "host");          // ba.hip, local_ba_impl
   if (const char* e = getenv("ASD_ASDNET_MATH")) {
     if (!strcmp(e, "f32")) c->net_split = 0;
     else if (!strcmp(e, "f16x2")) c->net_pieces = 2;

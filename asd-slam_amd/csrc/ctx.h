@@ -282,6 +282,7 @@ struct asd_ctx {
   float* d_wimg[7] = {};        // MFMA B-operand images, layers 2..7 (index 1..6)
   void* d_wx3[7] = {};          // the same weights split into three bf16 terms (asdnet.hip, split-operand kernels)
   bool match_replay_host = false;  // ASD_MATCH_REPLAY=host (read at asd_ctx_create): matcher claim replay on the host
+  bool ba_struct_host = false;     // ASD_BA_STRUCT=host (read at asd_ctx_create): LocalBA's active structure built on the host
   void* d_wx2[7] = {};          // layers 1..5 split into two fp16 terms of (weight * wx2_scale[l]) (ASD_ASDNET_MATH=f16x2)
   float wx2_scale[7] = {1, 1, 1, 1, 1, 1, 1};
   int net_pieces_req = 2;       // the form asked for at asd_ctx_create (ASD_ASDNET_MATH); asd_load_weights starts from it every time

@@ -699,6 +699,13 @@ int asd_sync(asd_ctx* ctx);
  * per-level thresholds derived from the host's logf at asd_ctx_create; this sweeps EVERY float in [lo, hi] and returns the
  * number of ratios for which the comparison rule and ceil(logf(r) / logf(scaleFactor)) (clamped) disagree (expected 0). */
 int32_t asd_debug_level_sweep(const asd_ctx* ctx, float lo, float hi, int64_t* n_checked);
+/* Test aid: which forms the last asd_local_ba (or the run collected by asd_local_ba_wait; not valid while a run is outstanding)
+ * took in each of its two rounds.  out[round] = {dense solve of the reduced pose system: 0 = k_ba_solve_lds (nPf <= 30),
+ * 1 = k_ba_chol_lds (31-32), 2 = k_ba_chol (>= 33), -1 = none (no free pose with an active edge); active structure:
+ * 0 = built on the device, 1 = built on the host; nPf, nLa, Ea: free poses, landmarks and edges of the active structure}.
+ * The structure is built once, for round 0: round 1 runs over it with its level-1 edges masked, so its values repeat round 0's.
+ * All -1 before any run, and for a round that did not start. */
+int32_t asd_debug_local_ba_forms(const asd_ctx* ctx, int32_t out[2][5]);
 /* Runs `reps` back-to-back repetitions of the ASDNet forward on resident buffers and
  * returns the average per-repetition device time (hipEvents on the ctx stream). */
 int asd_describe_timed(asd_ctx* ctx, const uint8_t* d_patches, int32_t n, float* d_desc,
