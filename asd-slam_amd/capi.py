@@ -523,6 +523,13 @@ class AsdHip:
         self._chk(self.lib.asd_debug_local_ba_forms(self.ctx, _p(out)))
         return out
 
+    def local_ba_lm(self):
+        """[2, 4] int32 per round of the last LocalBA: (iterations, trials, trial blocks enqueued, first chunk) --
+        asd_debug_local_ba_lm"""
+        out = np.empty((2, 4), np.int32)
+        self._chk(self.lib.asd_debug_local_ba_lm(self.ctx, _p(out)))
+        return out
+
     def match_project_keyframe(self, slot_cur, n_cur, valid, Xw, min_dist, max_dist, desc, kf_angle, occupied, Tcw, K, th, orb_dist,
                                check_ori=True):
         a = [_c(valid, np.uint8), _c(Xw, np.float32), _c(min_dist, np.float32), _c(max_dist, np.float32), _c(desc, np.float32),

@@ -892,7 +892,8 @@ __global__ __launch_bounds__(1024) void k_pose_edges(PoseEdgesArgs a) {
 struct LmState {
   double lambda, ni, currentChi, iniChi, rho;
   unsigned long long maxdiag_bits;   // max |diag(H)| over poses and landmarks as the bit pattern of a non-negative double
-  int it, qmax, nBad, done, need_lin, cur, trials, iters_done, chol_ok, iterations, first, pad_;   // cur: which of the two estimate buffers holds the accepted estimate
+  int it, qmax, nBad, done, need_lin, cur, trials, iters_done, chol_ok, iterations, first;   // cur: which of the two estimate buffers holds the accepted estimate
+  int active;   // set by k_ba_error's first pass of a round when an edge takes part; read and cleared by lm_begin_body
 };
 struct LmLog { double lambda, cur, temp, scale; };   // one record per trial (ASD_BA_DEBUG, tests)
 constexpr int kLmLogCap = 128;
@@ -994,9 +995,11 @@ __global__ __launch_bounds__(256) void k_ba_error(BaDev d, int robust, int alway
   const int buf = always ? d.lm->cur : 1 - d.lm->cur;   // the round's first pass looks at the accepted estimate, every other at the trial
   const int k = blockIdx.x * 256 + threadIdx.x;
   double part[1] = {0.0};
+  int active = 0;
   if (k < d.Ea) {
     const int e = d.act[k];
     if (!d.lvl[e]) {   // level-1 edges are outside the optimisation: their stored error stays as last computed, they add nothing
+      active = 1;
       ba_project_error(d, e, buf);
       const double c = (d.err[2 * e] * d.err[2 * e] + d.err[2 * e + 1] * d.err[2 * e + 1]) * d.info[e];
       double r0 = c, r1;
@@ -1006,6 +1009,8 @@ __global__ __launch_bounds__(256) void k_ba_error(BaDev d, int robust, int alway
   }
   block_reduce<1>(part, red, out);
   if (threadIdx.x == 0) st_agent(d.partial + blockIdx.x, out[0]);
+  // the round's first pass: does any edge take part?  Without one the round has no active vertex (landmarks are never fixed)
+  if (always && asd_syncthreads_or(active) && threadIdx.x == 0) __hip_atomic_store(&d.lm->active, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   if (!last_workgroup(d.tickets, (int)gridDim.x)) return;
   if (always) lm_begin_body(d, iterations, sh);
   else lm_control_body(d, sh);
@@ -1708,7 +1713,10 @@ __device__ void lm_begin_body(const BaDev& d, int iterations, double* sh) {
   S.lambda = -1; S.ni = 2; S.currentChi = sum; S.iniChi = sum; S.rho = 0;
   S.maxdiag_bits = 0;
   S.it = 0; S.qmax = 0; S.nBad = 0; S.done = iterations <= 0 ? 1 : 0; S.need_lin = 1; S.cur = d.lm->cur & 1; S.trials = 0; S.iters_done = 0;   // (cur carries over from the previous round)
-  S.chol_ok = 1; S.iterations = iterations; S.first = 1; S.pad_ = 0;
+  S.chol_ok = 1; S.iterations = iterations; S.first = 1; S.active = 0;
+  // every edge at level 1 (the second round after a gating that took them all): g2o's optimize() finds "0 vertices to optimize"
+  // and returns -1 before its first iteration (sparse_optimizer.cpp:356-359) -- no trial, the estimate and the stored errors stay
+  if (!__hip_atomic_load(&d.lm->active, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) { S.done = 1; S.iters_done = -1; }
   *d.lm = S;
   *d.lm_host = S;
 }
@@ -2058,6 +2066,7 @@ struct BaState {
   size_t h_po_cap = 0;
   struct BaLane* lane = nullptr;   // asd_local_ba_submit / _wait: the optional LocalBA lane (own thread, stream and events)
   int forms[2][5] = {{-1, -1, -1, -1, -1}, {-1, -1, -1, -1, -1}};   // asd_debug_local_ba_forms: per round of the last LocalBA
+  int lm_rounds[2][4] = {{-1, -1, -1, -1}, {-1, -1, -1, -1}};       // asd_debug_local_ba_lm: per round of the last LocalBA
 };
 
 // OPTIONAL lane, not the reference's order.  This fork of ORB-SLAM2 has no mapping thread: Tracking::CreateNewKeyFrame calls
@@ -2410,6 +2419,7 @@ int local_ba_impl(asd_ctx* ctx, BaState* s, asd_ba_problem* pr, asd_ba_result* r
   ASD_HIP_CHECK(ctx, hipMemsetAsync(d.tickets, 0, sizeof(int) * ((size_t)P + 2), st));
 
   for (auto& f : s->forms) for (int& v : f) v = -1;
+  for (auto& f : s->lm_rounds) for (int& v : f) v = -1;
   const auto t_uploaded = std::chrono::steady_clock::now();
   std::vector<uint8_t> level(E, 0);
   std::vector<int> act, pose_h(P), pt_h(L), pose_of_h, pt_of_h, pt_start, ps_start, ps_edges, ps_hv, blk_i, blk_j, pair_start, ph_of_k, cursor,
@@ -2681,6 +2691,7 @@ int local_ba_impl(asd_ctx* ctx, BaState* s, asd_ba_problem* pr, asd_ba_result* r
     ASD_HIP_CHECK(ctx, hipGetLastError());
     int& predicted = s->lm_blocks[round_idx];
     int chunk = predicted > 0 ? predicted : iterations;
+    const int first_chunk = iterations > 0 ? chunk : 0;
     int done = 0;
     // a round takes at most `iterations` iterations of at most ten trials each (levenberg.cpp:_maxTrialsAfterFailure): that, not a
     // fixed number of chunks, bounds the loop -- a slowly converging problem with many iterations is not a numeric failure
@@ -2695,9 +2706,20 @@ int local_ba_impl(asd_ctx* ctx, BaState* s, asd_ba_problem* pr, asd_ba_result* r
       if (s->h_lm->done) break;
       chunk = 2;
     }
-    if (iterations > 0 && !s->h_lm->done) { ctx->set_error("asd_local_ba: the Levenberg state did not finish"); return ASD_ERR_NUMERIC; }
+    // no block ran: wait for k_ba_error's first pass before reading its state (h_lm held the previous round's until then), and
+    // report the chi2 of the stored errors as they stand
+    if (iterations <= 0) {
+      hipLaunchKernelGGL(k_ba_chi2_stored, dim3(gE), dim3(256), 0, st, d, robust ? 1 : 0, s->h_partial);
+      ASD_HIP_CHECK(ctx, hipGetLastError());
+      ASD_HIP_CHECK(ctx, hipStreamSynchronize(st));
+    }
+    if (!s->h_lm->done) { ctx->set_error("asd_local_ba: the Levenberg state did not finish"); return ASD_ERR_NUMERIC; }
     done = s->h_lm->iters_done;
     predicted = s->h_lm->trials;
+    {
+      int* f = s->lm_rounds[round_idx];
+      f[0] = done; f[1] = s->h_lm->trials; f[2] = n_trials; f[3] = first_chunk;
+    }
     if (getenv("ASD_BA_DEBUG")) {
       std::vector<LmLog> lg(kLmLogCap);
       ASD_HIP_CHECK(ctx, hipMemcpy(lg.data(), d.lm_log, sizeof(LmLog) * kLmLogCap, hipMemcpyDeviceToHost));
@@ -2706,11 +2728,6 @@ int local_ba_impl(asd_ctx* ctx, BaState* s, asd_ba_problem* pr, asd_ba_result* r
       fprintf(stderr, "[ba] round %d: %d iterations, %d trials, %d blocks enqueued\n", round_idx, done, s->h_lm->trials, n_trials);
     }
     *iters_out = done;
-    if (iterations <= 0) {   // no block ran: report the chi2 of the stored errors as they stand
-      hipLaunchKernelGGL(k_ba_chi2_stored, dim3(gE), dim3(256), 0, st, d, robust ? 1 : 0, s->h_partial);
-      ASD_HIP_CHECK(ctx, hipGetLastError());
-      ASD_HIP_CHECK(ctx, hipStreamSynchronize(st));
-    }
     double sum = 0;
     for (int i = 0; i < gE; ++i) sum += s->h_partial[i];
     *chi_out = sum;
@@ -2864,6 +2881,14 @@ int32_t asd_debug_local_ba_forms(const asd_ctx* ctx, int32_t out[2][5]) {
   const BaState* s = static_cast<const BaState*>(ctx->ba);
   for (int r = 0; r < 2; ++r)
     for (int k = 0; k < 5; ++k) out[r][k] = s ? s->forms[r][k] : -1;
+  return ASD_OK;
+}
+
+int32_t asd_debug_local_ba_lm(const asd_ctx* ctx, int32_t out[2][4]) {
+  if (!ctx || !out) return ASD_ERR_INVALID;
+  const BaState* s = static_cast<const BaState*>(ctx->ba);
+  for (int r = 0; r < 2; ++r)
+    for (int k = 0; k < 4; ++k) out[r][k] = s ? s->lm_rounds[r][k] : -1;
   return ASD_OK;
 }
 

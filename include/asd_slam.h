@@ -624,8 +624,9 @@ typedef struct asd_ba_result {
   uint8_t* edge_outlier1;    /* [n_edges] moved to level 1 after the first round          */
   double   chi2_first;       /* active robust chi2 after optimize(its_first)              */
   double   chi2_second;      /* active chi2 after optimize(its_second)                    */
-  int32_t  iters_first;      /* LM iterations actually run                                */
-  int32_t  iters_second;
+  int32_t  iters_first;      /* LM iterations actually run, as g2o's optimize() returns   */
+  int32_t  iters_second;     /* them: -1 for a round without an active vertex (every edge */
+                             /* gated out after the first round), no trial, nothing moves  */
 } asd_ba_result;
 
 /* Numeric core of Optimizer::LocalBundleAdjustment (Optimizer.cc:484-650): BlockSolver_6_3
@@ -706,6 +707,12 @@ int32_t asd_debug_level_sweep(const asd_ctx* ctx, float lo, float hi, int64_t* n
  * The structure is built once, for round 0: round 1 runs over it with its level-1 edges masked, so its values repeat round 0's.
  * All -1 before any run, and for a round that did not start. */
 int32_t asd_debug_local_ba_forms(const asd_ctx* ctx, int32_t out[2][5]);
+/* Test aid: how the Levenberg rounds of the last asd_local_ba (or of the run collected by asd_local_ba_wait; not valid while a
+ * run is outstanding) went.  out[round] = {iterations done (the round's iters_first / iters_second), trials (solves, accepted
+ * and rejected), trial blocks enqueued (the blocks behind the round's end are no-ops), length of the first chunk of blocks
+ * (the trials the same round of the context's previous LocalBA took, else its_first / its_second; 0 when no block ran)}.
+ * Read from host-side bookkeeping: it adds no work to a run.  All -1 before any run, and for a round that did not start. */
+int32_t asd_debug_local_ba_lm(const asd_ctx* ctx, int32_t out[2][4]);
 /* Runs `reps` back-to-back repetitions of the ASDNet forward on resident buffers and
  * returns the average per-repetition device time (hipEvents on the ctx stream). */
 int asd_describe_timed(asd_ctx* ctx, const uint8_t* d_patches, int32_t n, float* d_desc,

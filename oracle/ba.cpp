@@ -424,8 +424,12 @@ struct BA {
     }
     return true;
   }
-  int optimize(int iterations, double* final_chi) {
+  // returns what SparseOptimizer::optimize does: the iterations run, or -1 when the round has no active vertex ("0 vertices to
+  // optimize", sparse_optimizer.cpp:356-359 -- every edge at level 1: landmarks are never fixed); *trials counts the solves
+  int optimize(int iterations, double* final_chi, int* trials) {
     init_active();
+    *trials = 0;
+    if (nPf + nLa == 0) return -1;
     double lambda = -1, ni = 2;
     int nBad = 0, done = 0;
     std::vector<double> x;
@@ -473,6 +477,7 @@ struct BA {
           pts = bpts;
         }
         qmax++;
+        ++*trials;
       } while (rho < 0 && qmax < 10);
       ++done;
       if (final_chi) *final_chi = currentChi;
@@ -536,8 +541,11 @@ int orc_local_ba(int n_poses, int n_points, int n_edges, double* poses, const ui
   ba.err.assign(2 * (size_t)n_edges, 0);
   ba.level.assign(n_edges, 0);
   ba.robust = true;
+  // every error at the input estimate: the first iteration recomputes them all, so this matters only to its1 = 0, where g2o itself
+  // would gate on errors it never computed (oracle/ref_g2o/driver.cpp computes them the same way)
+  for (int e = 0; e < n_edges; ++e) ba.project_error(e);
   double chi = 0;
-  out->iters_first = ba.optimize(its1, &chi);   // optimizer.initializeOptimization(); optimize(5)
+  out->iters_first = ba.optimize(its1, &chi, &out->trials_first);   // optimizer.initializeOptimization(); optimize(5)
   out->chi2_first = ba.active_robust_chi2();    // from the stored edge errors
   for (int e = 0; e < n_edges; ++e) {           // Optimizer.cc:616-631
     const bool bad = ba.chi2(e) > 5.991 || !ba.depth_positive(e);
@@ -546,7 +554,7 @@ int orc_local_ba(int n_poses, int n_points, int n_edges, double* poses, const ui
   }
   ba.robust = false;                            // e->setRobustKernel(0)
   chi = 0;
-  out->iters_second = ba.optimize(its2, &chi);  // initializeOptimization(0); optimize(10)
+  out->iters_second = ba.optimize(its2, &chi, &out->trials_second);  // initializeOptimization(0); optimize(10)
   out->chi2_second = ba.active_robust_chi2();
   for (int e = 0; e < n_edges; ++e) {           // Optimizer.cc:657-671 (level-1 edges keep their stale error)
     edge_chi2[e] = ba.chi2(e);

@@ -27,7 +27,7 @@ def _c(a, dt):
 
 class orc_ba_out(C.Structure):
     _fields_ = [("chi2_first", C.c_double), ("chi2_second", C.c_double), ("iters_first", C.c_int32),
-                ("iters_second", C.c_int32)]
+                ("iters_second", C.c_int32), ("trials_first", C.c_int32), ("trials_second", C.c_int32)]
 
 
 class Oracle:
@@ -264,7 +264,7 @@ class Oracle:
         assert rc == 0
         return dict(poses=poses, points=points, edge_chi2=chi2, edge_depth_pos=dpos, edge_outlier1=out1,
                     chi2_first=o.chi2_first, chi2_second=o.chi2_second, iters_first=o.iters_first,
-                    iters_second=o.iters_second)
+                    iters_second=o.iters_second, trials_first=o.trials_first, trials_second=o.trials_second)
 
     def tcw_to_pose7(self, T):
         T = _c(T, np.float32)
@@ -309,19 +309,35 @@ class RefDBoW2:
         return _bow_assemble(self.lib.ref_bow_assemble, word, weight, node, (int(weighting), int(scoring != 5), int(scoring == 1)))
 
 
+REF_G2O_ABI = 2   # oracle/ref_g2o/driver.cpp, ref_driver_abi
+
+
+def ref_g2o_abi(lib):
+    """revision of the driver a libg2o_ref.so was built from: 1 for one that predates ref_driver_abi"""
+    return int(lib.ref_driver_abi()) if hasattr(lib, "ref_driver_abi") else 1
+
+
 class RefG2O:
     """The reference's own vendored g2o compiled in place (oracle/ref_g2o -> oracle/_ref/libg2o_ref.so).
-    Same calling convention as Oracle.pose_optimize / Oracle.local_ba."""
+    Same calling convention as Oracle.pose_optimize / Oracle.local_ba.
+
+    oracle/_ref/ is a build product that is never committed, so it can predate the driver of this tree (it is rebuilt where the
+    reference's sources are present).  self.abi is the revision it was built from: local_ba reports trial counts and the Levenberg
+    trace, and computes every edge error ahead of an its_first = 0 round, only from revision 2 on.  Callers that need those ask
+    available(abi=2); with its_first and its_second >= 1 every revision computes the same."""
 
     def __init__(self):
         path = os.path.join(_HERE, "_ref", "libg2o_ref.so")
         if not os.path.exists(path):
             raise FileNotFoundError(path)
         self.lib = C.CDLL(path)
+        self.abi = ref_g2o_abi(self.lib)
 
     @staticmethod
-    def available():
-        return os.path.exists(os.path.join(_HERE, "_ref", "libg2o_ref.so"))
+    def available(abi=1):
+        if not os.path.exists(os.path.join(_HERE, "_ref", "libg2o_ref.so")):
+            return False
+        return abi <= 1 or RefG2O().abi >= abi
 
     def pose_optimize(self, pose7, Xw, obs, inv_sigma2, K):
         pose = _c(pose7, np.float64).copy()
@@ -345,9 +361,24 @@ class RefG2O:
                                    _p(e_pose), _p(e_obs), _p(e_info), _p(K), its_first, its_second, _p(chi2),
                                    _p(dpos), _p(out1), C.byref(o))
         assert rc == 0
-        return dict(poses=poses, points=points, edge_chi2=chi2, edge_depth_pos=dpos, edge_outlier1=out1,
-                    chi2_first=o.chi2_first, chi2_second=o.chi2_second, iters_first=o.iters_first,
-                    iters_second=o.iters_second)
+        res = dict(poses=poses, points=points, edge_chi2=chi2, edge_depth_pos=dpos, edge_outlier1=out1,
+                   chi2_first=o.chi2_first, chi2_second=o.chi2_second, iters_first=o.iters_first,
+                   iters_second=o.iters_second)
+        if self.abi >= 2:
+            res.update(trials_first=o.trials_first, trials_second=o.trials_second, lm_trace=[self._lm_trace(r) for r in range(2)])
+        elif its_first < 1:
+            raise RuntimeError("oracle/_ref/libg2o_ref.so predates ref_driver_abi 2: its_first = 0 needs a rebuilt library")
+        return res
+
+    def _lm_trace(self, rnd):
+        """the Levenberg trace of the last local_ba's round rnd (driver.cpp, ref_local_ba_trace): iters [n, 3] = (trials, lambda
+        after the iteration, activeRobustChi2 of the last trial's errors) per iteration; calls [m] = activeRobustChi2 read in front of
+        each computeActiveErrors, i.e. of the errors the call before it stored (calls[0] predates the round)"""
+        ni, nc = C.c_int32(), C.c_int32()
+        self.lib.ref_local_ba_trace(rnd, None, C.byref(ni), None, C.byref(nc))
+        iters, calls = np.zeros((ni.value, 3), np.float64), np.zeros(nc.value, np.float64)
+        assert self.lib.ref_local_ba_trace(rnd, _p(iters), C.byref(ni), _p(calls), C.byref(nc)) == 0
+        return dict(iters=iters, calls=calls)
 
 
 class OracleExtractor:

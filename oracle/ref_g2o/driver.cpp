@@ -9,12 +9,47 @@
 #include <vector>
 
 #include "g2o/core/block_solver.h"
+#include "g2o/core/hyper_graph_action.h"
 #include "g2o/core/optimization_algorithm_levenberg.h"
 #include "g2o/core/robust_kernel_impl.h"
 #include "g2o/solvers/linear_solver_dense.h"
 #include "g2o/types/types_six_dof_expmap.h"
 
-struct ref_ba_out { double chi2_first, chi2_second; int32_t iters_first, iters_second; };
+struct ref_ba_out { double chi2_first, chi2_second; int32_t iters_first, iters_second, trials_first, trials_second; };
+
+// Revision of this driver's entry points, read by oracle/pyoracle.py (RefG2O.abi).  A library built from an older driver has no
+// such symbol (revision 1): ref_local_ba without the trial counts, the trace or the edge errors computed ahead of an its1 = 0 round.
+extern "C" int ref_driver_abi() { return 2; }
+
+// The Levenberg trace of the last ref_local_ba, per round (ref_local_ba_trace reads it):
+//  - per iteration, from a post-iteration action: the trials it took (levenbergIteration()), the lambda it left behind
+//    (currentLambda()) and activeRobustChi2() over the stored errors -- those of its last trial, accepted or not;
+//  - per computeActiveErrors call, from a compute-error action, which runs IN FRONT of the computation: activeRobustChi2() of the
+//    errors the previous call stored.  A round makes 1 + trials calls per iteration (levenberg.cpp:74, :119), so entry j + 1 is the
+//    chi2 after call j, and the post-iteration chi2 of the round's last iteration closes the list.
+// Neither action recomputes anything: the estimate, the stored errors and the Levenberg state are what they would be without them.
+struct LmIter { double trials, lambda, chi2; };
+static std::vector<LmIter> g_iters[2];
+static std::vector<double> g_calls[2];
+static int g_round = 0;
+
+namespace {
+struct PostIteration : g2o::HyperGraphAction {
+  g2o::OptimizationAlgorithmLevenberg* lm;
+  explicit PostIteration(g2o::OptimizationAlgorithmLevenberg* a) : lm(a) {}
+  g2o::HyperGraphAction* operator()(const g2o::HyperGraph* graph, Parameters* = 0) {
+    const g2o::SparseOptimizer* o = static_cast<const g2o::SparseOptimizer*>(graph);
+    g_iters[g_round].push_back(LmIter{(double)lm->levenbergIteration(), lm->currentLambda(), o->activeRobustChi2()});
+    return this;
+  }
+};
+struct ComputeErrors : g2o::HyperGraphAction {
+  g2o::HyperGraphAction* operator()(const g2o::HyperGraph* graph, Parameters* = 0) {
+    g_calls[g_round].push_back(static_cast<const g2o::SparseOptimizer*>(graph)->activeRobustChi2());
+    return this;
+  }
+};
+}  // namespace
 
 static g2o::SE3Quat from7(const double* p) {
   return g2o::SE3Quat(Eigen::Quaterniond(p[3], p[0], p[1], p[2]), Eigen::Vector3d(p[4], p[5], p[6]));
@@ -123,6 +158,16 @@ extern "C" int ref_local_ba(int n_poses, int n_points, int n_edges, double* pose
     optimizer.addEdge(e);
     vpEdgesMono[k] = e;
   }
+  // every edge's error at the input estimate.  optimize() computes the active errors at the start of its first iteration, so this
+  // changes nothing when its1 >= 1; with its1 = 0 it computes none, and the gating below would read errors that were never
+  // computed (uninitialised memory: two runs of one problem disagree).  The oracle and asd_local_ba gate on these.
+  for (int k = 0; k < n_edges; ++k) vpEdgesMono[k]->computeError();
+  PostIteration post(solver);
+  ComputeErrors calls;
+  optimizer.addPostIterationAction(&post);
+  optimizer.addComputeErrorAction(&calls);
+  for (int r = 0; r < 2; ++r) { g_iters[r].clear(); g_calls[r].clear(); }
+  g_round = 0;
   optimizer.initializeOptimization();
   out->iters_first = optimizer.optimize(its1);
   out->chi2_first = optimizer.activeRobustChi2();  // from the edges' stored errors, nothing recomputed
@@ -133,8 +178,16 @@ extern "C" int ref_local_ba(int n_poses, int n_points, int n_edges, double* pose
     if (bad) e->setLevel(1);
     e->setRobustKernel(0);
   }
+  g_round = 1;
   optimizer.initializeOptimization(0);
   out->iters_second = optimizer.optimize(its2);
+  optimizer.removePostIterationAction(&post);
+  optimizer.removeComputeErrorAction(&calls);
+  int trials[2] = {0, 0};
+  for (int r = 0; r < 2; ++r)
+    for (const LmIter& it : g_iters[r]) trials[r] += (int)it.trials;
+  out->trials_first = trials[0];
+  out->trials_second = trials[1];
   for (int k = 0; k < n_edges; ++k) {
     g2o::EdgeSE3ProjectXYZ* e = vpEdgesMono[k];
     edge_chi2[k] = e->chi2();
@@ -147,5 +200,20 @@ extern "C" int ref_local_ba(int n_poses, int n_points, int n_edges, double* pose
     const Eigen::Vector3d& x = static_cast<g2o::VertexSBAPointXYZ*>(optimizer.vertex(l + maxKFid + 1))->estimate();
     points[3 * l] = x[0]; points[3 * l + 1] = x[1]; points[3 * l + 2] = x[2];
   }
+  return 0;
+}
+
+// the trace of the last ref_local_ba's round `round`: iters[n_iters][3] = {trials, lambda, chi2} per iteration, calls[n_calls] = the
+// compute-error action's readings (see g_calls).  With null buffers only the counts are returned.
+extern "C" int ref_local_ba_trace(int round, double* iters, int32_t* n_iters, double* calls, int32_t* n_calls) {
+  if (round < 0 || round > 1) return -1;
+  *n_iters = (int32_t)g_iters[round].size();
+  *n_calls = (int32_t)g_calls[round].size();
+  if (iters)
+    for (size_t i = 0; i < g_iters[round].size(); ++i) {
+      iters[3 * i] = g_iters[round][i].trials; iters[3 * i + 1] = g_iters[round][i].lambda; iters[3 * i + 2] = g_iters[round][i].chi2;
+    }
+  if (calls)
+    for (size_t i = 0; i < g_calls[round].size(); ++i) calls[i] = g_calls[round][i];
   return 0;
 }
