@@ -530,6 +530,15 @@ class AsdHip:
         self._chk(self.lib.asd_debug_local_ba_lm(self.ctx, _p(out)))
         return out
 
+    def pose_opt_debug(self):
+        """(store, rounds [4, 10] int32) of the last pose_optimize: store 2 compact LDS / 1 full LDS / 0 global; per round (state 0 ran /
+        1 not run as a repeat / -1 not reached, active edges, iterations, trials, passes, phase-2 passes, trials not positive
+        definite, nBad, ended on a rejected trial, iterations with a rejected trial followed by another) -- asd_debug_pose_opt"""
+        out = np.empty(41, np.int32)
+        self.lib.asd_debug_pose_opt.restype = C.c_int32
+        self._chk(self.lib.asd_debug_pose_opt(self.ctx, _p(out)))
+        return int(out[0]), out[1:].reshape(4, 10).copy()
+
     def match_project_keyframe(self, slot_cur, n_cur, valid, Xw, min_dist, max_dist, desc, kf_angle, occupied, Tcw, K, th, orb_dist,
                                check_ori=True):
         a = [_c(valid, np.uint8), _c(Xw, np.float32), _c(min_dist, np.float32), _c(max_dist, np.float32), _c(desc, np.float32),

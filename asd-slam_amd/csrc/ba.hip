@@ -198,6 +198,8 @@ struct PoseOptArgs {
 #define ASD_POSE_THREADS 512
 #endif
 constexpr int kPoseThreads = ASD_POSE_THREADS, kPoseWaves = kPoseThreads / 64;
+constexpr int kPoseTraceInts = ASD_POSE_OPT_DEBUG_INTS;   // store + 4 rounds x 10
+static_assert(kPoseTraceInts == 41, "pose_opt_body writes 1 + 4 x 10 values");
 struct PoseShared {
   Pose7 T, T0, Tbak, Teval;
   double H[36], b[6], x[6];
@@ -207,6 +209,8 @@ struct PoseShared {
   double pad_;  // sizeof % 16 == 0
   double lambda, ni, currentChi, iniChi, rho;
   int qmax, cont, ok, sys_valid, stop, npass;
+  int tr[8];  // TRACE form, per round: trials, phase-2 passes, trials not positive definite, iterations, active edges, ended on a rejected
+              // trial, iterations with a rejected trial that another iteration followed, -
   long long cyc[4];  // debug: edge loop, reduction, solve+oplus, LM bookkeeping
   long long wend[16], dbg[4];
 };
@@ -460,7 +464,9 @@ __device__ inline void pose_take_system(PoseShared& S) {  // thread 0: sums -> H
 // MODE (the EdgeStore form) is a template parameter, not a run-time switch: with a pointer that may be LDS or global the
 // compiler falls back to FLAT loads, whose latency dominated the edge loop.
 // (A = const PoseOptArgs: the kernel's argument segment)
-template <int MODE, class A>
+// TRACE: the form asd_pose_optimize launches, which reports what each round did (asd_debug_pose_opt).  A template parameter so that the
+// kernels of the fused chains hold none of its code.
+template <int MODE, bool TRACE, class A>
 __device__ __forceinline__ void pose_opt_body(A& a) {
   // (a = the kernel's argument block itself.  No private copy of it: a copy that is indexed at run time (pose0[t], isg_tab[t]) lives in
   // scratch memory, and every a.fx / a.n of the passes then is a scratch load)
@@ -583,9 +589,21 @@ __device__ __forceinline__ void pose_opt_body(A& a) {
     S.T0 = T0;
     S.T = T0;
   }
+  // Test aid (asd_debug_pose_opt): the store and ten numbers per round, by thread 0, behind the flags' 8-byte words.  Only the
+  // stand-alone call's kernels (TRACE) write it: the fused chains' io blocks have no room for it.
+  int32_t* const trc = TRACE ? reinterpret_cast<int32_t*>(a.io + 8 + (ne + 7) / 8) : nullptr;
+  if (trc && t == 0) {
+    trc[0] = MODE;
+    for (int q = 1; q < 41; ++q) trc[q] = -1;
+  }
   asd_syncthreads();
   bool robust = true;
   int nBad = 0;
+  auto put_round = [&](int round, int state) __attribute__((always_inline)) {   // thread 0
+    int32_t* r = trc + 1 + 10 * round;
+    r[0] = state; r[1] = S.tr[4]; r[2] = S.tr[3]; r[3] = S.tr[0]; r[4] = S.npass; r[5] = S.tr[1]; r[6] = S.tr[2]; r[7] = nBad;
+    r[8] = S.tr[5]; r[9] = S.tr[6];
+  };
   bool flags_changed = true;   // did the previous round's re-classification change any flag?
   for (int round = 0; round < 4; ++round) {
     // A round is a deterministic function of (input pose, active set, robust kernel on / off): it restarts from the input pose
@@ -594,13 +612,17 @@ __device__ __forceinline__ void pose_opt_body(A& a) {
     // the state they would leave is the state that is there.  (Typical steady-state frame: the outlier set is final after round 0 or 1.)
     const bool repeat = round >= 1 && round <= 2 && !flags_changed;
     if (!repeat) {
-    if (t == 0) { S.T = S.T0; S.npass = 0; for (int q = 0; q < 4; ++q) { S.cyc[q] = 0; S.dbg[q] = 0; } }  // every round restarts from the input pose (Optimizer.cc:337)
+    if (t == 0) {
+      S.T = S.T0; S.npass = 0; for (int q = 0; q < 4; ++q) { S.cyc[q] = 0; S.dbg[q] = 0; }
+      if (trc) for (int q = 0; q < 8; ++q) S.tr[q] = 0;
+    }  // every round restarts from the input pose (Optimizer.cc:337)
     asd_syncthreads();
     pose_pass(a, E, lvl, S, robust);
     asd_syncthreads();
     if (t < 64) pose_sums_wave0(S);
     asd_syncthreads();
     const bool any_active = S.sums[28] > 0.5;
+    if (trc && t == 0) S.tr[4] = (int)(S.sums[28] + 0.5);
     if (any_active) {
       // ---- g2o optimize(10): Levenberg (optimization_algorithm_levenberg.cpp:61-189) as a state machine run by thread 0 between
       // the passes.  Two barriers per pass: one publishes the pose the pass evaluates (and whether there is a pass at all), one
@@ -643,6 +665,7 @@ __device__ __forceinline__ void pose_opt_body(A& a) {
 #pragma unroll
         for (int r = 0; r < 6; ++r) S.x[r] = x[r];
         S.ok = ok ? 1 : 0;
+        if (trc) { S.tr[0]++; if (!ok) S.tr[2]++; }
         const long long c1 = a.debug ? clock64() : 0;
         if (ok) S.T = pose_oplus(S.T, x);
         S.cont = 1;
@@ -661,6 +684,7 @@ __device__ __forceinline__ void pose_opt_body(A& a) {
             const long long c0 = a.debug ? clock64() : 0;
             bool fresh_system = phase == 2;   // the pass was a plain evaluation at the current pose: start the next iteration from it
             bool over = false;
+            if (trc && phase == 2) S.tr[1]++;
             if (phase == 1) {
               double tempChi = S.sums[27];
               if (!S.ok) tempChi = 1.7976931348623157e308;
@@ -696,6 +720,11 @@ __device__ __forceinline__ void pose_opt_body(A& a) {
                 if (stop || it >= 10) over = true;
                 else if (accepted) fresh_system = true;
                 else { S.cont = 2; over = false; fresh_system = false; }   // next: a plain pass at the restored pose
+                if (trc) {
+                  S.tr[3] = it;
+                  if (over) S.tr[5] = accepted ? 0 : 1;
+                  else if (S.qmax > 1 || !accepted) S.tr[6]++;
+                }
                 if (!over && !accepted) { if (a.debug) S.cyc[3] += clock64() - c0; goto published; }
               }
             }
@@ -747,6 +776,9 @@ __device__ __forceinline__ void pose_opt_body(A& a) {
     if (a.debug && t == 0)
       printf("[pose_opt] round %d: %d passes, nBad %d; cycles/pass: edges %lld (slowest wave %lld) reduce %lld solve+oplus %lld (solve %lld) accept %lld\n", round, S.npass,
              nBad, S.cyc[0] / S.npass, S.dbg[0] / S.npass, S.cyc[1] / S.npass, S.cyc[2] / S.npass, S.dbg[1] / S.npass, S.cyc[3] / S.npass);
+    if (trc && t == 0) put_round(round, 0);
+    } else if (trc && t == 0) {
+      put_round(round, 1);
     }   // !repeat
     if (round == 2) robust = false;  // e->setRobustKernel(0)
     if (ne < 10) break;             // optimizer.edges().size() < 10
@@ -814,8 +846,8 @@ __device__ __forceinline__ void pose_opt_body(A& a) {
   }
 }
 
-template <int MODE>
-__global__ __launch_bounds__(kPoseThreads) void k_pose_opt(PoseOptArgs a_in) { pose_opt_body<MODE>(a_in); }
+template <int MODE, bool TRACE = false>
+__global__ __launch_bounds__(kPoseThreads) void k_pose_opt(PoseOptArgs a_in) { pose_opt_body<MODE, TRACE>(a_in); }
 
 // The claim replay and PoseOptimization of a tracking stage as ONE workgroup (asd_track_frame): resolve2_body on the solver's 512 threads,
 // then the solver (gather form: its edges come from the match table the replay has just written).  Stand-alone, k_pose_opt needs most of a
@@ -828,7 +860,7 @@ __global__ __launch_bounds__(kPoseThreads) void k_resolve_pose(Resolve2Args r, P
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   asd_syncthreads();
   __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-  pose_opt_body<2>(a_in);
+  pose_opt_body<2, false>(a_in);
 }
 
 // ---------------------------------------------------------------- fused tracking chains: edges made on the device
@@ -2067,6 +2099,8 @@ struct BaState {
   struct BaLane* lane = nullptr;   // asd_local_ba_submit / _wait: the optional LocalBA lane (own thread, stream and events)
   int forms[2][5] = {{-1, -1, -1, -1, -1}, {-1, -1, -1, -1, -1}};   // asd_debug_local_ba_forms: per round of the last LocalBA
   int lm_rounds[2][4] = {{-1, -1, -1, -1}, {-1, -1, -1, -1}};       // asd_debug_local_ba_lm: per round of the last LocalBA
+  int32_t po_trace[kPoseTraceInts];                                 // asd_debug_pose_opt: the last asd_pose_optimize (k_pose_opt's trc)
+  BaState() { for (int32_t& v : po_trace) v = -1; }
 };
 
 // OPTIONAL lane, not the reference's order.  This fork of ORB-SLAM2 has no mapping thread: Tracking::CreateNewKeyFrame calls
@@ -2228,11 +2262,15 @@ int asd_pose_optimize(asd_ctx* ctx, double* pose7, int32_t n, const double* Xw, 
   if (ctx && asd_track_busy(ctx, "asd_pose_optimize")) return ASD_ERR_INVALID;
   if (!ctx || !pose7 || n < 0 || !K || !n_inliers || (n > 0 && (!Xw || !obs || !inv_sigma2 || !outlier))) return ASD_ERR_INVALID;
   for (int i = 0; i < n; ++i) outlier[i] = 0;
-  if (n < 3) { *n_inliers = 0; return ASD_OK; }  // Optimizer.cc:323-324
+  if (n < 3) {  // Optimizer.cc:323-324
+    if (ctx->ba) for (int32_t& v : static_cast<BaState*>(ctx->ba)->po_trace) v = -1;
+    *n_inliers = 0;
+    return ASD_OK;
+  }
   (void)hipSetDevice(ctx->cfg.device);
   BaState* s = ba_state(ctx);
   int rc;
-  const size_t idx_off = (size_t)n * 48, in_bytes = idx_off + ((size_t)n + 63) / 64 * 64 + 64, io_bytes = 64 + (size_t)n + 64;
+  const size_t idx_off = (size_t)n * 48, in_bytes = idx_off + ((size_t)n + 63) / 64 * 64 + 64, trace_off = 64 + ((size_t)n + 7) / 8 * 8, io_bytes = trace_off + kPoseTraceInts * 4 + 64;   // io block: pose, nBad, flags, the test aid's trace
   if ((rc = s->po_Xw.ensure(ctx, in_bytes)) || (rc = s->po_err.ensure(ctx, (size_t)n * 64)) ||
       (rc = s->po_level.ensure(ctx, (size_t)2 * n)) || (rc = s->po_pose.ensure(ctx, io_bytes)))
     return rc;
@@ -2290,17 +2328,18 @@ int asd_pose_optimize(asd_ctx* ctx, double* pose7, int32_t n, const double* Xw, 
   a.debug = getenv("ASD_POSE_DEBUG") ? 1 : 0;
   static AsdPerDeviceOnce attr_set;
   if (attr_set.need(ctx->cfg.device)) {
-    ASD_HIP_CHECK(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(k_pose_opt<1>), hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024));
-    ASD_HIP_CHECK(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(k_pose_opt<2>), hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024));
+    ASD_HIP_CHECK(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(k_pose_opt<1, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024));
+    ASD_HIP_CHECK(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(k_pose_opt<2, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024));
     attr_set.done(ctx->cfg.device);
   }
   ASD_HIP_CHECK(ctx, hipEventRecord(ctx->ev0, st));
-  if (mode == 2) hipLaunchKernelGGL(k_pose_opt<2>, dim3(1), dim3(kPoseThreads), lds_compact, st, a);
-  else if (mode == 1) hipLaunchKernelGGL(k_pose_opt<1>, dim3(1), dim3(kPoseThreads), lds_full, st, a);
-  else hipLaunchKernelGGL(k_pose_opt<0>, dim3(1), dim3(kPoseThreads), 0, st, a);
+  // (the TRACE kernels: the only ones whose io block has room for the test aid's report)
+  if (mode == 2) hipLaunchKernelGGL((k_pose_opt<2, true>), dim3(1), dim3(kPoseThreads), lds_compact, st, a);
+  else if (mode == 1) hipLaunchKernelGGL((k_pose_opt<1, true>), dim3(1), dim3(kPoseThreads), lds_full, st, a);
+  else hipLaunchKernelGGL((k_pose_opt<0, true>), dim3(1), dim3(kPoseThreads), 0, st, a);
   ASD_HIP_CHECK(ctx, hipGetLastError());
   ASD_HIP_CHECK(ctx, hipEventRecord(ctx->ev1, st));
-  ASD_HIP_CHECK(ctx, hipMemcpyAsync(hio, s->po_pose.p, 64 + (size_t)n + 8, hipMemcpyDeviceToHost, st));
+  ASD_HIP_CHECK(ctx, hipMemcpyAsync(hio, s->po_pose.p, trace_off + kPoseTraceInts * 4, hipMemcpyDeviceToHost, st));
   auto tp2 = now();
   ASD_HIP_CHECK(ctx, hipStreamSynchronize(st));
   auto tp3 = now();
@@ -2315,6 +2354,7 @@ int asd_pose_optimize(asd_ctx* ctx, double* pose7, int32_t n, const double* Xw, 
   }
   memcpy(pose7, hio, 56);
   memcpy(outlier, hio + 8, n);
+  memcpy(s->po_trace, reinterpret_cast<const char*>(hio) + trace_off, sizeof(s->po_trace));
   *n_inliers = n - (int)(hio[7] + 0.5);
   return ASD_OK;
 }
@@ -2881,6 +2921,13 @@ int32_t asd_debug_local_ba_forms(const asd_ctx* ctx, int32_t out[2][5]) {
   const BaState* s = static_cast<const BaState*>(ctx->ba);
   for (int r = 0; r < 2; ++r)
     for (int k = 0; k < 5; ++k) out[r][k] = s ? s->forms[r][k] : -1;
+  return ASD_OK;
+}
+
+int32_t asd_debug_pose_opt(const asd_ctx* ctx, int32_t out[ASD_POSE_OPT_DEBUG_INTS]) {
+  if (!ctx || !out) return ASD_ERR_INVALID;
+  const BaState* s = static_cast<const BaState*>(ctx->ba);
+  for (int k = 0; k < kPoseTraceInts; ++k) out[k] = s ? s->po_trace[k] : -1;
   return ASD_OK;
 }
 

@@ -713,6 +713,19 @@ int32_t asd_debug_local_ba_forms(const asd_ctx* ctx, int32_t out[2][5]);
  * (the trials the same round of the context's previous LocalBA took, else its_first / its_second; 0 when no block ran)}.
  * Read from host-side bookkeeping: it adds no work to a run.  All -1 before any run, and for a round that did not start. */
 int32_t asd_debug_local_ba_lm(const asd_ctx* ctx, int32_t out[2][4]);
+/* Test aid: what the solver of the context's last asd_pose_optimize did.  out[0] = the edge store it took (2 = compact LDS,
+ * 1 = full f64 LDS, 0 = global memory; -1 for a call with fewer than 3 edges, which runs no solver), then ten values per round
+ * of Optimizer.cc:335-403, out[1 + 10 r + k]: {state: 0 = ran, 1 = not run because the previous re-classification changed no flag
+ * (the round would repeat the one before it), -1 = not reached (fewer than 10 edges); active edges; Levenberg iterations; trials
+ * (solves, accepted and rejected); passes over the edges; passes that re-evaluated the current pose after an iteration that ended
+ * on a rejected trial without ending the round; trials whose 6x6 system was not positive definite; nBad of the re-classification;
+ * 1 if the round ended on a rejected trial (the re-classification then reads the inliers' errors at the rejected pose);
+ * iterations that rejected a trial and were followed by another iteration}.  A round that was not run reports the numbers of the
+ * round it repeats; a round that was not reached reports -1 throughout.  Written by one thread of the stand-alone solver behind
+ * the outlier flags of the block the call copies back anyway; the fused tracking chains (asd_track_*) do not write it and do not
+ * change it.  All -1 before any run. */
+#define ASD_POSE_OPT_DEBUG_INTS 41
+int32_t asd_debug_pose_opt(const asd_ctx* ctx, int32_t out[ASD_POSE_OPT_DEBUG_INTS]);
 /* Runs `reps` back-to-back repetitions of the ASDNet forward on resident buffers and
  * returns the average per-repetition device time (hipEvents on the ctx stream). */
 int asd_describe_timed(asd_ctx* ctx, const uint8_t* d_patches, int32_t n, float* d_desc,

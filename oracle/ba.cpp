@@ -222,14 +222,25 @@ struct PoseProblem {
   }
 };
 
+// what oracle/ref_g2o/driver.cpp records of one round of g2o's PoseOptimization (orc_pose_optimize_trace)
+struct PoseTraceRound {
+  int active = 0, ret = 0, n_bad = 0, changed = 0, reinlier = 0, gate_edge = -1;
+  double pose[7] = {0, 0, 0, 0, 0, 0, 0}, gate_margin = 0;
+  std::vector<int> trials;     // per iteration
+  std::vector<double> calls;   // robust chi2 after every compute_active_errors
+};
+static thread_local PoseTraceRound g_ptrace[4];
+static thread_local int g_ptrace_rounds = 0;
+
 // one g2o optimize(iterations) call on the single-pose graph
-int pose_lm(PoseProblem& P, Pose& T, int iterations) {
+int pose_lm(PoseProblem& P, Pose& T, int iterations, PoseTraceRound* tr = nullptr) {
   double lambda = -1, ni = 2;
   int nBad = 0, done = 0;
   for (int it = 0; it < iterations; ++it) {
     P.compute_active_errors(T);
     double currentChi = P.active_robust_chi2(), tempChi = currentChi;
     const double iniChi = currentChi;
+    if (tr) tr->calls.push_back(currentChi);
     double H[36], b[6];
     P.build(T, H, b);
     if (it == 0) {
@@ -250,6 +261,7 @@ int pose_lm(PoseProblem& P, Pose& T, int iterations) {
       T = pose_oplus(T, x);
       P.compute_active_errors(T);
       tempChi = P.active_robust_chi2();
+      if (tr) tr->calls.push_back(tempChi);
       if (!ok2) tempChi = std::numeric_limits<double>::max();
       rho = currentChi - tempChi;
       double scale = 0;
@@ -271,6 +283,7 @@ int pose_lm(PoseProblem& P, Pose& T, int iterations) {
       qmax++;
     } while (rho < 0 && qmax < 10);
     ++done;
+    if (tr) tr->trials.push_back(qmax);
     if (qmax == 10 || rho == 0) break;
     if ((iniChi - currentChi) * 1e3 < iniChi) nBad++; else nBad = 0;
     if (nBad >= 3) break;
@@ -498,6 +511,7 @@ int orc_pose_optimize(double* pose7, int n, const double* Xw, const double* obs,
   // Optimizer.cc:239-413
   int nInitialCorrespondences = n;
   for (int i = 0; i < n; ++i) outlier[i] = 0;
+  g_ptrace_rounds = 0;
   if (nInitialCorrespondences < 3) return 0;
   PoseProblem P;
   P.n = n; P.Xw = Xw; P.obs = obs; P.info = inv_sigma2;
@@ -512,19 +526,44 @@ int orc_pose_optimize(double* pose7, int n, const double* Xw, const double* obs,
     T = T0;  // vSE3->setEstimate(Converter::toSE3Quat(pFrame->mTcw)) : every round restarts from the input pose
     int nact = 0;
     for (int i = 0; i < n; ++i) nact += !P.level[i];
-    if (nact > 0) pose_lm(P, T, 10);
+    PoseTraceRound& tr = g_ptrace[it];
+    tr = PoseTraceRound();
+    tr.active = nact;
+    tr.ret = nact > 0 ? pose_lm(P, T, 10, &tr) : -1;   // optimize(): -1 = no active vertex
+    pose_to7(T, tr.pose);
+    tr.gate_margin = 1e300;
     nBad = 0;
     for (int i = 0; i < n; i++) {
       if (outlier[i]) P.compute_error(T, i);
       const float chi2 = (float)P.chi2(i);
+      const double margin = std::fabs(P.chi2(i) - (double)kChi2Mono) / (double)kChi2Mono;
+      if (!(margin >= tr.gate_margin)) { tr.gate_margin = margin; tr.gate_edge = i; }
+      const uint8_t was = outlier[i];
       if (chi2 > kChi2Mono) { outlier[i] = 1; P.level[i] = 1; nBad++; }
       else { outlier[i] = 0; P.level[i] = 0; }
+      tr.changed += was != outlier[i];
+      tr.reinlier += was && !outlier[i];
     }
+    tr.n_bad = nBad;
+    g_ptrace_rounds = it + 1;
     if (it == 2) P.robust = false;  // e->setRobustKernel(0) on every edge
     if (n < 10) break;              // optimizer.edges().size() < 10
   }
   pose_to7(T, pose7);
   return nInitialCorrespondences - nBad;
+}
+
+int orc_pose_optimize_trace(int round, int32_t* hdr, double* misc, int32_t* trials, int32_t* n_iters, double* calls, int32_t* n_calls) {
+  if (round < 0 || round >= g_ptrace_rounds) return -1;
+  const PoseTraceRound& tr = g_ptrace[round];
+  hdr[0] = tr.active; hdr[1] = tr.ret; hdr[2] = tr.n_bad; hdr[3] = tr.changed; hdr[4] = tr.reinlier; hdr[5] = tr.gate_edge;
+  for (int q = 0; q < 7; ++q) misc[q] = tr.pose[q];
+  misc[7] = tr.gate_margin;
+  *n_iters = (int32_t)tr.trials.size();
+  for (size_t i = 0; i < tr.trials.size() && i < 10; ++i) trials[i] = tr.trials[i];
+  *n_calls = (int32_t)tr.calls.size();
+  for (size_t i = 0; i < tr.calls.size() && i < 110; ++i) calls[i] = tr.calls[i];
+  return g_ptrace_rounds;
 }
 
 int orc_local_ba(int n_poses, int n_points, int n_edges, double* poses, const uint8_t* fixed, double* points,

@@ -247,6 +247,10 @@ class Oracle:
         ninl = self.lib.orc_pose_optimize(_p(pose), Xw.shape[0], _p(Xw), _p(obs), _p(inv_sigma2), _p(K), _p(outlier))
         return pose, outlier, ninl
 
+    def pose_optimize_trace(self):
+        """per-round trace of this thread's last pose_optimize (see _pose_trace)"""
+        return _pose_trace(self.lib.orc_pose_optimize_trace)
+
     def local_ba(self, prob, its_first=5, its_second=10):
         poses = _c(prob["poses"], np.float64).copy()
         points = _c(prob["points"], np.float64).copy()
@@ -279,6 +283,23 @@ class Oracle:
         return T
 
 
+def _pose_trace(fn):
+    """rounds of the last pose_optimize (orc_pose_optimize_trace / ref_pose_optimize_trace): a list of dicts with active (edges at
+    initializeOptimization(0)), ret (what optimize(10) returned, -1 = no active vertex), n_bad, changed / reinlier (flags the
+    re-classification changed / of those outlier -> inlier), gate_edge and gate_margin (the edge nearest to the 5.991 gate and its
+    relative distance), pose (behind optimize()), trials (per iteration), calls (robust chi2 after every computeActiveErrors)"""
+    out = []
+    for r in range(4):
+        hdr, misc, trials, calls = np.zeros(6, np.int32), np.zeros(8, np.float64), np.zeros(10, np.int32), np.zeros(110, np.float64)
+        ni, nc = C.c_int32(), C.c_int32()
+        if fn(r, _p(hdr), _p(misc), _p(trials), C.byref(ni), _p(calls), C.byref(nc)) <= r:
+            break
+        out.append(dict(active=int(hdr[0]), ret=int(hdr[1]), n_bad=int(hdr[2]), changed=int(hdr[3]), reinlier=int(hdr[4]),
+                        gate_edge=int(hdr[5]), pose=misc[:7].copy(), gate_margin=float(misc[7]),
+                        trials=trials[:ni.value].tolist(), calls=calls[:nc.value].copy()))
+    return out
+
+
 def _bow_assemble(fn, word, weight, node, extra):
     word, node, weight = _c(word, np.int32), _c(node, np.int32), _c(weight, np.float64)
     n = len(word)
@@ -309,7 +330,7 @@ class RefDBoW2:
         return _bow_assemble(self.lib.ref_bow_assemble, word, weight, node, (int(weighting), int(scoring != 5), int(scoring == 1)))
 
 
-REF_G2O_ABI = 2   # oracle/ref_g2o/driver.cpp, ref_driver_abi
+REF_G2O_ABI = 3   # oracle/ref_g2o/driver.cpp, ref_driver_abi
 
 
 def ref_g2o_abi(lib):
@@ -324,7 +345,8 @@ class RefG2O:
     oracle/_ref/ is a build product that is never committed, so it can predate the driver of this tree (it is rebuilt where the
     reference's sources are present).  self.abi is the revision it was built from: local_ba reports trial counts and the Levenberg
     trace, and computes every edge error ahead of an its_first = 0 round, only from revision 2 on.  Callers that need those ask
-    available(abi=2); with its_first and its_second >= 1 every revision computes the same."""
+    available(abi=2); with its_first and its_second >= 1 every revision computes the same.  pose_optimize_trace needs revision 3;
+    pose_optimize itself is the same in every revision."""
 
     def __init__(self):
         path = os.path.join(_HERE, "_ref", "libg2o_ref.so")
@@ -345,6 +367,12 @@ class RefG2O:
         outlier = np.zeros(Xw.shape[0], np.uint8)
         ninl = self.lib.ref_pose_optimize(_p(pose), Xw.shape[0], _p(Xw), _p(obs), _p(inv_sigma2), _p(K), _p(outlier))
         return pose, outlier, ninl
+
+    def pose_optimize_trace(self):
+        """per-round trace of the last pose_optimize, from g2o's own actions (see _pose_trace); needs driver revision 3"""
+        if self.abi < 3:
+            raise RuntimeError("oracle/_ref/libg2o_ref.so predates ref_driver_abi 3: no ref_pose_optimize_trace")
+        return _pose_trace(self.lib.ref_pose_optimize_trace)
 
     def local_ba(self, prob, its_first=5, its_second=10):
         poses = _c(prob["poses"], np.float64).copy()

@@ -19,7 +19,8 @@ struct ref_ba_out { double chi2_first, chi2_second; int32_t iters_first, iters_s
 
 // Revision of this driver's entry points, read by oracle/pyoracle.py (RefG2O.abi).  A library built from an older driver has no
 // such symbol (revision 1): ref_local_ba without the trial counts, the trace or the edge errors computed ahead of an its1 = 0 round.
-extern "C" int ref_driver_abi() { return 2; }
+// Revision 2 has no ref_pose_optimize_trace.
+extern "C" int ref_driver_abi() { return 3; }
 
 // The Levenberg trace of the last ref_local_ba, per round (ref_local_ba_trace reads it):
 //  - per iteration, from a post-iteration action: the trials it took (levenbergIteration()), the lambda it left behind
@@ -33,19 +34,34 @@ static std::vector<LmIter> g_iters[2];
 static std::vector<double> g_calls[2];
 static int g_round = 0;
 
+// The same two actions trace ref_pose_optimize, per round of Optimizer.cc:335-403 (ref_pose_optimize_trace reads it), next to what the
+// driver itself sees between the rounds: the active edges after initializeOptimization(0), what optimize(10) returned, and the
+// re-classification's nBad, flag changes and distance from the 5.991 gate.
+struct PoseRound {
+  int active, ret, n_bad, changed, reinlier, gate_edge;
+  double pose[7], gate_margin;
+};
+static std::vector<LmIter> g_piters[4];
+static std::vector<double> g_pcalls[4];
+static PoseRound g_pround[4];
+static int g_prounds = 0;
+
 namespace {
 struct PostIteration : g2o::HyperGraphAction {
   g2o::OptimizationAlgorithmLevenberg* lm;
-  explicit PostIteration(g2o::OptimizationAlgorithmLevenberg* a) : lm(a) {}
+  std::vector<LmIter>* sink;   // [round]
+  PostIteration(g2o::OptimizationAlgorithmLevenberg* a, std::vector<LmIter>* s) : lm(a), sink(s) {}
   g2o::HyperGraphAction* operator()(const g2o::HyperGraph* graph, Parameters* = 0) {
     const g2o::SparseOptimizer* o = static_cast<const g2o::SparseOptimizer*>(graph);
-    g_iters[g_round].push_back(LmIter{(double)lm->levenbergIteration(), lm->currentLambda(), o->activeRobustChi2()});
+    sink[g_round].push_back(LmIter{(double)lm->levenbergIteration(), lm->currentLambda(), o->activeRobustChi2()});
     return this;
   }
 };
 struct ComputeErrors : g2o::HyperGraphAction {
+  std::vector<double>* sink;   // [round]
+  explicit ComputeErrors(std::vector<double>* s) : sink(s) {}
   g2o::HyperGraphAction* operator()(const g2o::HyperGraph* graph, Parameters* = 0) {
-    g_calls[g_round].push_back(static_cast<const g2o::SparseOptimizer*>(graph)->activeRobustChi2());
+    sink[g_round].push_back(static_cast<const g2o::SparseOptimizer*>(graph)->activeRobustChi2());
     return this;
   }
 };
@@ -92,28 +108,74 @@ extern "C" int ref_pose_optimize(double* pose7, int n, const double* Xw, const d
     optimizer.addEdge(e);
     vpEdgesMono.push_back(e);
   }
+  g_prounds = 0;
+  for (int r = 0; r < 4; ++r) { g_piters[r].clear(); g_pcalls[r].clear(); }
   if (nInitialCorrespondences < 3) return 0;
   const float chi2Mono[4] = {5.991, 5.991, 5.991, 5.991};
   const int its[4] = {10, 10, 10, 10};
   int nBad = 0;
+  PostIteration post(solver, g_piters);
+  ComputeErrors calls(g_pcalls);
+  optimizer.addPostIterationAction(&post);
+  optimizer.addComputeErrorAction(&calls);
   for (size_t it = 0; it < 4; it++) {
+    PoseRound& tr = g_pround[it];
+    g_round = (int)it;
     vSE3->setEstimate(T0);
     optimizer.initializeOptimization(0);
-    optimizer.optimize(its[it]);
+    tr.active = (int)optimizer.activeEdges().size();
+    tr.ret = optimizer.optimize(its[it]);
+    g_pcalls[it].push_back(optimizer.activeRobustChi2());   // closes the list: the chi2 the round's last computeActiveErrors left
+    to7(vSE3->estimate(), tr.pose);
+    tr.changed = tr.reinlier = 0;
+    tr.gate_margin = 1e300;
+    tr.gate_edge = -1;
     nBad = 0;
     for (size_t i = 0, iend = vpEdgesMono.size(); i < iend; i++) {
       g2o::EdgeSE3ProjectXYZOnlyPose* e = vpEdgesMono[i];
       if (outlier[i]) e->computeError();
       const float chi2 = e->chi2();
+      const double margin = std::fabs(e->chi2() - (double)chi2Mono[it]) / (double)chi2Mono[it];
+      if (!(margin >= tr.gate_margin)) { tr.gate_margin = margin; tr.gate_edge = (int)i; }   // (a NaN margin is kept: it fails every test)
+      const bool was = outlier[i];
       if (chi2 > chi2Mono[it]) { outlier[i] = true; e->setLevel(1); nBad++; }
       else { outlier[i] = false; e->setLevel(0); }
+      tr.changed += was != (bool)outlier[i];
+      tr.reinlier += was && !outlier[i];
       if (it == 2) e->setRobustKernel(0);
     }
+    tr.n_bad = nBad;
+    g_prounds = (int)it + 1;
     if (optimizer.edges().size() < 10) break;
   }
+  optimizer.removePostIterationAction(&post);
+  optimizer.removeComputeErrorAction(&calls);
   g2o::VertexSE3Expmap* vr = static_cast<g2o::VertexSE3Expmap*>(optimizer.vertex(0));
   to7(vr->estimate(), pose7);
   return nInitialCorrespondences - nBad;
+}
+
+// The trace of the last ref_pose_optimize's round `round`; returns the number of rounds it ran (0: fewer than 3 edges), -1 for a round
+// it did not run.  hdr[6] = {active edges at initializeOptimization(0), what optimize(10) returned (-1: no active vertex), nBad,
+// flags the re-classification changed, of those outlier -> inlier, the edge nearest to the 5.991 gate}; misc[8] = {the estimate
+// behind optimize(): 7, that edge's |chi2 - 5.991| / 5.991 as the re-classification read it}; trials[<= 10] per iteration
+// (levenbergIteration()); calls[n_calls <= 110]: activeRobustChi2 after each computeActiveErrors of the round, in order (an iteration
+// makes 1 + trials calls, levenberg.cpp:74, :119).  The compute-error action runs in front of the computation, so it reads what the
+// call before it stored: its first reading predates the round and is dropped, the reading behind optimize() closes the list.
+extern "C" int ref_pose_optimize_trace(int round, int32_t* hdr, double* misc, int32_t* trials, int32_t* n_iters, double* calls,
+                                       int32_t* n_calls) {
+  if (round < 0 || round >= g_prounds) return -1;
+  const PoseRound& tr = g_pround[round];
+  hdr[0] = tr.active; hdr[1] = tr.ret; hdr[2] = tr.n_bad; hdr[3] = tr.changed; hdr[4] = tr.reinlier; hdr[5] = tr.gate_edge;
+  for (int q = 0; q < 7; ++q) misc[q] = tr.pose[q];
+  misc[7] = tr.gate_margin;
+  *n_iters = (int32_t)g_piters[round].size();
+  for (size_t i = 0; i < g_piters[round].size() && i < 10; ++i) trials[i] = (int32_t)g_piters[round][i].trials;
+  const std::vector<double>& c = g_pcalls[round];
+  const size_t n = c.size() > 1 && tr.ret > 0 ? c.size() - 1 : 0;   // (a round without an active vertex computes nothing)
+  *n_calls = (int32_t)n;
+  for (size_t i = 0; i < n && i < 110; ++i) calls[i] = c[i + 1];
+  return g_prounds;
 }
 
 extern "C" int ref_local_ba(int n_poses, int n_points, int n_edges, double* poses, const uint8_t* fixed, double* points,
@@ -162,8 +224,8 @@ extern "C" int ref_local_ba(int n_poses, int n_points, int n_edges, double* pose
   // changes nothing when its1 >= 1; with its1 = 0 it computes none, and the gating below would read errors that were never
   // computed (uninitialised memory: two runs of one problem disagree).  The oracle and asd_local_ba gate on these.
   for (int k = 0; k < n_edges; ++k) vpEdgesMono[k]->computeError();
-  PostIteration post(solver);
-  ComputeErrors calls;
+  PostIteration post(solver, g_iters);
+  ComputeErrors calls(g_calls);
   optimizer.addPostIterationAction(&post);
   optimizer.addComputeErrorAction(&calls);
   for (int r = 0; r < 2; ++r) { g_iters[r].clear(); g_calls[r].clear(); }

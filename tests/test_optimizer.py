@@ -189,7 +189,8 @@ def test_hip_pose_optimization_storage_forms(hip, oracle, synth):
     (problems too large for LDS).  Inputs that are NOT f32-representable, or carry too many information values, must take
     the f64 forms and still match the oracle; sizes on both sides of the LDS limits."""
     rng = np.random.default_rng(5)
-    for n, seed, kind in ((1500, 41, "obs"), (1500, 42, "info"), (2300, 43, "obs"), (4300, 44, "compact"), (4500, 45, "obs")):
+    # (the store each case must take: 2 compact LDS, 1 full f64 LDS, 0 global memory -- reported by asd_debug_pose_opt)
+    for n, seed, kind, store in ((1500, 41, "obs", 1), (1500, 42, "info", 1), (2300, 43, "obs", 1), (4300, 44, "compact", 2), (4500, 45, "obs", 0)):
         pp = synth.pose_problem(n, seed=seed, outlier_frac=0.12)
         if kind == "obs":
             pp["obs"] = pp["obs"] + rng.uniform(-1e-9, 1e-9, pp["obs"].shape)     # no longer exact in f32
@@ -198,6 +199,7 @@ def test_hip_pose_optimization_storage_forms(hip, oracle, synth):
             pp["info"] = pp["info"] * (1.0 + 1e-3 * rng.integers(0, 40, pp["info"].shape))   # > 16 distinct values
             assert len(np.unique(pp["info"])) > 16
         got = hip.pose_optimize(pp["pose"], pp["Xw"], pp["obs"], pp["info"], pp["K"])
+        assert hip.pose_opt_debug()[0] == store, (n, kind, hip.pose_opt_debug()[0])
         exp = oracle.pose_optimize(pp["pose"], pp["Xw"], pp["obs"], pp["info"], pp["K"])
         np.testing.assert_allclose(got[0], exp[0], atol=POSE_ATOL, rtol=0)
         np.testing.assert_array_equal(got[1], exp[1])
