@@ -337,6 +337,16 @@ class AsdHip:
         self._chk(self.lib.asd_frame_set(self.ctx, slot, _p(kps), _p(d), len(kps), C.c_float(bounds[0]),
                                          C.c_float(bounds[1]), C.c_float(bounds[2]), C.c_float(bounds[3])))
 
+    def frame_set_from_ctx(self, slot, kps, bounds, src):
+        """asd_frame_set_from_ctx: asd_frame_set(desc == NULL) with the descriptors of `src`'s last extraction (the right frame of a stereo pair)"""
+        kps = _c(kps, KP_DTYPE)
+        self._chk(self.lib.asd_frame_set_from_ctx(self.ctx, slot, _p(kps), len(kps), C.c_float(bounds[0]), C.c_float(bounds[1]),
+                                                  C.c_float(bounds[2]), C.c_float(bounds[3]), src.ctx))
+
+    def extract_keep_pyramid(self, on=True):
+        """asd_extract_keep_pyramid: every submission keeps its own copy of its pyramid for asd_stereo_match"""
+        self._chk(self.lib.asd_extract_keep_pyramid(self.ctx, int(on)))
+
     def features_in_area(self, slot, x, y, r, min_level=-1, max_level=-1, cap=8192):
         out = np.empty(cap, np.int32)
         n = C.c_int32()

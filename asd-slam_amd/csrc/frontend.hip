@@ -1376,15 +1376,19 @@ extern "C" int asd_stereo_match(asd_ctx* ctx_left, asd_ctx* ctx_right, int32_t s
   const int N = FL.n, Nr = FR.n;
   *n_matched = 0;
   for (int i = 0; i < N; ++i) { u_right[i] = -1.0f; depth[i] = -1.0f; }
-  if (N == 0 || Nr == 0) return ASD_OK;
+  // (before the empty-frame return: a slot that was never set has n == 0 as well)
   if (!FL.d_kp || !FR.d_kp) { ctx->set_error("asd_stereo_match: frame slot not set"); return ASD_ERR_INVALID; }
+  if (N == 0 || Nr == 0) return ASD_OK;
   // the SAD windows are read from both contexts' pyramids: those must still hold the images the two frame slots came from -- either
   // the shared pyramids of two synchronous extractions (nothing submitted since), or the kept copies of the two submissions waited for
   // last (asd_extract_keep_pyramid: valid like that submission's descriptors, for two further submissions)
   const bool views = ctx_left->d_pyr_view && ctx_right->d_pyr_view;
-  if (!views && (asd_extractor_busy(ctx_left, "asd_stereo_match") || asd_extractor_busy(ctx_right, "asd_stereo_match"))) {
-    if (ctx != ctx_right) ctx->set_error("%s", ctx_right->last_error());
-    return ASD_ERR_INVALID;
+  if (!views) {
+    if (asd_extractor_busy(ctx_left, "asd_stereo_match")) return ASD_ERR_INVALID;
+    if (asd_extractor_busy(ctx_right, "asd_stereo_match")) {   // the message belongs on the context the caller asks for errors
+      if (ctx != ctx_right) ctx->set_error("%s", ctx_right->last_error());
+      return ASD_ERR_INVALID;
+    }
   }
   (void)hipSetDevice(ctx->cfg.device);
   // inside an asd_prep_async bracket (frame construction beside the tracking stages in flight) the call runs on the context's second

@@ -2,11 +2,16 @@
 // TEST INFRASTRUCTURE ONLY (see oracle.h).
 //
 // The function is dead code in the reference (no stereo Frame constructor survives), so there is nothing
-// to run it against: PARITY UNPINNED, restated from the source text.  Kept quirks: `thOrbDist` is an int that
-// truncates (TH_HIGH + TH_LOW) / 2 = 1.0 (:366); the row table is indexed with the truncated float row (:404); the SAD
-// values are exact integers in float; the parabola fit may produce NaN, which passes the [-1, 1] test (:491).
-// Guards added where the reference has undefined behaviour: row indices are clamped to the image, and an empty match
-// list skips the median filter (:519 reads vDistIdx[0]).
+// to run it against: PARITY UNPINNED, restated from the source text; tests/stereo_ref.py is a second, independent
+// statement in numpy and the two are compared bit for bit.  Kept quirks: `thOrbDist` is an int that truncates
+// (TH_HIGH + TH_LOW) / 2 = 1.0 (:366); the row table is indexed with the truncated float row (:404); the SAD values are
+// exact integers in float.  The parabola fit cannot produce NaN or leave [-1, 1]: past the bestincR test (:489) dist2 is
+// a strict first minimum, so dist1 > dist2, dist3 >= dist2, the denominator is positive and |deltaR| <= 0.5 (:499 is kept
+// as written and never taken).
+// Guards added where the reference has undefined behaviour or throws: row indices are clamped to the image; an 11 x 11
+// window that would leave the level image leaves the keypoint unmatched (the reference relies on cv::Mat::rowRange /
+// colRange throwing at :458 / :475) -- tested after the iniu / endu exit of :470, as the library does; an empty match
+// list skips the median filter (:522 reads vDistIdx[0]).
 #include <algorithm>
 #include <climits>
 #include <cmath>
@@ -85,7 +90,6 @@ extern "C" int orc_stereo_match(const orc_extractor* exL, const orc_extractor* e
           for (int dx = -w; dx <= w; ++dx) out[(dy + w) * 11 + dx + w] = (float)img[(size_t)(cy + dy) * P.w + cx + dx] - c * 1.0f;
       };
       float IL[121], IR[121];
-      patch(P.l, (int)scaleduL, (int)scaledvL, IL);
       float bestDistS = (float)INT_MAX;
       int bestincR = 0;
       const int L = 5;
@@ -93,6 +97,11 @@ extern "C" int orc_stereo_match(const orc_extractor* exL, const orc_extractor* e
       const float iniu = scaleduR0 + L - w;
       const float endu = scaleduR0 + L + w + 1;
       if (iniu < 0 || endu >= P.w) continue;
+      {  // the windows stay inside the level image: left [xl-5, xl+5] x [yl-5, yl+5], right [xr-10, xr+10] on the same rows
+        const int xl = (int)scaleduL, yl = (int)scaledvL, xr = (int)scaleduR0;
+        if (xl - w < 0 || xl + w >= P.w || yl - w < 0 || yl + w >= P.h || xr - L - w < 0 || xr + L + w >= P.w) continue;
+      }
+      patch(P.l, (int)scaleduL, (int)scaledvL, IL);
       for (int incR = -L; incR <= +L; incR++) {
         patch(P.r, (int)scaleduR0 + incR, (int)scaledvL, IR);
         double s = 0;

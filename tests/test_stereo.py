@@ -1,6 +1,10 @@
 """Frame::ComputeStereoMatches (Frame.cc:360-535): oracle sanity on CPU, HIP vs oracle on the GPU."""
+import ctypes as C
+
 import numpy as np
 import pytest
+
+from tests import stereo_ref as SR
 
 BOUNDS = (0.0, 1241.0, 0.0, 376.0)
 MB, FX = 0.54, 718.856
@@ -87,3 +91,602 @@ def test_stereo_match_argument_checks(pkg, synth):
     finally:
         L.close()
         R.close()
+
+
+# ---- every exit of Frame::ComputeStereoMatches against tests/stereo_ref.py ------------------------------------------------------
+# Three statements of one function are compared bit for bit: tests/stereo_ref.py (numpy, from Frame.cc:360-535), oracle/stereo.cpp
+# (C++) and k_stereo_match + the host code of asd_stereo_match (HIP).  The extractor keeps keypoints >= 16 px from every border of
+# their level, so on extracted keypoints most exits never fire; the C ABI takes any keypoint list (asd_frame_set), hence the crafted
+# lists below: real pyramids, hand-placed keypoints, hand-made descriptors.
+CW, CH = 640, 240                       # crafted scenes: small, eight levels down to 179 x 67
+SCENES = [(12, 2000, 1241, 376, MB, FX), (40, 1000, 1241, 376, MB, FX), (9, 2000, EUROC_W, EUROC_H, EUROC_MB, EUROC_FX)]
+# exits the crafted sets must reach; `delta_range` (:499) is excluded by name, with the NaN case: see test_crafted_sets_reach_every_exit
+CENSUS_ROWS = ("row_outside", "row_empty", "maxu_negative", "dist_threshold", "iniu_endu", "window_guard", "bestinc_edge",
+               "disparity_range", "clamped_0.01", "median_skipped", "tie", "median_removed", "rows_gt_64", "rows_gt_128", "matched")
+UNREACHABLE = ("delta_range",)
+
+
+def _fake_desc(p):
+    """the patches' own bytes as a stand-in descriptor (unit-normalised): all the association needs, and the naive oracle conv
+    would take minutes"""
+    d = p.reshape(len(p), -1)[:, ::8].astype(np.float32)
+    d -= d.mean(1, keepdims=True)
+    return (d / np.linalg.norm(d, axis=1, keepdims=True)).astype(np.float32)
+
+
+def _bits(a):
+    return np.ascontiguousarray(a, np.float32).view(np.uint32)
+
+
+class _Lists:
+    """left / right keypoint + descriptor lists under construction, and what each crafted left keypoint was built for"""
+
+    def __init__(self, scale, seed):
+        self.scale, self.rng = scale, np.random.default_rng(seed)
+        self.kl, self.dl, self.kr, self.dr = [], [], [], []
+        self.want_exit, self.want_iR, self.want_dist = {}, {}, {}
+
+    def unit(self):
+        g = self.rng.standard_normal(128)
+        return (g / np.linalg.norm(g)).astype(np.float32)      # against any other descriptor here: distance about 2, never < 1
+
+    def _kp(self, x, y, o):
+        return (np.float32(x), np.float32(y), np.float32(31.0) * self.scale[o], np.float32(0), np.float32(1), int(o))
+
+    def left(self, x, y, o, d=None, want=None, iR=None, dist=None):
+        self.kl.append(self._kp(x, y, o)); self.dl.append(self.unit() if d is None else d)
+        i = len(self.kl) - 1
+        if want is not None: self.want_exit[i] = (want,) if isinstance(want, str) else tuple(want)
+        if iR is not None: self.want_iR[i] = iR
+        if dist is not None: self.want_dist[i] = np.float32(dist)
+        return i
+
+    def right(self, x, y, o, d=None):
+        self.kr.append(self._kp(x, y, o)); self.dr.append(self.unit() if d is None else d)
+        return len(self.kr) - 1
+
+    def pair(self, xl, y, o, xr, o_r=None, y_r=None, want=None, check_iR=True):
+        """a left and a right keypoint that share a descriptor of their own (distance 0)"""
+        g = self.unit()
+        iR = self.right(xr, y if y_r is None else y_r, o if o_r is None else o_r, g)
+        return self.left(xl, y, o, g, want=want, iR=iR if check_iR else None), iR
+
+    def finish(self, kps_dtype, real_l=None, real_r=None, keep_r=None):
+        """crafted keypoints first (their indices stay what the builder returned), the extracted ones behind them"""
+        def cat(craft, d, real):
+            k = np.array(craft, kps_dtype) if craft else np.zeros(0, kps_dtype)
+            d = np.array(d, np.float32).reshape(len(k), 128)
+            if real is not None:
+                k, d = np.concatenate([k, real[0].astype(kps_dtype)]), np.concatenate([d, real[1].astype(np.float32)])
+            return np.ascontiguousarray(k), np.ascontiguousarray(d)
+        if real_r is not None and keep_r is not None:
+            real_r = (real_r[0][keep_r], real_r[1][keep_r])
+        return cat(self.kl, self.dl, real_l) + cat(self.kr, self.dr, real_r)
+
+
+def _level_sizes(pyr):
+    return [(im.shape[1], im.shape[0]) for im in pyr]
+
+
+def _craft_main(real_l, real_r, pyr, scale, disparity=12):
+    """Keypoint lists on a constant-disparity pair that reach every exit but the uR gate, the 0.01 clamp (sets of their own below)
+    and `no match at all`.  Crafted pairs carry a descriptor of their own, so which right keypoint each left one meets is decided
+    here; the SAD slide then runs on the real level images.  Right list: two crowded rows first (a right keypoint's position inside
+    a row of the table is its position among the list entries covering that row), other crafted entries, then the extracted ones."""
+    w, h = CW, CH
+    B = _Lists(scale, seed=7)
+    dt = real_l[0].dtype
+    sizes = _level_sizes(pyr)
+    rowA, rowB, band = 60, 150, (118, 124)          # > 128 candidates, > 64 candidates, no candidate at all
+    # -- first-minimum rule (:438 strict `<` in candidate order): identical right descriptors at two and three positions of one row;
+    # one wave lane takes positions lane, lane + 64, lane + 128 of the row, so the equal minima sit in different lanes (5 | 70),
+    # in one lane at different strides (10 | 74 | 138), in a later lane at an earlier stride (37 | 100).  The lowest position must win.
+    ties = []
+    for row, n_row, groups in ((rowA, 150, ((5, 70), (10, 74, 138), (20, 85, 149), (37, 100))), (rowB, 80, ((3, 67), (10, 40, 79)))):
+        base = len(B.kr)
+        slot = {p: (gi, k) for gi, grp in enumerate(groups) for k, p in enumerate(grp)}
+        gdesc = [B.unit() for _ in groups]
+        xL = [200.0 + 70.0 * gi for gi in range(len(groups))]
+        for p in range(n_row):
+            if p in slot:
+                gi, k = slot[p]
+                # entry k of a group: the true correspondence for even groups' first entry, 40 px steps away otherwise, so that a
+                # wrong winner gives another u_right
+                off = disparity + 40.0 * (k if gi % 2 == 0 else len(groups[gi]) - 1 - k)
+                B.right(xL[gi] - off, row, 0, gdesc[gi])
+            else:
+                B.right(8.0 + p * (w - 16.0) / n_row, row, 0)
+        for gi, grp in enumerate(groups):
+            ties.append(B.left(xL[gi], row, 0, gdesc[gi], iR=base + grp[0]))
+    # -- row outside the image: (int)vL outside [0, nRows); -0.5 and h - 0.5 truncate to rows inside and go on to the window guard
+    for y in (-3.5, -1.0, h, h + 2, h + 100):
+        B.left(300.0, y, 0, want="row_outside")
+    B.pair(300.0, -0.5, 0, 300.0 - disparity, y_r=1.0, want="window_guard")
+    B.pair(300.0, h - 0.5, 0, 300.0 - disparity, y_r=h - 2.0, want="window_guard")
+    # -- row with no candidates: every right keypoint whose rows touch the band is dropped
+    r_real = np.float32(2.0) * scale[real_r[0]["octave"]]
+    keep_r = ~((np.ceil(real_r[0]["y"] + r_real) >= band[0]) & (np.floor(real_r[0]["y"] - r_real) <= band[1]))
+    for y in (band[0] + 0.3, 121.0, band[1] + 0.9):
+        B.left(310.0, y, 0, want="row_empty")
+    # -- maxU < 0
+    for y in (rowA, rowB, 200.0, 90.0, 170.0):
+        B.pair(-0.5, y, 0, -0.5 - disparity, want="maxu_negative", check_iR=False)
+    # -- thOrbDist: `bestDist < 1`.  Non-unit descriptors that differ in component 0 alone: the f32 sum is that one square, exact
+    for k in range(3):
+        g = B.unit(); g[0] = 0
+        a = g.copy(); a[0] = 1.0                                 # distance exactly 1.0: refused
+        B.right(250.0 + 30 * k - disparity, 90.0, 0, g)
+        B.left(250.0 + 30 * k, 90.0, 0, a, want="dist_threshold", dist=1.0)
+        g = B.unit(); g[0] = 0
+        a = g.copy(); a[0] = np.float32(1.0 - 2.0 ** -12)        # (1 - 2^-12)^2 = 1 - 2^-11 + 2^-24, an f32 below 1: accepted
+        iR = B.right(250.0 + 30 * k - disparity, 100.0, 0, g)
+        B.left(250.0 + 30 * k, 100.0, 0, a, want=("matched", "median_removed"), iR=iR, dist=np.float32(a[0]) * np.float32(a[0]))
+    # -- octave window (:428): the nearest descriptor two levels away is refused, a farther one a level away is accepted
+    for k, (oL, far, near) in enumerate(((2, 4, 3), (3, 1, 2), (4, 6, 5), (2, 0, 1), (5, 7, 4))):
+        x, y = 180.0 + 60 * k, 170.0
+        g = B.unit()
+        gn = g.copy(); gn[1] += np.float32(0.1)
+        B.right(x - disparity, y, far, g)
+        iR = B.right(x - disparity, y, near, gn)
+        B.left(x, y, oL, g, iR=iR)
+        g = B.unit()                                             # ... and with nothing else on offer the keypoint stays unmatched
+        B.right(x - disparity, y + 12.0, far, g)
+        B.left(x, y + 12.0, oL, g, want="dist_threshold", dist=1.5)
+    # -- iniu / endu (:470): right keypoints at the right border of their level, and left of x = 0
+    for o in (0, 2, 5, 7):
+        uR = (sizes[o][0] - 8.0) * float(scale[o])
+        B.pair(uR + 1.0, 20.0 + 10 * o, o, uR, want="iniu_endu")
+    for k in range(2):
+        B.pair(5.0, 40.0 + 8 * k, 0, -3.0, want="iniu_endu")
+    # -- window rule: left keypoints within 5 px of the four borders of their level, right ones within 10 px of the left border
+    for o in (0, 3, 5):
+        s = float(scale[o])
+        B.pair(3.0 * s, 75.0 + 5 * o, o, 2.0 * s, want="window_guard")                   # left border (the right window leaves too)
+        B.pair(40.0 * s, 80.0 + 5 * o, o, 6.0 * s, want="window_guard")                  # the right windows alone
+    for o in (0, 4, 6):
+        s = float(scale[o])
+        B.pair((sizes[o][0] - 3.0) * s, 30.0 + 5 * o, o, (sizes[o][0] - 30.0) * s, want="window_guard")   # right border
+    for o in (1, 4, 7):
+        s = float(scale[o])
+        B.pair(300.0, 3.0 * s, o, 300.0 - disparity, want="window_guard")                # top
+        B.pair(330.0, min((sizes[o][1] - 3.0) * s, h - 1.5), o, 330.0 - disparity, want="window_guard")   # bottom
+    # the last position inside, and the first outside, at level 0 (the windows end on the image's last row / column)
+    B.pair(340.0, 5.0, 0, 340.0 - disparity, want=("matched", "median_removed"))
+    B.pair(340.0, 4.4, 0, 340.0 - disparity, want="window_guard")
+    B.pair(360.0, h - 6.0, 0, 360.0 - disparity, want=("matched", "median_removed"))
+    B.pair(360.0, h - 5.0, 0, 360.0 - disparity, want="window_guard")
+    B.pair(w - 6.0, 190.0, 0, w - 6.0 - disparity, want=("matched", "median_removed"))
+    B.pair(w - 5.0, 196.0, 0, w - 5.0 - disparity, want="window_guard")
+    B.pair(10.0 + disparity, 190.0, 0, 10.0, want=("matched", "median_removed"))
+    B.pair(9.0 + disparity, 196.0, 0, 9.0, want="window_guard")
+    # -- bestincR == +-5 (:489): a true correspondence whose uR0 is 5 level pixels off; at level 0 the true window has SAD 0
+    for k, off in enumerate((5, -5, 5, -5)):
+        B.pair(420.0 + 25 * k, 205.0, 0, 420.0 + 25 * k - disparity + off, want="bestinc_edge")
+    for k, (o, off) in enumerate(((2, 6), (3, -6), (4, 5))):
+        B.pair(200.0 + 60 * k, 215.0, o, 200.0 + 60 * k - disparity + off * float(scale[o]))
+    out = B.finish(dt, real_l, real_r, keep_r)
+    return out, B, ties
+
+
+def _craft_gate(real_l, real_r, scale, disparity, maxD):
+    """the inclusive gate uL - maxD <= uR <= uL (:433) on a pair whose disparity lies just inside maxD, so that an accepted right
+    keypoint goes on to a match and a refused one leaves -1: the gate shows in u_right, not only in the reference's best_iR"""
+    B = _Lists(scale, seed=11)
+    maxD = np.float32(maxD)
+    for k in range(4):
+        uL = np.float32(150.0 + 90 * k)
+        B.pair(uL, 50.0, 0, uL - maxD, want=("matched", "median_removed"))                                  # uR == uL - maxD
+        B.pair(uL, 80.0, 0, np.nextafter(uL - maxD, np.float32(-np.inf)), want="dist_threshold", check_iR=False)
+        B.pair(uL, 110.0, 0, uL, want=("matched", "median_removed"))                                        # uR == uL
+        B.pair(uL, 140.0, 0, np.nextafter(uL, np.float32(np.inf)), want="dist_threshold", check_iR=False)   # just above
+    return B.finish(real_l[0].dtype, real_l, real_r), B
+
+
+SYM_COLS, SYM_ROWS = (60, 120, 180, 240), (30, 55, 80, 105)
+
+
+def _symmetric(img):
+    """columns mirrored about the hand-placed keypoint columns: there SAD(-1) == SAD(+1), the parabola's deltaR is exactly 0"""
+    img = img.copy()
+    for c in SYM_COLS:
+        for k in range(1, 21):
+            img[:, c + k] = img[:, c - k]
+    return img
+
+
+def _craft_identical(scale, with_bottom, disparity=12):
+    """left == right (where with_bottom: in the upper half only; below it the right image is shifted and noisy).  Keypoints on the
+    mirror columns meet themselves with disparity exactly 0 (-> 0.01, :509-513); the others get a slightly negative disparity
+    (refused, :507) or a tiny positive one."""
+    B = _Lists(scale, seed=13)
+    sym = []
+    for c in SYM_COLS:
+        for y in SYM_ROWS:
+            sym.append(B.pair(float(c), float(y), 0, float(c))[0])
+    for k in range(24):
+        x, y = 30.0 + 11.0 * k, 20.0 + 4.0 * k
+        if min(abs(x - c) for c in SYM_COLS) > 27:
+            B.pair(x, y, 0, x)
+    if with_bottom:
+        for k in range(60):
+            x, y = 40.0 + 4.0 * k, 135.0 + (k % 10) * 10.0
+            B.pair(x, y, 0, x - disparity)
+    return B.finish(_kp_dtype()), B, sym
+
+
+def _kp_dtype():
+    return np.dtype([("x", np.float32), ("y", np.float32), ("size", np.float32), ("angle", np.float32), ("response", np.float32),
+                     ("octave", np.int32)])
+
+
+def _two_disparity_pair(synth, d_top=12, d_bottom=30, w=CW, h=CH, seed_t=2):
+    wide = synth.scene_frame(seed_t, w=w + 96, h=h)
+    left = np.ascontiguousarray(wide[:, 32:32 + w])
+    right = np.ascontiguousarray(np.concatenate([wide[:h // 2, 32 + d_top:32 + d_top + w], wide[h // 2:, 32 + d_bottom:32 + d_bottom + w]]))
+    return left, right
+
+
+def _identical_images(synth, with_bottom, disparity=12, w=320, h=CH):
+    wide = synth.scene_frame(4, w=w + 96, h=h)
+    left = _symmetric(np.ascontiguousarray(wide[:, 32:32 + w]))
+    right = left.copy()
+    if with_bottom:
+        noise = np.random.default_rng(5).integers(-3, 4, (h - h // 2, w))
+        right[h // 2:] = np.clip(wide[h // 2:, 32 + disparity:32 + disparity + w].astype(np.int64) + noise, 0, 255).astype(np.uint8)
+    return left, right
+
+
+CRAFTED = ("main", "gate", "identical", "identical_top", "nomatch_desc", "nomatch_rows_outside", "nomatch_rows_disjoint", "two_disparity")
+
+
+def _crafted_set(name, synth, extract):
+    """-> dict(left, right images, kl, dl, kr, dr, mb, mbf, plus what the set was built for).  `extract(side, image)` returns that
+    image's extracted keypoints and descriptors and leaves its pyramid in the side's extractor (oracle or HIP context)."""
+    S = dict(name=name, mb=MB, mbf=MBF, nfeat=1000)
+    if name in ("identical", "identical_top"):
+        S["left"], S["right"] = _identical_images(synth, name == "identical_top")
+    elif name == "two_disparity":
+        S["left"], S["right"] = _two_disparity_pair(synth)
+    elif name == "gate":
+        S["left"], S["right"] = _stereo_pair(synth, 3, seed_t=3, w=CW, h=CH)
+        S["mb"], S["mbf"] = 0.5, 1.7                        # maxD = f32(1.7) / f32(0.5), about 3.4 px
+    else:
+        S["left"], S["right"] = _stereo_pair(synth, 12, seed_t=1, w=CW, h=CH)
+    real_l, real_r, pyr, scale = extract(S["left"], S["right"])
+    S["scale"] = scale
+    if name == "main":
+        (S["kl"], S["dl"], S["kr"], S["dr"]), S["B"], S["ties"] = _craft_main(real_l, real_r, pyr, scale)
+    elif name == "gate":
+        (S["kl"], S["dl"], S["kr"], S["dr"]), S["B"] = _craft_gate(real_l, real_r, scale, 3, np.float32(S["mbf"]) / np.float32(S["mb"]))
+    elif name in ("identical", "identical_top"):
+        (S["kl"], S["dl"], S["kr"], S["dr"]), S["B"], S["sym"] = _craft_identical(scale, name == "identical_top")
+    else:
+        kl, dl, kr, dr = real_l[0].copy(), real_l[1].copy(), real_r[0].copy(), real_r[1].copy()
+        if name == "nomatch_desc":                            # every distance >= 1
+            dl, dr = synth.unit_descriptors(len(kl), seed=21), synth.unit_descriptors(len(kr), seed=22)
+        elif name == "nomatch_rows_outside":
+            kl["y"] += np.float32(CH)
+        elif name == "nomatch_rows_disjoint":
+            kl, dl = kl[kl["y"] > 100], dl[kl["y"] > 100]
+            kr, dr = kr[kr["y"] < 80], dr[kr["y"] < 80]
+        S["kl"], S["dl"], S["kr"], S["dr"] = kl, dl, kr, dr
+    return S
+
+
+def _check_set(S, res):
+    """what the builder placed, against what the reference reports for it"""
+    names = np.array(SR.EXITS)[res["exit"]]
+    B = S.get("B")
+    if B is not None:
+        for i, want in B.want_exit.items():
+            assert names[i] in want, f"{S['name']}: left keypoint {i} at ({S['kl']['x'][i]}, {S['kl']['y'][i]}) level {S['kl']['octave'][i]}: {names[i]}, built for {want}"
+        for i, iR in B.want_iR.items():
+            assert res["best_iR"][i] == iR, f"{S['name']}: left keypoint {i} met right keypoint {res['best_iR'][i]} ({names[i]}), built to meet {iR}"
+        for i, d in B.want_dist.items():
+            assert res["best_dist"][i] == d, (S["name"], i, res["best_dist"][i], d)
+    if S["name"] == "main":
+        assert res["tie"][S["ties"]].all() and (res["n_cand"][S["ties"][:4]] > 128).all() and (res["n_cand"][S["ties"][4:]] > 64).all()
+    if S["name"] in ("identical", "identical_top"):
+        sym = np.array(S["sym"])
+        assert res["clamped"][sym].all() and (res["deltaR"][sym] == 0).all() and (res["sad"][sym] == 0).all()
+        if S["name"] == "identical":                          # median SAD 0: 1.5 * 1.4 * 0 = 0 and nothing is < 0 -- everything is removed
+            assert res["n_matched"] == 0 and (res["u_right"] == -1).all() and (names[sym] == "median_removed").all()
+        else:                                                 # median SAD > 0: mvuRight = uL - 0.01 (in double, stored as float), mvDepth = mbf / 0.01f
+            assert (names[sym] == "matched").all()
+            np.testing.assert_array_equal(res["u_right"][sym], (S["kl"]["x"][sym].astype(np.float64) - 0.01).astype(np.float32))
+            assert (res["depth"][sym] == np.float32(S["mbf"]) / np.float32(0.01)).all()
+    if S["name"].startswith("nomatch"):
+        assert res["median_skipped"] and res["n_matched"] == 0 and (res["u_right"] == -1).all() and (res["depth"] == -1).all()
+    if S["name"] == "two_disparity":
+        ok = res["u_right"] >= 0
+        disp = S["kl"]["x"] - res["u_right"]
+        top, bottom = ok & (S["kl"]["y"] < CH // 2 - 24), ok & (S["kl"]["y"] > CH // 2 + 24)
+        assert top.sum() > 50 and bottom.sum() > 50
+        assert np.abs(np.median(disp[top]) - 12) < 0.3 and np.abs(np.median(disp[bottom]) - 30) < 0.3
+    reached = res["exit"] > SR.EXIT["bestinc_edge"]
+    assert np.isfinite(res["deltaR"][reached]).all() and (np.abs(res["deltaR"][reached]) <= 0.5).all()
+    assert not reached.any() or not (names == "delta_range").any()
+
+
+def _oracle_extract(oracle, nfeat, stand_in=True):
+    exl, exr = oracle.extractor(nfeat), oracle.extractor(nfeat)
+
+    def extract(left, right):
+        kl, pl = exl.extract(left, want_patches=stand_in)
+        kr, pr = exr.extract(right, want_patches=stand_in)
+        t = exl.tables()
+        pyr = [exl.level_image(l) for l in range(8)]
+        return (kl, _fake_desc(pl) if stand_in else None), (kr, _fake_desc(pr) if stand_in else None), pyr, t["scale"]
+    return exl, exr, extract
+
+
+def _ref_and_oracle(S, exl, exr):
+    t = exl.tables()
+    pyr_l, pyr_r = [exl.level_image(l) for l in range(8)], [exr.level_image(l) for l in range(8)]
+    res = SR.stereo_match(S["kl"], S["dl"], S["kr"], S["dr"], pyr_l, pyr_r, t["scale"], t["inv_scale"], S["mb"], S["mbf"])
+    eu, ez, en = exl.stereo_match(exr, S["kl"], S["dl"], S["kr"], S["dr"], S["mb"], S["mbf"])
+    np.testing.assert_array_equal(_bits(res["u_right"]), _bits(eu), err_msg=f"{S['name']}: mvuRight, numpy reference vs oracle")
+    np.testing.assert_array_equal(_bits(res["depth"]), _bits(ez), err_msg=f"{S['name']}: mvDepth, numpy reference vs oracle")
+    assert res["n_matched"] == en == int((eu >= 0).sum())
+    return res, (eu, ez, en)
+
+
+@pytest.fixture(scope="module")
+def crafted_cpu(oracle, synth):
+    """every crafted set on the oracle's pyramids with stand-in descriptors: (set, reference result), reference == oracle checked"""
+    out = {}
+    for name in CRAFTED:
+        exl, exr, extract = _oracle_extract(oracle, 1000)
+        S = _crafted_set(name, synth, extract)
+        out[name] = (S, _ref_and_oracle(S, exl, exr)[0])
+    return out
+
+
+@pytest.mark.parametrize("name", CRAFTED)
+def test_reference_equals_oracle_on_crafted_sets(crafted_cpu, name):
+    """numpy reference == oracle bit for bit (in the fixture), and every crafted keypoint leaves where it was built to leave"""
+    S, res = crafted_cpu[name]
+    _check_set(S, res)
+
+
+@pytest.mark.parametrize("disparity,nfeat,w,h,mb,fx", SCENES)
+def test_reference_equals_oracle_on_extracted_scenes(oracle, synth, disparity, nfeat, w, h, mb, fx):
+    """the three scenes of test_stereo_match_parity, stand-in descriptors: bit equality, |deltaR| <= 0.5, and they keep reaching
+    `matched` and the median filter's removal"""
+    left, right = _stereo_pair(synth, disparity, seed_t=1, w=w, h=h)
+    exl, exr, extract = _oracle_extract(oracle, nfeat)
+    (kl, dl), (kr, dr), _, _ = extract(left, right)
+    S = dict(name=f"scene{disparity}", kl=kl, dl=dl, kr=kr, dr=dr, mb=mb, mbf=mb * fx)
+    res, _ = _ref_and_oracle(S, exl, exr)
+    _check_set(S, res)
+    c = SR.census(res)
+    print(S["name"], c)
+    assert c["matched"] > 0.3 * len(kl) and c["median_removed"] > 0
+    ok = res["u_right"] >= 0
+    assert np.abs(np.median(kl["x"][ok] - res["u_right"][ok]) - disparity) < 0.3
+
+
+def test_crafted_sets_reach_every_exit(crafted_cpu):
+    """A condition, not a measurement: over the crafted sets the reference reports every exit and property of the coverage table at
+    least 3 times (`no match at all` is a property of a set: three sets).
+
+    Excluded by name: `delta_range` (:499, deltaR < -1 || deltaR > 1) and the NaN fit.  Past `bestincR == +-5` (:489) dist2 is the
+    strict first minimum of the eleven SAD values, so dist1 > dist2 and dist3 >= dist2.  SAD values are integers <= 121 * 510, exact
+    in f32 like their sums and differences here, so dist1 + dist3 - 2 dist2 > 0 and |dist1 - dist3| <= dist1 + dist3 - 2 dist2:
+    |deltaR| <= 0.5, the exit cannot be taken and the quotient is never 0 / 0.  _check_set asserts the bound on every set.
+
+    Counts per left keypoint with stand-in descriptors (real descriptors move the counts of the extracted keypoints a little):
+
+    exit / property                  main  gate  identical  identical_top  nomatch x 3     two_disparity  total
+    row outside image                   5     0          0              0  0 / 1008 / 0                0   1013
+    row with no candidates             65     0          0              0  0 / 0 / 630                 0    695
+    maxU < 0                            5     0          0              0  0                           0      5
+    best distance >= 1                228   324          0              0  1008 / 0 / 0              257   1817
+    iniu < 0 || endu >= cols            6     0          0              0  0                           0      6
+    window rule                        21     0          0              0  0                           0     21
+    bestincR == +-5                    26     0          0              6  0                          16     48
+    disparity outside [0, maxD)         1    86          3              3  0                           1     94
+    disparity <= 0 -> 0.01              0     0         16             16  0                           0     32
+    no match at all (per set)           0     0          0              0  1 / 1 / 1                   0      3
+    equal minimum distances             6     0          0              0  0                           0      6
+    removed by median filter          187   102         17             23  0                         238    567
+    rows with > 64 candidates         314   326          0              0  297 / 0 / 0               291   1228
+    rows with > 128 candidates         51     0          0              0  0                           0     51
+    matched                           537   512          0             48  0                         496   1593"""
+    total = {}
+    for name in CRAFTED:
+        c = SR.census(crafted_cpu[name][1])
+        print(f"{name:22s}", {k: v for k, v in c.items() if v})
+        for k, v in c.items():
+            total[k] = total.get(k, 0) + v
+    print("total".ljust(22), total)
+    assert set(CENSUS_ROWS) | set(UNREACHABLE) == set(total)
+    for row in CENSUS_ROWS:
+        assert total[row] >= 3, f"{row}: reached {total[row]} times"
+    for row in UNREACHABLE:
+        assert total[row] == 0
+
+
+# ---- HIP == numpy reference == oracle on the crafted sets ------------------------------------------------------------------------
+def _contexts(pkg, synth, w, h, nfeat=1000):
+    L = pkg.AsdHip(n_features=nfeat, max_width=w, max_height=h, max_patches=4096)
+    R = pkg.AsdHip(n_features=nfeat, max_width=w, max_height=h, max_patches=4096)
+    layers = synth.asdnet_weights(0)
+    L.load_weights(layers)
+    R.load_weights(layers)
+    return L, R
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("name", CRAFTED)
+def test_stereo_match_crafted_sets(pkg, oracle, synth, name):
+    """the crafted lists through asd_frame_set: HIP == numpy reference == oracle, u_right and depth as bit patterns, n_matched"""
+    L = R = None
+    try:
+        exl, exr, oextract = _oracle_extract(oracle, 1000, stand_in=False)
+
+        def extract(left, right):
+            nonlocal L, R
+            h, w = left.shape
+            L, R = _contexts(pkg, synth, w, h)
+            kl, dl = L.extract(left)
+            kr, dr = R.extract(right)
+            (okl, _), (okr, _), opyr, scale = oextract(left, right)
+            # the front ends agree first (keypoints and both pyramids), so that a difference below is the association's own
+            np.testing.assert_array_equal(okl, kl)
+            np.testing.assert_array_equal(okr, kr)
+            for l in range(8):
+                np.testing.assert_array_equal(L.level_image(l), exl.level_image(l), err_msg=f"left level {l}")
+                np.testing.assert_array_equal(R.level_image(l), exr.level_image(l), err_msg=f"right level {l}")
+            np.testing.assert_array_equal(L.scale_tables()["scale"], scale)
+            return (kl, dl), (kr, dr), [L.level_image(l) for l in range(8)], L.scale_tables()["scale"]
+
+        S = _crafted_set(name, synth, extract)
+        h, w = S["left"].shape
+        t = L.scale_tables()
+        pyr_l, pyr_r = [L.level_image(l) for l in range(8)], [R.level_image(l) for l in range(8)]
+        res = SR.stereo_match(S["kl"], S["dl"], S["kr"], S["dr"], pyr_l, pyr_r, t["scale"], t["inv_scale"], S["mb"], S["mbf"])
+        _check_set(S, res)
+        print(name, {k: v for k, v in SR.census(res).items() if v})
+        bounds = (0.0, float(w), 0.0, float(h))
+        L.frame_set(0, S["kl"], S["dl"], bounds)
+        L.frame_set(1, S["kr"], S["dr"], bounds)
+        gu, gz, gn = L.stereo_match(R, 0, 1, len(S["kl"]), S["mb"], S["mbf"])
+        eu, ez, en = exl.stereo_match(exr, S["kl"], S["dl"], S["kr"], S["dr"], S["mb"], S["mbf"])
+        names = np.array(SR.EXITS)[res["exit"]]
+        for what, g, r, e in (("mvuRight", gu, res["u_right"], eu), ("mvDepth", gz, res["depth"], ez)):
+            bad = np.nonzero(_bits(g) != _bits(r))[0]
+            assert len(bad) == 0, f"{name}: {what} HIP != numpy reference at {bad[:8]}: {g[bad[:8]]} vs {r[bad[:8]]}, reference exits {names[bad[:8]]}"
+            np.testing.assert_array_equal(_bits(r), _bits(e), err_msg=f"{name}: {what}, numpy reference vs oracle")
+        assert gn == res["n_matched"] == en
+    finally:
+        for c in (L, R):
+            if c is not None:
+                c.close()
+
+
+def _dev_image(ctx, im):
+    p = ctx.device_alloc(im.nbytes)
+    ctx.h2d(p, im)
+    return p
+
+
+@pytest.mark.gpu
+def test_stereo_match_on_kept_pyramids(pkg, synth):
+    """asd_extract_keep_pyramid + asd_frame_set_from_ctx, the path of the stereo host loop: with frames t, t+1, t+2 submitted on both
+    contexts, the association of frame t -- left descriptors adopted with asd_frame_set(desc == NULL), right ones from the right
+    context -- equals the synchronous two-extraction result bit for bit, also inside an asd_prep_async bracket; without kept
+    pyramids the call refuses to read a pyramid the workers own.  Only the stated validity window (two further submissions) is used."""
+    w, h, nT = CW, CH, 4
+    bounds = (0.0, float(w), 0.0, float(h))
+    L, R = _contexts(pkg, synth, w, h, nfeat=500)
+    try:
+        pairs = [_stereo_pair(synth, 12, seed_t=t, w=w, h=h) for t in range(nT)]
+        expect = []
+        for left, right in pairs:
+            kl, dl = L.extract(left)
+            kr, dr = R.extract(right)
+            L.frame_set(0, kl, dl, bounds)
+            L.frame_set(1, kr, dr, bounds)
+            expect.append((kl, kr) + L.stereo_match(R, 0, 1, len(kl), MB, MBF))
+            assert expect[-1][4] > 0.3 * len(kl)
+        assert any(not np.array_equal(expect[0][2], e[2]) for e in expect[1:])      # the frames differ: a stale pyramid would show
+        dl_, dr_ = [_dev_image(L, p[0]) for p in pairs], [_dev_image(R, p[1]) for p in pairs]
+
+        def submit(t):
+            L.extract_submit(dl_[t], w, h, w, device_resident=True)
+            R.extract_submit(dr_[t], w, h, w, device_resident=True)
+
+        def wait_and_match(t, bracket):
+            kl = L.extract_wait()[0].copy()
+            kr = R.extract_wait()[0].copy()
+            np.testing.assert_array_equal(kl, expect[t][0])
+            np.testing.assert_array_equal(kr, expect[t][1])
+            if bracket:
+                L.prep_async(1)
+            try:
+                L.frame_set(2, kl, None, bounds)
+                L.frame_set_from_ctx(3, kr, bounds, R)
+                u, z, n = L.stereo_match(R, 2, 3, len(kl), MB, MBF)
+            finally:
+                if bracket:
+                    L.prep_async(0)
+            np.testing.assert_array_equal(_bits(u), _bits(expect[t][2]), err_msg=f"frame {t}: mvuRight")
+            np.testing.assert_array_equal(_bits(z), _bits(expect[t][3]), err_msg=f"frame {t}: mvDepth")
+            assert n == expect[t][4]
+
+        L.extract_keep_pyramid(True)
+        R.extract_keep_pyramid(True)
+        for t in range(3):
+            submit(t)
+        wait_and_match(0, False)            # frames 1, 2 outstanding
+        submit(3)
+        wait_and_match(1, False)            # frames 2, 3 outstanding
+        wait_and_match(2, True)             # frame 3 outstanding
+        wait_and_match(3, True)
+        # kept pyramids off: with a submission outstanding the shared pyramids belong to the workers
+        L.extract_keep_pyramid(False)
+        R.extract_keep_pyramid(False)
+        R.extract_submit(dr_[0], w, h, w, device_resident=True)
+        with pytest.raises(Exception, match="outstanding"):             # the right context alone is busy: the left one reports it
+            L.stereo_match(R, 2, 3, len(expect[3][0]), MB, MBF)
+        L.extract_submit(dl_[0], w, h, w, device_resident=True)
+        with pytest.raises(Exception, match="outstanding"):
+            L.stereo_match(R, 2, 3, len(expect[3][0]), MB, MBF)
+        with pytest.raises(Exception, match="outstanding"):
+            L.extract_keep_pyramid(True)
+        L.extract_wait()
+        R.extract_wait()
+        kl, dl = L.extract(pairs[1][0])      # ... and both contexts go on working
+        kr, dr = R.extract(pairs[1][1])
+        L.frame_set(0, kl, dl, bounds)
+        L.frame_set(1, kr, dr, bounds)
+        u, z, n = L.stereo_match(R, 0, 1, len(kl), MB, MBF)
+        np.testing.assert_array_equal(_bits(u), _bits(expect[1][2]))
+        np.testing.assert_array_equal(_bits(z), _bits(expect[1][3]))
+        assert n == expect[1][4]
+        for c, ps in ((L, dl_), (R, dr_)):
+            for p in ps:
+                c.device_free(p)
+    finally:
+        L.close()
+        R.close()
+
+
+@pytest.mark.gpu
+def test_stereo_match_and_frame_set_from_ctx_refuse_bad_arguments(pkg, synth):
+    """contexts of different sizes, a slot never set, n different from the source's last extraction, a source without an extraction:
+    each is an error, and the contexts go on working"""
+    w, h = CW, CH
+    bounds = (0.0, float(w), 0.0, float(h))
+    L, R = _contexts(pkg, synth, w, h, nfeat=500)
+    S = pkg.AsdHip(n_features=500, max_width=320, max_height=h, max_patches=4096)
+    try:
+        S.load_weights(synth.asdnet_weights(0))
+        left, right = _stereo_pair(synth, 12, seed_t=1, w=w, h=h)
+        kl, dl = L.extract(left)
+        L.frame_set(0, kl, dl, bounds)
+        with pytest.raises(Exception, match="no extraction"):
+            L.frame_set_from_ctx(1, kl, bounds, R)                     # the source context has extracted nothing
+        kr, dr = R.extract(right)
+        with pytest.raises(Exception, match="adopts the last extract"):
+            L.frame_set_from_ctx(1, kr[:-1], bounds, R)                # n != the source's last extraction
+        with pytest.raises(Exception, match="adopts the last extract"):
+            L.frame_set(1, kl[:-1], None, bounds)
+        with pytest.raises(Exception, match="slot not set"):
+            L.stereo_match(R, 0, 1, len(kl), MB, MBF)                  # slot 1 was never set: the refused calls left it alone
+        with pytest.raises(Exception, match="slot not set"):
+            L.stereo_match(R, 5, 0, len(kl), MB, MBF)
+        S.extract(np.ascontiguousarray(right[:, :320]))
+        with pytest.raises(Exception, match="same size"):
+            L.stereo_match(S, 0, 0, len(kl), MB, MBF)                  # 640 x 240 against 320 x 240
+        L.frame_set_from_ctx(1, kr, bounds, R)
+        u, z, n = L.stereo_match(R, 0, 1, len(kl), MB, MBF)
+        L.frame_set(2, kr, dr, bounds)
+        u2, z2, n2 = L.stereo_match(R, 0, 2, len(kl), MB, MBF)
+        np.testing.assert_array_equal(_bits(u), _bits(u2))
+        np.testing.assert_array_equal(_bits(z), _bits(z2))
+        assert n == n2 and n > 0.3 * len(kl)
+    finally:
+        for c in (L, R, S):
+            c.close()
