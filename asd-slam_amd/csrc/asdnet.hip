@@ -6,7 +6,7 @@
 // the TorchScript module once per pyramid level with an H2D and a D2H copy each
 // (ORBextractor.cc:1217-1231); here all levels' patches go through one batch.
 //
-// Arithmetic: f32 results with f32 accumulation on the matrix cores, in one of two forms per layer (ctx->net_split):
+// Arithmetic: f32 results with f32 accumulation on the matrix cores, in one of two forms (ctx->net_split):
 //   K1  (k_conv_mfma, k_conv_mfma_p): f32 operands on v_mfma_f32_32x32x2_f32 (an exact f32 fma chain);
 //   K1s (k_conv_x3, default): each f32 operand split exactly into three bf16 terms, six products per multiply-add on
 //        the bf16 MFMA (v_mfma_f32_16x16x32_bf16) -- same error level, 3/8 of the matrix-pipe time (see K1s).
@@ -75,7 +75,7 @@ struct ConvCfg {
 // FUSE1: the kernel is conv2 and computes its own input (input_norm + conv1 + BN + ReLU, ASDNet.py:334-336,
 // 360-365) from the raw u8 patch while filling the LDS band, so conv1's 128 KB/patch activation never
 // exists in HBM.  `in` is then the u8 patch array and w1 / b1 the folded conv1 weights.
-template <int CIN, int COUT, int HIN, int S, int ROWS, int WM, int WN, int KC, int PP = 1, int RING = 2, int ABL = 0, bool FUSE1 = false>
+template <int CIN, int COUT, int HIN, int S, int ROWS, int WM, int WN, int KC, int PP = 1, int RING = 2, bool FUSE1 = false>
 __global__ __launch_bounds__(64 * WM * WN) void k_conv_mfma(const void* __restrict__ in_, const float* __restrict__ wimg,
                                                            const float* __restrict__ bias, float* __restrict__ out,
                                                            const float* __restrict__ w1, const float* __restrict__ b1, int n) {
@@ -135,43 +135,40 @@ __global__ __launch_bounds__(64 * WM * WN) void k_conv_mfma(const void* __restri
     // holds that quad's 36 weights + 4 biases in registers (they were 40 LDS reads per item before)
     constexpr int NPIX = C::INROWS * C::INCOLS;
     static_assert(NTH % 8 == 0, "a thread must keep its cout quad across items");
-    if (!(ABL & 1)) {
-      const int q = t & 7;
-      float wq[4][9], bq[4];
+    const int q = t & 7;
+    float wq[4][9], bq[4];
 #pragma unroll
-      for (int c = 0; c < 4; ++c) {
-        bq[c] = wsh[288 + 4 * q + c];
+    for (int c = 0; c < 4; ++c) {
+      bq[c] = wsh[288 + 4 * q + c];
 #pragma unroll
-        for (int k = 0; k < 9; ++k) wq[c][k] = wsh[(4 * q + c) * 9 + k];
-      }
-      for (int item = t; item < NPIX * 8; item += NTH) {
-        const int pix = item >> 3;
-        const int i = pix % C::INCOLS, j = pix / C::INCOLS;
-        const int oy = r0 - 1 + j, ox = i - 1;
-        f32x4 r = {0.f, 0.f, 0.f, 0.f};
-        if (oy >= 0 && oy < 32 && ox >= 0 && ox < 32) {
-          float a[9];
+      for (int k = 0; k < 9; ++k) wq[c][k] = wsh[(4 * q + c) * 9 + k];
+    }
+    for (int item = t; item < NPIX * 8; item += NTH) {
+      const int pix = item >> 3;
+      const int i = pix % C::INCOLS, j = pix / C::INCOLS;
+      const int oy = r0 - 1 + j, ox = i - 1;
+      f32x4 r = {0.f, 0.f, 0.f, 0.f};
+      if (oy >= 0 && oy < 32 && ox >= 0 && ox < 32) {
+        float a[9];
 #pragma unroll
-          for (int ky = 0; ky < 3; ++ky)
+        for (int ky = 0; ky < 3; ++ky)
 #pragma unroll
-            for (int kx = 0; kx < 3; ++kx) a[ky * 3 + kx] = pin[(j + ky) * 36 + ox + kx];  // pin row j <-> image row oy-1
+          for (int kx = 0; kx < 3; ++kx) a[ky * 3 + kx] = pin[(j + ky) * 36 + ox + kx];  // pin row j <-> image row oy-1
 #pragma unroll
-          for (int c = 0; c < 4; ++c) {
-            float acc1 = bq[c];
+        for (int c = 0; c < 4; ++c) {
+          float acc1 = bq[c];
 #pragma unroll
-            for (int k = 0; k < 9; ++k) acc1 += a[k] * wq[c][k];
-            r[c] = acc1 > 0.f ? acc1 : 0.f;
-          }
+          for (int k = 0; k < 9; ++k) acc1 += a[k] * wq[c][k];
+          r[c] = acc1 > 0.f ? acc1 : 0.f;
         }
-        *reinterpret_cast<f32x4*>(sact + pix * C::CPAD + 4 * q) = r;
       }
+      *reinterpret_cast<f32x4*>(sact + pix * C::CPAD + 4 * q) = r;
     }
   } else {
     const float* inp = static_cast<const float*>(in_) + (size_t)patch * HIN * HIN * CIN;
     // ---- stage the zero-padded input band(s) (NHWC rows are contiguous: coalesced 16-B loads)
     constexpr int C4 = CIN / 4;
     constexpr int NPIXB = C::INROWS * C::INCOLS;
-    if (!(ABL & 1))
     for (int idx = t; idx < PP * NPIXB * C4; idx += NTH) {
       const int c4 = idx % C4, pixg = idx / C4;
       const int pp = pixg / NPIXB, pix = pixg % NPIXB;
@@ -225,8 +222,7 @@ __global__ __launch_bounds__(64 * WM * WN) void k_conv_mfma(const void* __restri
       for (int mt = 0; mt < C::MT; ++mt)
 #pragma unroll
         for (int nt = 0; nt < C::NT; ++nt)
-          if (!(ABL & 2)) acc[mt][nt] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[mt][jj], b[nt][jj], acc[mt][nt], 0, 0, 0);
-          else { asm volatile("" :: "v"(a[mt][jj]), "v"(b[nt][jj])); }
+          acc[mt][nt] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[mt][jj], b[nt][jj], acc[mt][nt], 0, 0, 0);
   };
 
   if constexpr (RING == 3) {
@@ -234,7 +230,7 @@ __global__ __launch_bounds__(64 * WM * WN) void k_conv_mfma(const void* __restri
     load_ops(0, 0, a0, b0);
     for (int s = 0; s < C::NSTAGE; ++s) {
       f32x4 wreg[C::WREGS];
-      const bool pre = s + 2 < C::NSTAGE && !(ABL & 16);
+      const bool pre = s + 2 < C::NSTAGE;
       if (pre) {
         const float* wsrc = wimg + (size_t)(s + 2) * C::WCHUNK;
         for (int r = 0; r < C::WREGS; ++r)
@@ -263,12 +259,12 @@ __global__ __launch_bounds__(64 * WM * WN) void k_conv_mfma(const void* __restri
         for (int r = 0; r < C::WREGS; ++r)
           if (C::WQUADS >= NTH || t < C::WQUADS) *reinterpret_cast<f32x4*>(swn + (r * NTH + t) * 4) = wreg[r];
       }
-      if (!(ABL & 8)) asd_syncthreads();
+      asd_syncthreads();
     }
   } else {
     for (int s = 0; s < C::NSTAGE; ++s) {
       f32x4 wreg[C::WREGS];
-      if (s + 1 < C::NSTAGE && !(ABL & 16)) {
+      if (s + 1 < C::NSTAGE) {
         const float* wsrc = wimg + (size_t)(s + 1) * C::WCHUNK;
         for (int r = 0; r < C::WREGS; ++r)
           if (C::WQUADS >= NTH || t < C::WQUADS) wreg[r] = *reinterpret_cast<const f32x4*>(wsrc + (r * NTH + t) * 4);
@@ -279,12 +275,12 @@ __global__ __launch_bounds__(64 * WM * WN) void k_conv_mfma(const void* __restri
         load_ops(s, c8, a, b);
         mfma_step(a, b);
       }
-      if (s + 1 < C::NSTAGE && !(ABL & 16)) {
+      if (s + 1 < C::NSTAGE) {
         float* swn = sw + ((s + 1) & 1) * C::WCHUNK;
         for (int r = 0; r < C::WREGS; ++r)
           if (C::WQUADS >= NTH || t < C::WQUADS) *reinterpret_cast<f32x4*>(swn + (r * NTH + t) * 4) = wreg[r];
       }
-      if (!(ABL & 8)) asd_syncthreads();
+      asd_syncthreads();
     }
   }
 
@@ -299,9 +295,8 @@ __global__ __launch_bounds__(64 * WM * WN) void k_conv_mfma(const void* __restri
       for (int r = 0; r < 16; ++r) {
         const int m = (wm * C::MT + mt) * 32 + (r & 3) + 8 * (r >> 2) + 4 * h;
         const size_t o = (size_t)pp * C::HO * C::HO * COUT + (size_t)(m - pp * C::M_PATCH) * COUT + co;
-        float v = acc[mt][nt][r] + bv;
-        if (!(ABL & 4)) op[o] = v > 0.f ? v : 0.f;
-        else { asm volatile("" :: "v"(v)); }
+        const float v = acc[mt][nt][r] + bv;
+        op[o] = v > 0.f ? v : 0.f;
       }
     }
   }
@@ -450,7 +445,7 @@ __global__ __launch_bounds__(256) void k_conv_mfma_p(const float* __restrict__ i
 // Every f32 value is written exactly as x = h + m + l, three bf16 numbers (8 significant bits each, by truncation:
 // h = top 16 bits of x, m = top 16 bits of x - h, l = x - h - m, both subtractions exact).  The product of two such
 // values is the sum of nine bf16 x bf16 products, each exact in f32; the six of relative size >= 2^-16
-// (hh, hm, mh, mm, hl, lh) go through the bf16 MFMA (shape: ASD_X3_S16 below) with f32 accumulation, the three dropped ones are
+// (hh, hm, mh, mm, hl, lh) go through the bf16 MFMA (v_mfma_f32_16x16x32_bf16) with f32 accumulation, the three dropped ones are
 // <= 2^-23 relative -- below the rounding of an f32 fma chain.  Measured (tools/ubench/split_mfma.hip, K = 288 /
 // 1152 / 8192, rms error against f64): 8.7e-8 / 3.6e-7 / 2.7e-6 for this form, 8.9e-8 / 3.4e-7 / 2.4e-6 for
 // v_mfma_f32_32x32x2_f32.  The bf16 pipe runs 16x the f32 MFMA rate, so six products cost 3/8 of the f32 MFMAs.
@@ -462,14 +457,10 @@ __global__ __launch_bounds__(256) void k_conv_mfma_p(const float* __restrict__ i
 // (L2-resident, two chunks ahead, registers) and runs barrier-free after the band is staged; the workgroup covers
 // M_WG >= 128 pixels so that the weight stream stays at <= 16 B/clk/CU.
 // ------------------------------------------------------------------------------------------
-#ifndef ASD_X3_ABL
-#define ASD_X3_ABL 0  // tuning: 1 = weight stream pinned to chunk 0/1 (L1 hits), 2 = no band staging, 4 = no output stores,
-                      // 8 = no MFMAs, 32 = conv1 with one tap instead of nine, 64 = conv1 output written unsplit
-#endif
-// MFMA shape of the split-operand kernels: 1 = v_mfma_f32_16x16x32_bf16 (16-row tiles, 32-deep chunks; default),
-// 0 = v_mfma_f32_32x32x16_bf16.  Both take the same cycles; under the 16x16x32 form the chip holds a higher clock (in-kernel
-// 1.87-2.25 GHz against 1.67-1.99: conv4 168 -> 154, conv6 165 -> 150 us, ASDNet 0.89 -> 0.82 ms, and the latency-bound
-// tracking kernels gain from the clock too: 700 -> 766 frames/s).
+// MFMA shape of the split-operand kernels: v_mfma_f32_16x16x32_bf16 (16-row tiles, 32-deep chunks).  v_mfma_f32_32x32x16_bf16 takes
+// the same cycles, but under the 16x16x32 form the chip holds a higher clock (in-kernel 1.87-2.25 GHz against 1.67-1.99: conv4
+// 168 -> 154, conv6 165 -> 150 us, ASDNet 0.89 -> 0.82 ms, and the latency-bound tracking kernels gain from the clock too: 700 ->
+// 766 frames/s).
 // HAZARD (gfx950, measured stand-alone: tools/ubench/mfma_pk_hazard.hip, profiles/r02_mfma_pk_hazard*.txt): a packed-f32
 // instruction whose src1 takes its LOW-half operand from the HIGH register of the pair (v_pk_add_f32 ... op_sel:[0,1], what the
 // SLP vectoriser emits for "both halves use y.y") drops the low-half result in lanes 48-63 now and then while a wave that
@@ -477,9 +468,6 @@ __global__ __launch_bounds__(256) void k_conv_mfma_p(const float* __restrict__ i
 // not of this kernel: the 32x32x16 shape triggers it as well (round 1 thought it did not: it is 8x rarer next to this loop),
 // a plain f32 loop does not.  The library therefore contains no packed-f32 arithmetic at all (-fno-slp-vectorize in the
 // Makefile; `make check-isa` / tests/test_isa.py), and tests/test_frontend.py runs asd_dist_matrix beside the extractor.
-#ifndef ASD_X3_S16
-#define ASD_X3_S16 1
-#endif
 #define ASD_X3_PD 2  // A-operand prefetch distance in sub-tiles
 #ifndef ASD_X3_RB
 #define ASD_X3_RB 3  // chunks of B operands (weights) in flight per wave, where the layer's chunk count divides by it.  Round 5, N = 2000:
@@ -501,7 +489,7 @@ struct X3Cfg {
   // stride is (every A read took two passes: SQ_LDS_BANK_CONFLICT = half of SQ_LDS_IDX_ACTIVE in profiles/r05_asdnet_sq_counters_default.txt)
   // unless the first half's pixels are the even and the second half's the odd ones: x3_tile_pixel below.  Stride-2 layers only ever
   // touch even slots that way; they keep the pieces in planes ([p][g]: k-groups 16 B apart) instead.
-  static constexpr bool PLANAR = NP == 2 && S == 2 && ASD_X3_S16 != 0;
+  static constexpr bool PLANAR = NP == 2 && S == 2;
   static constexpr int GSTR = PLANAR ? 16 : GRPB;
   static constexpr int PSTR = PLANAR ? CIN * 2 : 16;
   static constexpr int NW = WM * WN;
@@ -510,15 +498,15 @@ struct X3Cfg {
   static constexpr int M_WG = PP * M_PATCH;
   static constexpr int MT = M_WG / 32 / WM;
   static constexpr int NT = COUT / 32 / WN;
-  static constexpr int KCH = ASD_X3_S16 ? 32 : 16;  // cin per k-chunk = K of the MFMA shape
+  static constexpr int KCH = 32;                    // cin per k-chunk = K of the MFMA shape
   static constexpr int NC16 = CIN / KCH;            // chunks per tap
   static constexpr int NCHUNK = 9 * NC16;
   static constexpr int CHUNKB = KCH * 2 * NP * COUT;  // bytes of weight image per chunk: [piece NP][k-group KCH/8][cout][8 x 16 bit]
   static constexpr int ACT_BYTES = INROWS * INCOLS * PIXB;
   static constexpr int LDS_BYTES = PP * ACT_BYTES;
   static_assert((PIXB / 16) % 2 == 1, "pixel stride must be an odd multiple of 16 B");
-  static constexpr int NCW = COUT / WN;               // couts per wave: a multiple of the MFMA tile width (16 or 32)
-  static_assert(M_WG % (32 * WM) == 0 && COUT % WN == 0 && NCW % (ASD_X3_S16 ? 16 : 32) == 0 && CIN % KCH == 0 && HO % ROWS == 0, "tile split");
+  static constexpr int NCW = COUT / WN;               // couts per wave: a multiple of the MFMA tile width
+  static_assert(M_WG % (32 * WM) == 0 && COUT % WN == 0 && NCW % 16 == 0 && CIN % KCH == 0 && HO % ROWS == 0, "tile split");
   static_assert(PP == 1 || ROWS == HO, "several patches per workgroup only for whole-patch bands");
   static_assert(M_PATCH % 32 == 0, "32-pixel MFMA tiles must not straddle patches");
 };
@@ -632,7 +620,7 @@ __device__ __forceinline__ void conv_x3_tile(const int bid, const void* __restri
   // accumulators are multiplied by out_scale = 1 / (in_scale * the layer's weight scale) in the epilogue (powers of two: exact)
   using C = X3Cfg<CIN, COUT, HIN, S, ROWS, WM, WN, PP, NP>;
   constexpr int NTH = C::NTH, MT = C::MT, NCW = C::NCW;
-  static_assert(!PAIR || (NP == 2 && ASD_X3_S16), "the pair format belongs to the two-piece form on the 16x16x32 shape");
+  static_assert(!PAIR || NP == 2, "the pair format belongs to the two-piece form");
   extern __shared__ __attribute__((aligned(16))) uint8_t smem_b[];
   // Inside the persistent launch this body is a loop body.  Everything below that depends only on the lane (operand offsets, the
   // weight stream's addresses) is loop invariant, and hoisted out of the tile loop it stays live across the whole body: 93 -> 240
@@ -641,7 +629,6 @@ __device__ __forceinline__ void conv_x3_tile(const int bid, const void* __restri
   asm volatile("" : "+v"(t));
   const int lane = t & 63, wave = t >> 6;
   const int wm = wave / WN, wn = wave % WN;
-  const int h = lane >> 5, li = lane & 31;
   constexpr int BANDS = C::HO / ROWS;
   const int patch = (bid / BANDS) * PP, band = bid % BANDS;
   const int r0 = band * ROWS;
@@ -649,16 +636,14 @@ __device__ __forceinline__ void conv_x3_tile(const int bid, const void* __restri
   if (stamps) st_t0 = st_t1 = __builtin_amdgcn_s_memtime();
 #define X3_STAMP(k) do { if (stamps && t == 0) stamps[16 * bid + (k)] = __builtin_amdgcn_s_memtime() - st_t0; } while (0)
 
-  // MFMA shape: 32x32x16 -> lane = (k-half h, row/col li of 32), one sub-tile per 32x32 tile; 16x16x32 -> lane = (k-group of
-  // four, row/col of 16), SUB = 2 sub-tiles per tile side
-  constexpr bool S16 = ASD_X3_S16;
-  constexpr int SUB = S16 ? 2 : 1, KG = C::KCH / 8, TW = 32 / SUB;
-  const int kg = S16 ? lane >> 4 : h, lr = S16 ? lane & 15 : li;
+  // MFMA shape 16x16x32: lane = (k-group of four, row/col of 16), SUB = 2 sub-tiles per 32-wide tile side
+  constexpr int SUB = 2, KG = C::KCH / 8, TW = 32 / SUB;
+  const int kg = lane >> 4, lr = lane & 15;
   // ---- B operand stream: chunk c = tap * NC16 + c16, this lane's 8 k values of (piece, k-group kg, cout)
   const uint8_t* wl = wimg + ((size_t)kg * COUT + wn * NCW + lr) * 16;
   constexpr int NB = NCW / TW;  // B sub-tiles of this wave
   auto load_b = [&](int c, u32x4 (&b)[NB][NP]) {
-    const uint8_t* wc = wl + (size_t)((ASD_X3_ABL & 1) ? (c & 1) : c) * C::CHUNKB;
+    const uint8_t* wc = wl + (size_t)c * C::CHUNKB;
 #pragma unroll
     for (int nb = 0; nb < NB; ++nb)
 #pragma unroll
@@ -734,48 +719,45 @@ __device__ __forceinline__ void conv_x3_tile(const int bid, const void* __restri
     // item = (pixel, octet of 8 couts); a thread keeps its octet and holds its 72 weights + 8 biases in registers.
     // Same f32 operation order per output as K1 (bias, then the nine taps in order)
     constexpr int NPIX = C::INROWS * C::INCOLS;
-    if (!(ASD_X3_ABL & 2)) {
-      const int q = t & 3;
-      float wq[8][9], bq1[8];
+    const int q = t & 3;
+    float wq[8][9], bq1[8];
 #pragma unroll
-      for (int c = 0; c < 8; ++c) {
-        bq1[c] = wsh[288 + 8 * q + c];
+    for (int c = 0; c < 8; ++c) {
+      bq1[c] = wsh[288 + 8 * q + c];
 #pragma unroll
-        for (int k = 0; k < 9; ++k) wq[c][k] = wsh[(8 * q + c) * 9 + k];
+      for (int k = 0; k < 9; ++k) wq[c][k] = wsh[(8 * q + c) * 9 + k];
+    }
+    for (int item = t; item < NPIX * 4; item += NTH) {
+      const int pix = item >> 2;
+      const int i = pix % C::INCOLS, j = pix / C::INCOLS;
+      const int oy = r0 - 1 + j, ox = i - 1;
+      f32x4 ra = {0.f, 0.f, 0.f, 0.f}, rb = {0.f, 0.f, 0.f, 0.f};
+      if (oy >= 0 && oy < 32 && ox >= 0 && ox < 32) {
+        float a[9];
+#pragma unroll
+        for (int ky = 0; ky < 3; ++ky)
+#pragma unroll
+          for (int kx = 0; kx < 3; ++kx) a[ky * 3 + kx] = pin[(j + ky) * 36 + ox + kx];  // pin row j <-> image row oy-1
+#pragma unroll
+        for (int c = 0; c < 8; ++c) {
+          float acc1 = bq1[c];
+#pragma unroll
+          for (int k = 0; k < 9; ++k) acc1 += a[k] * wq[c][k];
+          const float r = acc1 > 0.f ? acc1 : 0.f;
+          if (c < 4) ra[c] = r; else rb[c - 4] = r;
+        }
       }
-      for (int item = t; item < NPIX * 4; item += NTH) {
-        const int pix = item >> 2;
-        const int i = pix % C::INCOLS, j = pix / C::INCOLS;
-        const int oy = r0 - 1 + j, ox = i - 1;
-        f32x4 ra = {0.f, 0.f, 0.f, 0.f}, rb = {0.f, 0.f, 0.f, 0.f};
-        if (oy >= 0 && oy < 32 && ox >= 0 && ox < 32) {
-          float a[9];
-#pragma unroll
-          for (int ky = 0; ky < 3; ++ky)
-#pragma unroll
-            for (int kx = 0; kx < 3; ++kx) a[ky * 3 + kx] = pin[(j + ky) * 36 + ox + kx];  // pin row j <-> image row oy-1
-#pragma unroll
-          for (int c = 0; c < 8; ++c) {
-            float acc1 = bq1[c];
-#pragma unroll
-            for (int k = 0; k < ((ASD_X3_ABL & 32) ? 1 : 9); ++k) acc1 += a[k] * wq[c][k];
-            const float r = acc1 > 0.f ? acc1 : 0.f;
-            if (c < 4) ra[c] = r; else rb[c - 4] = r;
-          }
-        }
-        u32x4 ph, pm, pl;
-        uint8_t* dst = smem_b + pix * C::PIXB + q * C::GSTR;
-        if constexpr (NP == 2) {
-          split8_f16(ra, rb, in_scale, ph, pl);
-          *reinterpret_cast<u32x4*>(dst) = ph;
-          *reinterpret_cast<u32x4*>(dst + C::PSTR) = pl;
-        } else {
-          if constexpr ((ASD_X3_ABL & 64) != 0) { ph = __builtin_bit_cast(u32x4, ra); pm = __builtin_bit_cast(u32x4, rb); pl = ph; }
-          else split8(ra, rb, ph, pm, pl);
-          *reinterpret_cast<u32x4*>(dst) = ph;
-          *reinterpret_cast<u32x4*>(dst + 16) = pm;
-          *reinterpret_cast<u32x4*>(dst + 32) = pl;
-        }
+      u32x4 ph, pm, pl;
+      uint8_t* dst = smem_b + pix * C::PIXB + q * C::GSTR;
+      if constexpr (NP == 2) {
+        split8_f16(ra, rb, in_scale, ph, pl);
+        *reinterpret_cast<u32x4*>(dst) = ph;
+        *reinterpret_cast<u32x4*>(dst + C::PSTR) = pl;
+      } else {
+        split8(ra, rb, ph, pm, pl);
+        *reinterpret_cast<u32x4*>(dst) = ph;
+        *reinterpret_cast<u32x4*>(dst + 16) = pm;
+        *reinterpret_cast<u32x4*>(dst + 32) = pl;
       }
     }
   } else if constexpr (PAIR) {
@@ -788,7 +770,7 @@ __device__ __forceinline__ void conv_x3_tile(const int bid, const void* __restri
     constexpr int NROUND = (PP * NPIXB + PSTEP - 1) / PSTEP;
     constexpr int SBATCH = 8;
     const int c8 = t % C8, pix0 = t / C8;
-    for (int rb = 0; rb < ((ASD_X3_ABL & 2) ? 0 : NROUND); rb += SBATCH) {
+    for (int rb = 0; rb < NROUND; rb += SBATCH) {
       u32x4 v0[SBATCH], v1[SBATCH];
 #pragma unroll
       for (int b = 0; b < SBATCH; ++b) {
@@ -823,7 +805,7 @@ __device__ __forceinline__ void conv_x3_tile(const int bid, const void* __restri
     constexpr int NROUND = (PP * NPIXB + PSTEP - 1) / PSTEP;
     constexpr int SBATCH = 8;
     const int c8 = t % C8, pix0 = t / C8;
-    for (int rb = 0; rb < ((ASD_X3_ABL & 2) ? 0 : NROUND); rb += SBATCH) {
+    for (int rb = 0; rb < NROUND; rb += SBATCH) {
       f32x4 v0[SBATCH], v1[SBATCH];
 #pragma unroll
       for (int b = 0; b < SBATCH; ++b) {
@@ -862,21 +844,21 @@ __device__ __forceinline__ void conv_x3_tile(const int bid, const void* __restri
   asd_syncthreads();
   X3_STAMP(13);
 
-  // accumulators: [A sub-tile][B sub-tile]; a sub-tile is 32x32 (16 floats per lane) or 16x16 (4 floats per lane)
-  constexpr int NA = MT * SUB, AR = S16 ? 4 : 16;
-  typedef float accv __attribute__((ext_vector_type(S16 ? 4 : 16)));
+  // accumulators: [A sub-tile][B sub-tile]; a sub-tile is 16x16 (4 floats per lane)
+  constexpr int NA = MT * SUB, AR = 4;
+  typedef float accv __attribute__((ext_vector_type(4)));
   accv acc[NA][NB];
   for (int ma = 0; ma < NA; ++ma)
     for (int nb = 0; nb < NB; ++nb)
       for (int r = 0; r < AR; ++r) acc[ma][nb][r] = 0.f;
-  // pixel (index within the workgroup's M_WG output pixels) of row / column r16 of sub-tile sg.  Two-piece form on the 16x16x32 shape: the
+  // pixel (index within the workgroup's M_WG output pixels) of row / column r16 of sub-tile sg.  Two-piece form: the
   // order inside a sub-tile is chosen so that every ds_read_b128 lane group reads sixteen different 16-B slots (X3Cfg::PLANAR's comment;
   // checked for every tap, chunk and piece by tests/test_asdnet.py::test_lds_reads_are_conflict_free over the same formulas):
   //   stride 1, rows of >= 16 pixels: lanes 0-3, 12-15 take the even pixels of the sixteen, lanes 4-11 the odd ones;
   //   stride 2 (planar pieces): the natural order; with rows of eight pixels lanes 0-3, 12-15 take the first row, lanes 4-11 the second;
   //   stride 1, rows of eight pixels (conv6): a sub-tile is eight rows x two columns, the even column on lanes 0-3, 12-15.
   auto tile_pixel = [&](int sg, int r16) -> int {
-    if constexpr (NP == 2 && S16) {
+    if constexpr (NP == 2) {
       if constexpr (S == 1 && C::HO >= 16) return sg * 16 + (r16 < 4 ? 2 * r16 : r16 < 12 ? 2 * r16 - 7 : 2 * r16 - 16);
       else if constexpr (S == 2 && C::HO >= 16) return sg * 16 + r16;
       else if constexpr (S == 2) return sg * 16 + (r16 < 4 ? r16 : r16 < 12 ? r16 + 4 : r16 - 8);
@@ -905,15 +887,9 @@ __device__ __forceinline__ void conv_x3_tile(const int bid, const void* __restri
   auto bf = [](const u32x4& v) { return __builtin_bit_cast(bf16x8, v); };
   auto hf = [](const u32x4& v) { return __builtin_bit_cast(f16x8, v); };
   auto mma = [&](const u32x4& x, const u32x4& y, accv& c) {
-    if constexpr ((ASD_X3_ABL & 8) != 0) { asm volatile("" ::"v"(x), "v"(y)); }  // tuning: operands fetched, no MFMA
-#ifdef ASD_PAIR_NOTRANS   // timing experiment only (results are wrong): the pair epilogue behind untransposed accumulators
-    else if constexpr (PAIR) c = __builtin_amdgcn_mfma_f32_16x16x32_f16(hf(x), hf(y), c, 0, 0, 0);
-#endif
-    else if constexpr (PAIR) c = __builtin_amdgcn_mfma_f32_16x16x32_f16(hf(y), hf(x), c, 0, 0, 0);   // transposed: rows = couts, columns = pixels
-    else if constexpr (NP == 2 && S16) c = __builtin_amdgcn_mfma_f32_16x16x32_f16(hf(x), hf(y), c, 0, 0, 0);
-    else if constexpr (NP == 2) c = __builtin_amdgcn_mfma_f32_32x32x16_f16(hf(x), hf(y), c, 0, 0, 0);
-    else if constexpr (S16) c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(bf(x), bf(y), c, 0, 0, 0);
-    else c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(bf(x), bf(y), c, 0, 0, 0);
+    if constexpr (PAIR) c = __builtin_amdgcn_mfma_f32_16x16x32_f16(hf(y), hf(x), c, 0, 0, 0);   // transposed: rows = couts, columns = pixels
+    else if constexpr (NP == 2) c = __builtin_amdgcn_mfma_f32_16x16x32_f16(hf(x), hf(y), c, 0, 0, 0);
+    else c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(bf(x), bf(y), c, 0, 0, 0);
   };
 
   // A operands run PD sub-tiles ahead of the MFMAs through a register ring of PD + 1 slots; a loop iteration covers RB chunks x
@@ -974,7 +950,7 @@ __device__ __forceinline__ void conv_x3_tile(const int bid, const void* __restri
     if (t == 0) { stamps[16 * bid] = e_c - st_c; stamps[16 * bid + 1] = e_r - st_r; stamps[16 * bid + 2] = st_t1 - st_t0; stamps[16 * bid + 3] = st_c - st_t1; stamps[16 * bid + 6] = st_t0; }
   }
   // ---- epilogue: bias (folded BN) + ReLU, NHWC f32 store.  Lane owns one cout column and AR pixel rows of each sub-tile
-  // (32x32: rows (r & 3) + 8 (r >> 2) + 4 h; 16x16: rows 4 kg + r)
+  // (rows 4 kg + r)
   if constexpr (PAIR) {
     // lane = (pixel lr of the sub-tile, couts 4 kg .. 4 kg + 3): bias, ReLU (a NaN passes), the split of kActScale * v, a swap with
     // the neighbouring quarter-group and one 16-B store into [pixel][cout / 8][h | l][8]
@@ -998,7 +974,7 @@ __device__ __forceinline__ void conv_x3_tile(const int bid, const void* __restri
         const auto s0 = __builtin_amdgcn_permlane16_swap(hh[0], ll[0], false, false);
         const auto s1 = __builtin_amdgcn_permlane16_swap(hh[1], ll[1], false, false);
         uint8_t* o = opb + ((size_t)pp * C::HO * C::HO + (size_t)(m - pp * C::M_PATCH)) * COUT * 4 + (co0 >> 3) * 32 + (kg & 1) * 16;
-        if (!(ASD_X3_ABL & 4) || hh[0] == 0x12345u) *reinterpret_cast<u32x4*>(o) = u32x4{s0[0], s1[0], s0[1], s1[1]};
+        *reinterpret_cast<u32x4*>(o) = u32x4{s0[0], s1[0], s0[1], s1[1]};
       }
     }
   } else {
@@ -1011,11 +987,11 @@ __device__ __forceinline__ void conv_x3_tile(const int bid, const void* __restri
       const int pp = PP > 1 ? m0 / C::M_PATCH : 0;  // a sub-tile never straddles two patches
       if (PP > 1 && patch + pp >= n) continue;
       for (int r = 0; r < AR; ++r) {
-        const int m = S16 ? tile_pixel(m0 / TW, 4 * kg + r) : m0 + (r & 3) + 8 * (r >> 2) + 4 * h;
+        const int m = tile_pixel(m0 / TW, 4 * kg + r);
         const size_t o = (size_t)pp * C::HO * C::HO * COUT + (size_t)(m - pp * C::M_PATCH) * COUT + co;
         const float v = (NP == 2 ? acc[ma][nb][r] * out_scale : acc[ma][nb][r]) + bv;
         // ReLU; the fp16 form lets a NaN through (an activation beyond fp16's range must reach the descriptor, not become 0)
-        if (!(ASD_X3_ABL & 4) || v == 12345.f) op[o] = NP == 2 ? (v < 0.f ? 0.f : v) : (v > 0.f ? v : 0.f);
+        op[o] = NP == 2 ? (v < 0.f ? 0.f : v) : (v > 0.f ? v : 0.f);
       }
     }
   }
@@ -1308,7 +1284,6 @@ __global__ __launch_bounds__(256) void k_l2norm(const float* __restrict__ part, 
   desc[(size_t)p * 128 + lane + 64] = v1 / norm;
 }
 
-constexpr bool kPairOK = ASD_X3_S16 != 0;   // the pair format's transposed epilogue is written for the 16x16x32 shape
 // layer configurations: <CIN, COUT, HIN, S, ROWS, WM, WN, KC, PP, RING> (L3: persistent form, no PP / RING)
 #define L2_CFG 32, 32, 32, 1, 4, 4, 1, 16, 1, 3
 #define L3_CFG 32, 64, 32, 2, 4, 2, 2, 16
@@ -1327,11 +1302,7 @@ constexpr bool kPairOK = ASD_X3_S16 != 0;   // the pair format's transposed epil
 #define ASD_L2_WMN 4, 1
 #endif
 #ifndef ASD_L3_WMN
-#if ASD_X3_S16
 #define ASD_L3_WMN 1, 4
-#else
-#define ASD_L3_WMN 2, 2     // (the 32x32x16 shape needs 32 couts per wave)
-#endif
 #endif
 #ifndef ASD_L4_WMN
 #define ASD_L4_WMN 2, 2
@@ -1347,11 +1318,7 @@ constexpr bool kPairOK = ASD_X3_S16 != 0;   // the pair format's transposed epil
 // workgroup only and was slower that way).  Measured and not kept (N = 2000): 8-wave workgroups for conv4 / conv5 / conv6 (64 pixels x 16
 // couts per wave, two MFMA-issuing waves per SIMD and workgroup): 115 / 77 / 106 us against 97 / 71 / 95.
 #ifndef ASD_L5_RWMN
-#if ASD_X3_S16
 #define ASD_L5_RWMN 8, 1, 4
-#else
-#define ASD_L5_RWMN 4, 1, 4     // (the 32x32x16 build keeps the 4-row bands: the whole-patch form costs it five more minutes of compile time)
-#endif
 #endif
 #ifndef ASD_L6_WMN
 #define ASD_L6_WMN 1, 4
@@ -1363,7 +1330,7 @@ template <int CIN, int COUT, int HIN, int S, int ROWS, int WM, int WN, int KC, i
 hipError_t launch_conv(hipStream_t st, const void* in, const float* wimg, const float* bias, float* out, int n,
                        const float* w1 = nullptr, const float* b1 = nullptr) {
   using C = ConvCfg<CIN, COUT, HIN, S, ROWS, WM, WN, KC, PP, RING>;
-  auto kern = k_conv_mfma<CIN, COUT, HIN, S, ROWS, WM, WN, KC, PP, RING, 0, FUSE1>;
+  auto kern = k_conv_mfma<CIN, COUT, HIN, S, ROWS, WM, WN, KC, PP, RING, FUSE1>;
   constexpr int lds = C::LDS_BYTES + (FUSE1 ? ((ROWS + 4) * 36 + 320 + 8) * 4 : 0);
   static_assert(lds <= 160 * 1024, "band + weight ring do not fit LDS");
   static AsdPerDeviceOnce attr_set;   // per instantiation; the attribute belongs to the current device (the caller selected the context's)
@@ -1459,11 +1426,11 @@ inline float weight_scale_f16(const float* w, size_t count, const std::vector<fl
 }
 
 // split B-operand image of a 3x3 layer: [tap][cin/KCH][piece][k-group][cout][8 x 16 bit] with cin = KCH*c + 8*group + j
-// (KCH = 16 for the 32x32x16 MFMA shape, 32 for 16x16x32), BN scale folded in f32 first (the same folded value the f32 image holds).
+// (KCH = 32, the depth of the 16x16x32 MFMA shape), BN scale folded in f32 first (the same folded value the f32 image holds).
 // np = 3: exact bf16 pieces; np = 2: fp16 pieces of the folded weight times wscale.
 void build_wx3(const LayerSpec& L, const float* w, const std::vector<float>& inv, std::vector<uint16_t>& img, int np = 3, float wscale = 1.f) {
   img.assign((size_t)9 * L.cin * L.cout * np, 0);
-  constexpr int kch = ASD_X3_S16 ? 32 : 16, kg = kch / 8;
+  constexpr int kch = 32, kg = kch / 8;
   const int nc16 = L.cin / kch;
   for (int tap = 0; tap < 9; ++tap)
     for (int ci = 0; ci < L.cin; ++ci)
@@ -1503,7 +1470,6 @@ int asdnet_alloc(asd_ctx* ctx) {
   ASD_HIP_CHECK(ctx, hipHostMalloc(reinterpret_cast<void**>(&ctx->h_range), 64));
   *ctx->h_range = 0;
   if (const char* e = getenv("ASD_ASDNET_PAIR")) ctx->net_pair = atoi(e) != 0;
-  if (const char* e = getenv("ASD_ASDNET_RING")) ctx->ring_mask = atoi(e);
   return ASD_OK;
 }
 
@@ -1629,70 +1595,67 @@ static int asdnet_forward_one(asd_ctx* ctx, const uint8_t* d_patches, int n, flo
 #define PROF_MARK(i) do { if (prof) ASD_HIP_CHECK(ctx, hipEventRecord(ctx->prof_ev[pset][i], st)); } while (0)
   PROF_MARK(0);
   PROF_MARK(1);  // layer 0 (input_norm + conv1) is fused into conv2's band fill: no launch of its own
-  // ASD_ASDNET_MATH=f16x2: two fp16 pieces per operand, three products (kActScale and the per-layer weight scale are undone in the epilogue)
-  const bool p2 = ctx->net_pieces == 2;
-  // pair format between the layers: every layer on the two-piece kernels, and not the calibration pass (k_absmax reads f32)
-  const bool pair = kPairOK && p2 && (ctx->net_split & 63) == 63 && ctx->net_pair && !ctx->d_calib;
-  const float* x3_stats = nullptr;   // conv2 only: the patches' normalisation statistics (k_patch_stats)
+  // calibration (asd_load_weights): the largest |activation| each layer hands to the next one
+#define CALIB(l, buf, elems) do { if (ctx->d_calib) { hipLaunchKernelGGL(k_absmax, dim3(256), dim3(256), 0, st, buf, (size_t)n * (elems), ctx->d_calib + (l)); ASD_HIP_CHECK(ctx, hipGetLastError()); } } while (0)
+  ctx->d_act6 = a1;   // conv6's output, the last layer's input
+  if (ctx->net_split) {   // every layer on the split-operand kernels (K1s, K2s / K2p)
+    // ASD_ASDNET_MATH=f16x2: two fp16 pieces per operand, three products (kActScale and the per-layer weight scale are undone in the epilogue)
+    const bool p2 = ctx->net_pieces == 2;
+    // pair format between the layers: the two-piece kernels, and not the calibration pass (k_absmax reads f32)
+    const bool pair = p2 && ctx->net_pair && !ctx->d_calib;
+    const float* x3_stats = nullptr;   // conv2 only: the patches' normalisation statistics (k_patch_stats)
 #define X3_LAUNCH(CFG, FUSE, l, src, dst, w1p, b1p)                                                                                       \
-  (pair ? launch_conv_x3<CFG, FUSE, 2, kPairOK>(st, src, ctx->d_wx2[l], ctx->d_bias[l], dst, n, w1p, b1p, nullptr, nullptr, kActScale,       \
+  (pair ? launch_conv_x3<CFG, FUSE, 2, true>(st, src, ctx->d_wx2[l], ctx->d_bias[l], dst, n, w1p, b1p, nullptr, nullptr, kActScale,          \
                                      1.f / (kActScale * ctx->wx2_scale[l]), x3_stats)                                                               \
    : p2 ? launch_conv_x3<CFG, FUSE, 2>(st, src, ctx->d_wx2[l], ctx->d_bias[l], dst, n, w1p, b1p, nullptr, nullptr, kActScale,               \
                                      1.f / (kActScale * ctx->wx2_scale[l]), x3_stats)                                                               \
       : launch_conv_x3<CFG, FUSE, 3>(st, src, ctx->d_wx3[l], ctx->d_bias[l], dst, n, w1p, b1p, nullptr, nullptr, 1.f, 1.f,                \
                                      x3_stats))
-  if (ctx->net_split & 1) {
     // input_norm's mean / std of every patch once (k_patch_stats), in the head of the last layer's partial-sum buffer (free until that layer)
     hipLaunchKernelGGL(k_patch_stats, dim3(n), dim3(256), 0, st, d_patches, ctx->d_part, n);
     ASD_HIP_CHECK(ctx, hipGetLastError());
     x3_stats = ctx->d_part;
     ASD_HIP_CHECK(ctx, (X3_LAUNCH(L2S_CFG, true, 1, d_patches, a1, ctx->d_w1, ctx->d_bias[0])));
     x3_stats = nullptr;
-  }
-  else ASD_HIP_CHECK(ctx, (launch_conv<L2_CFG, true>(st, d_patches, ctx->d_wimg[1], ctx->d_bias[1], a1, n, ctx->d_w1, ctx->d_bias[0])));
-  // calibration (asd_load_weights): the largest |activation| each layer hands to the next one
-#define CALIB(l, buf, elems) do { if (ctx->d_calib) { hipLaunchKernelGGL(k_absmax, dim3(256), dim3(256), 0, st, buf, (size_t)n * (elems), ctx->d_calib + (l)); ASD_HIP_CHECK(ctx, hipGetLastError()); } } while (0)
-  CALIB(1, a1, 32 * 32 * 32);
-  PROF_MARK(2);
-  if (ctx->net_split & 2) ASD_HIP_CHECK(ctx, (X3_LAUNCH(L3S_CFG, false, 2, a1, a0, nullptr, nullptr)));
-  else
-  ASD_HIP_CHECK(ctx, (launch_conv_p<L3_CFG>(st, a1, ctx->d_wimg[2], ctx->d_bias[2], a0, n, ctx->num_cu)));
-  CALIB(2, a0, 16 * 16 * 64);
-  PROF_MARK(3);
-  const int ring = pair ? ctx->ring_mask : 0;   // asdnet_ring.hip (whole-patch LDS images, weights through an LDS-DMA ring): pair form only
-  float *src6 = a0, *dst6 = a1;   // conv6's input and output (the fc layer reads dst6)
-  if (ring & 4) {   // conv4 + conv5 in one launch (conv4's output never leaves LDS); the profile charges the launch to conv5's slot
-    PROF_MARK(4);
-    { const int rc = asdnet_ring_conv45(ctx, a0, a1, n, st); if (rc != ASD_OK) return rc; }
-    src6 = a1; dst6 = a0;
-  } else {
-    if (ring & 1) { const int rc = asdnet_ring_conv(ctx, 3, a0, a1, n, st); if (rc != ASD_OK) return rc; }
-    else if (ctx->net_split & 4) ASD_HIP_CHECK(ctx, (X3_LAUNCH(L4S_CFG, false, 3, a0, a1, nullptr, nullptr)));
-    else ASD_HIP_CHECK(ctx, (launch_conv<L4_CFG>(st, a0, ctx->d_wimg[3], ctx->d_bias[3], a1, n)));
+    CALIB(1, a1, 32 * 32 * 32);
+    PROF_MARK(2);
+    ASD_HIP_CHECK(ctx, (X3_LAUNCH(L3S_CFG, false, 2, a1, a0, nullptr, nullptr)));
+    CALIB(2, a0, 16 * 16 * 64);
+    PROF_MARK(3);
+    ASD_HIP_CHECK(ctx, (X3_LAUNCH(L4S_CFG, false, 3, a0, a1, nullptr, nullptr)));
     CALIB(3, a1, 16 * 16 * 64);
     PROF_MARK(4);
-    if (ctx->net_split & 8) ASD_HIP_CHECK(ctx, (X3_LAUNCH(L5S_CFG, false, 4, a1, a0, nullptr, nullptr)));
-    else
-    ASD_HIP_CHECK(ctx, (launch_conv<L5_CFG>(st, a1, ctx->d_wimg[4], ctx->d_bias[4], a0, n)));
-  }
-  CALIB(4, src6, 8 * 8 * 128);
-  PROF_MARK(5);
-  if (ring & 2) { const int rc = asdnet_ring_conv(ctx, 5, src6, dst6, n, st); if (rc != ASD_OK) return rc; }
-  else if (ctx->net_split & 16) ASD_HIP_CHECK(ctx, (X3_LAUNCH(L6S_CFG, false, 5, src6, dst6, nullptr, nullptr)));
-  else ASD_HIP_CHECK(ctx, (launch_conv<L6_CFG>(st, src6, ctx->d_wimg[5], ctx->d_bias[5], dst6, n)));
+    ASD_HIP_CHECK(ctx, (X3_LAUNCH(L5S_CFG, false, 4, a1, a0, nullptr, nullptr)));
+    CALIB(4, a0, 8 * 8 * 128);
+    PROF_MARK(5);
+    ASD_HIP_CHECK(ctx, (X3_LAUNCH(L6S_CFG, false, 5, a0, a1, nullptr, nullptr)));
 #undef X3_LAUNCH
-  CALIB(5, dst6, 8 * 8 * 128);
-#undef CALIB
-  PROF_MARK(6);
-  a1 = dst6;   // (the last layer's input)
-  ctx->d_act6 = dst6;
-  if (pair)
-    hipLaunchKernelGGL(k_fc_x2, dim3((npad + FCS_MP - 1) / FCS_MP, FC_SK), dim3(256), 0, st, reinterpret_cast<const uint8_t*>(a1),
-                       static_cast<const uint8_t*>(ctx->d_wx2[6]), ctx->d_part, n, npad, 1.f / (kActScale * ctx->wx2_scale[6]));
-  else if (ctx->net_split & 32)
-    hipLaunchKernelGGL(k_fc_x3, dim3((npad + FCS_MP - 1) / FCS_MP, FC_SK), dim3(256), 0, st, a1, static_cast<const uint8_t*>(ctx->d_wx3[6]), ctx->d_part, n, npad);
-  else
+    CALIB(5, a1, 8 * 8 * 128);
+    PROF_MARK(6);
+    if (pair)
+      hipLaunchKernelGGL(k_fc_x2, dim3((npad + FCS_MP - 1) / FCS_MP, FC_SK), dim3(256), 0, st, reinterpret_cast<const uint8_t*>(a1),
+                         static_cast<const uint8_t*>(ctx->d_wx2[6]), ctx->d_part, n, npad, 1.f / (kActScale * ctx->wx2_scale[6]));
+    else
+      hipLaunchKernelGGL(k_fc_x3, dim3((npad + FCS_MP - 1) / FCS_MP, FC_SK), dim3(256), 0, st, a1, static_cast<const uint8_t*>(ctx->d_wx3[6]), ctx->d_part, n, npad);
+  } else {   // ASD_ASDNET_MATH=f32: every layer on the f32 MFMA (K1, K1p, K2)
+    ASD_HIP_CHECK(ctx, (launch_conv<L2_CFG, true>(st, d_patches, ctx->d_wimg[1], ctx->d_bias[1], a1, n, ctx->d_w1, ctx->d_bias[0])));
+    CALIB(1, a1, 32 * 32 * 32);
+    PROF_MARK(2);
+    ASD_HIP_CHECK(ctx, (launch_conv_p<L3_CFG>(st, a1, ctx->d_wimg[2], ctx->d_bias[2], a0, n, ctx->num_cu)));
+    CALIB(2, a0, 16 * 16 * 64);
+    PROF_MARK(3);
+    ASD_HIP_CHECK(ctx, (launch_conv<L4_CFG>(st, a0, ctx->d_wimg[3], ctx->d_bias[3], a1, n)));
+    CALIB(3, a1, 16 * 16 * 64);
+    PROF_MARK(4);
+    ASD_HIP_CHECK(ctx, (launch_conv<L5_CFG>(st, a1, ctx->d_wimg[4], ctx->d_bias[4], a0, n)));
+    CALIB(4, a0, 8 * 8 * 128);
+    PROF_MARK(5);
+    ASD_HIP_CHECK(ctx, (launch_conv<L6_CFG>(st, a0, ctx->d_wimg[5], ctx->d_bias[5], a1, n)));
+    CALIB(5, a1, 8 * 8 * 128);
+    PROF_MARK(6);
     hipLaunchKernelGGL(k_fc_mfma, dim3((npad / 32 + FC_MT - 1) / FC_MT, FC_SK), dim3(256), 0, st, a1, ctx->d_wimg[6], ctx->d_part, n, npad);
+  }
+#undef CALIB
   ASD_HIP_CHECK(ctx, hipGetLastError());
   PROF_MARK(7);
   hipLaunchKernelGGL(k_l2norm, dim3((n + 3) / 4), dim3(256), 0, st, ctx->d_part, ctx->d_bias[6], d_desc, n, npad, range_flag);
@@ -1706,7 +1669,7 @@ static int asdnet_forward_one(asd_ctx* ctx, const uint8_t* d_patches, int n, flo
 static int asdnet_calibrate(asd_ctx* ctx, const float* const conv_w[7], const float* const bn_mean[7], const float* const bn_var[7], float eps) {
   ctx->calib_note.clear();
   ctx->net_pieces = ctx->net_pieces_req;   // every load starts from the form the context was created with: a fall-back is not sticky
-  if (ctx->net_pieces != 2 || !(ctx->net_split & 31)) return ASD_OK;   // only the fp16 form has a range
+  if (ctx->net_pieces != 2 || !ctx->net_split) return ASD_OK;   // only the fp16 form has a range
   if (const char* e = getenv("ASD_ASDNET_CALIBRATE")) if (atoi(e) == 0) return ASD_OK;   // tests of the run-time flag switch the guard at load off
   const int N = std::min(64, ctx->cfg.max_patches);   // (a context sized for fewer patches than the calibration set calibrates on what fits)
   constexpr float kCalibLimit = 2048.f;
@@ -1815,52 +1778,12 @@ int asdnet_profile_collect(asd_ctx* ctx) {
   return ASD_OK;
 }
 
-// debug / tuning aid (not part of the C ABI header): time conv2 with parts of the kernel removed
-// mode 0 = full, 1 = no activation staging, 2 = no MFMA, 3 = no epilogue stores
-template <int ABL>
-static int ablate_one(asd_ctx* ctx, int layer, int n, int reps, float* ms) {
-  hipStream_t st = ctx->stream;
-  float *a0 = ctx->d_act[0], *a1 = ctx->d_act[1];
-  hipError_t e = hipSuccess;
-  auto run = [&](int count) {
-    for (int r = 0; r < count; ++r) {
-      if (layer == 2) {
-        using C = ConvCfg<L2_CFG>;
-        constexpr int rows = C::M_PATCH / C::HO;
-        constexpr int lds = C::LDS_BYTES + ((rows + 4) * 36 + 320 + 8) * 4;
-        auto k = k_conv_mfma<L2_CFG, ABL, true>;
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-        hipLaunchKernelGGL(k, dim3(n * (C::HO / rows)), dim3(C::NTH), lds, st, (const void*)ctx->d_patches, ctx->d_wimg[1], ctx->d_bias[1], a1, ctx->d_w1, ctx->d_bias[0], n);
-      } else if (layer == 4) {
-        using C = ConvCfg<L4_CFG>;
-        auto k = k_conv_mfma<L4_CFG, ABL, false>;
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, C::LDS_BYTES);
-        hipLaunchKernelGGL(k, dim3(n * (C::HO * C::HO / C::M_PATCH)), dim3(C::NTH), C::LDS_BYTES, st, (const void*)a0, ctx->d_wimg[3], ctx->d_bias[3], a1, (const float*)nullptr, (const float*)nullptr, n);
-      } else {
-        using C = ConvCfg<L6_CFG>;
-        auto k = k_conv_mfma<L6_CFG, ABL, false>;
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, C::LDS_BYTES);
-        hipLaunchKernelGGL(k, dim3(((n + C::M_WG / C::M_PATCH - 1) / (C::M_WG / C::M_PATCH)) * (C::HO * C::HO / C::M_PATCH)), dim3(C::NTH), C::LDS_BYTES, st, (const void*)a0, ctx->d_wimg[5], ctx->d_bias[5], a1, (const float*)nullptr, (const float*)nullptr, n);
-      }
-    }
-  };
-  run(3);
-  ASD_HIP_CHECK(ctx, hipEventRecord(ctx->ev0, st));
-  run(reps);
-  ASD_HIP_CHECK(ctx, hipEventRecord(ctx->ev1, st));
-  ASD_HIP_CHECK(ctx, hipEventSynchronize(ctx->ev1));
-  ASD_HIP_CHECK(ctx, hipEventElapsedTime(ms, ctx->ev0, ctx->ev1));
-  *ms /= reps;
-  (void)e;
-  return ASD_OK;
-}
-
 // debug / test aid (not part of the C ABI header): the activation conv6 handed to the last layer in the most recent forward, first n
 // patches, as f32 [n][64 pixels][128 channels]; a context in the pair format returns (h + l) / kActScale (exact in f32).
 extern "C" int asd_debug_act6(asd_ctx* ctx, int n, float* out) {
   if (n < 0 || n > ctx->cfg.max_patches) return ASD_ERR_CAPACITY;
   ASD_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
-  const bool pair = kPairOK && ctx->net_pieces == 2 && (ctx->net_split & 63) == 63 && ctx->net_pair;
+  const bool pair = ctx->net_pieces == 2 && ctx->net_split && ctx->net_pair;
   const float* src = ctx->d_act6 ? ctx->d_act6 : ctx->d_act[1];
   if (!pair) { ASD_HIP_CHECK(ctx, hipMemcpy(out, src, (size_t)n * 8192 * 4, hipMemcpyDeviceToHost)); return ASD_OK; }
   std::vector<uint16_t> raw((size_t)n * 8192 * 2);
@@ -1887,9 +1810,9 @@ extern "C" int asd_debug_x3_clock(asd_ctx* ctx, int layer, int n, int reps, doub
     unsigned long long* sp = r + 1 == reps ? stamps : nullptr;
     hipError_t e = hipErrorInvalidValue;
     const bool p2 = ctx->net_pieces == 2;
-    const bool pair = kPairOK && p2 && (ctx->net_split & 63) == 63 && ctx->net_pair;
+    const bool pair = p2 && ctx->net_pair;
 #define X3_CLK(CFG, FUSE, l, src, dst, w1p, b1p)                                                                                          \
-  (pair ? launch_conv_x3<CFG, FUSE, 2, kPairOK>(st, src, ctx->d_wx2[l], ctx->d_bias[l], dst, n, w1p, b1p, sp, &grid, kActScale,               \
+  (pair ? launch_conv_x3<CFG, FUSE, 2, true>(st, src, ctx->d_wx2[l], ctx->d_bias[l], dst, n, w1p, b1p, sp, &grid, kActScale,                  \
                                      1.f / (kActScale * ctx->wx2_scale[l]))                                                                \
    : p2 ? launch_conv_x3<CFG, FUSE, 2>(st, src, ctx->d_wx2[l], ctx->d_bias[l], dst, n, w1p, b1p, sp, &grid, kActScale,                       \
                                      1.f / (kActScale * ctx->wx2_scale[l]))                                                                \
@@ -1921,23 +1844,4 @@ extern "C" int asd_debug_x3_clock(asd_ctx* ctx, int layer, int n, int reps, doub
     if (layer == 2) fprintf(stderr, "     since entry: patch arrived %.0f, staging loop done %.0f, barrier passed %.0f\n", med(9), med(12), med(13));
   }
   return ASD_OK;
-}
-
-// debug / tuning aid (not part of the C ABI header): time conv2 (fused) / conv4 / conv6 with parts removed.
-// mode bits: 1 = no input staging, 2 = no MFMA, 4 = no epilogue stores, 8 = no per-stage barrier, 16 = no weight streaming
-extern "C" int asd_debug_conv_ablate(asd_ctx* ctx, int layer, int n, int mode, int reps, float* ms) {
-  switch (mode) {
-    case 0: return ablate_one<0>(ctx, layer, n, reps, ms);
-    case 1: return ablate_one<1>(ctx, layer, n, reps, ms);
-    case 2: return ablate_one<2>(ctx, layer, n, reps, ms);
-    case 3: return ablate_one<3>(ctx, layer, n, reps, ms);
-    case 4: return ablate_one<4>(ctx, layer, n, reps, ms);
-    case 5: return ablate_one<5>(ctx, layer, n, reps, ms);
-    case 6: return ablate_one<6>(ctx, layer, n, reps, ms);
-    case 7: return ablate_one<7>(ctx, layer, n, reps, ms);
-    case 13: return ablate_one<13>(ctx, layer, n, reps, ms);   // MFMA loop, no per-stage barrier
-    case 21: return ablate_one<21>(ctx, layer, n, reps, ms);   // MFMA loop, no weight streaming
-    case 29: return ablate_one<29>(ctx, layer, n, reps, ms);   // MFMA loop, neither
-    default: return ASD_ERR_INVALID;
-  }
 }

@@ -112,8 +112,7 @@ int asd_ctx_create(const asd_config* cfg, asd_ctx** out) {
   }
   build_tables(c);
   // ASDNet arithmetic: split-operand kernels by default (two fp16 terms; ASD_ASDNET_MATH=bf16x3 for three bf16 terms);
-  // ASD_ASDNET_MATH=f32 keeps every layer on the f32 MFMA kernels,
-  // ASD_ASDNET_SPLIT_LAYERS=<mask> picks layers (bit 0 = conv2 ... bit 4 = conv6, bit 5 = fc)
+  // ASD_ASDNET_MATH=f32 keeps every layer on the f32 MFMA kernels (net_split: bit 0 = conv2 ... bit 4 = conv6, bit 5 = fc; all or none)
   c->net_split = 0x3f;
   if (const char* e = getenv("ASD_MATCH_REPLAY")) c->match_replay_host = !strcmp(e, "host");   // matcher.hip, k_resolve
   if (const char* e = getenv("ASD_BA_STRUCT")) c->ba_struct_host = !strcmp(e, "host");          // ba.hip, local_ba_impl
@@ -124,7 +123,6 @@ int asd_ctx_create(const asd_config* cfg, asd_ctx** out) {
     else if (strcmp(e, "split")) fprintf(stderr, "libasdhip: ASD_ASDNET_MATH=%s not understood (f32 | split | f16x2 | bf16x3); using f16x2\n", e);
   }
   c->net_pieces_req = c->net_pieces;
-  if (const char* e = getenv("ASD_ASDNET_SPLIT_LAYERS")) c->net_split = (int)strtol(e, nullptr, 0) & 0x3f;
   // tracking kernels (small, latency critical) outrank the pipelined extractor's stream
   int prio_least = 0, prio_greatest = 0;
   (void)hipDeviceGetStreamPriorityRange(&prio_least, &prio_greatest);

@@ -287,7 +287,7 @@ struct asd_ctx {
   float wx2_scale[7] = {1, 1, 1, 1, 1, 1, 1};
   int net_pieces_req = 2;       // the form asked for at asd_ctx_create (ASD_ASDNET_MATH); asd_load_weights starts from it every time
   int net_pieces = 2;           // 3 = bf16x3 (six products, exact operands), 2 = fp16x2 (three products, 22-bit operands)
-  int net_split = 1;            // ASD_ASDNET_MATH: 1 = split-bf16 kernels where a layer has one, 0 = f32 MFMA everywhere
+  int net_split = 0x3f;         // ASD_ASDNET_MATH: 0x3f = every layer on the split-operand kernels, 0 = f32 MFMA everywhere (asd_asdnet_split_mask)
   float* d_act[2] = {};         // ping-pong NHWC activations
   float* d_part = nullptr;      // split-K partials of the last layer
   int* h_range = nullptr;       // pinned: set by k_l2norm when a descriptor of an asd_describe* call came out non-finite (fp16x2 range)
@@ -295,8 +295,7 @@ struct asd_ctx {
   unsigned* d_calib = nullptr;  // calibration only: per-layer max |activation| as float bits (asdnet_forward_device fills it when set)
   bool pose_chain_kp_flags = false;   // the last pose_chain_enqueue wrote its outlier flags per keypoint (gather form of k_pose_opt)
   bool net_pair = true;         // two-piece form: activations between the layers as the fp16 piece pairs themselves (ASD_ASDNET_PAIR=0: f32 NHWC)
-  float* d_act6 = nullptr;      // where the last forward left conv6's output (d_act[0] or d_act[1]; asd_debug_act6)
-  int ring_mask = 0;            // ASD_ASDNET_RING: layers on the LDS-image / weight-ring kernels of asdnet_ring.hip (bit 0 conv4, bit 1 conv6, bit 2 conv4+conv5 fused)
+  float* d_act6 = nullptr;      // where the last forward left conv6's output (asd_debug_act6)
   uint8_t* d_patches = nullptr; // [max_patches][1024]
   float* d_desc = nullptr;      // [max_patches][128] descriptors of the last asd_extract / asd_describe
   bool keep_pyramid = false;    // asd_extract_keep_pyramid: every submission keeps a copy of its pyramid for asd_stereo_match
@@ -431,6 +430,3 @@ int asdnet_load_weights(asd_ctx* ctx, const float* const conv_w[7], const float*
 // range_flag: pinned host int the L2-norm kernel sets to 1 when a descriptor row is not finite (null = no report)
 int asdnet_forward_device(asd_ctx* ctx, const uint8_t* d_patches, int n, float* d_desc, hipStream_t st, int* range_flag = nullptr);
 int asdnet_profile_collect(asd_ctx* ctx);  // folds pending layer events into the totals (needs a synced stream)
-// asdnet_ring.hip: conv layers with both MFMA operands from LDS (whole-patch images, weights through an LDS-DMA ring); two-piece pair form only
-int asdnet_ring_conv(asd_ctx* ctx, int layer, const void* in, void* out, int n, hipStream_t st);
-int asdnet_ring_conv45(asd_ctx* ctx, const void* in, void* out, int n, hipStream_t st);

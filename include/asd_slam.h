@@ -667,7 +667,7 @@ int asd_profile_get(asd_ctx* ctx, int32_t layer, double* total_ms, int32_t* call
  * Both kernel families compute in f32: the split kernels write every f32 operand exactly as the sum of three bf16 terms
  * and accumulate the six significant cross products in f32 on the bf16 matrix pipe (error at the level of the f32 MFMA chain,
  * see asdnet.hip); the others use v_mfma_f32_32x32x2_f32.  Chosen at asd_ctx_create: environment ASD_ASDNET_MATH=f32 clears
- * every bit, ASD_ASDNET_SPLIT_LAYERS=<mask> sets them individually; default all conv layers split. */
+ * every bit; default all layers split (0x3f). */
 int32_t asd_asdnet_split_mask(const asd_ctx* ctx);
 /* How the split-operand 3x3 conv kernels carry an f32 operand (chosen at asd_ctx_create by ASD_ASDNET_MATH):
  *   2  ("f16x2", the default; "split" is an alias)  x 2^k = h + l with two fp16 terms (22 significant bits), the three products

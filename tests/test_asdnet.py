@@ -33,34 +33,6 @@ def test_hip_matches_golden(hip, asdnet_golden):
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("math", ["f16x2", "bf16x3"])
-def test_other_mfma_shape_build_matches_golden(pkg, synth, asdnet_golden, monkeypatch, math):
-    """build matrix: libasdhip_s32.so = the same sources with the split-operand kernels on the 32x32x16 MFMA shape
-    (ASD_X3_S16=0; the default is 16x16x32), in both operand forms.  Same golden descriptors, same tolerance, and within 2e-6
-    of the default build."""
-    import os
-    monkeypatch.setenv("ASD_ASDNET_MATH", math)
-    alt = os.path.join(os.path.dirname(pkg.lib_path()), "libasdhip_s32.so")
-    assert os.path.exists(alt), "libasdhip_s32.so not built: run __graft_entry__.build()"
-    monkeypatch.setenv("ASDHIP_LIB", alt)
-    other = pkg.AsdHip(n_features=500, max_width=640, max_height=240, max_patches=1024)
-    monkeypatch.delenv("ASDHIP_LIB")
-    base = pkg.AsdHip(n_features=500, max_width=640, max_height=240, max_patches=1024)
-    try:
-        g = asdnet_golden
-        layers = synth.asdnet_weights(int(g["weight_seed"]))
-        other.load_weights(layers)
-        base.load_weights(layers)
-        assert other.asdnet_split_mask() == 63 and other.asdnet_pieces() == (2 if math == "f16x2" else 3)
-        a, b = other.describe(g["patches"]), base.describe(g["patches"])
-        np.testing.assert_allclose(a, g["desc"], atol=DESC_ATOL, rtol=0)
-        np.testing.assert_allclose(a, b, atol=2e-6, rtol=0)
-    finally:
-        other.close()
-        base.close()
-
-
-@pytest.mark.gpu
 @pytest.mark.parametrize("n", [1, 31, 33, 257])
 def test_hip_matches_oracle_ragged(hip, oracle, synth, n):
     layers = synth.asdnet_weights(0)
@@ -246,33 +218,6 @@ def test_pair_format_is_bit_identical(pkg, synth, asdnet_golden, monkeypatch):
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("mask", [1, 2, 4, 6])
-def test_ring_kernels_are_bit_identical(pkg, synth, asdnet_golden, monkeypatch, mask):
-    """asdnet_ring.hip (whole-patch LDS images, weights through an LDS-DMA ring, conv4 -> conv5 fused through LDS) performs the products of
-    k_conv_x3's two-piece form in the same order, so the activation conv6 hands to the last layer and the descriptors are the same BITS as the
-    layer-by-layer kernels' (ASD_ASDNET_RING=0).  mask: bit 0 conv4, bit 1 conv6, bit 2 conv4 + conv5 in one launch.  Odd patch counts
-    exercise the two-patch tiles of conv6 and the persistent loop (more tiles than workgroups is covered at N = 2000 by the golden tests)."""
-    patches = np.concatenate([asdnet_golden["patches"], synth.random_patches(437, seed=23), np.full((2, 32, 32), 91, np.uint8)])
-    monkeypatch.setenv("ASD_ASDNET_RING", "0")
-    ref = pkg.AsdHip(n_features=500, max_width=640, max_height=240, max_patches=1024)
-    monkeypatch.setenv("ASD_ASDNET_RING", str(mask))
-    new = pkg.AsdHip(n_features=500, max_width=640, max_height=240, max_patches=1024)
-    monkeypatch.delenv("ASD_ASDNET_RING")
-    try:
-        w = synth.asdnet_weights(int(asdnet_golden["weight_seed"]))
-        ref.load_weights(w)
-        new.load_weights(w)
-        for n in (len(patches), 1, 64):
-            a, b = new.describe(patches[:n]), ref.describe(patches[:n])
-            np.testing.assert_array_equal(new.debug_act6(n), ref.debug_act6(n))
-            np.testing.assert_array_equal(a, b)
-        np.testing.assert_allclose(a[:64], asdnet_golden["desc"], atol=DESC_ATOL, rtol=0)
-    finally:
-        ref.close()
-        new.close()
-
-
-@pytest.mark.gpu
 def test_f16x2_range_is_an_error_not_a_nan(pkg, synth, monkeypatch):
     """f16x2 carries activations * 16 in fp16: an activation beyond 4094 cannot be represented.  Two guards (include/asd_slam.h,
     asd_asdnet_pieces): asd_load_weights' calibration batch notices weights that drive a layer past 2048 and switches the context to
@@ -350,7 +295,7 @@ def test_lds_reads_are_conflict_free(layer, CIN, HIN, S, ROWS):
     ds_read_b128 lane group touch sixteen different 16-B slots of the 256-B bank row, and the lane -> pixel map is a bijection
     onto the workgroup's output pixels.  A model of the address arithmetic in X3Cfg / conv_x3_tile (same constants, same
     expressions), not a run of the kernel: the kernel's bits are checked by the golden tests above, its LDS counters by
-    tools/ring_pmc.sh."""
+    tools/asdnet_pmc.sh."""
     HO = HIN // S
     INCOLS = (HO - 1) * S + 3
     PIXB = CIN * 4 + 16

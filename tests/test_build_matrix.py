@@ -13,8 +13,6 @@ CASES = [
     ({"ASD_UPLOAD_COPY": "1"}, ["tests/test_track_chain.py", "tests/test_matcher.py::test_host_and_device_replay_agree"]),
     # one extraction worker instead of two
     ({"ASD_EXTRACT_WORKERS": "1"}, ["tests/test_bench_host.py", "tests/test_kitti_configs.py"]),
-    # the experimental LDS-image / weight-ring ASDNet kernels (asdnet_ring.hip) through the whole extractor
-    ({"ASD_ASDNET_RING": "6"}, ["tests/test_asdnet.py", "tests/test_frontend.py::test_extract_kitti_size_bit_exact"]),
 ]
 
 

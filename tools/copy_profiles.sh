@@ -9,6 +9,6 @@ cp $O/bench_euroc_stereo.json $P/r05_bench_euroc_stereo.json; cp $O/kf_ops.json 
 cp $O/traffic_conv2.json $P/r05_traffic_conv2.json; cp $O/traffic_conv2.json $P/traffic_conv2.json; cp $O/asdnet_mfma_util.json $P/r05_asdnet_mfma_util.json
 cp $O/time_asdnet.txt $P/r05_time_asdnet.txt; cp $O/ba_times.txt $P/r05_ba_times.txt
 cp $O/prof_ba/ba_kernel_stats.csv $P/r05_local_ba_kernel_stats.csv
-cp $O/asdnet_phases.txt $P/r05_asdnet_phases.txt; cp $O/asdnet_ring_times.txt $P/r05_asdnet_ring_times.txt
-cp $O/asdnet_sq_counters_default.txt $P/r05_asdnet_sq_counters_default.txt; cp $O/asdnet_sq_counters_ring.txt $P/r05_asdnet_sq_counters_ring.txt
+cp $O/asdnet_phases.txt $P/r05_asdnet_phases.txt
+cp $O/asdnet_sq_counters_default.txt $P/r05_asdnet_sq_counters_default.txt
 cp $O/pose_determinism.txt $P/r05_pose_determinism.txt

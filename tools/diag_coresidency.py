@@ -1,8 +1,7 @@
 """Library-level view of the round-1 co-residency failure: asd_dist_matrix (caller's stream) while the read-ahead
 extractor runs ASDNet on its own streams.  Run once per library build:
 
-    ASDHIP_LIB=asd-slam_amd/libasdhip_slp.so python tools/diag_coresidency.py     # SLP-vectorised victims, 16x16x32 MFMA
-    ASDHIP_LIB=asd-slam_amd/libasdhip_slp32.so python tools/diag_coresidency.py   # SLP-vectorised victims, 32x32x16 MFMA
+    ASDHIP_LIB=asd-slam_amd/libasdhip_slp.so python tools/diag_coresidency.py     # SLP-vectorised victims
     python tools/diag_coresidency.py                                              # shipped build
 
 Prints, per build, how many of the concurrent asd_dist_matrix calls returned a value that differs from the same call made on

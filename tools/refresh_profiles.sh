@@ -34,11 +34,9 @@ rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_ba -o ba -- pyth
 find $O/prof_ba -name "*kernel_trace.csv" -delete
 # what a workgroup of every conv layer spends its life on, at three load levels (in-kernel stamps)
 for n in 64 256 2000; do echo "n=$n"; ASD_X3_PHASES=1 python3 tools/x3_clock.py $n 2>&1; done > $O/asdnet_phases.txt
-# the experimental LDS-image / weight-ring kernels (asdnet_ring.hip): per-layer times and SQ counters beside the default kernels'
-for m in 0 1 2 4 6; do echo "ASD_ASDNET_RING=$m"; ASD_ASDNET_RING=$m python3 tools/time_asdnet.py 2000 20 2>&1 | tail -2; done > $O/asdnet_ring_times.txt
-RING=0 bash tools/ring_pmc.sh > $O/asdnet_sq_counters_default.txt 2>&1
-RING=6 bash tools/ring_pmc.sh > $O/asdnet_sq_counters_ring.txt 2>&1
-rm -rf gpurun_out/ringpmc
+# SQ counters of the split-operand conv kernels (LDS busy / bank conflicts, instruction mix, waits, matrix-pipe cycles)
+bash tools/asdnet_pmc.sh > $O/asdnet_sq_counters_default.txt 2>&1
+rm -rf out/asdnet_pmc
 # PoseOptimization beside the extractor: one result over thousands of calls
 python3 tools/diag/pose_determinism.py 3000 beside > $O/pose_determinism.txt 2>&1
 python3 tools/diag/ba_determinism.py 600 >> $O/pose_determinism.txt 2>&1

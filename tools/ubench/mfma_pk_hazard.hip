@@ -1,4 +1,4 @@
-// Stand-alone reproducer for the round-1 co-residency failure (asdnet.hip, ASD_X3_S16): does a kernel that issues
+// Stand-alone reproducer for the round-1 co-residency failure (asdnet.hip, the split-operand kernels): does a kernel that issues
 // v_mfma_f32_16x16x32_bf16 corrupt packed-f32 vector arithmetic (v_pk_add_f32 / v_pk_mul_f32) of ANOTHER kernel running on
 // the same CUs?  No library code: an aggressor kernel (bare MFMA loop, random bf16 operands in registers, optional LDS
 // traffic) runs on stream A for tens of milliseconds; a victim kernel runs repeatedly on stream B meanwhile and every lane's
