@@ -757,6 +757,18 @@ class AsdHip:
                                          int(check_ori), _p(out), C.byref(n)))
         return out, n.value
 
+    def match_bow_kf(self, slot1, slot2, n1, nodes1, nodes2, has_mp1, has_mp2, nn_ratio=0.85, check_ori=True):
+        """ORBmatcher::SearchByBoW(KeyFrame*, KeyFrame*, vpMatches12) (ORBmatcher.cc:533-666; LoopClosing.cc:277 builds the matcher
+        with nnratio 0.85 and the orientation check): (match12[n1] = keypoint of keyframe 2 or -1, number of matches)"""
+        fa, ka = make_fv(nodes1)
+        fb, kb = make_fv(nodes2)
+        h1, h2 = _c(has_mp1, np.uint8), _c(has_mp2, np.uint8)
+        out = np.empty(n1, np.int32)
+        n = C.c_int32()
+        self._chk(self.lib.asd_match_bow_kf(self.ctx, slot1, slot2, C.byref(fa), C.byref(fb), _p(h1), _p(h2), C.c_float(nn_ratio),
+                                            int(check_ori), _p(out), C.byref(n)))
+        return out, n.value
+
     def match_triangulate(self, slot1, slot2, n1, nodes1, nodes2, has_mp1, has_mp2, F12, ex, ey, check_ori=False):
         fa, ka = make_fv(nodes1)
         fb, kb = make_fv(nodes2)
@@ -777,6 +789,28 @@ class AsdHip:
         self._chk(self.lib.asd_pose_optimize(self.ctx, _p(pose), n, _p(Xw), _p(obs), _p(inv_sigma2), _p(K),
                                              _p(outlier), C.byref(ninl)))
         return pose, outlier, ninl.value
+
+    def optimize_sim3(self, sim3, P1c, P2c, obs1, obs2, inv_sigma2_1, inv_sigma2_2, K1, K2, th2=10.0, fix_scale=False):
+        """Optimizer::OptimizeSim3 (Optimizer.cc:1002-1194) over n correspondences: (sim3[8] = qx qy qz qw tx ty tz s, keep[n], nIn).
+        On the early return (fewer than 10 pairs left after the first round) sim3 comes back as it went in and nIn is 0."""
+        S = _c(sim3, np.float64).copy()
+        a = [_c(x, np.float64) for x in (P1c, P2c, obs1, obs2, inv_sigma2_1, inv_sigma2_2, K1, K2)]
+        n = len(a[4])
+        keep = np.zeros(n, np.uint8)
+        n_in = C.c_int32()
+        self._chk(self.lib.asd_optimize_sim3(self.ctx, _p(S), n, *[_p(x) for x in a], C.c_float(th2), int(bool(fix_scale)),
+                                             _p(keep), C.byref(n_in)))
+        return S, keep, n_in.value
+
+    def debug_optimize_sim3(self):
+        """what the last optimize_sim3 did: dict(rounds=[dict(active, iterations, trials, ends_rejected)] for the rounds that ran,
+        n_bad, cap (the second round's iteration limit, 5 or 10), early, n) -- asd_debug_optimize_sim3"""
+        out = np.full(12, -1, np.int32)
+        self.lib.asd_debug_optimize_sim3.restype = C.c_int32
+        self._chk(self.lib.asd_debug_optimize_sim3(self.ctx, _p(out)))
+        rounds = [dict(active=int(out[4 * r]), iterations=int(out[4 * r + 1]), trials=int(out[4 * r + 2]), ends_rejected=int(out[4 * r + 3]))
+                  for r in range(2) if out[4 * r] >= 0]
+        return dict(rounds=rounds, n_bad=int(out[8]), cap=int(out[9]), early=int(out[10]), n=int(out[11]))
 
     def _ba_pack(self, prob, its_first, its_second):
         poses = _c(prob["poses"], np.float64).copy()

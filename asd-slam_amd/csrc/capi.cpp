@@ -13,6 +13,7 @@ void matcher_free(asd_ctx* ctx);
 void ba_free(asd_ctx* ctx);
 void mapping_free(asd_ctx* ctx);
 void bow_free(asd_ctx* ctx);
+void sim3_free(asd_ctx* ctx);
 
 namespace {
 inline int cv_round(double v) { return (int)std::lrint(v); }  // cvRound: round-half-to-even
@@ -155,6 +156,7 @@ int asd_ctx_destroy(asd_ctx* ctx) {
   ba_free(ctx);
   mapping_free(ctx);
   bow_free(ctx);
+  sim3_free(ctx);
   ctx->scratch.release();
   ctx->stereo_scratch.release();
   ctx->up.release();
@@ -247,6 +249,7 @@ int asd_last_stage_ms(const asd_ctx* ctx, const char* stage, float* ms) {
   else if (!strcmp(stage, "extract")) *ms = ctx->ms_extract;
   else if (!strcmp(stage, "match")) *ms = ctx->ms_match;
   else if (!strcmp(stage, "ba")) *ms = ctx->ms_ba;
+  else if (!strcmp(stage, "sim3")) *ms = ctx->ms_sim3;
   else return ASD_ERR_INVALID;
   return ASD_OK;
 }

@@ -333,6 +333,9 @@ struct asd_ctx {
   // ---- vocabulary + BoW scratch (state private to bow.hip)
   void* bow = nullptr;
 
+  // ---- OptimizeSim3's test aid (state private to sim3.hip)
+  void* sim3 = nullptr;
+
   // ---- per-layer profiling (asd_profile_enable).  The extraction worker enqueues forwards while the caller enables /
   // reads the profile: every access to the prof_* fields below happens under prof_mutex.
   std::mutex prof_mutex;
@@ -347,7 +350,7 @@ struct asd_ctx {
 
   // ---- timing
   hipEvent_t ev0 = nullptr, ev1 = nullptr, ev2 = nullptr;
-  float ms_asdnet = 0, ms_extract = 0, ms_match = 0, ms_ba = 0;
+  float ms_asdnet = 0, ms_extract = 0, ms_match = 0, ms_ba = 0, ms_sim3 = 0;
 
   // the extraction worker thread reports errors too: the message is written under a lock, and asd_last_error hands
   // out a copy that stays put until the next call of asd_last_error on this context
@@ -393,6 +396,7 @@ void matcher_free(asd_ctx* ctx);
 void ba_free(asd_ctx* ctx);
 void mapping_free(asd_ctx* ctx);
 void bow_free(asd_ctx* ctx);
+void sim3_free(asd_ctx* ctx);
 // The claim replay that makes d_src, to run in FRONT of the solver inside its workgroup (k_resolve_pose, ba.hip) instead of as a kernel of
 // its own: args = the Resolve2Args of resolve2.h (both translation units include it), kind 0 / 1, nq = its query count, lds = the
 // dynamic LDS the replay needs.  pose_chain_fused_ok says whether that form exists for (kind, nq, n_cur).

@@ -2844,6 +2844,55 @@ int asd_match_bow(asd_ctx* ctx, int32_t slot_kf, int32_t slot_f, const asd_featu
   return ASD_OK;
 }
 
+// SearchByBoW(KeyFrame*, KeyFrame*, ...) (ORBmatcher.cc:533-666): the same list search, another replay.  A candidate of keyframe 2
+// needs a map point and must not have been taken (vbMatched2, :587), the claim is on keyframe 2's index, the threshold is strict
+// (:609) and the histogram holds idx1 (:625).
+int asd_match_bow_kf(asd_ctx* ctx, int32_t slot1, int32_t slot2, const asd_feature_vector* fv1, const asd_feature_vector* fv2,
+                     const uint8_t* has_mp1, const uint8_t* has_mp2, float nn_ratio, int32_t check_orientation,
+                     int32_t* match12, int32_t* n_matches) {
+  AsdFrameSlot *K1 = slot_of(ctx, slot1), *K2 = slot_of(ctx, slot2);
+  if (!K1 || !K2 || !has_mp1 || !has_mp2 || !match12 || !n_matches || !fv_valid(fv1, K1->n) || !fv_valid(fv2, K2->n)) return ASD_ERR_INVALID;
+  (void)hipSetDevice(ctx->cfg.device);
+  MatcherState* m = mstate(ctx);
+  std::fill(match12, match12 + K1->n, -1);
+  *n_matches = 0;
+  std::vector<ListQuery> lq;
+  const float* dist = nullptr;
+  int rc = list_search(ctx, m, *K1, *K2, fv1, fv2, has_mp1, /*skip_if_set=*/false, lq, &dist);
+  if (rc != ASD_OK) return rc;
+  int nmatches = 0;
+  std::vector<uint8_t> matched2((size_t)K2->n, 0);
+  std::vector<int> hist[HISTO];
+  for (const ListQuery& Q : lq) {  // reference order: node by node, keyframe 1's keypoints of the node in order (:561-634)
+    float best1 = 256, best2 = 256;
+    int best_idx = -1;
+    for (int t = Q.cbeg; t < Q.cend; ++t) {
+      const int j = fv2->idx[t];
+      if (matched2[j] || !has_mp2[j]) continue;
+      const float d = dist[Q.ooff + (t - Q.cbeg)];
+      if (d < best1) { best2 = best1; best1 = d; best_idx = j; }
+      else if (d < best2) best2 = d;
+    }
+    if (best1 < TH_LOW && best1 < nn_ratio * best2) {
+      match12[Q.qrow] = best_idx;
+      matched2[best_idx] = 1;
+      if (check_orientation) hist[rot_bin(K1->kps[Q.qrow].angle, K2->kps[best_idx].angle)].push_back(Q.qrow);
+      nmatches++;
+    }
+  }
+  if (check_orientation) {
+    int cnt[HISTO], a, b, c;
+    for (int k = 0; k < HISTO; ++k) cnt[k] = (int)hist[k].size();
+    three_maxima(cnt, a, b, c);
+    for (int k = 0; k < HISTO; ++k) {
+      if (k == a || k == b || k == c) continue;
+      for (int i1 : hist[k]) { match12[i1] = -1; nmatches--; }
+    }
+  }
+  *n_matches = nmatches;
+  return ASD_OK;
+}
+
 int asd_match_triangulate(asd_ctx* ctx, int32_t slot1, int32_t slot2, const asd_feature_vector* fv1,
                           const asd_feature_vector* fv2, const uint8_t* has_mp1, const uint8_t* has_mp2, const float* F12,
                           float ex, float ey, int32_t check_orientation, int32_t* matches12, int32_t* n_matches) {

@@ -232,6 +232,28 @@ class ORBmatcher {
     return n;
   }
 
+  // int SearchByBoW(KeyFrame* pKF1, KeyFrame* pKF2, vector<MapPoint*>& vpMatches12)  (:533), the loop-closing overload
+  // (LoopClosing.cc:304).  vpMatches12[i1] = pKF2's map point id matched to pKF1's keypoint i1, -1 = NULL; vnIdx2[i1] = that
+  // point's keypoint in pKF2 (what pMP2->GetIndexInKeyFrame(pKF2) gives OptimizeSim3, Optimizer.cc:1063).  mvpMapPoints[i] >= 0
+  // stands for "the keyframe has a map point there and it is not bad".
+  int SearchByBoW(const FrameView& KF1, const FeatVec& fv1, const FrameView& KF2, const FeatVec& fv2, std::vector<int32_t>& vpMatches12,
+                  std::vector<int32_t>& vnIdx2) {
+    std::vector<uint8_t> h1(KF1.N(), 0), h2(KF2.N(), 0);
+    for (int i = 0; i < KF1.N(); ++i) h1[i] = KF1.mvpMapPoints.size() == (size_t)KF1.N() && KF1.mvpMapPoints[i] >= 0;
+    for (int i = 0; i < KF2.N(); ++i) h2[i] = KF2.mvpMapPoints.size() == (size_t)KF2.N() && KF2.mvpMapPoints[i] >= 0;
+    vnIdx2.assign(KF1.N(), -1);
+    vpMatches12.assign(KF1.N(), -1);
+    int32_t n = 0;
+    const asd_feature_vector a = fv1.view(), b = fv2.view();
+    if (asd_match_bow_kf(c_.get(), KF1.slot, KF2.slot, &a, &b, h1.data(), h2.data(), mfNNratio, mbCheckOrientation, vnIdx2.data(), &n) != ASD_OK) {
+      vnIdx2.assign(KF1.N(), -1);
+      return 0;
+    }
+    for (int i = 0; i < KF1.N(); ++i)
+      if (vnIdx2[i] >= 0) vpMatches12[i] = KF2.mvpMapPoints[vnIdx2[i]];
+    return n;
+  }
+
   // int SearchForTriangulation(KeyFrame* pKF1, KeyFrame* pKF2, cv::Mat F12, vector<pair<size_t,size_t>>& vMatchedPairs,
   //                            bool bOnlyStereo)  (:669).  (ex, ey) = epipole of camera 1 in image 2 (:675-683).
   int SearchForTriangulation(const FrameView& KF1, const FeatVec& fv1, const FrameView& KF2, const FeatVec& fv2, const float F12[9],
@@ -304,6 +326,43 @@ struct Optimizer {
     for (size_t k = 0; k < idx.size(); ++k) pFrame->mvbOutlier[idx[k]] = out[k];
     asd_pose7_to_tcw(pose, pFrame->mTcw);
     return ninl;
+  }
+
+  // int static OptimizeSim3(KeyFrame* pKF1, KeyFrame* pKF2, vector<MapPoint*>& vpMatches1, g2o::Sim3& g2oS12, const float th2,
+  //                         const bool bFixScale)  (Optimizer.cc:1002).  vpMatches1[i] = pKF2's map point id matched to pKF1's keypoint i
+  // (-1 = NULL) and vnIdx2[i] its keypoint in pKF2, as SearchByBoW / SearchBySim3 leave them; `points` = the caller's map point
+  // table those ids index.  g2oS12 = qx qy qz qw tx ty tz s.  Returns nIn; matches the optimiser dropped are set to -1 in both
+  // vectors; on the early return (:1165) it returns 0 and leaves g2oS12 alone.  invLevelSigma2_1 / _2 = mvInvLevelSigma2.
+  static int OptimizeSim3(Context& c, const FrameView& KF1, const FrameView& KF2, const std::vector<MapPointView>& points,
+                          std::vector<int32_t>& vpMatches1, std::vector<int32_t>& vnIdx2, double g2oS12[8], float th2, bool bFixScale,
+                          const Camera& K1, const Camera& K2, const std::vector<float>& invLevelSigma2_1,
+                          const std::vector<float>& invLevelSigma2_2) {
+    std::vector<int> idx;
+    std::vector<double> P1c, P2c, o1, o2, s1, s2;
+    auto to_camera = [](const float* T, const float* X, std::vector<double>& out) {   // R * P3Dw + t in f32 (cv::Mat CV_32F), :1071
+      for (int r = 0; r < 3; ++r) out.push_back((double)((T[r * 4] * X[0] + T[r * 4 + 1] * X[1] + T[r * 4 + 2] * X[2]) + T[r * 4 + 3]));
+    };
+    for (int i = 0; i < KF1.N(); ++i) {
+      if (vpMatches1[i] < 0) continue;
+      const int i2 = vnIdx2[i];
+      if (KF1.mvpMapPoints[i] < 0 || i2 < 0) continue;                               // :1065-1089
+      idx.push_back(i);
+      to_camera(KF1.mTcw, points[KF1.mvpMapPoints[i]].Xw, P1c);
+      to_camera(KF2.mTcw, points[vpMatches1[i]].Xw, P2c);
+      o1.push_back(KF1.mvKeysUn[i].x); o1.push_back(KF1.mvKeysUn[i].y);
+      o2.push_back(KF2.mvKeysUn[i2].x); o2.push_back(KF2.mvKeysUn[i2].y);
+      s1.push_back(invLevelSigma2_1[KF1.mvKeysUn[i].octave]);
+      s2.push_back(invLevelSigma2_2[KF2.mvKeysUn[i2].octave]);
+    }
+    const double k1[4] = {K1.fx, K1.fy, K1.cx, K1.cy}, k2[4] = {K2.fx, K2.fy, K2.cx, K2.cy};
+    std::vector<uint8_t> keep(idx.size() + 1, 0);
+    int32_t nIn = 0;
+    if (asd_optimize_sim3(c.get(), g2oS12, (int32_t)idx.size(), P1c.data(), P2c.data(), o1.data(), o2.data(), s1.data(), s2.data(), k1, k2, th2,
+                          bFixScale, keep.data(), &nIn) != ASD_OK)
+      return 0;
+    for (size_t k = 0; k < idx.size(); ++k)
+      if (!keep[k]) { vpMatches1[idx[k]] = -1; vnIdx2[idx[k]] = -1; }
+    return nIn;
   }
 
   // void static LocalBundleAdjustment(KeyFrame* pKF, bool* pbStopFlag, Map* pMap)  (Optimizer.cc:415): the
@@ -409,6 +468,110 @@ struct LocalMapping {
   static int LocalBundleAdjustmentSubmit(Context& c, asd_ba_problem* problem, asd_ba_result* result) { return asd_local_ba_submit(c.get(), problem, result); }
   static int LocalBundleAdjustmentWait(Context& c) { return asd_local_ba_wait(c.get()); }
   static bool Busy(Context& c) { return asd_local_ba_poll(c.get()) == 1; }
+};
+
+// LoopClosing::ComputeSim3, the numeric body for ONE loop candidate (LoopClosing.cc:304, :346-375, :415): every search and the
+// refinement run behind the C ABI; what stays with the caller is Sim3Solver (:312-337, a three-point closed form inside RANSAC),
+// handed in as a callback that turns the BoW matches into (s, R row-major 3x3, t) of pKF2 -> mpCurrentKF, or returns false.
+struct LoopClosing {
+  struct Result { bool bMatch = false; int nBoW = 0, nSim3 = 0, nInliers = 0, nTotalMatches = 0; double g2oScm[8] = {0, 0, 0, 1, 0, 0, 0, 1}; };
+  // `points` = the caller's map point table (ids as in mvpMapPoints); vpLoopMapPoints = ids of the points of the loop keyframe and
+  // its neighbours (:393-412); vpCurrentMatchedPoints[i] = id matched to the current keyframe's keypoint i on return.
+  template <class Sim3SolverFn>
+  static Result ComputeSim3Candidate(Context& c, const FrameView& CurrentKF, const ORBmatcher::FeatVec& fvCur, const FrameView& KF,
+                                     const ORBmatcher::FeatVec& fvKF, const std::vector<MapPointView>& points,
+                                     const std::vector<int32_t>& vpLoopMapPoints, const Camera& K, const std::vector<float>& invLevelSigma2,
+                                     bool bFixScale, Sim3SolverFn solver, std::vector<int32_t>& vpCurrentMatchedPoints) {
+    Result r;
+    ORBmatcher matcher(c, 0.85f, true);                                                   // :277
+    std::vector<int32_t> vpMatches, vnIdx2;
+    r.nBoW = matcher.SearchByBoW(CurrentKF, fvCur, KF, fvKF, vpMatches, vnIdx2);          // :304
+    if (r.nBoW < 20) return r;                                                            // :305
+    float s = 1.f, R[9], t[3];
+    if (!solver(vpMatches, vnIdx2, &s, R, t)) return r;                                   // :337 (the caller keeps only the RANSAC inliers, :349-354)
+    // matcher.SearchBySim3(mpCurrentKF, pKF, vpMapPointMatches, s, R, t, 7.5)  (:359)
+    const int n1 = CurrentKF.N(), n2 = KF.N();
+    auto gather = [&](const FrameView& F, std::vector<uint8_t>& has, std::vector<float>& Xw, std::vector<float>& mind, std::vector<float>& maxd,
+                      std::vector<float>& desc) {
+      has.assign(F.N(), 0); Xw.assign((size_t)F.N() * 3, 0.f); mind.assign(F.N(), 0.f); maxd.assign(F.N(), 0.f); desc.assign((size_t)F.N() * ASD_DESC_DIM, 0.f);
+      for (int i = 0; i < F.N(); ++i) {
+        const int id = F.mvpMapPoints.size() == (size_t)F.N() ? F.mvpMapPoints[i] : -1;
+        if (id < 0) continue;
+        has[i] = 1;
+        for (int k = 0; k < 3; ++k) Xw[3 * i + k] = points[id].Xw[k];
+        mind[i] = points[id].mfMinDistance; maxd[i] = points[id].mfMaxDistance;
+        for (int k = 0; k < ASD_DESC_DIM; ++k) desc[(size_t)i * ASD_DESC_DIM + k] = points[id].descriptor[k];
+      }
+    };
+    std::vector<uint8_t> has1, has2;
+    std::vector<float> X1, X2, mn1, mx1, mn2, mx2, d1, d2;
+    gather(CurrentKF, has1, X1, mn1, mx1, d1);
+    gather(KF, has2, X2, mn2, mx2, d2);
+    for (int i = 0; i < n1; ++i)                                                          // vbAlreadyMatched1 / 2 (ORBmatcher.cc:1118-1134)
+      if (vpMatches[i] >= 0) { has1[i] = 0; if (vnIdx2[i] >= 0) has2[vnIdx2[i]] = 0; }
+    std::vector<int32_t> m12(n1, -1);
+    int32_t nfound = 0;
+    const float Kv[4] = {K.fx, K.fy, K.cx, K.cy};
+    if (asd_match_sim3(c.get(), CurrentKF.slot, KF.slot, has1.data(), has2.data(), X1.data(), X2.data(), mn1.data(), mx1.data(), mn2.data(), mx2.data(),
+                       d1.data(), d2.data(), CurrentKF.mTcw, KF.mTcw, s, R, t, Kv, 7.5f, m12.data(), &nfound) != ASD_OK)
+      return r;
+    for (int i = 0; i < n1; ++i)
+      if (m12[i] >= 0 && m12[i] < n2) { vpMatches[i] = KF.mvpMapPoints[m12[i]]; vnIdx2[i] = m12[i]; }
+    r.nSim3 = nfound;
+    // g2o::Sim3 gScm(R, t, s); Optimizer::OptimizeSim3(mpCurrentKF, pKF, vpMapPointMatches, gScm, 10, mbFixScale)  (:361-362)
+    double q[4];
+    {
+      double pose[7];
+      const float T[16] = {R[0], R[1], R[2], t[0], R[3], R[4], R[5], t[1], R[6], R[7], R[8], t[2], 0, 0, 0, 1};
+      asd_tcw_to_pose7(T, pose);
+      for (int k = 0; k < 4; ++k) q[k] = pose[k];
+    }
+    double S[8] = {q[0], q[1], q[2], q[3], t[0], t[1], t[2], s};
+    r.nInliers = Optimizer::OptimizeSim3(c, CurrentKF, KF, points, vpMatches, vnIdx2, S, 10.f, bFixScale, K, K, invLevelSigma2, invLevelSigma2);
+    for (int k = 0; k < 8; ++k) r.g2oScm[k] = S[k];
+    if (r.nInliers < 20) return r;                                                        // :364
+    r.bMatch = true;
+    // mg2oScw = gScm * gSmw, gSmw = (pKF's rotation, translation, 1)  (:368-370); mScw = Converter::toCvMat(mg2oScw) = [s R | t]
+    float Scw[16];
+    {
+      const double pose[7] = {S[0], S[1], S[2], S[3], 0, 0, 0};
+      float Rm[16];
+      asd_pose7_to_tcw(pose, Rm);
+      for (int i = 0; i < 3; ++i) {
+        for (int j = 0; j < 3; ++j) {
+          double a = 0;
+          for (int k = 0; k < 3; ++k) a += (double)Rm[i * 4 + k] * KF.mTcw[k * 4 + j];
+          Scw[i * 4 + j] = (float)(S[7] * a);
+        }
+        double b = 0;
+        for (int k = 0; k < 3; ++k) b += (double)Rm[i * 4 + k] * KF.mTcw[k * 4 + 3];
+        Scw[i * 4 + 3] = (float)(S[7] * b + S[4 + i]);
+      }
+      Scw[12] = Scw[13] = Scw[14] = 0.f; Scw[15] = 1.f;
+    }
+    // matcher.SearchByProjection(mpCurrentKF, mScw, mvpLoopMapPoints, mvpCurrentMatchedPoints, 10)  (:415)
+    const int nl = (int)vpLoopMapPoints.size();
+    std::vector<uint8_t> valid(nl, 1);
+    std::vector<float> Xl((size_t)nl * 3), nrm((size_t)nl * 3), mnl(nl), mxl(nl), dl((size_t)nl * ASD_DESC_DIM);
+    std::vector<int32_t> matched_kp(n1, -1);
+    for (int m = 0; m < nl; ++m) {
+      const MapPointView& P = points[vpLoopMapPoints[m]];
+      for (int k = 0; k < 3; ++k) { Xl[3 * m + k] = P.Xw[k]; nrm[3 * m + k] = P.normal[k]; }
+      mnl[m] = P.mfMinDistance; mxl[m] = P.mfMaxDistance;
+      for (int k = 0; k < ASD_DESC_DIM; ++k) dl[(size_t)m * ASD_DESC_DIM + k] = P.descriptor[k];
+      for (int i = 0; i < n1; ++i) if (vpMatches[i] == vpLoopMapPoints[m]) valid[m] = 0;  // spAlreadyFound (ORBmatcher.cc:321)
+    }
+    for (int i = 0; i < n1; ++i) if (vpMatches[i] >= 0) matched_kp[i] = nl;                // occupied on entry
+    int32_t nproj = 0;
+    if (asd_match_project_sim3(c.get(), CurrentKF.slot, Scw, nl, valid.data(), Xl.data(), nrm.data(), mnl.data(), mxl.data(), dl.data(), Kv, 10,
+                               matched_kp.data(), &nproj) != ASD_OK)
+      return r;
+    vpCurrentMatchedPoints = vpMatches;
+    for (int i = 0; i < n1; ++i)
+      if (matched_kp[i] >= 0 && matched_kp[i] < nl) vpCurrentMatchedPoints[i] = vpLoopMapPoints[matched_kp[i]];
+    for (int i = 0; i < n1; ++i) r.nTotalMatches += vpCurrentMatchedPoints[i] >= 0;        // :418-423
+    return r;
+  }
 };
 
 // MapPoint::ComputeDistinctiveDescriptors for a batch of map points (MapPoint.cc:271-338): observations[s] = the

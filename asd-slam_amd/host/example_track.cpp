@@ -115,6 +115,7 @@ int main(int argc, char** argv) {
     // Frame::ComputeBoW + SearchByBoW(KeyFrame*, Frame&, ...) (Tracking::TrackReferenceKeyFrame, Tracking.cc:607-620) with a
     // small random vocabulary standing in for the missing vocabulary file: k = 8, L = 2, node ids breadth-first
     int nbow = 0;
+    bool loop_ok = false;
     {
       const int k = 8, L = 2, n_nodes = 1 + k + k * k;
       std::vector<int32_t> start(n_nodes + 1, 0), kids, word(n_nodes, -1);
@@ -138,10 +139,25 @@ int main(int argc, char** argv) {
       asd::ORBmatcher bowmatcher(ctx, 0.7f, true);                               // Tracking.cc:616
       std::vector<int32_t> vpMapPointMatches;
       nbow = bowmatcher.SearchByBoW(F[0], fv0, F[1], fv1, vpMapPointMatches);
+      // LoopClosing::ComputeSim3 for one candidate (LoopClosing.cc:304-375, :415) with frame 1 as the current keyframe and frame 0 as
+      // the loop candidate: SearchByBoW(KF, KF), the caller's Sim3 (here the known relative pose instead of Sim3Solver's RANSAC),
+      // SearchBySim3, OptimizeSim3 and SearchByProjection(KF, Scw) -- every step but the solver behind the C ABI
+      std::vector<int32_t> loop_ids(mps.size()), vpCurrentMatchedPoints;
+      for (size_t i = 0; i < mps.size(); ++i) loop_ids[i] = (int32_t)i;
+      const float* T1 = F[1].mTcw;   // frame 0 sits at the origin: S12 = (R1w, t1w, 1)
+      auto solver = [&](const std::vector<int32_t>&, const std::vector<int32_t>&, float* s12, float* R12, float* t12) {
+        *s12 = 1.f;
+        for (int r = 0; r < 3; ++r) { for (int q = 0; q < 3; ++q) R12[r * 3 + q] = T1[r * 4 + q]; t12[r] = T1[r * 4 + 3]; }
+        return true;
+      };
+      const asd::LoopClosing::Result lc = asd::LoopClosing::ComputeSim3Candidate(ctx, F[1], fv1, F[0], fv0, mps, loop_ids, K, extractor.GetInverseScaleSigmaSquares(),
+                                                                                  false, solver, vpCurrentMatchedPoints);
+      printf("loop: bow=%d sim3=%d inliers=%d total=%d match=%d scale=%.6f\n", lc.nBoW, lc.nSim3, lc.nInliers, lc.nTotalMatches, (int)lc.bMatch, lc.g2oScm[7]);
+      loop_ok = lc.bMatch && lc.nInliers >= 20;   // LoopClosing.cc:364
     }
     printf("kp0=%d kp1=%d matches=%d inliers=%d fused=%d bow=%d t=(%.4f %.4f %.4f)\n", F[0].N(), F[1].N(), nmatches, ninl, nfused, nbow,
            F[1].mTcw[3], F[1].mTcw[7], F[1].mTcw[11]);
-    return (nmatches > 100 && ninl > 50 && nfused > 0 && nbow > 0 && chain_ok) ? 0 : 1;
+    return (nmatches > 100 && ninl > 50 && nfused > 0 && nbow > 0 && chain_ok && loop_ok) ? 0 : 1;
   } catch (const std::exception& e) {
     fprintf(stderr, "error: %s\n", e.what());
     return 3;

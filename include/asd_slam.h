@@ -488,6 +488,16 @@ int asd_match_bow(asd_ctx* ctx, int32_t slot_kf, int32_t slot_f, const asd_featu
                   const asd_feature_vector* fv_f, const uint8_t* has_mp_kf, float nn_ratio,
                   int32_t check_orientation, int32_t* match_f, int32_t* n_matches);
 
+/* ORBmatcher::SearchByBoW(KeyFrame* pKF1, KeyFrame* pKF2, vector<MapPoint*>& vpMatches12) (ORBmatcher.cc:533-666), the
+ * loop-closing overload (LoopClosing.cc:304): slot1 / slot2 hold the two keyframes, has_mp1/2[i] = the keyframe has a map point at
+ * keypoint i that is not bad.  It differs from the KF-Frame overload above in that a candidate of keyframe 2 needs a map point and
+ * must not have been taken yet (vbMatched2, claimed in the reference's visiting order), in the strict threshold bestDist1 < TH_LOW
+ * (:609; the other overload has <=, :231), and in that the orientation histogram holds keyframe 1's indices.
+ * Output match12[n1] = keypoint index in keyframe 2 whose map point vpMatches12[i1] is, or -1; *n_matches = return value. */
+int asd_match_bow_kf(asd_ctx* ctx, int32_t slot1, int32_t slot2, const asd_feature_vector* fv1, const asd_feature_vector* fv2,
+                     const uint8_t* has_mp1, const uint8_t* has_mp2, float nn_ratio, int32_t check_orientation,
+                     int32_t* match12, int32_t* n_matches);
+
 /* M4: ORBmatcher::SearchForTriangulation(pKF1, pKF2, F12, vMatchedPairs, bOnlyStereo=false)
  * (ORBmatcher.cc:669-822): has_mp1 / has_mp2 mark keypoints that already hold a map point,
  * F12[9] row-major f32 fundamental matrix, epipole (ex, ey) of camera 1 in image 2 as computed at
@@ -656,7 +666,7 @@ int asd_pose7_to_tcw(const double* pose7, float* Tcw16);
 
 /* ---- instrumentation ----------------------------------------------------------------- */
 /* Device-side duration of the kernels enqueued by the most recent call of the named stage,
- * measured with hipEvents on the ctx stream.  stage: "asdnet", "extract", "match", "ba". */
+ * measured with hipEvents on the ctx stream.  stage: "asdnet", "extract", "match", "ba", "sim3" (asd_optimize_sim3). */
 int asd_last_stage_ms(const asd_ctx* ctx, const char* stage, float* ms);
 /* Per-kernel device time of the ASDNet forward, accumulated with hipEvents recorded on the ctx
  * stream between the layer launches of every forward while enabled.  layer 0 = input_norm+conv1,
@@ -726,6 +736,29 @@ int32_t asd_debug_local_ba_lm(const asd_ctx* ctx, int32_t out[2][4]);
  * change it.  All -1 before any run. */
 #define ASD_POSE_OPT_DEBUG_INTS 41
 int32_t asd_debug_pose_opt(const asd_ctx* ctx, int32_t out[ASD_POSE_OPT_DEBUG_INTS]);
+/* Optimizer::OptimizeSim3 (Optimizer.cc:1002-1194) on g2o's VertexSim3Expmap, EdgeSim3ProjectXYZ and EdgeInverseSim3ProjectXYZ
+ * (types_seven_dof_expmap.h:48-193) with their NUMERIC Jacobians (base_binary_edge.hpp:130-206, delta = 1e-9), Levenberg as in
+ * asd_pose_optimize: optimize(5) over all 2 n edges, pairs with chi2 > th2 on either edge dropped (the errors as the round's last
+ * evaluation left them, :1146), optimize(nBad > 0 ? 10 : 5) over the rest, final count.
+ *  sim3[8]  in/out  qx qy qz qw tx ty tz s  (g2oS12), f64
+ *  n pairs (<= 65535) = the correspondences the reference adds edges for (:1065-1131), in ascending i:
+ *  P1c[n][3] = R1w*P3D1w + t1w, P2c[n][3] likewise (f64, f32-representable), obs1/obs2[n][2] = mvKeysUn pt,
+ *  inv_sigma2_1/2[n], K1[4], K2[4] = fx fy cx cy, th2 (10 in the reference, LoopClosing.cc:362), fix_scale.
+ *  keep[n] out: 1 = vpMatches1[idx] still set on return; *n_in = return value.
+ * Where nCorrespondences - nBad < 10 after the first round (:1164) the reference returns 0 in front of :1191: *n_in = 0, keep
+ * carries the first round's drops and sim3 is NOT written.  n == 0 is that case (g2o's optimize() returns -1 on the empty graph).
+ * The result is one bit pattern over repeated calls.  Against the reference's own g2o it agrees as far as two builds of that g2o
+ * agree with each other (tests/golden/make_sim3_golden.py): the numeric Jacobians put the noise floor near 1e-7, not 1e-8. */
+int asd_optimize_sim3(asd_ctx* ctx, double* sim3, int32_t n, const double* P1c, const double* P2c, const double* obs1,
+                      const double* obs2, const double* inv_sigma2_1, const double* inv_sigma2_2, const double* K1,
+                      const double* K2, float th2, int32_t fix_scale, uint8_t* keep, int32_t* n_in);
+/* Test aid: what the context's last asd_optimize_sim3 did.  out[4 r + k], r = round 0 / 1: {active edges, Levenberg iterations
+ * (optimize()'s return value: -1 with no active edge), trials (solves, accepted and rejected), 1 if the round's last trial was
+ * rejected}, -1 throughout for a second round that did not run; out[8] = nBad of the first re-classification, out[9] = the second
+ * round's iteration cap (5 or 10, :1158-1162; chosen in front of the early return), out[10] = 1 on the early return of :1165,
+ * out[11] = n.  Written by one thread into the block the call copies back anyway.  All -1 before any run. */
+#define ASD_SIM3_OPT_DEBUG_INTS 12
+int32_t asd_debug_optimize_sim3(const asd_ctx* ctx, int32_t out[ASD_SIM3_OPT_DEBUG_INTS]);
 /* Runs `reps` back-to-back repetitions of the ASDNet forward on resident buffers and
  * returns the average per-repetition device time (hipEvents on the ctx stream). */
 int asd_describe_timed(asd_ctx* ctx, const uint8_t* d_patches, int32_t n, float* d_desc,
