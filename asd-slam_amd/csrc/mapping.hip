@@ -1,7 +1,7 @@
 // mapping.hip -- new-map-point triangulation for the local-mapping thread.
 //
 // Replaces the per-match body of LocalMapping::CreateNewMapPoints (reference
-// src/vslam/src/LocalMapping.cc:386-519, monocular branch): parallax gate, linear triangulation through the
+// src/vslam/src/LocalMapping.cc:386-523, monocular branch): parallax gate, linear triangulation through the
 // 4x4 SVD, cheirality, reprojection chi2 in both keyframes and the scale-consistency gate.  Every match is
 // independent, so one lane handles one match; the keyframes' keypoints are already resident in the frame
 // slots (asd_frame_set).  The arithmetic follows the reference's OpenCV 3.2.0 evaluation order (f32 data,
@@ -118,7 +118,7 @@ __device__ Row4 svd4_last_vt(Row4 A0, Row4 A1, Row4 A2, Row4 A3) {
   return V3;
 }
 
-// the per-match body of LocalMapping::CreateNewMapPoints (LocalMapping.cc:386-519) for one pair of keypoints
+// the per-match body of LocalMapping::CreateNewMapPoints (LocalMapping.cc:386-523) for one pair of keypoints
 __device__ __forceinline__ void triangulate_one(const TriParams& P, const float4 a, const float4 b, float (&X)[3], unsigned char& ok_out) {
   const int o1 = __float_as_int(a.z), o2 = __float_as_int(b.z);
   unsigned char ok = 0;

@@ -607,7 +607,7 @@ inline int ComputeBoW(Context& c, const FrameView& F, std::vector<std::pair<int3
   return ASD_OK;
 }
 
-// LocalMapping::CreateNewMapPoints, per-match body (:386-519): x3D[3*i..] and ok[i] for every matched pair
+// LocalMapping::CreateNewMapPoints, per-match body (:386-523): x3D[3*i..] and ok[i] for every matched pair
 inline int TriangulateMatches(Context& c, const FrameView& KF1, const FrameView& KF2, const Camera& K1, const Camera& K2,
                               const std::vector<std::pair<size_t, size_t>>& vMatchedIndices, std::vector<float>& x3D,
                               std::vector<uint8_t>& ok) {

@@ -519,13 +519,13 @@ int asd_fuse_search(asd_ctx* ctx, int32_t slot_kf, int32_t n_mp, const uint8_t* 
                     const float* normal, const float* min_dist, const float* max_dist, const float* desc,
                     const float* Tcw, const float* K, float th, int32_t* best_idx, float* best_dist);
 
-/* LocalMapping::CreateNewMapPoints, per-match body (LocalMapping.cc:386-519, monocular branch): for each
+/* LocalMapping::CreateNewMapPoints, per-match body (LocalMapping.cc:386-523, monocular branch): for each
  * match (idx1[i] in frame slot1 = current keyframe, idx2[i] in slot2 = neighbour) run the parallax gate
- * (0 < cos < 0.9998), the linear triangulation (4x4 SVD, :437-453), cheirality in both cameras, the 5.991
+ * (0 < cos < 0.9998), the linear triangulation (4x4 SVD, :432-450), cheirality in both cameras, the 5.991
  * reprojection gates and the scale-consistency gate (ratioFactor = 1.5*scaleFactor).  ok[i] = 1 and x3D[i]
  * = the new point when the reference would create a MapPoint, else ok[i] = 0 and x3D[i] = 0.  The caller
  * keeps the pointer-graph part (new MapPoint, AddObservation, ComputeDistinctiveDescriptors ->
- * asd_distinctive_descriptor, UpdateNormalAndDepth, :497-515).  Tcw row-major 4x4 f32, K = fx fy cx cy. */
+ * asd_distinctive_descriptor, UpdateNormalAndDepth, :527-542).  Tcw row-major 4x4 f32, K = fx fy cx cy. */
 int asd_triangulate_pairs(asd_ctx* ctx, int32_t slot1, int32_t slot2, int32_t n_pairs, const int32_t* idx1,
                           const int32_t* idx2, const float* Tcw1, const float* Tcw2, const float* K1,
                           const float* K2, float* x3D, uint8_t* ok, int32_t* n_ok);
@@ -534,11 +534,11 @@ int asd_triangulate_pairs(asd_ctx* ctx, int32_t slot1, int32_t slot2, int32_t n_
  * SearchInNeighbors (:557-636) runs Fuse against 20 + second neighbours both ways: 40-100 matcher calls per keyframe, each a
  * few hundred microseconds as a call of its own.  The batch entry points take all of them in ONE submission: one upload, one
  * launch chain, one synchronisation.  What makes that legitimate: inside one call the searches do not feed each other --
- * vbMatched2 is never set in SearchForTriangulation (ORBmatcher.cc:688, :729), Fuse's Replace / AddObservation side effects
+ * vbMatched2 is never set in SearchForTriangulation (ORBmatcher.cc:685, :730), Fuse's Replace / AddObservation side effects
  * never enter the search (:938-956) -- and the only coupling BETWEEN the reference's consecutive calls is a filter the caller
  * applies when it walks the results in the reference's order: a keypoint of the current keyframe that an earlier neighbour
- * already gave a map point is skipped for later neighbours (pKF1->GetMapPoint(idx1), ORBmatcher.cc:703-707 after
- * LocalMapping.cc:497-503), a map point an earlier Fuse replaced is bad for later ones (:840-846).  Every result equals the
+ * already gave a map point is skipped for later neighbours (pKF1->GetMapPoint(idx1), ORBmatcher.cc:708-712 after
+ * LocalMapping.cc:527-533), a map point an earlier Fuse replaced is bad for later ones (:846-850).  Every result equals the
  * per-pair call's (asd_match_triangulate + asd_triangulate_pairs, asd_fuse_search) bit for bit. */
 
 /* The keyframe's DBoW2::FeatureVector resident beside its descriptors (slot must hold the frame): node ids ascending. */
@@ -547,7 +547,7 @@ int asd_frame_set_bow(asd_ctx* ctx, int32_t slot, const asd_feature_vector* fv);
 typedef struct asd_kf_neighbor {
   int32_t slot;              /* frame slot of the neighbour keyframe (asd_frame_set + asd_frame_set_bow done) */
   const uint8_t* has_mp;     /* [n_keypoints of that slot] it already holds a map point there */
-  float F12[9];              /* fundamental matrix, current keyframe -> neighbour (LocalMapping.cc:547-555), row-major f32 */
+  float F12[9];              /* fundamental matrix, current keyframe -> neighbour (LocalMapping.cc:638-655), row-major f32 */
   float ex, ey;              /* epipole of the current camera in the neighbour's image (ORBmatcher.cc:675-683) */
   float Tcw[16];             /* the neighbour's pose */
   float K[4];                /* its intrinsics fx fy cx cy */
@@ -573,7 +573,7 @@ int asd_fuse_search_batch(asd_ctx* ctx, int32_t n_calls, const asd_fuse_call* ca
                           float th, int32_t* best_idx, float* best_dist);
 
 /* vt.row(3) of cv::SVD::compute(A, w, u, vt, MODIFY_A|FULL_UV) for n row-major 4x4 f32 matrices
- * (the call at LocalMapping.cc:444); v is [n][4].  Exposed for the parity tests of the SVD itself. */
+ * (the call at LocalMapping.cc:440); v is [n][4].  Exposed for the parity tests of the SVD itself. */
 int asd_svd4_null(asd_ctx* ctx, int32_t n, const float* A, float* v);
 
 /* ---- stereo association (dead code in the reference: no stereo Frame constructor survives) ----

@@ -1,5 +1,5 @@
 // oracle/mapping.cpp -- CPU restatement of LocalMapping::CreateNewMapPoints' per-match triangulation
-// (src/vslam/src/LocalMapping.cc:386-519).  TEST INFRASTRUCTURE ONLY (see oracle.h).
+// (src/vslam/src/LocalMapping.cc:386-523).  TEST INFRASTRUCTURE ONLY (see oracle.h).
 //
 // The reference leans on OpenCV 3.2.0 (absent third-party blob, src/3rd_party/opencv3_catkin) for
 //   - MatExpr `s*row - row`  -> cv::addWeighted (float data, double weights)        [matop.cpp, arithm]
@@ -121,7 +121,7 @@ void orc_svd4_vt(const float* A, float* vt) {
   memcpy(vt, Vt, sizeof Vt);
 }
 
-// LocalMapping.cc:386-519, monocular branch (bStereo1 = bStereo2 = false)
+// LocalMapping.cc:386-523, monocular branch (bStereo1 = bStereo2 = false)
 int orc_triangulate_pairs(const orc_keypoint* kps1, const orc_keypoint* kps2, int n_pairs, const int32_t* idx1,
                           const int32_t* idx2, const float* Tcw1, const float* Tcw2, const float* K1, const float* K2,
                           float scale_factor, int nlevels, float* x3D_out, uint8_t* ok) {

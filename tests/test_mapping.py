@@ -1,4 +1,4 @@
-"""Local-mapping triangulation (LocalMapping::CreateNewMapPoints per-match body, LocalMapping.cc:386-519):
+"""Local-mapping triangulation (LocalMapping::CreateNewMapPoints per-match body, LocalMapping.cc:386-523):
 oracle known-answer checks on CPU, HIP-vs-oracle parity on the GPU through the C ABI."""
 import numpy as np
 import pytest
@@ -178,7 +178,7 @@ def _kf_with_neighbours(n, n_nb, seed):
         kb["y"][~vis] = rng.uniform(19, 356, (~vis).sum()).astype(np.float32)
         perm = rng.permutation(n)
         kb, db = kb[perm].copy(), perturbed_descriptors(dc[perm], 0.03, seed + 10 + b)
-        # F12 of (current, neighbour) as LocalMapping::ComputeF12 builds it (:547-555): K1^-T [t12]x R12 K2^-1
+        # F12 of (current, neighbour) as LocalMapping::ComputeF12 builds it (:638-655): K1^-T [t12]x R12 K2^-1
         R1w, t1w, R2w, t2w = Rc, tc, Tb[:3, :3].astype(np.float64), Tb[:3, 3].astype(np.float64)
         R12 = R1w @ R2w.T
         t12 = -R1w @ R2w.T @ t2w + t1w
@@ -196,7 +196,7 @@ def _kf_with_neighbours(n, n_nb, seed):
 def test_create_map_points_batch_equals_the_per_pair_calls(hip, oracle, n, n_nb):
     """asd_create_map_points_batch (every neighbour in one submission) against asd_match_triangulate + asd_triangulate_pairs per
     neighbour AND against the oracle directly (oracle.match_triangulate = ORBmatcher::SearchForTriangulation :669-822,
-    oracle.triangulate_pairs = LocalMapping::CreateNewMapPoints' per-match body :386-519): the same match ids, the same accept
+    oracle.triangulate_pairs = LocalMapping::CreateNewMapPoints' per-match body :386-523): the same match ids, the same accept
     flags, the same coordinates bit for bit"""
     kc, dc, Tc, nodes_c, has_c, nbs = _kf_with_neighbours(n, n_nb, 900 + n)
     hip.frame_set(0, kc, dc, BOUNDS)
