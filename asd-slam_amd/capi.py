@@ -112,6 +112,19 @@ def undistort_map(K, dist, w, h):
     return xy, frac
 
 
+def bow_score(scoring, v1, v2):
+    """asd_bow_score: TemplatedVocabulary::score(v1, v2) for scoring 0 L1 / 1 L2 / 5 DOT_PRODUCT (host only, no context) -> float.
+    v1, v2 = (word ids strictly ascending, values)."""
+    lib = load_library()
+    lib.asd_last_error.restype = C.c_char_p
+    i1, x1, i2, x2 = _c(v1[0], np.int32), _c(v1[1], np.float64), _c(v2[0], np.int32), _c(v2[1], np.float64)
+    out = C.c_double(0.0)
+    rc = lib.asd_bow_score(int(scoring), len(i1), _p(i1), _p(x1), len(i2), _p(i2), _p(x2), C.byref(out))
+    if rc != 0:
+        raise AsdError(rc, lib.asd_last_error(None).decode())
+    return out.value
+
+
 class AsdHip:
     """One asd_ctx (= one HIP device + stream)."""
 
@@ -696,6 +709,62 @@ class AsdHip:
                                            C.byref(nw), _p(fnode), _p(fstart), _p(fidx), C.byref(nn)))
         return (bid[:nw.value].copy(), bval[:nw.value].copy()), \
                (fnode[:nn.value].copy(), fstart[:nn.value + 1].copy(), fidx[:fstart[nn.value]].copy())
+
+    # ---- keyframe database (KeyFrameDatabase.cc)
+    def kfdb_clear(self, scoring=-1):
+        self._chk(self.lib.asd_kfdb_clear(self.ctx, int(scoring)))
+
+    def kfdb_add(self, kf, bow, global_map=True):
+        ids, vals = _c(bow[0], np.int32), _c(bow[1], np.float64)
+        self._chk(self.lib.asd_kfdb_add(self.ctx, int(kf), len(ids), _p(ids), _p(vals), int(bool(global_map))))
+
+    def kfdb_erase(self, kf):
+        self._chk(self.lib.asd_kfdb_erase(self.ctx, int(kf)))
+
+    def kfdb_score(self, bow, kfs):
+        """f64 score of the query BowVector against the named entries"""
+        ids, vals, kfs = _c(bow[0], np.int32), _c(bow[1], np.float64), _c(kfs, np.int32)
+        out = np.empty(len(kfs), np.float64)
+        self._chk(self.lib.asd_kfdb_score(self.ctx, len(ids), _p(ids), _p(vals), len(kfs), _p(kfs), _p(out)))
+        return out
+
+    def _kfdb_query(self, call):
+        cap = int(self.kfdb_debug()[0])
+        kf, sc, n = np.empty(max(cap, 1), np.int32), np.empty(max(cap, 1), np.float32), C.c_int32(0)
+        self._chk(call(cap, _p(kf), _p(sc), C.byref(n)))
+        return kf[:n.value].copy(), sc[:n.value].copy()
+
+    def kfdb_query_loop(self, bow, connected, min_score, only_global_map=False):
+        """-> lScoreAndMatch as (keyframe ids, float32 scores) in the reference's list order"""
+        ids, vals, con = _c(bow[0], np.int32), _c(bow[1], np.float64), _c(connected, np.int32)
+        return self._kfdb_query(lambda cap, kf, sc, n: self.lib.asd_kfdb_query_loop(
+            self.ctx, len(ids), _p(ids), _p(vals), len(con), _p(con), C.c_float(min_score), int(bool(only_global_map)), cap, kf, sc, n))
+
+    def kfdb_query_reloc(self, bow, only_global_map=False):
+        ids, vals = _c(bow[0], np.int32), _c(bow[1], np.float64)
+        return self._kfdb_query(lambda cap, kf, sc, n: self.lib.asd_kfdb_query_reloc(
+            self.ctx, len(ids), _p(ids), _p(vals), int(bool(only_global_map)), cap, kf, sc, n))
+
+    def kfdb_select(self, mode, neigh):
+        """mode 0 loop / 1 reloc; neigh = one list of up to 10 neighbour ids per scored keyframe -> candidate ids"""
+        nb = np.full((len(neigh), 10), -1, np.int32)
+        for i, row in enumerate(neigh):
+            row = list(row)[:10]
+            nb[i, :len(row)] = row
+        cand, n = np.empty(max(len(neigh), 1), np.int32), C.c_int32(0)
+        self._chk(self.lib.asd_kfdb_select(self.ctx, int(mode), len(neigh), _p(nb), len(neigh), _p(cand), C.byref(n)))
+        return cand[:n.value].copy()
+
+    def kfdb_debug(self, kf=None):
+        """kf None -> (live entries, live words, entry capacity, word capacity, growths); else dict of the entry's query fields"""
+        if kf is None:
+            out = np.zeros(5, np.int64)
+            self._chk(self.lib.asd_debug_kfdb(self.ctx, _p(out)))
+            return tuple(int(x) for x in out)
+        out, sc = np.zeros(4, np.int32), np.zeros(2, np.float32)
+        self._chk(self.lib.asd_debug_kfdb_entry(self.ctx, int(kf), _p(out), _p(sc)))
+        return dict(loop_stamped=bool(out[0]), loop_words=int(out[1]), reloc_stamped=bool(out[2]), reloc_words=int(out[3]),
+                    loop_score=np.float32(sc[0]), reloc_score=np.float32(sc[1]))
 
     def bank_put(self, first_row, desc):
         desc = _c(desc, np.float32)

@@ -176,6 +176,11 @@ void bow_free(asd_ctx* ctx) {
   ctx->bow = nullptr;
 }
 
+int bow_loaded_scoring(asd_ctx* ctx) {
+  const BowState* b = static_cast<const BowState*>(ctx->bow);
+  return b && b->loaded ? b->scoring : -1;
+}
+
 extern "C" {
 
 int asd_voc_load(asd_ctx* ctx, int32_t n_nodes, int32_t k, int32_t L, int32_t weighting, int32_t scoring,

@@ -157,6 +157,7 @@ int asd_ctx_destroy(asd_ctx* ctx) {
   mapping_free(ctx);
   bow_free(ctx);
   sim3_free(ctx);
+  kfdb_free(ctx);
   ctx->scratch.release();
   ctx->stereo_scratch.release();
   ctx->up.release();
@@ -175,7 +176,11 @@ int asd_ctx_destroy(asd_ctx* ctx) {
   return ASD_OK;
 }
 
-const char* asd_last_error(const asd_ctx* ctx) { return ctx ? const_cast<asd_ctx*>(ctx)->last_error() : "null context"; }
+const char* asd_last_error(const asd_ctx* ctx) { 
+  if (ctx) return const_cast<asd_ctx*>(ctx)->last_error();
+  const char* e = kfdb_host_error();   // the entry points without a context report per thread
+  return e[0] ? e : "null context";
+}
 
 int asd_get_scale_tables(const asd_ctx* ctx, float* scale, float* inv_scale, float* sigma2, float* inv_sigma2,
                          int32_t* fpl) {
@@ -250,6 +255,7 @@ int asd_last_stage_ms(const asd_ctx* ctx, const char* stage, float* ms) {
   else if (!strcmp(stage, "match")) *ms = ctx->ms_match;
   else if (!strcmp(stage, "ba")) *ms = ctx->ms_ba;
   else if (!strcmp(stage, "sim3")) *ms = ctx->ms_sim3;
+  else if (!strcmp(stage, "kfdb")) *ms = ctx->ms_kfdb;
   else return ASD_ERR_INVALID;
   return ASD_OK;
 }

@@ -336,6 +336,9 @@ struct asd_ctx {
   // ---- OptimizeSim3's test aid (state private to sim3.hip)
   void* sim3 = nullptr;
 
+  // ---- keyframe database (state private to kfdb.hip)
+  void* kfdb = nullptr;
+
   // ---- per-layer profiling (asd_profile_enable).  The extraction worker enqueues forwards while the caller enables /
   // reads the profile: every access to the prof_* fields below happens under prof_mutex.
   std::mutex prof_mutex;
@@ -350,7 +353,7 @@ struct asd_ctx {
 
   // ---- timing
   hipEvent_t ev0 = nullptr, ev1 = nullptr, ev2 = nullptr;
-  float ms_asdnet = 0, ms_extract = 0, ms_match = 0, ms_ba = 0, ms_sim3 = 0;
+  float ms_asdnet = 0, ms_extract = 0, ms_match = 0, ms_ba = 0, ms_sim3 = 0, ms_kfdb = 0;
 
   // the extraction worker thread reports errors too: the message is written under a lock, and asd_last_error hands
   // out a copy that stays put until the next call of asd_last_error on this context
@@ -397,6 +400,8 @@ void ba_free(asd_ctx* ctx);
 void mapping_free(asd_ctx* ctx);
 void bow_free(asd_ctx* ctx);
 void sim3_free(asd_ctx* ctx);
+void kfdb_free(asd_ctx* ctx);
+const char* kfdb_host_error();   // the message of this thread's last asd_bow_score (a call without a context)
 // The claim replay that makes d_src, to run in FRONT of the solver inside its workgroup (k_resolve_pose, ba.hip) instead of as a kernel of
 // its own: args = the Resolve2Args of resolve2.h (both translation units include it), kind 0 / 1, nq = its query count, lds = the
 // dynamic LDS the replay needs.  pose_chain_fused_ok says whether that form exists for (kind, nq, n_cur).

@@ -470,10 +470,88 @@ struct LocalMapping {
   static bool Busy(Context& c) { return asd_local_ba_poll(c.get()) == 1; }
 };
 
+// DBoW2::BowVector as asd_compute_bow hands it out: word ids ascending, one value per word
+struct BowVector {
+  std::vector<int32_t> id;
+  std::vector<double> val;
+  int size() const { return (int)id.size(); }
+};
+
+// ---- KeyFrameDatabase (KeyFrameDatabase.h; src/vslam/src/KeyFrameDatabase.cc) -----------------
+// Keyframes are named by their mnId.  The BowVectors live in HBM inside the context; the reference's per-keyframe query fields
+// (mnLoopQuery, mnLoopWords, mLoopScore, mnRelocQuery, mnRelocWords, mRelocScore) live with them, so the KeyFrame class needs none
+// of them any more.  One database per Context.
+class KeyFrameDatabase {
+ public:
+  // KeyFrameDatabase(const ORBVocabulary& voc) (:34-38): scoring -1 = the scoring of the vocabulary loaded with asd_voc_load
+  explicit KeyFrameDatabase(Context& c, int scoring = -1) : c_(c) {
+    if (asd_kfdb_clear(c_.get(), scoring) != ASD_OK) throw std::runtime_error(c_.error());
+    scoring_ = scoring;
+  }
+  int add(int32_t mnId, const BowVector& mBowVec, bool bGlobalMapFlag) {                                    // :41-47
+    return asd_kfdb_add(c_.get(), mnId, mBowVec.size(), mBowVec.id.data(), mBowVec.val.data(), bGlobalMapFlag ? 1 : 0);
+  }
+  int erase(int32_t mnId) { return asd_kfdb_erase(c_.get(), mnId); }                                        // :49-70
+  int clear() { return asd_kfdb_clear(c_.get(), scoring_); }                                                // :72-76
+  // vector<KeyFrame*> DetectLoopCandidates(KeyFrame* pKF, float minScore, bool only_global_map) (:80-204).  vConnected =
+  // pKF->GetConnectedKeyFrames() as ids; neighbours(id) = GetBestCovisibilityKeyFrames(10) of keyframe id, as ids (at most 10 are read)
+  template <class NeighboursFn>
+  std::vector<int32_t> DetectLoopCandidates(const BowVector& mBowVec, const std::vector<int32_t>& vConnected, float minScore,
+                                            bool only_global_map, NeighboursFn neighbours) {
+    return run(0, [&](int32_t cap, int32_t* kf, float* sc, int32_t* n) {
+      return asd_kfdb_query_loop(c_.get(), mBowVec.size(), mBowVec.id.data(), mBowVec.val.data(), (int32_t)vConnected.size(), vConnected.data(),
+                                 minScore, only_global_map ? 1 : 0, cap, kf, sc, n);
+    }, neighbours);
+  }
+  // vector<KeyFrame*> DetectRelocalizationCandidates(Frame* F, bool only_global_map) (:206-322)
+  template <class NeighboursFn>
+  std::vector<int32_t> DetectRelocalizationCandidates(const BowVector& mBowVec, bool only_global_map, NeighboursFn neighbours) {
+    return run(1, [&](int32_t cap, int32_t* kf, float* sc, int32_t* n) {
+      return asd_kfdb_query_reloc(c_.get(), mBowVec.size(), mBowVec.id.data(), mBowVec.val.data(), only_global_map ? 1 : 0, cap, kf, sc, n);
+    }, neighbours);
+  }
+ private:
+  template <class QueryFn, class NeighboursFn>
+  std::vector<int32_t> run(int mode, QueryFn query, NeighboursFn neighbours) {
+    int64_t dbg[5] = {0, 0, 0, 0, 0};
+    asd_debug_kfdb(c_.get(), dbg);
+    const int32_t cap = (int32_t)dbg[0];   // live entries: no list is longer
+    std::vector<int32_t> kf(cap + 1), cand(cap + 1);
+    std::vector<float> sc(cap + 1);
+    int32_t n = 0, nc = 0;
+    if (query(cap, kf.data(), sc.data(), &n) != ASD_OK) return {};
+    std::vector<int32_t> neigh((size_t)n * 10 + 1, -1);
+    for (int32_t i = 0; i < n; ++i) {
+      const std::vector<int32_t> v = neighbours(kf[i]);
+      for (size_t k = 0; k < v.size() && k < 10; ++k) neigh[(size_t)i * 10 + k] = v[k];
+    }
+    if (asd_kfdb_select(c_.get(), mode, n, neigh.data(), cap, cand.data(), &nc) != ASD_OK) return {};
+    cand.resize(nc);
+    return cand;
+  }
+  Context& c_;
+  int scoring_ = -1;
+};
+
 // LoopClosing::ComputeSim3, the numeric body for ONE loop candidate (LoopClosing.cc:304, :346-375, :415): every search and the
 // refinement run behind the C ABI; what stays with the caller is Sim3Solver (:312-337, a three-point closed form inside RANSAC),
 // handed in as a callback that turns the BoW matches into (s, R row-major 3x3, t) of pKF2 -> mpCurrentKF, or returns false.
 struct LoopClosing {
+  // LoopClosing::DetectLoop's lowest score to a connected keyframe (LoopClosing.cc:154-168): vConnected = the ids of
+  // mpCurrentKF->GetVectorCovisibleKeyFrames() that are not bad (all of them must be in the database); 1 when there is none.
+  // The result is DetectLoopCandidates' minScore (:171).
+  static float DetectLoopMinScore(Context& c, const BowVector& CurrentBowVec, const std::vector<int32_t>& vConnected) {
+    float minScore = 1;
+    std::vector<double> score(vConnected.size() + 1);
+    if (asd_kfdb_score(c.get(), CurrentBowVec.size(), CurrentBowVec.id.data(), CurrentBowVec.val.data(), (int32_t)vConnected.size(),
+                       vConnected.data(), score.data()) != ASD_OK)
+      return minScore;
+    for (size_t i = 0; i < vConnected.size(); ++i) {
+      const float s = (float)score[i];
+      if (s < minScore) minScore = s;
+    }
+    return minScore;
+  }
   struct Result { bool bMatch = false; int nBoW = 0, nSim3 = 0, nInliers = 0, nTotalMatches = 0; double g2oScm[8] = {0, 0, 0, 1, 0, 0, 0, 1}; };
   // `points` = the caller's map point table (ids as in mvpMapPoints); vpLoopMapPoints = ids of the points of the loop keyframe and
   // its neighbours (:393-412); vpCurrentMatchedPoints[i] = id matched to the current keyframe's keypoint i on return.

@@ -75,6 +75,7 @@ typedef struct asd_keypoint {
 /* ---- context ------------------------------------------------------------------------ */
 int asd_ctx_create(const asd_config* cfg, asd_ctx** out);
 int asd_ctx_destroy(asd_ctx* ctx);
+/* (ctx == NULL: the message of the calling thread's last asd_bow_score, the one failing call that has no context) */
 const char* asd_last_error(const asd_ctx* ctx);
 const char* asd_version(void);
 
@@ -666,7 +667,8 @@ int asd_pose7_to_tcw(const double* pose7, float* Tcw16);
 
 /* ---- instrumentation ----------------------------------------------------------------- */
 /* Device-side duration of the kernels enqueued by the most recent call of the named stage,
- * measured with hipEvents on the ctx stream.  stage: "asdnet", "extract", "match", "ba", "sim3" (asd_optimize_sim3). */
+ * measured with hipEvents on the ctx stream.  stage: "asdnet", "extract", "match", "ba", "sim3" (asd_optimize_sim3),
+ * "kfdb" (the scoring pass of the last asd_kfdb_score / asd_kfdb_query_*, its upload included). */
 int asd_last_stage_ms(const asd_ctx* ctx, const char* stage, float* ms);
 /* Per-kernel device time of the ASDNet forward, accumulated with hipEvents recorded on the ctx
  * stream between the layer launches of every forward while enabled.  layer 0 = input_norm+conv1,
@@ -759,6 +761,73 @@ int asd_optimize_sim3(asd_ctx* ctx, double* sim3, int32_t n, const double* P1c, 
  * out[11] = n.  Written by one thread into the block the call copies back anyway.  All -1 before any run. */
 #define ASD_SIM3_OPT_DEBUG_INTS 12
 int32_t asd_debug_optimize_sim3(const asd_ctx* ctx, int32_t out[ASD_SIM3_OPT_DEBUG_INTS]);
+/* ---- keyframe database and BoW score ------------------------------------------------------
+ * TemplatedVocabulary::score (TemplatedVocabulary.h:1264-1269) -> L1Scoring / L2Scoring / DotProductScoring::score
+ * (src/dbow2/DBoW2/ScoringObject.cpp:23-68, :73-120, :271-311) of two BowVectors given as (word id strictly ascending, value).  Host
+ * only: no context, no device (like asd_undistort_map).  scoring = asd_voc_load's enum: 0 L1, 1 L2, 5 DOT_PRODUCT; 2 CHI_SQUARE, 3 KL
+ * and 4 BHATTACHARYYA are not offered (ASD_ERR_INVALID; asd_last_error(NULL) says so) -- KL needs log(), which the device cannot
+ * match bit for bit.  v1 = (id1, val1) is score()'s first argument.  The sum is the reference's chain: f64, one term per common word in
+ * ascending word order, no FMA; two L1 vectors without a common word score -0.0 (-score / 2.0).  Ids that are not strictly ascending:
+ * ASD_ERR_INVALID. */
+int asd_bow_score(int32_t scoring, int32_t n1, const int32_t* id1, const double* val1, int32_t n2, const int32_t* id2,
+                  const double* val2, double* score);
+
+/* KeyFrameDatabase (src/vslam/src/KeyFrameDatabase.cc), one per context: the keyframes' BowVectors live in HBM and every query is one
+ * brute-force scoring pass over them (kfdb.hip).  All calls run on the context's stream with buffers of their own: they are legal
+ * while submissions of asd_extract_submit are outstanding and while an asd_track_* call is armed; they add no stream.
+ *
+ * asd_kfdb_clear   the constructor / clear() (:34-38, :72-76): empties the database and sets the scoring every later call uses
+ *                  (0 | 1 | 5; -1 = the loaded vocabulary's, ASD_ERR_INVALID when none is loaded).  A context starts with an empty L1 database.
+ * asd_kfdb_add     add() (:41-47).  kf = the caller's keyframe id (mnId, any int32 >= 0); global_map = KeyFrame::GetGlobalMapFlag().
+ *                  An id already present is ASD_ERR_INVALID (the reference would list the keyframe twice; that is not reproduced).
+ *                  An empty BowVector is a legal entry that no query ever finds.
+ * asd_kfdb_erase   erase() (:49-70).  An unknown id is ASD_OK (the reference's loop finds nothing).  It invalidates the state a
+ *                  query left for asd_kfdb_select.
+ * asd_kfdb_score   mpVoc->score(query, entry) as f64 for the n named entries: the body of DetectLoop's minScore loop
+ *                  (LoopClosing.cc:154-168; the caller casts to float and takes the minimum).  An unknown id is ASD_ERR_INVALID.
+ *                  Changes no per-entry state.
+ *
+ * Per-entry state, kept between queries like the reference's KeyFrame fields: mnLoopQuery / mnLoopWords / mLoopScore,
+ * mnRelocQuery / mnRelocWords / mRelocScore, the global-map flag and an add sequence number.  Two deliberate differences:
+ * every query stamps with a fresh number, so the coincidences of the reference's initial values mnLoopQuery(0) / mnRelocQuery(-1) with
+ * a keyframe of id 0 / a frame of id -1 are not reproduced; and mLoopScore / mRelocScore, which the reference never initialises
+ * (KeyFrame.cc:150, :181), start at 0.0f. */
+int asd_kfdb_clear(asd_ctx* ctx, int32_t scoring);
+int asd_kfdb_add(asd_ctx* ctx, int32_t kf, int32_t n_words, const int32_t* bow_id, const double* bow_val, int32_t global_map);
+int asd_kfdb_erase(asd_ctx* ctx, int32_t kf);
+int asd_kfdb_score(asd_ctx* ctx, int32_t n_q, const int32_t* q_id, const double* q_val, int32_t n, const int32_t* kfs, double* score);
+/* KeyFrameDatabase::DetectLoopCandidates (:80-204) and ::DetectRelocalizationCandidates (:206-322), each in two calls, because
+ * GetBestCovisibilityKeyFrames(10) is pointer-graph state of the caller and which keyframes need it is known only after scoring.
+ *
+ * asd_kfdb_query_loop   :85-149.  connected = pKF->GetConnectedKeyFrames() as ids (ids not in the database are ignored): they never
+ *   enter lKFsSharingWords.  minCommonWords = (int)(maxCommonWords * 0.6f) (this fork; upstream 0.8f), gate mnLoopWords > minCommonWords;
+ *   mLoopScore is stored for every keyframe that passes the gate, in front of the si >= min_score and only_global_map tests (:142-147).
+ *   Output: lScoreAndMatch as (scored_kf, scored_score = float si) in the reference's list order, *n_scored entries.
+ * asd_kfdb_query_reloc  :208-266.  only_global_map is applied in front of the list (:229): a keyframe that is not global-map is
+ *   stamped and has its words counted but is never scored.  minCommonWords = (int)(max * 0.8f).
+ * asd_kfdb_select       the covisibility accumulation and the retain filter (:153-203 for mode 0, :271-321 for mode 1) over the state
+ *   the last query of that mode left.  neigh[n_scored][10] = GetBestCovisibilityKeyFrames(10) of scored_kf[i] as ids, -1 padded; ids
+ *   that are not in the database are legal (keyframes whose query stamp does not match).  Loop: a neighbour counts when this query
+ *   stamped it and its words are > minCommonWords (:167), bestAccScore starts at min_score, retain is > 0.55f * bestAccScore (this fork;
+ *   upstream 0.75f).  Reloc: only the stamp is checked (:286), so a neighbour that shares a word but was not scored by this query
+ *   contributes the score an earlier reloc query left on it (0.0f when there was none); bestAccScore starts at 0, retain is
+ *   > 0.75f * bestAccScore.  All in f32.  Output: vpLoopCandidates / vpRelocCandidates as ids in the reference's order (duplicates
+ *   dropped, first occurrence kept).  n_scored == 0 gives *n_cand = 0; an n_scored that is not the last query's (or an
+ *   asd_kfdb_erase since that query) is ASD_ERR_INVALID.
+ * ASD_ERR_CAPACITY when `capacity` is too small (*n_scored / *n_cand then hold the count needed; a query may simply be repeated) and
+ * for a query of more than 13653 words (the query vector is staged in LDS). */
+int asd_kfdb_query_loop(asd_ctx* ctx, int32_t n_q, const int32_t* q_id, const double* q_val, int32_t n_connected,
+                        const int32_t* connected, float min_score, int32_t only_global_map, int32_t capacity, int32_t* scored_kf,
+                        float* scored_score, int32_t* n_scored);
+int asd_kfdb_query_reloc(asd_ctx* ctx, int32_t n_q, const int32_t* q_id, const double* q_val, int32_t only_global_map,
+                         int32_t capacity, int32_t* scored_kf, float* scored_score, int32_t* n_scored);
+int asd_kfdb_select(asd_ctx* ctx, int32_t mode, int32_t n_scored, const int32_t* neigh, int32_t capacity, int32_t* cand,
+                    int32_t* n_cand);
+/* Test aids.  asd_debug_kfdb: out = {live entries, live words, entry capacity, word capacity, number of arena growths}.
+ * asd_debug_kfdb_entry: out = {stamped by the last loop query, loop words, stamped by the last reloc query, reloc words},
+ * score = {loop score, reloc score}; ASD_ERR_INVALID for an id that is not in the database. */
+int32_t asd_debug_kfdb(asd_ctx* ctx, int64_t out[5]);
+int32_t asd_debug_kfdb_entry(asd_ctx* ctx, int32_t kf, int32_t out[4], float score[2]);
 /* Runs `reps` back-to-back repetitions of the ASDNet forward on resident buffers and
  * returns the average per-repetition device time (hipEvents on the ctx stream). */
 int asd_describe_timed(asd_ctx* ctx, const uint8_t* d_patches, int32_t n, float* d_desc,
