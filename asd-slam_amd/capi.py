@@ -235,7 +235,9 @@ class AsdHip:
 
     # ---- extractor
     def extract(self, image, n_features_override=0):
-        image = _c(image, np.uint8)
+        image = np.asarray(image, np.uint8)
+        if image.strides[1] != 1 or image.strides[0] < image.shape[1]:   # rows of adjacent bytes with any stride >= width go as they are
+            image = _c(image, np.uint8)
         h, w = image.shape
         cap = self.cfg.max_patches
         kps = np.zeros(cap, KP_DTYPE)
@@ -342,6 +344,14 @@ class AsdHip:
         n = C.c_int32()
         self._chk(self.lib.asd_get_raw_corners(self.ctx, level, cap, _p(x), _p(y), _p(r), C.byref(n)))
         return x[:n.value].copy(), y[:n.value].copy(), r[:n.value].copy()
+
+    def patches(self):
+        """asd_get_patches: the 32x32 patches of the last synchronous extraction, u8 [n, 32, 32] in keypoint order"""
+        cap = self.cfg.max_patches
+        out = np.empty((cap, 32, 32), np.uint8)
+        n = C.c_int32()
+        self._chk(self.lib.asd_get_patches(self.ctx, cap, _p(out), C.byref(n)))
+        return out[:n.value].copy()
 
     # ---- frames / matchers
     def frame_set(self, slot, kps, desc, bounds):

@@ -217,6 +217,7 @@ int asd_describe(asd_ctx* ctx, const uint8_t* patches, int32_t n, float* desc) {
   if (!ctx->weights_loaded) { ctx->set_error("asd_load_weights has not been called"); return ASD_ERR_NO_WEIGHTS; }
   if (n == 0) return ASD_OK;
   if (asd_extractor_busy(ctx, "asd_describe")) return ASD_ERR_INVALID;
+  ctx->patches_n = 0;   // the extraction's patches are overwritten
   (void)hipSetDevice(ctx->cfg.device);
   ASD_HIP_CHECK(ctx, hipMemcpyAsync(ctx->d_patches, patches, (size_t)n * 1024, hipMemcpyHostToDevice, ctx->stream));
   ASD_HIP_CHECK(ctx, hipEventRecord(ctx->ev0, ctx->stream));

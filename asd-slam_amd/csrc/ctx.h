@@ -297,6 +297,7 @@ struct asd_ctx {
   bool net_pair = true;         // two-piece form: activations between the layers as the fp16 piece pairs themselves (ASD_ASDNET_PAIR=0: f32 NHWC)
   float* d_act6 = nullptr;      // where the last forward left conv6's output (asd_debug_act6)
   uint8_t* d_patches = nullptr; // [max_patches][1024]
+  int patches_n = 0;            // patches the last synchronous extraction left in d_patches (asd_get_patches); 0 once asd_describe overwrote them
   float* d_desc = nullptr;      // [max_patches][128] descriptors of the last asd_extract / asd_describe
   bool keep_pyramid = false;    // asd_extract_keep_pyramid: every submission keeps a copy of its pyramid for asd_stereo_match
   const uint8_t* d_pyr_view = nullptr;   // that copy of the submission waited for last (null: the shared pyramid of a synchronous extraction)

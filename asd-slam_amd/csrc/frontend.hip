@@ -554,6 +554,10 @@ static int configure_size(asd_ctx* ctx, FrontendState* fe, int w, int h) {
     consts_once.done(ctx->cfg.device);
   }
   PyrDev& P = fe->pyr;
+  // the tables are rewritten from here on: a refusal below must not leave them passing for the previous size.  Until the next accepted
+  // extraction this state counts as never configured -- asd_stereo_match then refuses ("extract the left and the right image ... first")
+  // or goes by the read-ahead extractor's other front-half state, where it used to match against this state's stale geometry
+  fe->cfg_w = fe->cfg_h = 0;
   P.nlevels = nl;
   int off = 0, tiles = 0;
   size_t tx = 0, ty = 0;
@@ -855,7 +859,8 @@ static int extract_finish(asd_ctx* ctx, ExtractSlot& S, int n, asd_keypoint* kps
 }
 
 static int extract_check(asd_ctx* ctx, const uint8_t* image, int32_t width, int32_t height, int32_t stride) {
-  if (!ctx || !image || stride < width) return ASD_ERR_INVALID;
+  if (!ctx || !image) return ASD_ERR_INVALID;
+  if (width < 1 || height < 1 || stride < width) { ctx->set_error("image %dx%d with stride %d: stride < width or an empty image", width, height, stride); return ASD_ERR_INVALID; }
   if (width > ctx->cfg.max_width || height > ctx->cfg.max_height) { ctx->set_error("image %dx%d exceeds ctx capacity %dx%d", width, height, ctx->cfg.max_width, ctx->cfg.max_height); return ASD_ERR_CAPACITY; }
   if (!ctx->weights_loaded) { ctx->set_error("asd_load_weights has not been called"); return ASD_ERR_NO_WEIGHTS; }
   if (ctx->und && (width != ctx->und->w || height != ctx->und->h)) {
@@ -886,8 +891,10 @@ static int extract_impl(asd_ctx* ctx, const uint8_t* image, bool image_on_device
   ExtractJob J;
   J.image = image; J.on_device = image_on_device; J.w = width; J.h = height; J.stride = stride; J.nfeat = n_features_override;
   int32_t n = 0;
+  ctx->patches_n = 0;
   if ((rc = extract_front(ctx, fe, J, S, ctx->stream, ctx->ev2, kps, &n)) != ASD_OK) return rc;
   *n_out = n;
+  ctx->patches_n = n;
   ctx->last_n = n;
   ctx->d_desc_last = S.d_desc;
   ctx->d_pyr_view = nullptr;   // the shared pyramid holds this frame
@@ -1226,6 +1233,18 @@ int asd_get_raw_corners(asd_ctx* ctx, int32_t level, int32_t capacity, float* x,
     if (x) x[i] = fe->raw_x[level][i];
     if (y) y[i] = fe->raw_y[level][i];
     if (response) response[i] = fe->raw_r[level][i];
+  }
+  *n_out = n;
+  return ASD_OK;
+}
+
+int asd_get_patches(asd_ctx* ctx, int32_t capacity, uint8_t* out, int32_t* n_out) {
+  if (!ctx || !ctx->fe || !n_out || capacity < 0 || (capacity > 0 && !out)) return ASD_ERR_INVALID;
+  if (asd_extractor_busy(ctx, "asd_get_patches")) return ASD_ERR_INVALID;
+  const int n = std::min(ctx->patches_n, (int)capacity);
+  if (n > 0) {
+    ASD_HIP_CHECK(ctx, hipMemcpyAsync(out, ctx->d_patches, (size_t)n * 1024, hipMemcpyDeviceToHost, ctx->stream));
+    ASD_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
   }
   *n_out = n;
   return ASD_OK;

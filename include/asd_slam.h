@@ -123,7 +123,7 @@ int asd_extract_device(asd_ctx* ctx, const uint8_t* d_image, int32_t width, int3
  * same results asd_extract would.  Up to ASD_EXTRACT_QUEUE submissions may be outstanding; the worker runs
  * the front half (pyramid .. patch gather) of the next queued frame underneath the ASDNet pass of the
  * previous one.  `image` must stay valid until its wait.  While submissions are outstanding the worker owns the
- * shared front-end and ASDNet buffers: asd_extract*, asd_describe*, asd_get_level_image / asd_get_raw_corners and
+ * shared front-end and ASDNet buffers: asd_extract*, asd_describe*, asd_get_level_image / asd_get_raw_corners / asd_get_patches and
  * asd_stereo_match return ASD_ERR_INVALID ("... submission(s) outstanding") instead of racing with it.  If the
  * extractor's streams / buffers cannot be created the call fails and the next submit starts over.  The device-resident
  * descriptors of a waited frame (asd_frame_set with desc == NULL) stay valid for two further submissions. */
@@ -154,6 +154,10 @@ int asd_get_level_image(asd_ctx* ctx, int32_t level, int32_t blurred, uint8_t* o
  * reference's vToDistributeKeys order; coordinates are relative to minBorder (16). */
 int asd_get_raw_corners(asd_ctx* ctx, int32_t level, int32_t capacity, float* x, float* y,
                         float* response, int32_t* n_out);
+/* The 32x32 patches the last asd_extract / asd_extract_device gathered for ASDNet (ORBextractor.cc:1113-1115: the
+ * blurred level, keypoint at [16][16]), in keypoint order: out[min(n, capacity)][32][32], *n_out = min(n, capacity).
+ * A later asd_describe overwrites them, after which *n_out = 0 until the next extraction; refused while submissions are outstanding, like the calls above. */
+int asd_get_patches(asd_ctx* ctx, int32_t capacity, uint8_t* out, int32_t* n_out);
 
 /* ---- undistortion in front of the extractor (Tracking.cc:104,125) -------------------
  * Tracking::GrabImageMonocular and Tracking::Loc call cv::undistort(im, mImGray, mK, mDistCoef) on every image

@@ -1,5 +1,7 @@
 """Extractor front-end: oracle known-answer tests (OpenCV 3.2.0 semantics are
 parity-unpinned: no OpenCV here, no reference vectors) and HIP-vs-oracle bit-exactness."""
+import ctypes
+
 import numpy as np
 import pytest
 
@@ -180,6 +182,18 @@ def test_extract_small_and_odd_sizes(hip, oracle, synth):
     view = big[10:300, 100:900]
     kps_a, desc_a = hip.extract(np.ascontiguousarray(view))
     assert len(kps_a) > 500
+    d_big = hip.device_alloc(big.nbytes)
+    try:
+        hip.h2d(d_big, big)
+        kps_b, desc_b = hip.extract_device(ctypes.c_void_p(d_big.value + 10 * 1241 + 100), 800, 290, 1241)
+        np.testing.assert_array_equal(hip.level_image(0), view)
+        np.testing.assert_array_equal(kps_b, kps_a)
+        np.testing.assert_array_equal(desc_b, desc_a)
+        kps_c, desc_c = hip.extract(view)                 # pageable host memory with the same stride
+        np.testing.assert_array_equal(kps_c, kps_a)
+        np.testing.assert_array_equal(desc_c, desc_a)
+    finally:
+        hip.device_free(d_big)
 
 
 @pytest.mark.gpu
