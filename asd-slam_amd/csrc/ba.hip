@@ -865,7 +865,7 @@ __global__ __launch_bounds__(kPoseThreads) void k_resolve_pose(Resolve2Args r, P
 
 // ---------------------------------------------------------------- fused tracking chains: edges made on the device
 // The unary edges of PoseOptimization (Optimizer.cc:272-310) straight from match results that live on the device: keypoint
-// j gets an edge when it holds a map point -- src[j] >= 0 names a row of the world-position table tab (the match k_resolve
+// j gets an edge when it holds a map point -- src[j] >= 0 names a row of the world-position table tab (the match k_resolve2
 // wrote), or hold[j] != 0 says the keypoint already held one on entry with its position in own[j].  Edge order = keypoint
 // order, as the reference's loop over mvpMapPoints (:281): the same records, in the same order, as asd_pose_optimize
 // receives from a host that packs them -- so the fused chain returns the same bits as the two separate calls.
@@ -2193,41 +2193,39 @@ bool pose_chain_fused_ok(const asd_ctx* ctx, int kind, int nq, int n_cur, size_t
 }
 
 // the solver's argument block for device-resident matches (gather form, mode 2)
-static PoseOptArgs pose_chain_args(asd_ctx* ctx, BaState* s, int n_cur, const int* d_src, const float4* d_kp, const float* d_tab, const uint8_t* d_hold,
-                                   const float* d_own, const double* pose7, const double* K, double* d_io, const double* d_pose0, double* d_io_dev,
-                                   const AsdBetweenArgs* between) {
+static PoseOptArgs pose_chain_args(asd_ctx* ctx, BaState* s, const AsdPoseChainArgs& c) {
   PoseOptArgs a{};
-  a.n = n_cur;
-  a.g_src = d_src; a.g_hold = d_hold; a.g_tab = d_tab; a.g_own = d_own; a.g_kp = d_kp; a.g_ncur = n_cur;
+  a.n = c.n_cur;
+  a.g_src = c.d_match; a.g_hold = c.d_hold; a.g_tab = c.d_points; a.g_own = c.d_own; a.g_kp = c.d_kp; a.g_ncur = c.n_cur;
   for (int k = 0; k < 16; ++k) a.isg_tab[k] = k < ctx->cfg.n_levels ? (double)ctx->inv_sigma2[k] : 0.0;   // invSigma2 is a float in the reference (Optimizer.cc:300)
-  if (pose7) memcpy(a.pose0, pose7, 56);
-  a.pose0_dev = d_pose0; a.io_dev = d_io_dev;
-  a.between = between;
-  a.fx = K[0]; a.fy = K[1]; a.cx = K[2]; a.cy = K[3];
-  a.soa_g = s->po_err.as<double>(); a.flags_g = s->po_level.as<uint8_t>(); a.io = d_io;
+  if (c.pose7) memcpy(a.pose0, c.pose7, 56);
+  a.pose0_dev = c.d_pose0; a.io_dev = c.d_io_dev;
+  a.between = c.between;
+  a.fx = c.K[0]; a.fy = c.K[1]; a.cx = c.K[2]; a.cy = c.K[3];
+  a.soa_g = s->po_err.as<double>(); a.flags_g = s->po_level.as<uint8_t>(); a.io = c.d_io;
   a.use_lds = 2;
   a.debug = 0;
   return a;
 }
 
-int pose_chain_enqueue(asd_ctx* ctx, int n_cur, const int* d_src, const float4* d_kp, const float* d_tab, const uint8_t* d_hold,
-                       const float* d_own, const double* pose7, const double* K, double* d_io, const double* d_pose0, double* d_io_dev,
-                       const AsdBetweenArgs* between, const AsdFusedReplay* fused) {
+int pose_chain_enqueue(asd_ctx* ctx, const AsdPoseChainArgs& c) {
   // every input is already on the device (the caller packed the tables into its one upload block), the results go to d_io
   // inside the caller's one result block: no copy is enqueued here
   BaState* s = ba_state(ctx);
   hipStream_t st = ctx->stream;
+  const int n_cur = c.n_cur;
+  const AsdFusedReplay* fused = c.fused;
   int rc;
   if ((rc = pose_chain_reserve(ctx, n_cur)) != ASD_OK) return rc;
   const size_t idx_off = (size_t)n_cur * 48;
   const size_t lds_compact = (size_t)n_cur * 35 + 16;
   const int mode = pose_chain_lds_form(ctx, n_cur) ? 2 : 0;
-  PoseOptArgs a = pose_chain_args(ctx, s, n_cur, d_src, d_kp, d_tab, d_hold, d_own, pose7, K, d_io, d_pose0, d_io_dev, between);
+  PoseOptArgs a = pose_chain_args(ctx, s, c);
   a.use_lds = mode;
   if (mode != 2) {   // larger than LDS: edge records through HBM
     a.g_src = nullptr; a.g_hold = nullptr; a.g_tab = nullptr; a.g_own = nullptr; a.g_kp = nullptr; a.g_ncur = 0;
     PoseEdgesArgs e{};
-    e.n_cur = n_cur; e.src = d_src; e.hold = d_hold; e.tab = d_tab; e.own = d_own; e.kp = d_kp;
+    e.n_cur = n_cur; e.src = c.d_match; e.hold = c.d_hold; e.tab = c.d_points; e.own = c.d_own; e.kp = c.d_kp;
     for (int l = 0; l < ASD_MAX_LEVELS; ++l) e.inv_sigma2[l] = l < ctx->cfg.n_levels ? ctx->inv_sigma2[l] : 0.f;
     e.edges = s->po_Xw.as<double>(); e.isgi = s->po_Xw.as<uint8_t>() + idx_off; e.n_out = s->pc_n.as<int>();
     hipLaunchKernelGGL(k_pose_edges, dim3(1), dim3(1024), 0, st, e);
@@ -2235,7 +2233,7 @@ int pose_chain_enqueue(asd_ctx* ctx, int n_cur, const int* d_src, const float4* 
     a.n_dev = s->pc_n.as<int>();
     a.edges = s->po_Xw.as<double>(); a.isgi = s->po_Xw.as<uint8_t>() + idx_off;
   }
-  if ((d_pose0 || d_io_dev) && mode != 2) { ctx->set_error("pose chain: the device-side hand-over needs the LDS form of the solver (frame too large)"); return ASD_ERR_CAPACITY; }
+  if ((c.d_pose0 || c.d_io_dev) && mode != 2) { ctx->set_error("pose chain: the device-side hand-over needs the LDS form of the solver (frame too large)"); return ASD_ERR_CAPACITY; }
   if (fused) {
     if (mode != 2 || !pose_chain_fused_ok(ctx, fused->kind, fused->nq, n_cur, fused->lds)) { ctx->set_error("pose chain: no fused replay + solver form for this frame"); return ASD_ERR_CAPACITY; }
     const Resolve2Args& r = *static_cast<const Resolve2Args*>(fused->args);
@@ -2251,7 +2249,6 @@ int pose_chain_enqueue(asd_ctx* ctx, int n_cur, const int* d_src, const float4* 
   } else if (mode == 2) hipLaunchKernelGGL(k_pose_opt<2>, dim3(1), dim3(kPoseThreads), lds_compact, st, a);
   else hipLaunchKernelGGL(k_pose_opt<0>, dim3(1), dim3(kPoseThreads), 0, st, a);
   ASD_HIP_CHECK(ctx, hipGetLastError());
-  ctx->pose_chain_kp_flags = mode == 2;   // the form of the flags in d_io: per keypoint + edge count (gather form), or per edge
   return ASD_OK;
 }
 

@@ -115,7 +115,7 @@ int asd_ctx_create(const asd_config* cfg, asd_ctx** out) {
   // ASDNet arithmetic: split-operand kernels by default (two fp16 terms; ASD_ASDNET_MATH=bf16x3 for three bf16 terms);
   // ASD_ASDNET_MATH=f32 keeps every layer on the f32 MFMA kernels (net_split: bit 0 = conv2 ... bit 4 = conv6, bit 5 = fc; all or none)
   c->net_split = 0x3f;
-  if (const char* e = getenv("ASD_MATCH_REPLAY")) c->match_replay_host = !strcmp(e, "host");   // matcher.hip, k_resolve
+  if (const char* e = getenv("ASD_MATCH_REPLAY")) c->match_replay_host = !strcmp(e, "host");   // matcher.hip, replay_on_device
   if (const char* e = getenv("ASD_BA_STRUCT")) c->ba_struct_host = !strcmp(e, "host");          // ba.hip, local_ba_impl
   if (const char* e = getenv("ASD_ASDNET_MATH")) {
     if (!strcmp(e, "f32")) c->net_split = 0;

@@ -293,7 +293,6 @@ struct asd_ctx {
   int* h_range = nullptr;       // pinned: set by k_l2norm when a descriptor of an asd_describe* call came out non-finite (fp16x2 range)
   std::string calib_note;       // what asd_load_weights' calibration found (empty: nothing to report)
   unsigned* d_calib = nullptr;  // calibration only: per-layer max |activation| as float bits (asdnet_forward_device fills it when set)
-  bool pose_chain_kp_flags = false;   // the last pose_chain_enqueue wrote its outlier flags per keypoint (gather form of k_pose_opt)
   bool net_pair = true;         // two-piece form: activations between the layers as the fp16 piece pairs themselves (ASD_ASDNET_PAIR=0: f32 NHWC)
   float* d_act6 = nullptr;      // where the last forward left conv6's output (asd_debug_act6)
   uint8_t* d_patches = nullptr; // [max_patches][1024]
@@ -408,15 +407,27 @@ const char* kfdb_host_error();   // the message of this thread's last asd_bow_sc
 // dynamic LDS the replay needs.  pose_chain_fused_ok says whether that form exists for (kind, nq, n_cur).
 struct AsdFusedReplay { const void* args; int kind; int nq; size_t lds; };
 bool pose_chain_fused_ok(const asd_ctx* ctx, int kind, int nq, int n_cur, size_t lds);
-// ba.hip: PoseOptimization enqueued behind device-resident matches (fused tracking chains; see the definition)
-// d_pose0 (optional): the start pose on the device (the previous stage's result block), pose7 is then ignored; d_io_dev (optional): a
-// second copy of the result block in device memory for the kernels of a following stage (asd_track_frame)
-// between (optional, with d_io_dev; DEVICE memory): the work between the two tracking stages as the kernel's tail (asd_between_body)
-int pose_chain_enqueue(asd_ctx* ctx, int n_cur, const int* d_src, const float4* d_kp, const float* d_tab, const uint8_t* d_hold,
-                       const float* d_own, const double* pose7, const double* K, double* d_io, const double* d_pose0 = nullptr,
-                       double* d_io_dev = nullptr, const AsdBetweenArgs* between = nullptr, const AsdFusedReplay* fused = nullptr);
+// ba.hip: PoseOptimization enqueued behind device-resident matches (fused tracking chains; see the definition).  Every pointer but pose7
+// and K is device memory (d_io may be pinned host memory: the kernel stores its results there directly)
+struct AsdPoseChainArgs {
+  int n_cur;
+  const int* d_match;              // [n_cur] row of d_points, or -1 (the match table the claim replay wrote)
+  const float4* d_kp;              // the frame's keypoints
+  const float* d_points;           // [.][3] world positions the match table names
+  const uint8_t* d_hold;           // [n_cur] or null: the keypoint held a map point on entry ...
+  const float* d_own;              // [n_cur][3] or null: ... at this position
+  const double* pose7;             // host: the start pose (read now, passed by value), ignored with d_pose0
+  const double* K;                 // host: fx, fy, cx, cy
+  double* d_io;                    // out: pose[7], n_bad, flags, edge count, stamps (pose_chain_io_bytes)
+  const double* d_pose0;           // optional: the start pose on the device (the previous stage's result block)
+  double* d_io_dev;                // optional: a second copy of the result block in device memory for the kernels of a following stage
+  const AsdBetweenArgs* between;   // optional, with d_io_dev: the work between the two tracking stages as the kernel's tail (asd_between_body)
+  const AsdFusedReplay* fused;     // optional: the stage's claim replay in front of the solver, inside its workgroup
+};
+int pose_chain_enqueue(asd_ctx* ctx, const AsdPoseChainArgs& c);
 int pose_chain_reserve(asd_ctx* ctx, int n_cur);   // its allocations and kernel attributes, ahead of time (see the definition)
-// true when pose_chain_enqueue will take the LDS (gather) form for a frame of n_cur keypoints
+// true when pose_chain_enqueue will take the LDS (gather) form for a frame of n_cur keypoints: the outlier flags then come back per KEYPOINT
+// with the edge count behind them, otherwise (edge records through HBM) per edge
 inline bool pose_chain_lds_form(const asd_ctx* ctx, int n_cur) { return ctx->cfg.n_levels <= 16 && (size_t)n_cur * 35 + 16 <= 150 * 1024; }
 inline size_t pose_chain_io_bytes(int n_cur) { return 64 + ((size_t)n_cur + 7) / 8 * 8 + 64; }   // (+ two 100 MHz stamps behind the edge count: kernel entry, exit)   // pose[7], n_bad, flags (8-B words), edge count
 // capi.cpp

@@ -46,7 +46,7 @@ struct GridDev {
 // (candidate index, distance).  Arithmetic of the cell range / distance tests is the float
 // arithmetic of Frame.cc:226-265 verbatim.
 //
-// SORT = true (the device claim replay, k_resolve; round 4): the query's list leaves the kernel in PREFERENCE order instead -- ascending
+// SORT = true (the device claim replay, k_resolve2; round 4): the query's list leaves the kernel in PREFERENCE order instead -- ascending
 // (distance bits, position in Frame::GetFeaturesInArea order), which is the order the reference's strict `<` walks settle ties in
 // (ORBmatcher.cc:86-104, :1392-1404: the first candidate in visiting order wins among equal distances) -- with its four best entries
 // also in a compact per-query table.  The replay then needs the head of each list only: "best candidate no earlier map point holds"
@@ -70,7 +70,7 @@ __global__ __launch_bounds__(64 * kSearchWaves) void k_window_search(GridDev G, 
                                                        const float* __restrict__ qdesc, const float* __restrict__ cdesc,
                                                        int* __restrict__ q_off, int* __restrict__ q_cnt,
                                                        int* __restrict__ total, int cap, int* __restrict__ out_idx,
-                                                       float* __restrict__ out_dist, unsigned* __restrict__ out_meta, SortArgs S) {
+                                                       float* __restrict__ out_dist, SortArgs S) {
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int q = blockIdx.x * kSearchWaves + wave;
   // the waves of a workgroup reserve their segments with ONE atomicAdd (2000 same-address atomics, one per query, were a
@@ -122,7 +122,6 @@ __global__ __launch_bounds__(64 * kSearchWaves) void k_window_search(GridDev G, 
     const float sqd = distance(idx);
     out_idx[off + p] = idx;
     out_dist[off + p] = sqd;
-    if (out_meta) out_meta[off + p] = ((unsigned)p << 16) | (unsigned)q;   // position in the list | query
   };
   // the general walk (any window, any list length): one dependent chain cell range -> items -> keypoints per column and pass
   auto walk = [&](int pass) {
@@ -437,7 +436,7 @@ hipError_t copy_rows(hipStream_t st, void* dst, const void* src, size_t bytes) {
 // LAST writer = the largest q picking it.
 // KIND 0 = SearchByProjection(frame, frame) (:1318-1452): best only, TH_HIGH, rotation histogram over every write.
 // KIND 1 = SearchByProjection(frame, points) (:44-122): best / second best with levels and the ratio test; counts twice.
-// Round 2-3 solved the recurrence with every candidate bidding for its query in every iteration (k_resolve: 86-91 us for the frame-to-frame
+// Round 2-3 solved the recurrence with every candidate bidding for its query in every iteration (historical, removed: `k_resolve`, 86-91 us for the frame-to-frame
 // search); since round 4 the search hands its lists over in preference order and the replay walks their heads (resolve2.h: 33-40 us) --
 // the bidding kernel was removed in round 5 (DESIGN.md section 4.0c keeps its numbers).
 // (the claim replay over sorted lists -- Resolve2Args, resolve2_body -- lives in resolve2.h: ba.hip runs it inside k_resolve_pose)
@@ -627,7 +626,6 @@ struct MatcherState {
   int last_total[4] = {1 << 15, 1 << 15, 1 << 15, 1 << 15};  // candidates the previous search of each kind produced
   WinQuery *d_queries = nullptr, *h_queries = nullptr;   // h_* pinned
   int *d_q_off = nullptr, *d_q_cnt = nullptr, *d_total = nullptr, *d_idx = nullptr;
-  unsigned* d_meta = nullptr;  // per candidate: position in its list << 16 | query (k_resolve)
   float* d_dist = nullptr;
   int *h_q = nullptr;      // [2*q_cap + 1]: off, cnt, total
   int* h_idx = nullptr;
@@ -644,9 +642,6 @@ struct MatcherState {
   size_t h_attr_cap[2] = {0, 0};
   hipEvent_t ev_attr[2] = {nullptr, nullptr};
   int attr_turn = 0;
-  // device-side replay (k_resolve): pinned staging for flags in / matches out
-  int* h_res = nullptr;      // [res_cap + 4] ints, then res_cap bytes of flags
-  int res_cap = 0;
   bool replay_host = false;  // ASD_MATCH_REPLAY=host at asd_ctx_create
 };
 
@@ -671,18 +666,17 @@ int ensure_queries(asd_ctx* ctx, MatcherState* m, int nq) {
   m->q_cap = cap;
   return ASD_OK;
 }
-// device candidate buffers (k_window_search's output, k_resolve's input): 12 B per candidate
+// device candidate buffers (k_window_search's output, k_resolve2's input): 8 B per candidate, twice over
 int ensure_cands_dev(asd_ctx* ctx, MatcherState* m, size_t n) {
   if (n <= (size_t)m->cand_cap) return ASD_OK;
   if (n > ((size_t)1 << 30)) { ctx->set_error("candidate buffers: %zu entries asked for", n); return ASD_ERR_CAPACITY; }
   const size_t cap = std::max(n + n / 2, (size_t)1 << 18);
-  if (m->d_idx) { (void)hipFree(m->d_idx); (void)hipFree(m->d_dist); (void)hipFree(m->d_meta); }
-  m->d_idx = nullptr; m->d_dist = nullptr; m->d_meta = nullptr;
+  if (m->d_idx) { (void)hipFree(m->d_idx); (void)hipFree(m->d_dist); }
+  m->d_idx = nullptr; m->d_dist = nullptr;
   m->cand_cap = 0;
   // idx / dist twice over: k_window_search<true> writes the sorted copy of a list that took its slow path into the second half
   ASD_HIP_CHECK(ctx, hipMalloc(&m->d_idx, 2 * cap * sizeof(int)));
   ASD_HIP_CHECK(ctx, hipMalloc(&m->d_dist, 2 * cap * sizeof(float)));
-  ASD_HIP_CHECK(ctx, hipMalloc(&m->d_meta, cap * sizeof(unsigned)));
   m->cand_cap = (int)std::min(cap, (size_t)0x7fffffff);
   return ASD_OK;
 }
@@ -752,7 +746,7 @@ int window_search(asd_ctx* ctx, MatcherState* m, const AsdFrameSlot& F, int nq, 
     GridDev G{F.d_kp, F.d_cell_start, F.d_cell_items, F.min_x, F.min_y, F.inv_w, F.inv_h};
     ASD_HIP_CHECK(ctx, hipEventRecord(ctx->ev0, st));
     hipLaunchKernelGGL(k_window_search<false>, dim3((nq + kSearchWaves - 1) / kSearchWaves), dim3(64 * kSearchWaves), 0, st, G, m->d_queries, nq, d_q, F.d_desc, d_off, d_cnt,
-                       d_total, m->cand_cap, m->d_idx, m->d_dist, (unsigned*)nullptr, SortArgs{});
+                       d_total, m->cand_cap, m->d_idx, m->d_dist, SortArgs{});
     ASD_HIP_CHECK(ctx, hipGetLastError());
     ASD_HIP_CHECK(ctx, hipEventRecord(ctx->ev1, st));
     ASD_HIP_CHECK(ctx, hipMemcpyAsync(m->h_q, d_off, ((size_t)2 * nq + 1) * sizeof(int), hipMemcpyDeviceToHost, st));
@@ -790,7 +784,7 @@ int window_search(asd_ctx* ctx, MatcherState* m, const AsdFrameSlot& F, int nq, 
 }
 
 
-// where the claim / ratio / histogram replay runs: on the device (k_resolve, default) or on the host over the copied-back
+// where the claim / ratio / histogram replay runs: on the device (k_resolve2, default) or on the host over the copied-back
 // candidate lists (ASD_MATCH_REPLAY=host in the environment of asd_ctx_create; also taken when the tables would
 // not fit the workgroup's LDS or there are more than 4096 queries)
 size_t resolve_lds_bytes(int kind, int n_cur, int nq) {
@@ -804,191 +798,361 @@ bool replay_on_device(const MatcherState* m, int kind, int n_cur, int nq) {
   return !m->replay_host && n_cur > 0 && n_cur < 65536 && nq <= max_q && resolve_lds_bytes(kind, n_cur, nq) <= 96 * 1024;
 }
 
-// k_window_search + k_resolve<KIND> behind one synchronisation: queries are in m->h_queries[0..nq), flags (may be null) are
-// copied through pinned staging, match_cur[n_cur] / *n_matches come back.  kp_last = last frame's device keypoints (KIND 0).
-// what a fused chain adds to a search: tables that travel in the search's upload block, and room for its results in the
-// search's result block
-constexpr int kChainTabs = 8;
-struct ChainHook {
-  const void* src[kChainTabs] = {};   // host tables that travel in the upload block (world positions, flags, ...)
-  size_t bytes[kChainTabs] = {};
-  size_t result_bytes = 0;            // room wanted in the result block
-  // optional: the queries are made on the device from the uploaded tables (frustum test + window of every map point)
-  // instead of being copied from m->h_queries; called after the upload, before the search
-  // (h_tab: the same tables inside the pinned upload block; tail: the copy the kernel carries, see UploadTail)
-  std::function<int(WinQuery* d_queries, void* const* d_tab, void* const* h_tab, const UploadTail& tail)> prepare;
-  // enqueue the chain's kernels: match table, the uploaded tables, where the results go (all device pointers)
-  // fused (may be null): the stage's claim replay, to run in FRONT of the solver inside its workgroup (k_resolve_pose) instead of as a kernel of its own
-  std::function<int(const int* d_match, void* const* d_tab, void* d_result, const AsdFusedReplay* fused)> enqueue;
-  const void* h_result = nullptr;     // out: the chain's results on the host after the call
-  bool kp_flags = false;              // out: the form pose_chain_enqueue gave the flags in that block (per keypoint + edge count, or per edge) --
-                                      // carried with the chain: the context-wide pose_chain_kp_flags belongs to whichever chain was enqueued last
+// bank rows named by a caller: rows[i] for every i (or every i with used[i]) inside the descriptor bank and, with `attr_too`, inside the
+// attribute bank as well
+int check_bank_rows(asd_ctx* ctx, const MatcherState* m, const int32_t* rows, const uint8_t* used, int n, bool attr_too) {
+  for (int i = 0; i < n; ++i) {
+    if (used && !used[i]) continue;
+    if (rows[i] < 0 || rows[i] >= m->bank_cap) { ctx->set_error("bank row %d out of range (descriptor bank: %d rows)", rows[i], m->bank_cap); return ASD_ERR_INVALID; }
+    if (attr_too && rows[i] >= m->attr_cap) { ctx->set_error("bank row %d out of range (attribute bank: %d rows)", rows[i], m->attr_cap); return ASD_ERR_INVALID; }
+  }
+  return ASD_OK;
+}
+
+// ---- one tracking stage ------------------------------------------------------------------------------------------------------------
+// [query kernel] -> k_window_search<true> -> claim replay -> [PoseOptimization], described by ONE struct and enqueued by ONE function
+// (enqueue_stage).  asd_match_project_* and the single-stage asd_track_* chains run one stage behind one synchronisation
+// (search_and_resolve: with a second search after a candidate overflow, or deferred); asd_track_frame runs two with the between-stage
+// block and no second search.  Every pointer of a description is final when it is built -- device memory, or the context's pinned upload /
+// result blocks, which do not move after AsdXfer::begin -- so a stage can be enqueued a second time from the same description.
+struct StageSolver {               // PoseOptimization behind the replay, on the match table it wrote (pose_chain_enqueue)
+  const float* d_points;           // [.][3] world positions the match table names
+  const uint8_t* d_hold;           // [n_cur] or null: keypoints that held a map point on entry ...
+  const float* d_own;              // [n_cur][3] or null: ... and that point's position
+  double pose0[7];                 // the start pose, unless
+  const double* d_pose0;           // non-null: it is read from the device (the stage in front wrote it)
+  double K[4];
+  double* io;                      // the solver's reservation in the result block (pinned: the kernel stores there directly)
+  double* d_io_dev;                // optional: a second copy in device memory for the stage behind
+  const AsdBetweenArgs* d_between; // optional: the work between two stages as the solver's tail
+};
+enum QuerySource { kQueriesUploaded, kQueriesProject, kQueriesFrustum };   // the host's table inside the upload block, or the kernel that writes it
+enum StageUpload { kUploadElsewhere, kUploadCopy, kUploadCarried };       // the upload block: an earlier stage's business / a copy in front of
+                                                                           // the stage / carried by the tail blocks of the stage's query kernel
+struct TrackStage {
+  int kind, nq;                    // 0 frame to frame, 1 local map; number of queries
+  const AsdFrameSlot* F;           // the current frame
+  QuerySource source;
+  ProjectArgs project;             // kQueriesProject
+  FrustumArgs frustum;             // kQueriesFrustum
+  StageUpload upload;
+  const WinQuery* d_queries;
+  const float* d_qdesc;            // the queries' descriptor table (m->d_qdesc or m->d_bank)
+  const float4* kp_last;           // kind 0: the last frame's keypoints
+  const uint8_t* d_obs_pos;        // [nq] or null: Observations() > 0 per query
+  const uint8_t* d_occupied;       // [n_cur] or null: keypoints that hold a map point on entry (kind 1)
+  int check_ori;
+  float nn_ratio;
+  int *d_off, *d_cnt;              // [nq] each: the lists' offsets and pickable heads
+  int* d_total;                    // the candidate counter (a zeroed word of the upload block)
+  uint16_t* d_top;                 // [nq][kTop]
+  int *d_out, *h_out;              // match table [n_cur] + counters: the result block's reservation on the device and its pinned twin
+  bool timed;                      // ASD_TIMING: event records around search + replay (the "match" clock of asd_last_stage_ms)
+  bool has_solver;
+  StageSolver solver;
 };
 
-template <int KIND>
-int search_and_resolve(asd_ctx* ctx, MatcherState* m, const AsdFrameSlot& F, int nq, const float* d_q, const float4* kp_last,
-                       const uint8_t* obs_pos, const uint8_t* occupied, int check_ori, float nn_ratio, int32_t* match_cur,
-                       int32_t* n_matches, ChainHook* chain = nullptr, std::function<int()>* defer = nullptr) {
-  // One upload block (queries, the zeroed candidate counter, flags, the chain's tables), the kernels back to back, one result
-  // block (match table, counters, the chain's results), one synchronisation: a copy costs 15-25 us on this stream whatever
-  // its size (rocprof timeline), five of them per call were a third of the call.
-  // Split in two: `attempt` enqueues everything (inputs are consumed: they live in the pinned upload block from then on),
-  // `complete` synchronises, handles a candidate-buffer overflow (grow, enqueue again) and unpacks.  With `defer` the caller gets
-  // `complete` back instead of having it run (asd_track_async / asd_track_finish); `chain` must then outlive it.
+// the copy of the upload block that a query kernel's tail blocks carry (the query table is the block's first reservation: the copy starts
+// behind it); not carried: the kernel has query blocks only
+UploadTail upload_tail(const AsdXfer& up, int nq, bool carried) {
+  return UploadTail{reinterpret_cast<const uint4*>(up.h), reinterpret_cast<uint4*>(up.d), carried ? ((size_t)nq * sizeof(WinQuery) + 255) / 256 * 16 : 0,
+                    carried ? (up.used + 15) / 16 : 0, (nq + 255) / 256};
+}
+
+// k_project_queries' constants (the tables, the query table and the upload tail belong to the stage that owns them)
+ProjectArgs project_args(const asd_ctx* ctx, const AsdFrameSlot& C, const AsdFrameSlot& L, const float* Tcw, const float* K, float th) {
+  ProjectArgs pa{};
+  pa.n = L.n; pa.kp_last = L.d_kp;
+  memcpy(pa.T, Tcw, sizeof pa.T);
+  pa.fx = K[0]; pa.fy = K[1]; pa.cx = K[2]; pa.cy = K[3];
+  pa.min_x = C.min_x; pa.max_x = C.max_x; pa.min_y = C.min_y; pa.max_y = C.max_y; pa.th = th;
+  for (int l = 0; l < ASD_MAX_LEVELS; ++l) pa.scale[l] = l < ctx->cfg.n_levels ? ctx->scale[l] : 0.f;
+  return pa;
+}
+// k_frustum_queries' constants.  The frame pose by value (Tcw, host) or from device memory (T_dev[19]: Tcw + Ow, written by the stage in front)
+FrustumArgs frustum_args(const asd_ctx* ctx, const AsdFrameSlot& F, int n, const float* Tcw, const float* T_dev, const float* K, float cos_limit, float th) {
+  FrustumArgs fa{};
+  fa.n = n; fa.n_levels = ctx->cfg.n_levels; fa.bfactor = th != 1.0;
+  if (Tcw) {
+    memcpy(fa.T, Tcw, sizeof fa.T);
+    for (int i = 0; i < 3; ++i) {  // mOw = -mRcw.t()*mtcw (Frame.cc:157): transposed gemm accumulates in double
+      double sum = 0;
+      for (int k = 0; k < 3; ++k) sum += (double)Tcw[k * 4 + i] * (double)Tcw[k * 4 + 3];
+      fa.Ow[i] = (float)(-1.0 * sum);
+    }
+  }
+  fa.T_dev = T_dev;
+  fa.fx = K[0]; fa.fy = K[1]; fa.cx = K[2]; fa.cy = K[3];
+  fa.min_x = F.min_x; fa.max_x = F.max_x; fa.min_y = F.min_y; fa.max_y = F.max_y;
+  fa.cos_limit = cos_limit; fa.th = th;
+  for (int l = 0; l < ASD_MAX_LEVELS; ++l) { fa.level_thr[l] = ctx->level_thr[l]; fa.scale[l] = l < ctx->cfg.n_levels ? ctx->scale[l] : 0.f; }
+  return fa;
+}
+// the replay's argument block of a stage; returns the dynamic LDS it needs
+size_t resolve2_args(const MatcherState* m, const TrackStage& s, Resolve2Args* out) {
+  const int n_cur = s.F->n;
+  Resolve2Args a{};
+  a.nq = s.nq; a.n_cur = n_cur;
+  a.q_off = s.d_off; a.q_cnt = s.d_cnt; a.idx = m->d_idx; a.dist = m->d_dist; a.top_idx = s.d_top;
+  a.total = s.d_total; a.cap = m->cand_cap;
+  a.obs_pos = s.d_obs_pos;
+  a.kp_cur = s.F->d_kp; a.kp_last = s.kp_last;
+  a.check_ori = s.check_ori; a.nn_ratio = s.nn_ratio;
+  a.match_cur = s.d_out; a.n_matches = s.d_out + n_cur; a.mirror = s.h_out;
+  // the sorted lists' copy in LDS (for queries whose four best are all held): what the previous search of this kind produced and
+  // a quarter on top, as far as the 96 KB this kernel may ask for allow; entries beyond it are read from global memory
+  const size_t fixed = resolve_lds_bytes(s.kind, n_cur, s.nq), per = s.kind == 1 ? 6 : 2;
+  a.stage_cap = (int)std::min<size_t>(((size_t)m->last_total[s.kind] * 5 / 4 + 1023) / 1024 * 1024, ((size_t)96 * 1024 - fixed) / per / 8 * 8);
+  *out = a;
+  return fixed + (size_t)a.stage_cap * per;
+}
+// more than 64 KB of dynamic LDS has to be asked for once per kernel and device: a runtime request, made ahead of a chain's first launch
+int resolve2_attributes(asd_ctx* ctx) {
+  static AsdPerDeviceOnce attrs;
+  if (!attrs.need(ctx->cfg.device)) return ASD_OK;
+  const void* ks[] = {reinterpret_cast<const void*>(k_resolve2<0, 2>), reinterpret_cast<const void*>(k_resolve2<0, 4>),
+                      reinterpret_cast<const void*>(k_resolve2<1, 2>), reinterpret_cast<const void*>(k_resolve2<1, 4>)};
+  for (const void* k : ks) ASD_HIP_CHECK(ctx, hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024));
+  attrs.done(ctx->cfg.device);
+  return ASD_OK;
+}
+hipError_t launch_resolve2(hipStream_t st, int kind, const Resolve2Args& a, size_t lds) {
+  auto go = [&](auto kern) { hipLaunchKernelGGL(kern, dim3(1), dim3(kResolve2Threads), lds, st, a); };
+  const bool two = a.nq <= 2 * kResolve2Threads;   // queries per thread
+  if (kind == 0) { if (two) go(k_resolve2<0, 2>); else go(k_resolve2<0, 4>); }
+  else { if (two) go(k_resolve2<1, 2>); else go(k_resolve2<1, 4>); }
+  return hipGetLastError();
+}
+// With a PoseOptimization behind the search, replay and solver are ONE workgroup (k_resolve_pose: resolve2_body on the solver's threads, then
+// the solver) where the stage's tables fit: as two kernels the solver waits 35-55 us for a CU of its own behind the replay, beside the
+// extractor's ASDNet workgroups
+bool stage_fuses(const asd_ctx* ctx, const MatcherState* m, const TrackStage& s) {
+  Resolve2Args a;
+  return s.has_solver && pose_chain_fused_ok(ctx, s.kind, s.nq, s.F->n, resolve2_args(m, s, &a));
+}
+
+// Enqueues one stage on the context's stream: [upload copy] [query kernel] search, then the replay as k_resolve2 [and the solver], or -- with
+// `fuse` (stage_fuses) -- replay and solver as one workgroup.  Launches only: every allocation and attribute was asked for by the caller.
+int enqueue_stage(asd_ctx* ctx, const MatcherState* m, const TrackStage& s, bool fuse) {
+  hipStream_t st = ctx->stream;
+  const AsdFrameSlot& F = *s.F;
+  int rc;
+  if (s.upload == kUploadCopy) ASD_HIP_CHECK(ctx, ctx->up.upload(st));
+  if (s.source == kQueriesProject) {
+    const UploadTail& t = s.project.up;
+    hipLaunchKernelGGL(k_project_queries, dim3(t.q_blocks + (t.n16 ? kUploadTailBlocks : 0)), dim3(256), 0, st, s.project);
+    ASD_HIP_CHECK(ctx, hipGetLastError());
+  } else if (s.source == kQueriesFrustum) {
+    const UploadTail& t = s.frustum.up;
+    hipLaunchKernelGGL(k_frustum_queries, dim3(t.q_blocks + (t.n16 ? kUploadTailBlocks : 0)), dim3(256), 0, st, s.frustum);
+    ASD_HIP_CHECK(ctx, hipGetLastError());
+  }
+  // (two timed event records per chain, each a barrier packet on the stream -- only when somebody asked for timings)
+  if (s.timed) ASD_HIP_CHECK(ctx, hipEventRecord(ctx->ev0, st));
+  // the lists in preference order (k_window_search<true>), the replay over their heads
+  const GridDev G{F.d_kp, F.d_cell_start, F.d_cell_items, F.min_x, F.min_y, F.inv_w, F.inv_h};
+  const SortArgs sa{s.d_occupied, s.kind == 0 ? TH_HIGH : __builtin_huge_valf(), s.d_top};
+  hipLaunchKernelGGL(k_window_search<true>, dim3((s.nq + kSearchWaves - 1) / kSearchWaves), dim3(64 * kSearchWaves), 0, st, G, s.d_queries, s.nq, s.d_qdesc, F.d_desc, s.d_off,
+                     s.d_cnt, s.d_total, m->cand_cap, m->d_idx, m->d_dist, sa);
+  ASD_HIP_CHECK(ctx, hipGetLastError());
+  Resolve2Args ra;
+  const size_t lds = resolve2_args(m, s, &ra);
+  if (!fuse) {
+    ASD_HIP_CHECK(ctx, launch_resolve2(st, s.kind, ra, lds));
+    if (s.timed) ASD_HIP_CHECK(ctx, hipEventRecord(ctx->ev1, st));
+  }
+  if (s.has_solver) {
+    const StageSolver& v = s.solver;
+    const AsdFusedReplay fr{&ra, s.kind, s.nq, lds};
+    AsdPoseChainArgs c{};
+    c.n_cur = F.n; c.d_match = s.d_out; c.d_kp = F.d_kp;
+    c.d_points = v.d_points; c.d_hold = v.d_hold; c.d_own = v.d_own;
+    c.pose7 = v.d_pose0 ? nullptr : v.pose0; c.K = v.K;
+    c.d_io = v.io; c.d_pose0 = v.d_pose0; c.d_io_dev = v.d_io_dev; c.between = v.d_between;
+    c.fused = fuse ? &fr : nullptr;
+    if ((rc = pose_chain_enqueue(ctx, c)) != ASD_OK) return rc;
+  }
+  if (fuse && s.timed) ASD_HIP_CHECK(ctx, hipEventRecord(ctx->ev1, st));   // (the "match" clock then covers the solver too)
+  return ASD_OK;
+}
+// the one event record at a chain's end.  The completion waits for THIS point of the stream, not for the stream: a split-phase caller
+// enqueues the next frame's grid and descriptor copies behind the chain, and they are not part of its result
+int record_chain_end(asd_ctx* ctx) {
+  if (!ctx->ev_chain) ASD_HIP_CHECK(ctx, hipEventCreateWithFlags(&ctx->ev_chain, hipEventDisableTiming));
+  ASD_HIP_CHECK(ctx, hipEventRecord(ctx->ev_chain, ctx->stream));
+  return ASD_OK;
+}
+
+// A solver's result block -- pose[7], n_bad, flags, edge count -- into the caller's arrays.  kp_flags (pose_chain_lds_form): the flags
+// come per keypoint with the edge count behind them; otherwise per edge, edges in keypoint order: keypoint j carries one when it held a
+// map point on entry (hold) or was matched.  Fewer than 3 edges leave the pose as it started (Optimizer.cc:323-324; the kernel cleared the flags).
+void unpack_solver_block(const double* h_io, int n_cur, bool kp_flags, const int32_t* match, const uint8_t* hold, const double* pose_start, double* pose,
+                         uint8_t* outlier, int32_t* n_inliers) {
+  int ne = 0;
+  if (kp_flags) {
+    ne = (int)(h_io[8 + (n_cur + 7) / 8] + 0.5);
+    memcpy(outlier, h_io + 8, (size_t)n_cur);
+  } else {
+    auto edge = [&](int j) { return (hold && hold[j]) || match[j] >= 0; };
+    for (int j = 0; j < n_cur; ++j) ne += edge(j);
+    const uint8_t* flags = reinterpret_cast<const uint8_t*>(h_io + 8);
+    for (int j = 0, e = 0; j < n_cur; ++j) outlier[j] = edge(j) && ne >= 3 ? flags[e++] : 0;
+  }
+  memcpy(pose, ne < 3 ? pose_start : h_io, 56);
+  *n_inliers = ne < 3 ? 0 : ne - (int)(h_io[7] + 0.5);
+}
+
+// What the host hands a single stage (search_and_resolve copies the tables into the upload block, in the order of the fields below; a null
+// table takes no room).  The search's own inputs first, then what a chain adds: the query kernel's tables and the solver's.
+struct StageInputs {
+  int kind = 0, nq = 0;
+  const float* d_qdesc = nullptr;
+  const float4* kp_last = nullptr;
+  const uint8_t* obs_pos = nullptr;     // [nq] or null
+  const uint8_t* occupied = nullptr;    // [n_cur] (kind 1)
+  int check_ori = 0;
+  float nn_ratio = 0.f;
+  QuerySource source = kQueriesUploaded;   // kQueriesUploaded: m->h_queries[0..nq)
+  ProjectArgs project{};                // constants (project_args / frustum_args); search_and_resolve points them at the tables
+  FrustumArgs frustum{};
+  bool has_solver = false;
+  double pose0[7] = {}, K[4] = {};
+  const float* points = nullptr;        // [n_points][3] positions the match table names, or
+  int n_points = 0;
+  const float* d_points = nullptr;      // ... the table on the device already
+  const uint8_t* has_mp = nullptr;      // [nq] k_project_queries
+  const float* own = nullptr;           // [n_cur][3] the solver's d_own
+  const uint8_t* hold = nullptr;        // [n_cur] the solver's d_hold (its own copy of `occupied`)
+  const float* normal = nullptr;        // [nq][3], [nq], [nq]: k_frustum_queries, with `points`
+  const float* min_dist = nullptr;
+  const float* max_dist = nullptr;
+  const int32_t* rows = nullptr;        // [nq] bank rows of the queries' descriptors, or null: row = query index
+};
+
+// One stage behind one synchronisation: one upload block (queries, the zeroed candidate counter, flags, the chain's tables), the kernels back
+// to back, one result block (match table, counters, the solver's results): a copy costs 15-25 us on this stream whatever its size
+// (rocprof timeline), five of them per call were a third of the call.
+// Split in two: `attempt` enqueues everything (inputs are consumed: they live in the pinned upload block from then on), `complete`
+// synchronises, handles a candidate-buffer overflow (grow, enqueue again from the same description) and unpacks match_cur[n_cur] / *n_matches.
+// With `defer` the caller gets `complete` back instead of having it run (asd_track_async / asd_track_finish).  *solver_io: where the
+// solver's result block will be on the host.
+int search_and_resolve(asd_ctx* ctx, MatcherState* m, const AsdFrameSlot& F, const StageInputs& in, int32_t* match_cur, int32_t* n_matches,
+                       const double** solver_io = nullptr, std::function<int()>* defer = nullptr) {
   if (asd_track_busy(ctx, "matcher call")) return ASD_ERR_INVALID;
-  const int n_cur = F.n;
+  static const bool timing = getenv("ASD_TIMING") != nullptr;
+  static const bool tail_upload = getenv("ASD_UPLOAD_COPY") == nullptr;   // ASD_UPLOAD_COPY=1 (copy commands instead of copy kernels) makes the upload a command of its own
+  const int n_cur = F.n, nq = in.nq, kind = in.kind;
   // A deferred completion (asd_track_async) runs after the caller may have rewritten bank rows and other frame slots
   // (include/asd_slam.h allows asd_bank_put* / asd_frame_set in between), so it must never have to search again: the candidate
   // buffers are sized for the worst case up front -- a query's list holds at most every keypoint of the frame -- and an
-  // overflow at completion is an error, not a retry.  (12 B x nq x n_cur: 96 MB at 4000 x 2000; 288 GB of HBM make that a non-issue.)
+  // overflow at completion is an error, not a retry.  (16 B x nq x n_cur: 128 MB at 4000 x 2000; 288 GB of HBM make that a non-issue.)
   const bool deferred = defer != nullptr;
   int rc = ensure_cands_dev(ctx, m, deferred ? std::max((size_t)nq * (size_t)std::max(n_cur, 1), (size_t)1) : (size_t)1);
   if (rc != ASD_OK) return rc;
   hipStream_t st = ctx->stream;
-  const AsdFrameSlot* Fp = &F;
-  {
-    AsdXfer &up = ctx->up, &down = ctx->down;
-    size_t extra = 0;
-    if (chain) for (int i = 0; i < kChainTabs; ++i) extra += chain->bytes[i] + 256;
-    ASD_HIP_CHECK(ctx, up.begin(st, (size_t)nq * sizeof(WinQuery) + 256 + (size_t)nq + (size_t)n_cur + 1024 + extra));
-    ASD_HIP_CHECK(ctx, down.begin(st, ((size_t)n_cur + 16) * sizeof(int) + 256 + (chain ? chain->result_bytes : 0)));
-    ASD_HIP_CHECK(ctx, ctx->scratch.reserve(AsdDevBuf::padded((size_t)nq * 4) + AsdDevBuf::padded((size_t)nq * kTop * 2)));
-  }
-  int* d_pick = ctx->scratch.carve<int>(nq);
-  uint16_t* d_top_idx = ctx->scratch.carve<uint16_t>((size_t)nq * kTop);
-  const bool dev_queries = chain && chain->prepare;
-  const size_t o_q = dev_queries ? ctx->up.reserve((size_t)nq * sizeof(WinQuery)) : ctx->up.add(m->h_queries, (size_t)nq * sizeof(WinQuery));
-  const size_t o_total = ctx->up.zeros(sizeof(int));
-  const bool has_obs = obs_pos != nullptr;
-  const size_t o_obs = has_obs ? ctx->up.add(obs_pos, nq) : 0;
-  const size_t o_occ = KIND == 1 ? ctx->up.add(occupied, n_cur) : 0;
-  std::array<size_t, kChainTabs> o_tab{};
-  std::array<bool, kChainTabs> has_tab{};
-  if (chain) for (int i = 0; i < kChainTabs; ++i) if (chain->src[i]) { o_tab[i] = ctx->up.add(chain->src[i], chain->bytes[i]); has_tab[i] = true; }
-  const size_t o_out = ctx->down.reserve(((size_t)n_cur + 16) * sizeof(int));
-  const size_t o_res = chain ? ctx->down.reserve(chain->result_bytes) : 0;
+  AsdXfer &up = ctx->up, &down = ctx->down;
+  const size_t io_bytes = in.has_solver ? pose_chain_io_bytes(n_cur) : 0;
+  ASD_HIP_CHECK(ctx, up.begin(st, (size_t)nq * (sizeof(WinQuery) + 1 + 12 + 12 + 4 + 4 + 4) + (size_t)in.n_points * 12 + (size_t)n_cur * (1 + 12 + 1) + 16 * 256));
+  ASD_HIP_CHECK(ctx, down.begin(st, ((size_t)n_cur + 16) * sizeof(int) + 256 + io_bytes));
+  ASD_HIP_CHECK(ctx, ctx->scratch.reserve(AsdDevBuf::padded((size_t)nq * kTop * 2)));
+  // every runtime request of the chain that is not a launch happens here, before the first kernel goes out
+  if ((rc = resolve2_attributes(ctx)) != ASD_OK || (in.has_solver && (rc = pose_chain_reserve(ctx, n_cur)) != ASD_OK)) return rc;
 
-  auto attempt = [=]() -> int {
-    AsdXfer &up = ctx->up, &down = ctx->down;
-    const AsdFrameSlot& F = *Fp;
-    int* d_out = down.dev<int>(o_out);
-    int* d_off = m->d_q_off;
-    int* d_cnt = m->d_q_off + nq;
-    int* d_total = up.dev<int>(o_total);
-    int rc;
-    // ASD_UPLOAD_COPY=1 (copy commands instead of copy kernels) makes the upload a command of its own
-    static const bool tail_upload = getenv("ASD_UPLOAD_COPY") == nullptr;
-    const bool carried = dev_queries && tail_upload;
-    if (!carried) ASD_HIP_CHECK(ctx, up.upload(st));
-    void *d_tab[kChainTabs], *h_tab[kChainTabs];
-    for (int i = 0; i < kChainTabs; ++i) {
-      d_tab[i] = has_tab[i] ? up.dev<void>(o_tab[i]) : nullptr;
-      h_tab[i] = has_tab[i] ? (carried ? up.host<void>(o_tab[i]) : up.dev<void>(o_tab[i])) : nullptr;
-    }
-    if (dev_queries) {
-      // the query table is the block's first reservation: the copy starts behind it
-      const UploadTail tail{reinterpret_cast<const uint4*>(up.h), reinterpret_cast<uint4*>(up.d), carried ? ((size_t)nq * sizeof(WinQuery) + 255) / 256 * 16 : 0,
-                            carried ? (up.used + 15) / 16 : 0, 0};
-      if ((rc = chain->prepare(up.dev<WinQuery>(o_q), d_tab, h_tab, tail)) != ASD_OK) return rc;
-    }
-    GridDev G{F.d_kp, F.d_cell_start, F.d_cell_items, F.min_x, F.min_y, F.inv_w, F.inv_h};
-    // (the "match" stage clock of asd_last_stage_ms: two timed event records per chain, each a barrier packet on the stream -- only
-    // when somebody asked for timings)
-    static const bool stage_timing = getenv("ASD_TIMING") != nullptr;
-    if (stage_timing) ASD_HIP_CHECK(ctx, hipEventRecord(ctx->ev0, st));
-    constexpr bool zero_copy = true;   // results stored by the kernels straight into the pinned block
-    {
-      // the lists in preference order (k_window_search<true>), the replay over their heads (k_resolve2)
-      SortArgs sa{KIND == 1 ? up.dev<uint8_t>(o_occ) : nullptr, KIND == 0 ? TH_HIGH : __builtin_huge_valf(), d_top_idx};
-      hipLaunchKernelGGL(k_window_search<true>, dim3((nq + kSearchWaves - 1) / kSearchWaves), dim3(64 * kSearchWaves), 0, st, G, up.dev<WinQuery>(o_q), nq, d_q, F.d_desc, d_off,
-                         d_cnt, d_total, m->cand_cap, m->d_idx, m->d_dist, (unsigned*)nullptr, sa);
-      ASD_HIP_CHECK(ctx, hipGetLastError());
-      Resolve2Args a{};
-      a.nq = nq; a.n_cur = n_cur;
-      a.q_off = d_off; a.q_cnt = d_cnt; a.idx = m->d_idx; a.dist = m->d_dist; a.top_idx = d_top_idx;
-      a.total = d_total; a.cap = m->cand_cap;
-      a.obs_pos = has_obs ? up.dev<uint8_t>(o_obs) : nullptr;
-      a.kp_cur = F.d_kp; a.kp_last = kp_last;
-      a.check_ori = check_ori; a.nn_ratio = nn_ratio;
-      a.match_cur = d_out; a.n_matches = d_out + n_cur;
-      a.mirror = zero_copy ? down.host<int>(o_out) : nullptr;
-      // the sorted lists' copy in LDS (for queries whose four best are all held): what the previous search of this kind produced and
-      // a quarter on top, as far as the 96 KB this kernel may ask for allow; entries beyond it are read from global memory
-      const size_t fixed = resolve_lds_bytes(KIND, n_cur, nq), per = KIND == 1 ? 6 : 2;
-      a.stage_cap = (int)std::min<size_t>(((size_t)m->last_total[KIND] * 5 / 4 + 1023) / 1024 * 1024, ((size_t)96 * 1024 - fixed) / per / 8 * 8);
-      const size_t lds = fixed + (size_t)a.stage_cap * per;
-      auto launch = [&](auto kern) -> hipError_t {
-        static AsdPerDeviceOnce attr_set;   // per instantiation and device: more than 64 KB of dynamic LDS has to be asked for once
-        if (attr_set.need(ctx->cfg.device)) {
-          const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024);
-          if (e != hipSuccess) return e;
-          attr_set.done(ctx->cfg.device);
-        }
-        hipLaunchKernelGGL(kern, dim3(1), dim3(kResolve2Threads), lds, st, a);
-        return hipGetLastError();
-      };
-      // With a PoseOptimization chained behind the search, replay and solver are ONE workgroup (k_resolve_pose: resolve2_body on the solver's
-      // threads, then the solver) where the stage's tables fit: as two kernels the solver waits 35-55 us for a CU of its own behind the replay,
-      // beside the extractor's ASDNet workgroups (round 4 had this form in asd_track_frame only; the two-call form is the headline since round 5)
-      const bool fuse = chain && pose_chain_fused_ok(ctx, KIND, nq, n_cur, lds);
-      if (fuse) {
-        const AsdFusedReplay fr{&a, KIND, nq, lds};
-        if ((rc = chain->enqueue(d_out, d_tab, down.host<void>(o_res), &fr)) != ASD_OK) return rc;
-        chain->h_result = down.host<void>(o_res);
-        chain->kp_flags = ctx->pose_chain_kp_flags;
-        if (stage_timing) ASD_HIP_CHECK(ctx, hipEventRecord(ctx->ev1, st));   // (the "match" stage clock then covers the solver too)
-      } else {
-        if (nq <= 2 * kResolve2Threads) ASD_HIP_CHECK(ctx, launch(k_resolve2<KIND, 2>));
-        else ASD_HIP_CHECK(ctx, launch(k_resolve2<KIND, 4>));
-        if (stage_timing) ASD_HIP_CHECK(ctx, hipEventRecord(ctx->ev1, st));
-        if (chain) {
-          if ((rc = chain->enqueue(d_out, d_tab, zero_copy ? down.host<void>(o_res) : down.dev<void>(o_res), nullptr)) != ASD_OK) return rc;
-          chain->h_result = down.host<void>(o_res);
-          chain->kp_flags = ctx->pose_chain_kp_flags;
-        }
-      }
-    }
-    if (!zero_copy) ASD_HIP_CHECK(ctx, down.download(st));
-    // the completion waits for THIS point of the stream, not for the stream: a split-phase caller enqueues the next frame's grid
-    // and descriptor copies behind the chain, and they are not part of its result
-    if (!ctx->ev_chain) ASD_HIP_CHECK(ctx, hipEventCreateWithFlags(&ctx->ev_chain, hipEventDisableTiming));
-    ASD_HIP_CHECK(ctx, hipEventRecord(ctx->ev_chain, st));
-    return ASD_OK;
+  TrackStage s{};
+  s.kind = kind; s.nq = nq; s.F = &F;
+  s.source = in.source;
+  s.upload = in.source != kQueriesUploaded && tail_upload ? kUploadCarried : kUploadCopy;
+  s.d_qdesc = in.d_qdesc; s.kp_last = in.kp_last; s.check_ori = in.check_ori; s.nn_ratio = in.nn_ratio;
+  s.d_off = m->d_q_off; s.d_cnt = m->d_q_off + nq;
+  s.d_top = ctx->scratch.carve<uint16_t>((size_t)nq * kTop);
+  s.timed = timing;
+  // the upload block: the query table first (a query kernel writes the device twin, the tail blocks copy what lies behind it)
+  const size_t o_q = in.source == kQueriesUploaded ? up.add(m->h_queries, (size_t)nq * sizeof(WinQuery)) : up.reserve((size_t)nq * sizeof(WinQuery));
+  const size_t o_total = up.zeros(sizeof(int));
+  s.d_queries = up.dev<WinQuery>(o_q);
+  s.d_total = up.dev<int>(o_total);
+  if (in.obs_pos) s.d_obs_pos = up.dev<uint8_t>(up.add(in.obs_pos, nq));
+  if (kind == 1) s.d_occupied = up.dev<uint8_t>(up.add(in.occupied, n_cur));
+  // a query kernel that carries the upload reads its tables from the PINNED block, the kernels behind it the device twin
+  const bool carried = s.upload == kUploadCarried;
+  const void *q_points = nullptr, *q_has = nullptr, *q_normal = nullptr, *q_min = nullptr, *q_max = nullptr, *q_rows = nullptr;
+  auto table = [&](const void* src, size_t bytes, const void** for_query) -> const void* {
+    if (!src) return nullptr;
+    const size_t o = up.add(src, bytes);
+    if (for_query) *for_query = carried ? up.host<void>(o) : up.dev<void>(o);
+    return up.dev<void>(o);
+  };
+  const void* d_points = table(in.points, (size_t)in.n_points * 12, &q_points);
+  (void)table(in.has_mp, nq, &q_has);
+  const void* d_own = table(in.own, (size_t)n_cur * 12, nullptr);
+  const void* d_hold = table(in.hold, n_cur, nullptr);
+  (void)table(in.normal, (size_t)nq * 12, &q_normal);
+  (void)table(in.min_dist, (size_t)nq * 4, &q_min);
+  (void)table(in.max_dist, (size_t)nq * 4, &q_max);
+  (void)table(in.rows, (size_t)nq * 4, &q_rows);
+  if (in.source == kQueriesProject) {
+    s.project = in.project;
+    s.project.Xw = static_cast<const float*>(q_points); s.project.has_mp = static_cast<const uint8_t*>(q_has); s.project.rows = static_cast<const int*>(q_rows);
+    s.project.queries = up.dev<WinQuery>(o_q);
+    s.project.up = upload_tail(up, nq, carried);
+  } else if (in.source == kQueriesFrustum) {
+    s.frustum = in.frustum;
+    s.frustum.Xw = static_cast<const float*>(q_points); s.frustum.normal = static_cast<const float*>(q_normal);
+    s.frustum.min_dist = static_cast<const float*>(q_min); s.frustum.max_dist = static_cast<const float*>(q_max);
+    s.frustum.rows = static_cast<const int*>(q_rows);
+    s.frustum.queries = up.dev<WinQuery>(o_q);
+    s.frustum.up = upload_tail(up, nq, carried);
+  }
+  // the result block: results stored by the kernels straight into the pinned block
+  const size_t o_out = down.reserve(((size_t)n_cur + 16) * sizeof(int));
+  s.d_out = down.dev<int>(o_out); s.h_out = down.host<int>(o_out);
+  s.has_solver = in.has_solver;
+  if (in.has_solver) {
+    StageSolver& v = s.solver;
+    v.d_points = in.d_points ? in.d_points : static_cast<const float*>(d_points);
+    v.d_hold = static_cast<const uint8_t*>(d_hold); v.d_own = static_cast<const float*>(d_own);
+    memcpy(v.pose0, in.pose0, sizeof v.pose0); memcpy(v.K, in.K, sizeof v.K);
+    v.io = down.host<double>(down.reserve(io_bytes));
+    if (solver_io) *solver_io = v.io;
+  }
+  int* const h_total = up.host<int>(o_total);
+  const int* const h_out = s.h_out;
+
+  auto attempt = [ctx, m, s]() -> int {
+    const int rc = enqueue_stage(ctx, m, s, stage_fuses(ctx, m, s));
+    return rc != ASD_OK ? rc : record_chain_end(ctx);
   };
 
   auto complete = [=]() -> int {
-    const int* h_out = ctx->down.host<int>(o_out);
     int rc;
     for (int round = 0;; ++round) {
       ASD_HIP_CHECK(ctx, hipEventSynchronize(ctx->ev_chain));
       const int total = h_out[n_cur + 1];
-      m->last_total[KIND] = total;
+      m->last_total[kind] = total;
       if (total > m->cand_cap && deferred) {   // cannot happen with the worst-case sizing above; never search again over state the caller may have changed
         ctx->set_error("asd_track_finish: %d candidates overflowed the %d-entry buffers of a deferred stage", total, m->cand_cap);
         return ASD_ERR_CAPACITY;
       }
-      if (total > m->cand_cap && round == 0) {  // the candidate buffers overflowed (k_resolve did not run): grow and search again
+      if (total > m->cand_cap && round == 0) {  // the candidate buffers overflowed (the replay did not run): grow and search again
         if ((rc = ensure_cands_dev(ctx, m, (size_t)total)) != ASD_OK) return rc;
-        *ctx->up.host<int>(o_total) = 0;
+        *h_total = 0;
         if ((rc = attempt()) != ASD_OK) return rc;
         continue;
       }
       break;
     }
-    static const bool stage_timing = getenv("ASD_TIMING") != nullptr;
-    if (stage_timing) ASD_HIP_CHECK(ctx, hipEventElapsedTime(&ctx->ms_match, ctx->ev0, ctx->ev1));
+    if (timing) ASD_HIP_CHECK(ctx, hipEventElapsedTime(&ctx->ms_match, ctx->ev0, ctx->ev1));
     else ctx->ms_match = 0.f;
     memcpy(match_cur, h_out, (size_t)n_cur * sizeof(int));
     *n_matches = h_out[n_cur];
-    static const bool timing = getenv("ASD_TIMING") != nullptr;
     if (timing) {
       static double acc[2]; static long calls[2]; static long rounds[2]; static double st_us[2][8];
-      acc[KIND] += ctx->ms_match; rounds[KIND] += h_out[n_cur + 2];
-      for (int i = 0; i < 8; ++i) st_us[KIND][i] += 0.01 * h_out[n_cur + 3 + i];
-      if (++calls[KIND] % 200 == 0)
-        fprintf(stderr, "[search+resolve kind %d] device %.3f ms, %.1f iterations, %d candidates; replay: staging %.1f us, iterations %.1f us (the first %.1f; thread 0 work %.1f, barrier + verdict %.1f), outputs %.1f us\n", KIND,
-                acc[KIND] / calls[KIND], (double)rounds[KIND] / calls[KIND], h_out[n_cur + 1], st_us[KIND][0] / calls[KIND], st_us[KIND][1] / calls[KIND],
-                st_us[KIND][3] / calls[KIND], st_us[KIND][4] / calls[KIND], st_us[KIND][5] / calls[KIND], st_us[KIND][2] / calls[KIND]);
+      acc[kind] += ctx->ms_match; rounds[kind] += h_out[n_cur + 2];
+      for (int i = 0; i < 8; ++i) st_us[kind][i] += 0.01 * h_out[n_cur + 3 + i];
+      if (++calls[kind] % 200 == 0)
+        fprintf(stderr, "[search+resolve kind %d] device %.3f ms, %.1f iterations, %d candidates; replay: staging %.1f us, iterations %.1f us (the first %.1f; thread 0 work %.1f, barrier + verdict %.1f), outputs %.1f us\n", kind,
+                acc[kind] / calls[kind], (double)rounds[kind] / calls[kind], h_out[n_cur + 1], st_us[kind][0] / calls[kind], st_us[kind][1] / calls[kind],
+                st_us[kind][3] / calls[kind], st_us[kind][4] / calls[kind], st_us[kind][5] / calls[kind], st_us[kind][2] / calls[kind]);
     }
     return ASD_OK;
   };
@@ -1029,9 +1193,9 @@ void matcher_free(asd_ctx* ctx) {
   }
   if (ctx->matcher) {
     MatcherState* m = static_cast<MatcherState*>(ctx->matcher);
-    void* dev[] = {m->d_queries, m->d_q_off, m->d_idx, m->d_dist, m->d_meta, m->d_qdesc, m->d_bank, m->d_attr};
+    void* dev[] = {m->d_queries, m->d_q_off, m->d_idx, m->d_dist, m->d_qdesc, m->d_bank, m->d_attr};
     for (void* p : dev) if (p) (void)hipFree(p);
-    void* host[] = {m->h_queries, m->h_q, m->h_idx, m->h_dist, m->h_qdesc, m->h_res, m->h_attr[0], m->h_attr[1]};
+    void* host[] = {m->h_queries, m->h_q, m->h_idx, m->h_dist, m->h_qdesc, m->h_attr[0], m->h_attr[1]};
     for (void* p : host) if (p) (void)hipHostFree(p);
     for (hipEvent_t e : m->ev_attr) if (e) (void)hipEventDestroy(e);
     delete m;
@@ -1109,7 +1273,7 @@ static int frame_set_impl(asd_ctx* ctx, int32_t slot, const asd_keypoint* kps, c
   for (int i = 0; i < n; ++i) {
     float ob;
     memcpy(&ob, &kps[i].octave, sizeof ob);  // octave travels as raw int bits in .z
-    hk[i] = make_float4(kps[i].x, kps[i].y, ob, kps[i].angle);  // .w = angle (rotation histogram of k_resolve)
+    hk[i] = make_float4(kps[i].x, kps[i].y, ob, kps[i].angle);  // .w = angle (rotation histogram of k_resolve2)
   }
   memcpy(hs, F->cell_start.data(), (GC * GR + 1) * sizeof(int));
   if (!F->cell_items.empty()) memcpy(hi, F->cell_items.data(), F->cell_items.size() * sizeof(int));
@@ -1258,8 +1422,9 @@ int asd_distinctive_descriptor_batch(asd_ctx* ctx, int32_t n_sets, const int32_t
 static int match_project_frame_impl(asd_ctx* ctx, int32_t slot_cur, int32_t slot_last, const uint8_t* has_mp, const float* Xw,
                             const float* mp_desc, const int32_t* mp_rows, const float* Tcw, const float* K, float th,
                             int32_t check_orientation, int32_t* match_cur, int32_t* n_matches, const uint8_t* obs_pos,
-                            ChainHook* chain = nullptr, bool* chained = nullptr, std::function<int()>* defer = nullptr) {
-  if (chained) *chained = false;
+                            StageInputs* chain = nullptr, const double** solver_io = nullptr, std::function<int()>* defer = nullptr) {
+  // chain: what asd_track_motion_model adds to the stage (query kernel, solver); *solver_io stays null when the stage was not chained --
+  // nothing to search, or the replay ran on the host
   AsdFrameSlot *C = slot_of(ctx, slot_cur), *L = slot_of(ctx, slot_last);
   if (!C || !L || !has_mp || !Xw || (!mp_desc && !mp_rows) || !Tcw || !K || !match_cur || !n_matches) return ASD_ERR_INVALID;
   (void)hipSetDevice(ctx->cfg.device);
@@ -1270,17 +1435,13 @@ static int match_project_frame_impl(asd_ctx* ctx, int32_t slot_cur, int32_t slot
   int rc = ensure_queries(ctx, m, L->n);
   if (rc != ASD_OK) return rc;
   if (mp_desc) { if ((rc = upload_qdesc(ctx, m, mp_desc, L->n)) != ASD_OK) return rc; }
-  else {
-    for (int i = 0; i < L->n; ++i)
-      if (has_mp[i] && (mp_rows[i] < 0 || mp_rows[i] >= m->bank_cap)) { ctx->set_error("bank row %d out of range", mp_rows[i]); return ASD_ERR_INVALID; }
-  }
+  else if ((rc = check_bank_rows(ctx, m, mp_rows, has_mp, L->n, false)) != ASD_OK) return rc;
   static const bool timing = getenv("ASD_TIMING") != nullptr;
   static double tacc[3]; static long tcalls;
   const auto tm0 = std::chrono::steady_clock::now();
   const float fx = K[0], fy = K[1], cx = K[2], cy = K[3];
   const bool on_device = replay_on_device(m, 0, C->n, L->n);
-  if (chain && !on_device) chain->prepare = nullptr;   // host replay: the queries are needed here
-  if (!(chain && chain->prepare))                      // (else: k_project_queries writes them on the device, asd_track_motion_model)
+  if (!(on_device && chain && chain->source == kQueriesProject))   // (else: k_project_queries writes them on the device, asd_track_motion_model)
   for (int i = 0; i < L->n; ++i) {  // projection, ORBmatcher.cc:1343-1368
     WinQuery& Q = m->h_queries[i];
     Q = WinQuery{0.f, 0.f, 0.f, 0, 0, -1};
@@ -1298,9 +1459,12 @@ static int match_project_frame_impl(asd_ctx* ctx, int32_t slot_cur, int32_t slot
   }
   if (on_device)   // search + claims + rotation histogram on the device, one synchronisation, 4 B per keypoint back
   {
-    if (chained) *chained = chain != nullptr;
-    return search_and_resolve<0>(ctx, m, *C, L->n, mp_desc ? m->d_qdesc : m->d_bank, L->d_kp, obs_pos, nullptr, check_orientation, 0.f,
-                                 match_cur, n_matches, chain, defer);
+    StageInputs plain;
+    StageInputs& in = chain ? *chain : plain;
+    in.kind = 0; in.nq = L->n;
+    in.d_qdesc = mp_desc ? m->d_qdesc : m->d_bank; in.kp_last = L->d_kp;
+    in.obs_pos = obs_pos; in.check_ori = check_orientation;
+    return search_and_resolve(ctx, m, *C, in, match_cur, n_matches, solver_io, defer);
   }
   SearchResult R;
   const auto tm1 = std::chrono::steady_clock::now();
@@ -1371,8 +1535,7 @@ static int match_project_frame_impl(asd_ctx* ctx, int32_t slot_cur, int32_t slot
 static int match_project_points_impl(asd_ctx* ctx, int32_t slot_cur, int32_t n_mp, const uint8_t* in_view, const float* proj,
                              const int32_t* level, const float* view_cos, const float* desc, const int32_t* rows,
                              const uint8_t* occupied, float th, float nn_ratio, int32_t* match_cur, int32_t* n_matches,
-                             const uint8_t* obs_pos, ChainHook* chain = nullptr, bool* chained = nullptr, std::function<int()>* defer = nullptr) {
-  if (chained) *chained = false;
+                             const uint8_t* obs_pos, StageInputs* chain = nullptr, const double** solver_io = nullptr, std::function<int()>* defer = nullptr) {
   AsdFrameSlot* F = slot_of(ctx, slot_cur);
   if (!F || n_mp < 0 || !match_cur || !n_matches || (n_mp > 0 && (!in_view || !proj || !level || !view_cos || (!desc && !rows))) ||
       (F->n > 0 && !occupied))
@@ -1393,14 +1556,17 @@ static int match_project_points_impl(asd_ctx* ctx, int32_t slot_cur, int32_t n_m
     if (lvl < 0 || lvl >= ctx->cfg.n_levels) { ctx->set_error("map point %d: level %d out of range", q, lvl); return ASD_ERR_INVALID; }
     float r = view_cos[q] > 0.998 ? 2.5f : 4.0f;  // RadiusByViewingCos (:126-132)
     if (bFactor) r *= th;
-    if (!desc && (rows[q] < 0 || rows[q] >= m->bank_cap)) { ctx->set_error("bank row %d out of range", rows[q]); return ASD_ERR_INVALID; }
+    if (!desc && (rc = check_bank_rows(ctx, m, rows + q, nullptr, 1, false)) != ASD_OK) return rc;
     Q = WinQuery{proj[2 * q], proj[2 * q + 1], r * ctx->scale[lvl], lvl - 1, lvl, desc ? q : rows[q]};
   }
   if (desc && (rc = upload_qdesc(ctx, m, desc, n_mp)) != ASD_OK) return rc;
   if (replay_on_device(m, 1, F->n, n_mp)) {
-    if (chained) *chained = chain != nullptr;
-    return search_and_resolve<1>(ctx, m, *F, n_mp, desc ? m->d_qdesc : m->d_bank, nullptr, obs_pos, occupied, 0, nn_ratio, match_cur,
-                                 n_matches, chain, defer);
+    StageInputs plain;
+    StageInputs& in = chain ? *chain : plain;
+    in.kind = 1; in.nq = n_mp;
+    in.d_qdesc = desc ? m->d_qdesc : m->d_bank;
+    in.obs_pos = obs_pos; in.occupied = occupied; in.nn_ratio = nn_ratio;
+    return search_and_resolve(ctx, m, *F, in, match_cur, n_matches, solver_io, defer);
   }
   SearchResult R;
   if ((rc = window_search(ctx, m, *F, n_mp, desc ? m->d_qdesc : m->d_bank, &R, 1)) != ASD_OK) return rc;
@@ -1468,34 +1634,27 @@ int asd_match_project_points_bank(asd_ctx* ctx, int32_t slot_cur, int32_t n_mp, 
 // submission each: search, claim replay, edge assembly and the pose solver are enqueued back to back on the context's stream
 // and the host synchronises once, instead of search -> host -> solver with two round trips.  Same kernels, same edge order
 // (keypoint order, Optimizer.cc:281) as the separate calls, so the results are the same bits (tests/test_track_chain.py).
+// Every chain entry point has one shape: fill the stage's inputs (StageInputs: copied into the upload block when the stage is enqueued, so
+// that it can be enqueued again after a candidate overflow), call search_and_resolve, complete (finish_chain).
 namespace {
-// after the chain: outlier flags per KEYPOINT from the per-edge bytes, or the whole PoseOptimization through the separate
-// entry point when the matches were replayed on the host (ASD_MATCH_REPLAY=host, very large inputs)
-int finish_pose_chain(asd_ctx* ctx, const AsdFrameSlot& C, const std::function<const float*(int)>& point_of, bool chained, const double* h_io,
-                      const double* Kd, double* pose7, uint8_t* outlier, int32_t* n_inliers, bool kp_flags) {
+// the solver's part of a chain's stage inputs
+void chain_solver_inputs(StageInputs* in, const double* pose7, const float* K) {
+  in->has_solver = true;
+  memcpy(in->pose0, pose7, sizeof in->pose0);
+  for (int i = 0; i < 4; ++i) in->K[i] = (double)K[i];
+}
+// The stage was not chained (nothing to search, or the matches were replayed on the host: ASD_MATCH_REPLAY=host, very large inputs): the
+// whole PoseOptimization through the separate entry point.  Runs inside the call, so it may read the caller's tables: keypoint j's point is
+// own[j] where hold[j], else points[match_cur[j]].
+int pose_optimize_host_matches(asd_ctx* ctx, const AsdFrameSlot& C, const int32_t* match_cur, const float* points, const uint8_t* hold, const float* own,
+                               const double* K, double* pose7, uint8_t* outlier, int32_t* n_inliers) {
   const int n_cur = C.n;
-  if (chained && kp_flags) {
-    // the gather form of k_pose_opt hands the flags over per keypoint with the edge count behind them: no walk over the keypoints
-    const int ne = (int)(h_io[8 + (n_cur + 7) / 8] + 0.5);
-    memcpy(outlier, h_io + 8, (size_t)n_cur);
-    *n_inliers = 0;
-    if (ne < 3) return ASD_OK;   // Optimizer.cc:323-324 (the kernel left the pose as it was and cleared the flags)
-    memcpy(pose7, h_io, 56);
-    *n_inliers = ne - (int)(h_io[7] + 0.5);
-    return ASD_OK;
-  }
+  auto point_of = [&](int j) -> const float* { return hold && hold[j] ? own + 3 * (size_t)j : (match_cur[j] >= 0 ? points + 3 * (size_t)match_cur[j] : nullptr); };
   std::vector<int> kp_of_edge;
   for (int j = 0; j < n_cur; ++j) { outlier[j] = 0; if (point_of(j)) kp_of_edge.push_back(j); }
   const int ne = (int)kp_of_edge.size();
   *n_inliers = 0;
   if (ne < 3) return ASD_OK;   // Optimizer.cc:323-324
-  if (chained) {
-    memcpy(pose7, h_io, 56);
-    const uint8_t* flags = reinterpret_cast<const uint8_t*>(h_io + 8);
-    for (int e = 0; e < ne; ++e) outlier[kp_of_edge[e]] = flags[e];
-    *n_inliers = ne - (int)(h_io[7] + 0.5);
-    return ASD_OK;
-  }
   std::vector<double> Xd((size_t)3 * ne), obs((size_t)2 * ne), info(ne);
   std::vector<uint8_t> out(ne);
   for (int e = 0; e < ne; ++e) {
@@ -1505,65 +1664,52 @@ int finish_pose_chain(asd_ctx* ctx, const AsdFrameSlot& C, const std::function<c
     obs[2 * e] = (double)C.kps[jk].x; obs[2 * e + 1] = (double)C.kps[jk].y;
     info[e] = (double)ctx->inv_sigma2[C.kps[jk].octave];
   }
-  const int rc = asd_pose_optimize(ctx, pose7, ne, Xd.data(), obs.data(), info.data(), Kd, out.data(), n_inliers);
+  const int rc = asd_pose_optimize(ctx, pose7, ne, Xd.data(), obs.data(), info.data(), K, out.data(), n_inliers);
   if (rc != ASD_OK) return rc;
   for (int e = 0; e < ne; ++e) outlier[kp_of_edge[e]] = out[e];
   return ASD_OK;
 }
+// Completes a chained stage -- the search's completion, then the solver's block into the caller's arrays -- or hands the completion to the
+// caller (`defer`, asd_track_async).  The completion reads the caller's OUTPUT arrays and, of the inputs, only copies made here: the start
+// pose and, where the flags come back per edge, the `hold` flags.
+int finish_chain(asd_ctx* ctx, const AsdFrameSlot& F, const StageInputs& in, const std::function<int()>& search_done, const double* h_io, double* pose7,
+                 int32_t* match_cur, uint8_t* outlier, int32_t* n_inliers, std::function<int()>* defer) {
+  const int n_cur = F.n;
+  const bool kp_flags = pose_chain_lds_form(ctx, n_cur);
+  std::array<double, 7> p0;
+  memcpy(p0.data(), in.pose0, sizeof in.pose0);
+  std::shared_ptr<std::vector<uint8_t>> hold;
+  if (in.hold && !kp_flags) hold = std::make_shared<std::vector<uint8_t>>(in.hold, in.hold + n_cur);
+  auto fin = [=]() -> int {
+    if (search_done) { const int r = search_done(); if (r != ASD_OK) return r; }
+    unpack_solver_block(h_io, n_cur, kp_flags, match_cur, hold ? hold->data() : nullptr, p0.data(), pose7, outlier, n_inliers);
+    return ASD_OK;
+  };
+  if (defer && search_done) { *defer = fin; return ASD_OK; }
+  return fin();
+}
 
-// The three chains share one shape: build the hook (everything its callbacks need captured BY VALUE: they may run again from
-// the completion when the candidate buffers overflowed), enqueue, then either run the completion or hand it to the caller
-// (`defer`, asd_track_async).  The completion reads the caller's OUTPUT arrays and, of the inputs, only copies made here.
 int track_motion_model_impl(asd_ctx* ctx, int32_t slot_cur, int32_t slot_last, const uint8_t* has_mp, const float* Xw, const float* mp_desc,
                             const int32_t* mp_rows, const float* Tcw, const float* K, float th, int32_t check_orientation,
                             const uint8_t* mp_obs_positive, double* pose7, int32_t* match_cur, int32_t* n_matches, uint8_t* outlier,
                             int32_t* n_inliers, std::function<int()>* defer) {
   AsdFrameSlot *C = slot_of(ctx, slot_cur), *L = slot_of(ctx, slot_last);
   if (!C || !L || !pose7 || !outlier || !n_inliers || !K) return ASD_ERR_INVALID;
-  const std::array<double, 4> Kd = {(double)K[0], (double)K[1], (double)K[2], (double)K[3]};
-  std::array<double, 7> p0;
-  memcpy(p0.data(), pose7, sizeof(double) * 7);
-  auto chain = std::make_shared<ChainHook>();
-  chain->src[0] = Xw; chain->bytes[0] = (size_t)L->n * 12;
-  chain->result_bytes = pose_chain_io_bytes(C->n);
-  chain->enqueue = [ctx, C, Kd, p0](const int* d_match, void* const* d_tab, void* d_result, const AsdFusedReplay* fused) {
-    return pose_chain_enqueue(ctx, C->n, d_match, C->d_kp, static_cast<const float*>(d_tab[0]), nullptr, nullptr, p0.data(), Kd.data(), static_cast<double*>(d_result),
-                              nullptr, nullptr, nullptr, fused);
-  };
+  StageInputs in;
+  chain_solver_inputs(&in, pose7, K);
+  in.points = Xw; in.n_points = L->n;
   if (has_mp && Xw && Tcw && L->n > 0) {   // the projection loop on the device too (2000 points: ~45 us of host time otherwise)
-    chain->src[1] = has_mp; chain->bytes[1] = (size_t)L->n;
-    if (mp_rows) { chain->src[2] = mp_rows; chain->bytes[2] = (size_t)L->n * 4; }
-    ProjectArgs pa{};
-    pa.n = L->n; pa.kp_last = L->d_kp;
-    memcpy(pa.T, Tcw, sizeof pa.T);
-    pa.fx = K[0]; pa.fy = K[1]; pa.cx = K[2]; pa.cy = K[3];
-    pa.min_x = C->min_x; pa.max_x = C->max_x; pa.min_y = C->min_y; pa.max_y = C->max_y; pa.th = th;
-    for (int l = 0; l < ASD_MAX_LEVELS; ++l) pa.scale[l] = l < ctx->cfg.n_levels ? ctx->scale[l] : 0.f;
-    const bool by_rows = mp_rows != nullptr;
-    chain->prepare = [ctx, pa, by_rows](WinQuery* d_queries, void* const*, void* const* h_tab, const UploadTail& tail) -> int {
-      ProjectArgs a = pa;
-      a.Xw = static_cast<const float*>(h_tab[0]); a.has_mp = static_cast<const uint8_t*>(h_tab[1]);
-      a.rows = by_rows ? static_cast<const int*>(h_tab[2]) : nullptr;
-      a.queries = d_queries;
-      a.up = tail;
-      a.up.q_blocks = (a.n + 255) / 256;
-      hipLaunchKernelGGL(k_project_queries, dim3(a.up.q_blocks + (tail.n16 ? kUploadTailBlocks : 0)), dim3(256), 0, ctx->stream, a);
-      ASD_HIP_CHECK(ctx, hipGetLastError());
-      return ASD_OK;
-    };
+    in.source = kQueriesProject;
+    in.project = project_args(ctx, *C, *L, Tcw, K, th);
+    in.has_mp = has_mp; in.rows = mp_rows;
   }
-  bool chained = false;
+  const double* h_io = nullptr;
   std::function<int()> search_done;
-  int rc = match_project_frame_impl(ctx, slot_cur, slot_last, has_mp, Xw, mp_desc, mp_rows, Tcw, K, th, check_orientation, match_cur, n_matches,
-                                    mp_obs_positive, chain.get(), &chained, defer ? &search_done : nullptr);
+  const int rc = match_project_frame_impl(ctx, slot_cur, slot_last, has_mp, Xw, mp_desc, mp_rows, Tcw, K, th, check_orientation, match_cur, n_matches,
+                                          mp_obs_positive, &in, &h_io, defer ? &search_done : nullptr);
   if (rc != ASD_OK) return rc;
-  auto fin = [=]() -> int {
-    if (search_done) { const int r = search_done(); if (r != ASD_OK) return r; }
-    return finish_pose_chain(ctx, *C, [=](int j) -> const float* { return match_cur[j] >= 0 ? Xw + 3 * (size_t)match_cur[j] : nullptr; }, chained,
-                             static_cast<const double*>(chain->h_result), Kd.data(), pose7, outlier, n_inliers, chain->kp_flags);
-  };
-  if (defer && search_done) { *defer = fin; return ASD_OK; }   // (a search that finished on the host is complete already)
-  return fin();
+  if (!h_io) return pose_optimize_host_matches(ctx, *C, match_cur, Xw, nullptr, nullptr, in.K, pose7, outlier, n_inliers);
+  return finish_chain(ctx, *C, in, search_done, h_io, pose7, match_cur, outlier, n_inliers, defer);
 }
 
 int track_local_map_impl(asd_ctx* ctx, int32_t slot_cur, int32_t n_mp, const uint8_t* in_view, const float* proj, const int32_t* level,
@@ -1572,37 +1718,17 @@ int track_local_map_impl(asd_ctx* ctx, int32_t slot_cur, int32_t n_mp, const uin
                          int32_t* match_cur, int32_t* n_matches, uint8_t* outlier, int32_t* n_inliers, std::function<int()>* defer) {
   AsdFrameSlot* F = slot_of(ctx, slot_cur);
   if (!F || !pose7 || !outlier || !n_inliers || !K || (n_mp > 0 && !mp_Xw) || (F->n > 0 && (!occupied || !cur_Xw))) return ASD_ERR_INVALID;
-  const std::array<double, 4> Kd = {(double)K[0], (double)K[1], (double)K[2], (double)K[3]};
-  std::array<double, 7> p0;
-  memcpy(p0.data(), pose7, sizeof(double) * 7);
-  auto chain = std::make_shared<ChainHook>();
-  chain->src[0] = mp_Xw; chain->bytes[0] = (size_t)n_mp * 12;
-  chain->src[1] = cur_Xw; chain->bytes[1] = (size_t)F->n * 12;
-  chain->src[2] = occupied; chain->bytes[2] = (size_t)F->n;
-  chain->result_bytes = pose_chain_io_bytes(F->n);
-  chain->enqueue = [ctx, F, Kd, p0](const int* d_match, void* const* d_tab, void* d_result, const AsdFusedReplay* fused) {
-    return pose_chain_enqueue(ctx, F->n, d_match, F->d_kp, static_cast<const float*>(d_tab[0]), static_cast<const uint8_t*>(d_tab[2]),
-                              static_cast<const float*>(d_tab[1]), p0.data(), Kd.data(), static_cast<double*>(d_result), nullptr, nullptr, nullptr, fused);
-  };
-  bool chained = false;
+  StageInputs in;
+  chain_solver_inputs(&in, pose7, K);
+  in.points = mp_Xw; in.n_points = n_mp;
+  in.own = cur_Xw; in.hold = occupied;
+  const double* h_io = nullptr;
   std::function<int()> search_done;
-  int rc = match_project_points_impl(ctx, slot_cur, n_mp, in_view, proj, level, view_cos, desc, rows, occupied, th, nn_ratio, match_cur, n_matches,
-                                     mp_obs_positive, chain.get(), &chained, defer ? &search_done : nullptr);
+  const int rc = match_project_points_impl(ctx, slot_cur, n_mp, in_view, proj, level, view_cos, desc, rows, occupied, th, nn_ratio, match_cur, n_matches,
+                                           mp_obs_positive, &in, &h_io, defer ? &search_done : nullptr);
   if (rc != ASD_OK) return rc;
-  if (defer && search_done) {
-    auto occ = std::make_shared<std::vector<uint8_t>>(occupied, occupied + F->n);   // the completion must not read the caller's inputs
-    *defer = [=]() -> int {
-      const int r = search_done();
-      if (r != ASD_OK) return r;
-      const uint8_t* oc = occ->data();
-      return finish_pose_chain(ctx, *F, [=](int j) -> const float* { return (oc[j] || match_cur[j] >= 0) ? reinterpret_cast<const float*>(oc) : nullptr; },
-                               true, static_cast<const double*>(chain->h_result), Kd.data(), pose7, outlier, n_inliers, chain->kp_flags);
-    };
-    return ASD_OK;
-  }
-  return finish_pose_chain(ctx, *F, [&](int j) -> const float* {
-    return occupied[j] ? cur_Xw + 3 * (size_t)j : (match_cur[j] >= 0 ? mp_Xw + 3 * (size_t)match_cur[j] : nullptr); }, chained,
-    static_cast<const double*>(chain->h_result), Kd.data(), pose7, outlier, n_inliers, chain->kp_flags);
+  if (!h_io) return pose_optimize_host_matches(ctx, *F, match_cur, mp_Xw, occupied, cur_Xw, in.K, pose7, outlier, n_inliers);
+  return finish_chain(ctx, *F, in, search_done, h_io, pose7, match_cur, outlier, n_inliers, defer);
 }
 
 // Tracking::SearchLocalPoints (Tracking.cc:803-851: isInFrustum for every local map point, then SearchByProjection) +
@@ -1633,65 +1759,23 @@ int track_local_points_impl(asd_ctx* ctx, int32_t slot_cur, int32_t n_mp, const 
   *n_matches = 0;
   int rc = ensure_queries(ctx, m, n_mp);
   if (rc != ASD_OK) return rc;
-  if (!desc)
-    for (int q = 0; q < n_mp; ++q)
-      if (rows[q] < 0 || rows[q] >= m->bank_cap) { ctx->set_error("bank row %d out of range", rows[q]); return ASD_ERR_INVALID; }
+  if (!desc && (rc = check_bank_rows(ctx, m, rows, nullptr, n_mp, false)) != ASD_OK) return rc;
   if (desc && (rc = upload_qdesc(ctx, m, desc, n_mp)) != ASD_OK) return rc;
-  const std::array<double, 4> Kd = {(double)K[0], (double)K[1], (double)K[2], (double)K[3]};
-  std::array<double, 7> p0;
-  memcpy(p0.data(), pose7, sizeof(double) * 7);
-  FrustumArgs fa{};
-  fa.n = n_mp; fa.n_levels = ctx->cfg.n_levels; fa.bfactor = th != 1.0;
-  memcpy(fa.T, Tcw, sizeof fa.T);
-  for (int i = 0; i < 3; ++i) {  // mOw = -mRcw.t()*mtcw (Frame.cc:157): transposed gemm accumulates in double
-    double sum = 0;
-    for (int k = 0; k < 3; ++k) sum += (double)Tcw[k * 4 + i] * (double)Tcw[k * 4 + 3];
-    fa.Ow[i] = (float)(-1.0 * sum);
-  }
-  fa.fx = K[0]; fa.fy = K[1]; fa.cx = K[2]; fa.cy = K[3];
-  fa.min_x = F->min_x; fa.max_x = F->max_x; fa.min_y = F->min_y; fa.max_y = F->max_y;
-  fa.cos_limit = cos_limit; fa.th = th;
-  for (int l = 0; l < ASD_MAX_LEVELS; ++l) { fa.level_thr[l] = ctx->level_thr[l]; fa.scale[l] = l < ctx->cfg.n_levels ? ctx->scale[l] : 0.f; }
-  auto chain = std::make_shared<ChainHook>();
-  chain->src[0] = Xw; chain->bytes[0] = (size_t)n_mp * 12;
-  chain->src[1] = cur_Xw; chain->bytes[1] = (size_t)F->n * 12;
-  chain->src[2] = occupied; chain->bytes[2] = (size_t)F->n;
-  chain->src[3] = normal; chain->bytes[3] = (size_t)n_mp * 12;
-  chain->src[4] = min_dist; chain->bytes[4] = (size_t)n_mp * 4;
-  chain->src[5] = max_dist; chain->bytes[5] = (size_t)n_mp * 4;
-  const bool by_rows = desc == nullptr;
-  if (by_rows) { chain->src[6] = rows; chain->bytes[6] = (size_t)n_mp * 4; }
-  chain->result_bytes = pose_chain_io_bytes(F->n);
-  chain->prepare = [ctx, fa, by_rows, n_mp](WinQuery* d_queries, void* const*, void* const* h_tab, const UploadTail& tail) -> int {
-    FrustumArgs a = fa;
-    a.Xw = static_cast<const float*>(h_tab[0]); a.normal = static_cast<const float*>(h_tab[3]);
-    a.min_dist = static_cast<const float*>(h_tab[4]); a.max_dist = static_cast<const float*>(h_tab[5]);
-    a.rows = by_rows ? static_cast<const int*>(h_tab[6]) : nullptr;
-    a.queries = d_queries;
-    a.up = tail;
-    a.up.q_blocks = (n_mp + 255) / 256;
-    hipLaunchKernelGGL(k_frustum_queries, dim3(a.up.q_blocks + (tail.n16 ? kUploadTailBlocks : 0)), dim3(256), 0, ctx->stream, a);
-    ASD_HIP_CHECK(ctx, hipGetLastError());
-    return ASD_OK;
-  };
-  chain->enqueue = [ctx, F, Kd, p0](const int* d_match, void* const* d_tab, void* d_result, const AsdFusedReplay* fused) {
-    return pose_chain_enqueue(ctx, F->n, d_match, F->d_kp, static_cast<const float*>(d_tab[0]), static_cast<const uint8_t*>(d_tab[2]),
-                              static_cast<const float*>(d_tab[1]), p0.data(), Kd.data(), static_cast<double*>(d_result), nullptr, nullptr, nullptr, fused);
-  };
+  StageInputs in;
+  in.kind = 1; in.nq = n_mp;
+  in.d_qdesc = desc ? m->d_qdesc : m->d_bank;
+  in.obs_pos = mp_obs_positive; in.occupied = occupied; in.nn_ratio = nn_ratio;
+  in.source = kQueriesFrustum;
+  in.frustum = frustum_args(ctx, *F, n_mp, Tcw, nullptr, K, cos_limit, th);
+  chain_solver_inputs(&in, pose7, K);
+  in.points = Xw; in.n_points = n_mp;
+  in.own = cur_Xw; in.hold = occupied;
+  in.normal = normal; in.min_dist = min_dist; in.max_dist = max_dist;
+  in.rows = desc ? nullptr : rows;
+  const double* h_io = nullptr;
   std::function<int()> search_done;
-  rc = search_and_resolve<1>(ctx, m, *F, n_mp, desc ? m->d_qdesc : m->d_bank, nullptr, mp_obs_positive, occupied, 0, nn_ratio, match_cur, n_matches,
-                             chain.get(), defer ? &search_done : nullptr);
-  if (rc != ASD_OK) return rc;
-  auto occ = std::make_shared<std::vector<uint8_t>>(occupied, occupied + F->n);   // the completion must not read the caller's inputs
-  auto fin = [=]() -> int {
-    if (search_done) { const int r = search_done(); if (r != ASD_OK) return r; }
-    const uint8_t* oc = occ->data();
-    // chained: finish_pose_chain only asks which keypoints carry an edge (the positions went to the device in the upload block)
-    return finish_pose_chain(ctx, *F, [=](int j) -> const float* { return (oc[j] || match_cur[j] >= 0) ? reinterpret_cast<const float*>(oc) : nullptr; },
-                             true, static_cast<const double*>(chain->h_result), Kd.data(), pose7, outlier, n_inliers, chain->kp_flags);
-  };
-  if (defer && search_done) { *defer = fin; return ASD_OK; }
-  return fin();
+  if ((rc = search_and_resolve(ctx, m, *F, in, match_cur, n_matches, &h_io, defer ? &search_done : nullptr)) != ASD_OK) return rc;
+  return finish_chain(ctx, *F, in, search_done, h_io, pose7, match_cur, outlier, n_inliers, defer);
 }
 
 // The same with the map points named by ROW of the banks (descriptor bank: MapPoint::mDescriptor, attribute bank: position, normal, distance
@@ -1709,66 +1793,32 @@ int track_local_points_rows_impl(asd_ctx* ctx, int32_t slot_cur, int32_t n_mp, c
     ctx->set_error("asd_track_local_points_rows: %d map points / %d keypoints are outside the device replay (use asd_track_local_points_bank)", n_mp, F->n);
     return ASD_ERR_CAPACITY;
   }
-  for (int q = 0; q < n_mp; ++q)
-    if (rows[q] < 0 || rows[q] >= m->bank_cap || rows[q] >= m->attr_cap) { ctx->set_error("row %d out of range (descriptor bank %d rows, attribute bank %d)", rows[q], m->bank_cap, m->attr_cap); return ASD_ERR_INVALID; }
+  int rc = check_bank_rows(ctx, m, rows, nullptr, n_mp, true);
+  if (rc != ASD_OK) return rc;
   std::fill(match_cur, match_cur + F->n, -1);
   *n_matches = 0;
-  int rc = ensure_queries(ctx, m, n_mp);
-  if (rc != ASD_OK) return rc;
+  if ((rc = ensure_queries(ctx, m, n_mp)) != ASD_OK) return rc;
   if (m->cxw_cap < (size_t)n_mp * 3) {
     if (m->d_cxw) { ASD_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream)); (void)hipFree(m->d_cxw); m->d_cxw = nullptr; m->cxw_cap = 0; }
     const size_t want = (size_t)n_mp * 3 + (size_t)n_mp / 2 * 3 + 3072;
     ASD_HIP_CHECK(ctx, hipMalloc(&m->d_cxw, want * sizeof(float)));
     m->cxw_cap = want;
   }
-  const std::array<double, 4> Kd = {(double)K[0], (double)K[1], (double)K[2], (double)K[3]};
-  std::array<double, 7> p0;
-  memcpy(p0.data(), pose7, sizeof(double) * 7);
-  FrustumArgs fa{};
-  fa.n = n_mp; fa.n_levels = ctx->cfg.n_levels; fa.bfactor = th != 1.0;
-  memcpy(fa.T, Tcw, sizeof fa.T);
-  for (int i = 0; i < 3; ++i) {  // mOw = -mRcw.t()*mtcw (Frame.cc:157): transposed gemm accumulates in double
-    double sum = 0;
-    for (int k = 0; k < 3; ++k) sum += (double)Tcw[k * 4 + i] * (double)Tcw[k * 4 + 3];
-    fa.Ow[i] = (float)(-1.0 * sum);
-  }
-  fa.fx = K[0]; fa.fy = K[1]; fa.cx = K[2]; fa.cy = K[3];
-  fa.min_x = F->min_x; fa.max_x = F->max_x; fa.min_y = F->min_y; fa.max_y = F->max_y;
-  fa.cos_limit = cos_limit; fa.th = th;
-  for (int l = 0; l < ASD_MAX_LEVELS; ++l) { fa.level_thr[l] = ctx->level_thr[l]; fa.scale[l] = l < ctx->cfg.n_levels ? ctx->scale[l] : 0.f; }
-  fa.attr = m->d_attr; fa.T_dev = nullptr; fa.skip = nullptr; fa.xw_out = m->d_cxw;
-  auto chain = std::make_shared<ChainHook>();
-  chain->src[1] = cur_Xw; chain->bytes[1] = (size_t)F->n * 12;
-  chain->src[2] = occupied; chain->bytes[2] = (size_t)F->n;
-  chain->src[6] = rows; chain->bytes[6] = (size_t)n_mp * 4;
-  chain->result_bytes = pose_chain_io_bytes(F->n);
-  chain->prepare = [ctx, fa, n_mp](WinQuery* d_queries, void* const*, void* const* h_tab, const UploadTail& tail) -> int {
-    FrustumArgs a = fa;
-    a.rows = static_cast<const int*>(h_tab[6]);
-    a.queries = d_queries;
-    a.up = tail;
-    a.up.q_blocks = (n_mp + 255) / 256;
-    hipLaunchKernelGGL(k_frustum_queries, dim3(a.up.q_blocks + (tail.n16 ? kUploadTailBlocks : 0)), dim3(256), 0, ctx->stream, a);
-    ASD_HIP_CHECK(ctx, hipGetLastError());
-    return ASD_OK;
-  };
-  float* d_cxw = m->d_cxw;
-  chain->enqueue = [ctx, F, Kd, p0, d_cxw](const int* d_match, void* const* d_tab, void* d_result, const AsdFusedReplay* fused) {
-    return pose_chain_enqueue(ctx, F->n, d_match, F->d_kp, d_cxw, static_cast<const uint8_t*>(d_tab[2]), static_cast<const float*>(d_tab[1]), p0.data(), Kd.data(),
-                              static_cast<double*>(d_result), nullptr, nullptr, nullptr, fused);
-  };
+  StageInputs in;
+  in.kind = 1; in.nq = n_mp;
+  in.d_qdesc = m->d_bank;
+  in.obs_pos = mp_obs_positive; in.occupied = occupied; in.nn_ratio = nn_ratio;
+  in.source = kQueriesFrustum;
+  in.frustum = frustum_args(ctx, *F, n_mp, Tcw, nullptr, K, cos_limit, th);
+  in.frustum.attr = m->d_attr; in.frustum.xw_out = m->d_cxw;   // the bank form: positions are read from the attribute bank and written out for the solver
+  chain_solver_inputs(&in, pose7, K);
+  in.d_points = m->d_cxw;
+  in.own = cur_Xw; in.hold = occupied;
+  in.rows = rows;
+  const double* h_io = nullptr;
   std::function<int()> search_done;
-  rc = search_and_resolve<1>(ctx, m, *F, n_mp, m->d_bank, nullptr, mp_obs_positive, occupied, 0, nn_ratio, match_cur, n_matches, chain.get(), defer ? &search_done : nullptr);
-  if (rc != ASD_OK) return rc;
-  auto occ = std::make_shared<std::vector<uint8_t>>(occupied, occupied + F->n);   // the completion must not read the caller's inputs
-  auto fin = [=]() -> int {
-    if (search_done) { const int r = search_done(); if (r != ASD_OK) return r; }
-    const uint8_t* oc = occ->data();
-    return finish_pose_chain(ctx, *F, [=](int j) -> const float* { return (oc[j] || match_cur[j] >= 0) ? reinterpret_cast<const float*>(oc) : nullptr; },
-                             true, static_cast<const double*>(chain->h_result), Kd.data(), pose7, outlier, n_inliers, chain->kp_flags);
-  };
-  if (defer && search_done) { *defer = fin; return ASD_OK; }
-  return fin();
+  if ((rc = search_and_resolve(ctx, m, *F, in, match_cur, n_matches, &h_io, defer ? &search_done : nullptr)) != ASD_OK) return rc;
+  return finish_chain(ctx, *F, in, search_done, h_io, pose7, match_cur, outlier, n_inliers, defer);
 }
 
 // asd_track_async / asd_track_finish: run an asd_track_* entry point split in two
@@ -1859,6 +1909,7 @@ int track_frame_impl(asd_ctx* ctx, const asd_track_frame_args& A, std::function<
       !A.n_matches1 || !A.outlier1 || !A.n_inliers1 || !A.match2 || !A.n_matches2 || !A.outlier2 || !A.n_inliers2)
     return ASD_ERR_INVALID;
   if (asd_track_busy(ctx, "asd_track_frame")) return ASD_ERR_INVALID;
+  static const bool timing = getenv("ASD_TIMING") != nullptr;
   (void)hipSetDevice(ctx->cfg.device);
   MatcherState* m = mstate(ctx);
   const int nl = L->n, nc = C->n, ncand = A.n_cand;
@@ -1868,13 +1919,10 @@ int track_frame_impl(asd_ctx* ctx, const asd_track_frame_args& A, std::function<
                    kResolve2Threads * 4, kResolve2MaxRounds * 512);
     return ASD_ERR_CAPACITY;
   }
-  for (int i = 0; i < nl; ++i)
-    if (A.has_mp[i] && (A.last_rows[i] < 0 || A.last_rows[i] >= m->bank_cap)) { ctx->set_error("bank row %d out of range", A.last_rows[i]); return ASD_ERR_INVALID; }
-  for (int c = 0; c < ncand; ++c)
-    if (A.cand_rows[c] < 0 || A.cand_rows[c] >= m->bank_cap || A.cand_rows[c] >= m->attr_cap) { ctx->set_error("candidate row %d out of range (descriptor bank %d rows, attribute bank %d)", A.cand_rows[c], m->bank_cap, m->attr_cap); return ASD_ERR_INVALID; }
+  int rc;
+  if ((rc = check_bank_rows(ctx, m, A.last_rows, A.has_mp, nl, false)) != ASD_OK || (rc = check_bank_rows(ctx, m, A.cand_rows, nullptr, ncand, true)) != ASD_OK) return rc;
   // nothing is searched twice here: the candidate buffers take the worst case up front (a list holds at most every keypoint)
-  int rc = ensure_cands_dev(ctx, m, (size_t)std::max(nl, ncand) * (size_t)nc);
-  if (rc != ASD_OK) return rc;
+  if ((rc = ensure_cands_dev(ctx, m, (size_t)std::max(nl, ncand) * (size_t)nc)) != ASD_OK) return rc;
   hipStream_t st = ctx->stream;
   AsdXfer &up = ctx->up, &down = ctx->down;
   const size_t io_bytes = pose_chain_io_bytes(nc);
@@ -1885,136 +1933,69 @@ int track_frame_impl(asd_ctx* ctx, const asd_track_frame_args& A, std::function<
   need += pad((size_t)ncand * sizeof(WinQuery)) + 2 * pad((size_t)nl * 4) + 2 * pad((size_t)ncand * 4) + pad((size_t)nl * kTop * 2) + pad((size_t)ncand * kTop * 2) +
           pad(nc) + pad((size_t)nc * 12) + pad(ncand) + pad((size_t)ncand * 12) + pad(32 * 4) + pad(io_bytes);
   ASD_HIP_CHECK(ctx, ctx->scratch.reserve(need));
+  // every runtime request of the chain that is not a launch happens here, before the first kernel goes out
+  if ((rc = pose_chain_reserve(ctx, nc)) != ASD_OK || (rc = resolve2_attributes(ctx)) != ASD_OK) return rc;
+  TrackStage s1{}, s2{};
+  s1.kind = 0; s1.nq = nl; s2.kind = 1; s2.nq = ncand;
+  s1.F = s2.F = C;
+  s1.d_qdesc = s2.d_qdesc = m->d_bank;
   WinQuery* d_q2 = ctx->scratch.carve<WinQuery>(ncand);
-  int *d_off1 = ctx->scratch.carve<int>(nl), *d_cnt1 = ctx->scratch.carve<int>(nl), *d_off2 = ctx->scratch.carve<int>(ncand), *d_cnt2 = ctx->scratch.carve<int>(ncand);
-  uint16_t *d_top1 = ctx->scratch.carve<uint16_t>((size_t)nl * kTop), *d_top2 = ctx->scratch.carve<uint16_t>((size_t)ncand * kTop);
+  s1.d_off = ctx->scratch.carve<int>(nl); s1.d_cnt = ctx->scratch.carve<int>(nl); s2.d_off = ctx->scratch.carve<int>(ncand); s2.d_cnt = ctx->scratch.carve<int>(ncand);
+  s1.d_top = ctx->scratch.carve<uint16_t>((size_t)nl * kTop); s2.d_top = ctx->scratch.carve<uint16_t>((size_t)ncand * kTop);
   uint8_t* d_occ = ctx->scratch.carve<uint8_t>(nc);
   float* d_curXw = ctx->scratch.carve<float>((size_t)nc * 3);
   uint8_t* d_skip = ctx->scratch.carve<uint8_t>(ncand);
   float* d_cXw = ctx->scratch.carve<float>((size_t)ncand * 3);
   float* d_T1 = ctx->scratch.carve<float>(32);
   double* d_io1 = reinterpret_cast<double*>(ctx->scratch.carve<char>(io_bytes));
-  // one upload block: the motion-model stage's query table (written on the device) first, the copy the kernel carries behind it
+  // one upload block: the motion-model stage's query table (written on the device) first, the copy its query kernel carries behind it
   const size_t o_q1 = up.reserve((size_t)nl * sizeof(WinQuery));
-  const size_t o_tot1 = up.zeros(sizeof(int)), o_tot2 = up.zeros(sizeof(int));
-  const size_t o_obs1 = A.last_obs_positive ? up.add(A.last_obs_positive, nl) : 0, o_obs2 = A.cand_obs_positive ? up.add(A.cand_obs_positive, ncand) : 0;
+  s1.d_total = up.dev<int>(up.zeros(sizeof(int))); s2.d_total = up.dev<int>(up.zeros(sizeof(int)));
+  if (A.last_obs_positive) s1.d_obs_pos = up.dev<uint8_t>(up.add(A.last_obs_positive, nl));
+  if (A.cand_obs_positive) s2.d_obs_pos = up.dev<uint8_t>(up.add(A.cand_obs_positive, ncand));
   const size_t o_has = up.add(A.has_mp, nl), o_Xw = up.add(A.Xw_last, (size_t)nl * 12), o_rows1 = up.add(A.last_rows, (size_t)nl * 4);
   const size_t o_lc = A.last_cand ? up.add(A.last_cand, (size_t)nl * 4) : 0, o_crows = up.add(A.cand_rows, (size_t)ncand * 4);
-  const size_t o_btw = up.reserve(sizeof(AsdBetweenArgs));   // (filled below, before the launch whose tail blocks copy the block to the device)
+  const size_t o_btw = up.reserve(sizeof(AsdBetweenArgs));
   const size_t o_out1 = down.reserve(((size_t)nc + 16) * sizeof(int)), o_res1 = down.reserve(io_bytes);
   const size_t o_out2 = down.reserve(((size_t)nc + 16) * sizeof(int)), o_res2 = down.reserve(io_bytes);
-  const bool has_obs1 = A.last_obs_positive != nullptr, has_obs2 = A.cand_obs_positive != nullptr, has_lc = A.last_cand != nullptr;
-  const std::array<double, 4> Kd = {(double)A.K[0], (double)A.K[1], (double)A.K[2], (double)A.K[3]};
-
-  {
+  s1.d_out = down.dev<int>(o_out1); s1.h_out = down.host<int>(o_out1);
+  s2.d_out = down.dev<int>(o_out2); s2.h_out = down.host<int>(o_out2);
+  {   // what happens between the stages is the tail of the motion-model stage's solver (the workgroup that has just written the flags and
+      // the pose: no launch, no second read of them); its arguments travel in the upload block
     AsdBetweenArgs b{};
     b.n_cur = nc; b.n_last = nl; b.n_cand = ncand;
-    b.match1 = down.dev<int>(o_out1); b.io1 = d_io1; b.Xw_last = up.dev<float>(o_Xw); b.last_cand = has_lc ? up.dev<int>(o_lc) : nullptr;
+    b.match1 = s1.d_out; b.io1 = d_io1; b.Xw_last = up.dev<float>(o_Xw); b.last_cand = A.last_cand ? up.dev<int>(o_lc) : nullptr;
     memcpy(b.T_pred, A.Tcw, sizeof b.T_pred);
     b.occ = d_occ; b.cur_Xw = d_curXw; b.skip = d_skip; b.T1 = d_T1;
     memcpy(up.host<char>(o_btw), &b, sizeof b);
   }
-  {
-    // every runtime request of the chain that is not a launch happens here, before the first kernel goes out
-    if ((rc = pose_chain_reserve(ctx, nc)) != ASD_OK) return rc;
-    static AsdPerDeviceOnce attrs;
-    if (attrs.need(ctx->cfg.device)) {
-      const void* ks[] = {reinterpret_cast<const void*>(k_resolve2<0, 2>), reinterpret_cast<const void*>(k_resolve2<0, 4>),
-                          reinterpret_cast<const void*>(k_resolve2<1, 2>), reinterpret_cast<const void*>(k_resolve2<1, 4>)};
-      for (const void* k : ks) ASD_HIP_CHECK(ctx, hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024));
-      attrs.done(ctx->cfg.device);
-    }
-  }
-  // ---- motion-model stage: projection arguments (launched below)
-  ProjectArgs pa{};
-  {
-    pa.n = nl; pa.kp_last = L->d_kp;
-    memcpy(pa.T, A.Tcw, sizeof pa.T);
-    pa.fx = A.K[0]; pa.fy = A.K[1]; pa.cx = A.K[2]; pa.cy = A.K[3];
-    pa.min_x = C->min_x; pa.max_x = C->max_x; pa.min_y = C->min_y; pa.max_y = C->max_y; pa.th = A.th;
-    for (int l = 0; l < ASD_MAX_LEVELS; ++l) pa.scale[l] = l < ctx->cfg.n_levels ? ctx->scale[l] : 0.f;
-    pa.Xw = up.host<float>(o_Xw); pa.has_mp = up.host<uint8_t>(o_has); pa.rows = up.host<int>(o_rows1);   // the query blocks read the pinned block
-    pa.queries = up.dev<WinQuery>(o_q1);
-    pa.up = UploadTail{reinterpret_cast<const uint4*>(up.h), reinterpret_cast<uint4*>(up.d), ((size_t)nl * sizeof(WinQuery) + 255) / 256 * 16, (up.used + 15) / 16,
-                       (nl + 255) / 256};
-  }
-  auto resolve_launch = [&](auto kern, const Resolve2Args& a, size_t lds) -> hipError_t {   // (attributes: set above)
-    hipLaunchKernelGGL(kern, dim3(1), dim3(kResolve2Threads), lds, st, a);
-    return hipGetLastError();
-  };
-  // the replay's arguments of a stage (every pointer is known before anything is launched)
-  auto replay_args = [&](int KIND, int nq, int* d_off, int* d_cnt, int* d_total, uint16_t* d_top, const uint8_t* d_obs, const float4* kp_last, int check_ori,
-                         float nn_ratio, int* d_out, int* h_out, size_t* lds_out) {
-    Resolve2Args a{};
-    a.nq = nq; a.n_cur = nc;
-    a.q_off = d_off; a.q_cnt = d_cnt; a.idx = m->d_idx; a.dist = m->d_dist; a.top_idx = d_top;
-    a.total = d_total; a.cap = m->cand_cap;
-    a.obs_pos = d_obs;
-    a.kp_cur = C->d_kp; a.kp_last = kp_last;
-    a.check_ori = check_ori; a.nn_ratio = nn_ratio;
-    a.match_cur = d_out; a.n_matches = d_out + nc; a.mirror = h_out;
-    const size_t fixed = resolve_lds_bytes(KIND, nc, nq), per = KIND == 1 ? 6 : 2;
-    a.stage_cap = (int)std::min<size_t>(((size_t)m->last_total[KIND] * 5 / 4 + 1023) / 1024 * 1024, ((size_t)96 * 1024 - fixed) / per / 8 * 8);
-    *lds_out = fixed + (size_t)a.stage_cap * per;
-    return a;
-  };
-  auto search = [&](int KIND, int nq, const WinQuery* d_q, int* d_off, int* d_cnt, int* d_total, uint16_t* d_top, const uint8_t* d_occ_in) -> int {
-    GridDev G{C->d_kp, C->d_cell_start, C->d_cell_items, C->min_x, C->min_y, C->inv_w, C->inv_h};
-    SortArgs sa{d_occ_in, KIND == 0 ? TH_HIGH : __builtin_huge_valf(), d_top};
-    hipLaunchKernelGGL(k_window_search<true>, dim3((nq + kSearchWaves - 1) / kSearchWaves), dim3(64 * kSearchWaves), 0, st, G, d_q, nq, m->d_bank, C->d_desc, d_off, d_cnt,
-                       d_total, m->cand_cap, m->d_idx, m->d_dist, (unsigned*)nullptr, sa);
-    ASD_HIP_CHECK(ctx, hipGetLastError());
-    return ASD_OK;
-  };
-  size_t lds1 = 0, lds2 = 0;
-  Resolve2Args ra1 = replay_args(0, nl, d_off1, d_cnt1, up.dev<int>(o_tot1), d_top1, has_obs1 ? up.dev<uint8_t>(o_obs1) : nullptr, L->d_kp, A.check_orientation, 0.f,
-                                 down.dev<int>(o_out1), down.host<int>(o_out1), &lds1);
-  Resolve2Args ra2 = replay_args(1, ncand, d_off2, d_cnt2, up.dev<int>(o_tot2), d_top2, has_obs2 ? up.dev<uint8_t>(o_obs2) : nullptr, nullptr, 0, A.nn_ratio,
-                                 down.dev<int>(o_out2), down.host<int>(o_out2), &lds2);
-  // replay + solver of a stage as ONE workgroup where the stage's tables fit (k_resolve_pose); two kernels otherwise
-  const bool fuse_now = pose_chain_fused_ok(ctx, 0, nl, nc, lds1) && pose_chain_fused_ok(ctx, 1, ncand, nc, lds2);
-  AsdFusedReplay fr1{&ra1, 0, nl, lds1}, fr2{&ra2, 1, ncand, lds2};
-  FrustumArgs fa{};
-  fa.n = ncand; fa.n_levels = ctx->cfg.n_levels; fa.bfactor = A.th_local != 1.0;
-  fa.fx = A.K[0]; fa.fy = A.K[1]; fa.cx = A.K[2]; fa.cy = A.K[3];
-  fa.min_x = C->min_x; fa.max_x = C->max_x; fa.min_y = C->min_y; fa.max_y = C->max_y;
-  fa.cos_limit = A.viewing_cos_limit; fa.th = A.th_local;
-  for (int l = 0; l < ASD_MAX_LEVELS; ++l) { fa.level_thr[l] = ctx->level_thr[l]; fa.scale[l] = l < ctx->cfg.n_levels ? ctx->scale[l] : 0.f; }
-  fa.rows = up.dev<int>(o_crows); fa.queries = d_q2;
-  fa.up = UploadTail{nullptr, nullptr, 0, 0, (ncand + 255) / 256};
-  fa.T_dev = d_T1; fa.attr = m->d_attr; fa.skip = d_skip; fa.xw_out = d_cXw;
-  auto project = [&]() -> int {
-    hipLaunchKernelGGL(k_project_queries, dim3(pa.up.q_blocks + kUploadTailBlocks), dim3(256), 0, st, pa);
-    ASD_HIP_CHECK(ctx, hipGetLastError());
-    return ASD_OK;
-  };
-  auto frustum = [&]() -> int {
-    hipLaunchKernelGGL(k_frustum_queries, dim3((ncand + 255) / 256), dim3(256), 0, st, fa);
-    ASD_HIP_CHECK(ctx, hipGetLastError());
-    return ASD_OK;
-  };
-  {
-    if ((rc = project()) != ASD_OK || (rc = search(0, nl, up.dev<WinQuery>(o_q1), d_off1, d_cnt1, up.dev<int>(o_tot1), d_top1, nullptr)) != ASD_OK) return rc;
-    if (!fuse_now) {
-      if (nl <= 2 * kResolve2Threads) ASD_HIP_CHECK(ctx, resolve_launch(k_resolve2<0, 2>, ra1, lds1));
-      else ASD_HIP_CHECK(ctx, resolve_launch(k_resolve2<0, 4>, ra1, lds1));
-    }
-    // ... what happens between the stages is the tail of the stage's PoseOptimization kernel (the workgroup that has just written the
-    // flags and the pose: no launch, no second read of them)
-    if ((rc = pose_chain_enqueue(ctx, nc, down.dev<int>(o_out1), C->d_kp, up.dev<float>(o_Xw), nullptr, nullptr, A.pose7, Kd.data(), down.host<double>(o_res1), nullptr,
-                                 d_io1, up.dev<AsdBetweenArgs>(o_btw), fuse_now ? &fr1 : nullptr)) != ASD_OK)
-      return rc;
-    if ((rc = frustum()) != ASD_OK || (rc = search(1, ncand, d_q2, d_off2, d_cnt2, up.dev<int>(o_tot2), d_top2, d_occ)) != ASD_OK) return rc;
-    if (!fuse_now) {
-      if (ncand <= 2 * kResolve2Threads) ASD_HIP_CHECK(ctx, resolve_launch(k_resolve2<1, 2>, ra2, lds2));
-      else ASD_HIP_CHECK(ctx, resolve_launch(k_resolve2<1, 4>, ra2, lds2));
-    }
-    if ((rc = pose_chain_enqueue(ctx, nc, down.dev<int>(o_out2), C->d_kp, d_cXw, d_occ, d_curXw, nullptr, Kd.data(), down.host<double>(o_res2), d_io1, nullptr, nullptr,
-                                 fuse_now ? &fr2 : nullptr)) != ASD_OK)
-      return rc;
-  }
-  if (!ctx->ev_chain) ASD_HIP_CHECK(ctx, hipEventCreateWithFlags(&ctx->ev_chain, hipEventDisableTiming));
-  ASD_HIP_CHECK(ctx, hipEventRecord(ctx->ev_chain, st));
+  // ---- motion-model stage: its query kernel reads the pinned block and carries the upload
+  s1.source = kQueriesProject; s1.upload = kUploadCarried;
+  s1.project = project_args(ctx, *C, *L, A.Tcw, A.K, A.th);
+  s1.project.Xw = up.host<float>(o_Xw); s1.project.has_mp = up.host<uint8_t>(o_has); s1.project.rows = up.host<int>(o_rows1);
+  s1.project.queries = up.dev<WinQuery>(o_q1);
+  s1.project.up = upload_tail(up, nl, true);
+  s1.d_queries = up.dev<WinQuery>(o_q1);
+  s1.kp_last = L->d_kp; s1.check_ori = A.check_orientation;
+  s1.has_solver = true;
+  s1.solver.d_points = up.dev<float>(o_Xw);
+  memcpy(s1.solver.pose0, A.pose7, sizeof s1.solver.pose0);
+  for (int i = 0; i < 4; ++i) s1.solver.K[i] = s2.solver.K[i] = (double)A.K[i];
+  s1.solver.io = down.host<double>(o_res1); s1.solver.d_io_dev = d_io1; s1.solver.d_between = up.dev<AsdBetweenArgs>(o_btw);
+  // ---- local-map stage: everything it reads was left on the device by the stage in front (pose, occupied keypoints, candidates to skip)
+  s2.source = kQueriesFrustum; s2.upload = kUploadElsewhere;
+  s2.frustum = frustum_args(ctx, *C, ncand, nullptr, d_T1, A.K, A.viewing_cos_limit, A.th_local);
+  s2.frustum.rows = up.dev<int>(o_crows); s2.frustum.queries = d_q2;
+  s2.frustum.up = upload_tail(up, ncand, false);
+  s2.frustum.attr = m->d_attr; s2.frustum.skip = d_skip; s2.frustum.xw_out = d_cXw;
+  s2.d_queries = d_q2;
+  s2.d_occupied = d_occ; s2.nn_ratio = A.nn_ratio;
+  s2.has_solver = true;
+  s2.solver.d_points = d_cXw; s2.solver.d_hold = d_occ; s2.solver.d_own = d_curXw;
+  s2.solver.d_pose0 = d_io1; s2.solver.io = down.host<double>(o_res2);
+  // replay + solver of a stage as ONE workgroup where both stages' tables fit (k_resolve_pose); two kernels each otherwise
+  const bool fuse = stage_fuses(ctx, m, s1) && stage_fuses(ctx, m, s2);
+  if ((rc = enqueue_stage(ctx, m, s1, fuse)) != ASD_OK || (rc = enqueue_stage(ctx, m, s2, fuse)) != ASD_OK || (rc = record_chain_end(ctx)) != ASD_OK) return rc;
 
   asd_track_frame_args O = A;   // (only the output pointers are used below)
   std::array<double, 7> p_in;
@@ -2030,17 +2011,13 @@ int track_frame_impl(asd_ctx* ctx, const asd_track_frame_args& A, std::function<
     auto unpack = [&](const int* h_out, const double* h_io, const double* p_start, int32_t* match, int32_t* n_matches, uint8_t* outlier, double* pose, int32_t* n_inl) {
       memcpy(match, h_out, (size_t)nc * sizeof(int));
       *n_matches = h_out[nc];
-      const int ne = (int)(h_io[8 + (nc + 7) / 8] + 0.5);
-      memcpy(outlier, h_io + 8, (size_t)nc);
-      memcpy(pose, ne < 3 ? p_start : h_io, 56);   // Optimizer.cc:323-324: fewer than 3 correspondences leave the pose alone
-      *n_inl = ne < 3 ? 0 : ne - (int)(h_io[7] + 0.5);
+      unpack_solver_block(h_io, nc, true, match, nullptr, p_start, pose, outlier, n_inl);   // (pose_chain_lds_form holds: checked on entry)
     };
     unpack(h1, ctx->down.host<double>(o_res1), p_in.data(), O.match1, O.n_matches1, O.outlier1, O.pose1, O.n_inliers1);
     double p1[7];
     memcpy(p1, O.pose1, 56);
     unpack(h2, ctx->down.host<double>(o_res2), p1, O.match2, O.n_matches2, O.outlier2, O.pose7, O.n_inliers2);
     ctx->ms_match = 0.f;
-    static const bool timing = getenv("ASD_TIMING") != nullptr;
     if (timing) {   // k_resolve2's own stamps (10 ns units), averaged over 200 frames
       static double acc[2][5], tl[8]; static long calls;
       const int* hh[2] = {h1, h2};

@@ -13,10 +13,10 @@ constexpr int HISTO = ASD_HISTO_LENGTH;
 constexpr int kTop = 4;                          // sorted lists: entries per query in the compact head table
 
 // ---- claim replay over SORTED lists (round 4; the default) -------------------------------------------------------------
-// Same recurrence, same fixed-point iteration, same claim tables as k_resolve above -- what changed is how a map point finds its
-// pick inside an iteration.  k_resolve keeps all ~12 k candidates in registers and lets every one of them bid for its query with a
-// 64-bit LDS atomicMin in EVERY iteration (24 candidates per thread, 13 iterations: 90 us on one workgroup).  k_window_search<true>
-// hands the lists over in preference order, so "the best candidate no earlier map point holds" is the first entry of the list whose
+// The recurrence, its fixed-point iteration and the claim tables are described in matcher.hip ("claim / ratio / rotation-histogram replay on
+// the device").  The removed bid replay of rounds 2-3 (historical: `k_resolve`) kept all ~12 k candidates in registers and let every one of
+// them bid for its query with a 64-bit LDS atomicMin in EVERY iteration (24 candidates per thread, 13 iterations: 90 us on one workgroup).
+// k_window_search<true> hands the lists over in preference order, so "the best candidate no earlier map point holds" is the first entry of the list whose
 // keypoint carries no such claim, and the second best (KIND 1) the next one.
 // KIND 0 (best only): "keypoint j is held against q" can only become true and never false again from one iteration to the next --
 // the smallest claimant of j finds everything in front of j in its list still held and j still free, so it picks j again -- hence a

@@ -517,7 +517,7 @@ def test_match_project_frame_obs_positive(hip, oracle, synth, n, ori):
 
 @pytest.mark.gpu
 def test_host_and_device_replay_agree(pkg, oracle, synth, monkeypatch):
-    """The claim / ratio / histogram replay runs on the device (k_resolve: the serial recurrence solved by fixed-point
+    """The claim / ratio / histogram replay runs on the device (k_resolve2: the serial recurrence solved by fixed-point
     iteration) by default and on the host over the copied-back candidate lists with ASD_MATCH_REPLAY=host (also the
     fallback for very large inputs): both against the oracle on contested inputs, all-positive and mixed flags."""
     monkeypatch.setenv("ASD_MATCH_REPLAY", "host")

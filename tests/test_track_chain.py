@@ -614,3 +614,101 @@ def test_track_local_points_rows_refuses_bad_rows(hip, synth):
         hip.track_local_points_rows(0, 300, neg, T, K, occ, cur_Xw, 1.0, 0.8, pose0, split=True)
     good = hip.track_local_points_rows(0, 300, rows, T, K, occ, cur_Xw, 1.0, 0.8, pose0)
     assert good[1] > 0
+
+
+@pytest.mark.gpu
+def test_chain_with_a_frame_beyond_the_solver_lds(pkg, oracle, synth):
+    """A frame of 4389 keypoints is the smallest whose PoseOptimization edge store leaves the workgroup's LDS (4389 x 35 + 16 > 150 KB): the
+    chains then run k_resolve2 as a kernel of its own, k_pose_edges and k_pose_opt<0> (edge records through HBM), and the completion takes
+    the per-edge form of the outlier flags.  The shared context stops at 4096 keypoints, so this test has a context of its own.
+    Motion-model stage: 600 last-frame points (the replay stays on the device) against the separate calls and the oracle -- matches, counts
+    and flags equal, the pose within POSE_TOL (not bits: the separate call's edges take the compact LDS store, the chain's the HBM store);
+    the split form returns the synchronous call's bits.  The same again with a tenth of the keypoints 3.5-6 px off their map point's
+    projection, so that the per-edge flags are not all zero (52 outliers among 495 edges).  Seed 7000, picked on the CPU: at the oracle's
+    result no edge's final chi2 lies within 1e-4 relative of 5.991 in either run (the nearest |chi2 / 5.991 - 1| is 1.000 to four digits:
+    inliers far below the bound, outliers beyond twice the bound), so a 1e-8 pose difference cannot flip a flag.
+    Local-map stage (900 map points, th = 1.0): asd_track_local_map on asd_frustum's outputs, asd_track_local_points with inline
+    descriptors and by bank row, and asd_track_local_points_rows run the same kernels here: the same bits in every output.
+    asd_track_frame refuses such a frame before it launches anything."""
+    n_cur, n_last, n_mp, th = 4389, 600, 900, 15.0
+    kl, dl, kc, dc, Xw, has, mp_desc, T, K = _m1_case(synth, n_cur, 7000)
+    kl, dl, Xw, has, mp_desc = kl[:n_last], dl[:n_last], Xw[:n_last], has[:n_last], mp_desc[:n_last]
+    pose0 = _pose7(pose_T(rv=(0.012, -0.018, 0.006), t=(0.12, -0.04, 0.33)))
+    h = pkg.AsdHip(n_features=2000, max_width=1241, max_height=376, max_patches=4608)
+    try:
+        h.frame_set(1, kl, dl, BOUNDS)
+        # ---- motion-model stage
+        for displaced in (False, True):
+            if displaced:
+                r15 = np.random.default_rng(15)
+                off = r15.choice(n_cur, n_cur // 10, replace=False)
+                kc = kc.copy()
+                kc["x"][off] += r15.choice([-1.0, 1.0], len(off)).astype(np.float32) * r15.uniform(3.5, 6.0, len(off)).astype(np.float32)
+            h.frame_set(0, kc, dc, BOUNDS)
+            exp = _separate_m1(h, n_cur, kc, has, Xw, mp_desc, T, K, th, True, pose0)
+            got = h.track_motion_model(0, 1, n_cur, has, Xw, mp_desc, T, K, th, pose0, True)
+            np.testing.assert_array_equal(got[0], exp[0])
+            assert got[1] == exp[1] and got[4] == exp[4]
+            np.testing.assert_array_equal(got[3], exp[3])
+            assert np.abs(got[2] - exp[2]).max() <= POSE_TOL
+            om, onm = oracle.match_project_frame(oracle.frame(kc, dc, BOUNDS), oracle.frame(kl, dl, BOUNDS), has, Xw, mp_desc, T, K, th, True)
+            np.testing.assert_array_equal(got[0], om)
+            assert got[1] == onm
+            j = np.nonzero(om >= 0)[0]
+            inv_sigma2 = h.scale_tables()["inv_sigma2"].astype(np.float64)
+            op, oo, oi = oracle.pose_optimize(pose0, Xw[om[j]].astype(np.float64), np.stack([kc["x"][j], kc["y"][j]], 1).astype(np.float64),
+                                              inv_sigma2[kc["octave"][j]], K.astype(np.float64))
+            assert np.abs(got[2] - op).max() <= POSE_TOL and got[4] == oi
+            np.testing.assert_array_equal(got[3][j], oo)
+            assert len(j) > 0.5 * has.sum() and bool(oo.any()) == displaced
+            assert not got[3][om < 0].any()
+            cp = [a.copy() for a in (has, Xw, mp_desc, T, K, pose0)]
+            assert h.track_motion_model(0, 1, n_cur, cp[0], cp[1], cp[2], cp[3], cp[4], th, cp[5], True, split=True) is None
+            for a in cp:
+                a[:] = 3
+            gs = h.track_finish()
+            for a, b in zip(gs, got):
+                np.testing.assert_array_equal(a, b)
+        # ---- local-map stage
+        rng = np.random.default_rng(291 + n_mp)
+        src = rng.integers(0, n_cur, n_mp)
+        uv = np.stack([kc["x"][src], kc["y"][src]], 1) + rng.uniform(-1.5, 1.5, (n_mp, 2)).astype(np.float32)
+        uv[: n_mp // 12] += 2500                                   # outside the image
+        depth = rng.uniform(3, 60, n_mp)
+        depth[n_mp // 12: n_mp // 8] *= -1                         # behind the camera
+        mXw = backproject(T, K, uv, depth)
+        Ow = -(T[:3, :3].astype(np.float64).T @ T[:3, 3].astype(np.float64))
+        normal = mXw.astype(np.float64) - Ow
+        dist = np.linalg.norm(normal, axis=1)
+        normal = normal / dist[:, None] + rng.normal(0, 0.45, normal.shape)
+        normal = (normal / np.linalg.norm(normal, axis=1, keepdims=True)).astype(np.float32)
+        maxd = (dist * SCALES[kc["octave"][src]] * rng.uniform(0.7, 1.4, n_mp)).astype(np.float32)
+        mind = (maxd / np.float32(SCALES[7]) * rng.uniform(0.8, 1.3, n_mp)).astype(np.float32)
+        desc = perturbed_descriptors(dc[src], 0.05, 292)
+        occupied = (rng.uniform(size=n_cur) < 0.3).astype(np.uint8)
+        cur_Xw = backproject(T, K, np.stack([kc["x"], kc["y"]], 1) + rng.uniform(-0.7, 0.7, (n_cur, 2)).astype(np.float32), rng.uniform(4, 50, n_cur))
+        p2 = _pose7(pose_T(rv=(0.011, -0.021, 0.004), t=(0.09, -0.06, 0.31)))
+        rows = np.arange(12000, 12000 + n_mp, dtype=np.int32)
+        h.bank_put(12000, desc)
+        h.mpbank_put(12000, mXw, normal, mind, maxd)
+        in_view, proj, level, vc = h.frustum(0, mXw, normal, mind, maxd, T, K)
+        assert 0.2 * n_mp < in_view.sum() < 0.9 * n_mp
+        e2 = h.track_local_map(0, n_cur, in_view, proj, level, vc, desc, mXw, occupied, cur_Xw, 1.0, 0.8, K, p2)
+        assert e2[1] > 0 and e2[4] > 100
+        others = [h.track_local_points(0, n_cur, mXw, normal, mind, maxd, desc, T, K, occupied, cur_Xw, 1.0, 0.8, p2),
+                  h.track_local_points(0, n_cur, mXw, normal, mind, maxd, rows, T, K, occupied, cur_Xw, 1.0, 0.8, p2),
+                  h.track_local_points_rows(0, n_cur, rows, T, K, occupied, cur_Xw, 1.0, 0.8, p2)]
+        cp = [a.copy() for a in (rows, T, K, occupied, cur_Xw, p2)]
+        assert h.track_local_points_rows(0, n_cur, cp[0], cp[1], cp[2], cp[3], cp[4], 1.0, 0.8, cp[5], split=True) is None
+        for a in cp:
+            a[:] = 3
+        others.append(h.track_finish())
+        for g in others:
+            for a, b in zip(g, e2):
+                np.testing.assert_array_equal(a, b)
+        # ---- asd_track_frame: outside the one-submission form
+        with pytest.raises(RuntimeError, match="outside what the one-submission form handles") as ei:
+            h.track_frame(0, 1, n_cur, has, Xw, rows[:n_last], None, T, K, th, pose0, rows, 1.0, 0.8)
+        assert ei.value.code == -5            # ASD_ERR_CAPACITY
+    finally:
+        h.close()

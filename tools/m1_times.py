@@ -1,4 +1,4 @@
-"""asd_match_project_frame / _points on an idle device and beside the read-ahead extractor: device time and the k_resolve
+"""asd_match_project_frame / _points on an idle device and beside the read-ahead extractor: device time and the k_resolve2
 phase stamps (ASD_TIMING=1 prints them every 200 calls)."""
 import os
 import sys
