@@ -83,6 +83,19 @@ class asd_ba_result(C.Structure):
                 ("iters_first", C.c_int32), ("iters_second", C.c_int32)]
 
 
+class asd_sim3_ransac_problem(C.Structure):
+    _fields_ = [("n", C.c_int32), ("X1c", C.c_void_p), ("X2c", C.c_void_p), ("max_err1", C.c_void_p), ("max_err2", C.c_void_p),
+                ("K1", C.c_float * 4), ("K2", C.c_float * 4), ("fix_scale", C.c_int32), ("min_inliers", C.c_int32), ("n_iter", C.c_int32),
+                ("draws", C.c_void_p), ("best_inliers", C.c_int32), ("best_updated", C.c_int32), ("R12", C.c_float * 9), ("t12", C.c_float * 3),
+                ("s12", C.c_float), ("T12", C.c_float * 16), ("found", C.c_int32), ("iterations_done", C.c_int32), ("n_inliers", C.c_int32),
+                ("inliers", C.c_void_p)]
+
+
+class asd_sim3_ransac_debug(C.Structure):
+    _fields_ = [("idx", C.c_int32 * 3), ("count", C.c_int32), ("T12", C.c_float * 16), ("T21", C.c_float * 16), ("s", C.c_float),
+                ("q", C.c_double * 4)]
+
+
 def _p(a):
     return None if a is None else a.ctypes.data_as(C.c_void_p)
 
@@ -123,6 +136,13 @@ def bow_score(scoring, v1, v2):
     if rc != 0:
         raise AsdError(rc, lib.asd_last_error(None).decode())
     return out.value
+
+
+def sim3_ransac_max_iterations(n, probability, min_inliers, max_iterations):
+    """asd_sim3_ransac_max_iterations: Sim3Solver::SetRansacParameters' mRansacMaxIts (Sim3Solver.cc:114-138; host only, no context)"""
+    lib = load_library()
+    lib.asd_sim3_ransac_max_iterations.restype = C.c_int32
+    return int(lib.asd_sim3_ransac_max_iterations(C.c_int32(n), C.c_double(probability), C.c_int32(min_inliers), C.c_int32(max_iterations)))
 
 
 class AsdHip:
@@ -890,6 +910,50 @@ class AsdHip:
         rounds = [dict(active=int(out[4 * r]), iterations=int(out[4 * r + 1]), trials=int(out[4 * r + 2]), ends_rejected=int(out[4 * r + 3]))
                   for r in range(2) if out[4 * r] >= 0]
         return dict(rounds=rounds, n_bad=int(out[8]), cap=int(out[9]), early=int(out[10]), n=int(out[11]))
+
+    def sim3_ransac(self, problems):
+        """asd_sim3_ransac: Sim3Solver::iterate (Sim3Solver.cc:140-207) for a batch of solvers.  problems = dicts with n, X1c, X2c,
+        max_err1, max_err2, K1, K2, fix_scale, min_inliers, n_iter, draws [n_iter][3], best_inliers (further keys are ignored) -> one dict
+        per problem: best_inliers, best_updated, R12, t12, s12, T12 (as they went in -- NaN-filled here -- unless best_updated), found,
+        iterations_done, n_inliers, inliers [n] uint8."""
+        arr = (asd_sim3_ransac_problem * max(len(problems), 1))()
+        keep = []
+        for j, q in enumerate(problems):
+            n = int(q["n"])
+            a = [_c(q["X1c"], np.float32), _c(q["X2c"], np.float32), _c(q["max_err1"], np.float32), _c(q["max_err2"], np.float32),
+                 _c(q["draws"], np.int32), np.zeros(max(n, 1), np.uint8)]
+            keep.append(a)
+            P = arr[j]
+            P.n = n
+            P.X1c, P.X2c, P.max_err1, P.max_err2, P.draws, P.inliers = (x.ctypes.data for x in a)
+            P.K1 = (C.c_float * 4)(*[float(k) for k in q["K1"]])
+            P.K2 = (C.c_float * 4)(*[float(k) for k in q["K2"]])
+            P.fix_scale, P.min_inliers, P.n_iter, P.best_inliers = int(q["fix_scale"]), int(q["min_inliers"]), int(q["n_iter"]), int(q["best_inliers"])
+            P.best_updated, P.found, P.iterations_done, P.n_inliers = -1, -1, -1, -1
+            nan = float("nan")
+            P.R12 = (C.c_float * 9)(*[nan] * 9)
+            P.t12 = (C.c_float * 3)(*[nan] * 3)
+            P.T12 = (C.c_float * 16)(*[nan] * 16)
+            P.s12 = nan
+        self._chk(self.lib.asd_sim3_ransac(self.ctx, len(problems), arr))
+        out = []
+        for j, q in enumerate(problems):
+            P = arr[j]
+            out.append(dict(best_inliers=int(P.best_inliers), best_updated=int(P.best_updated), R12=np.array(P.R12, np.float32).reshape(3, 3),
+                            t12=np.array(P.t12, np.float32), s12=np.float32(P.s12), T12=np.array(P.T12, np.float32).reshape(4, 4),
+                            found=int(P.found), iterations_done=int(P.iterations_done), n_inliers=int(P.n_inliers),
+                            inliers=keep[j][5][:int(q["n"])].copy()))
+        return out
+
+    def debug_sim3_ransac(self, problem, hypothesis):
+        """one iteration of the last sim3_ransac: dict(idx [3], count, T12, T21 (4x4 f32), s (f32), q (w x y z, f64)) -- asd_debug_sim3_ransac"""
+        d = asd_sim3_ransac_debug()
+        self.lib.asd_debug_sim3_ransac.restype = C.c_int32
+        rc = self.lib.asd_debug_sim3_ransac(self.ctx, int(problem), int(hypothesis), C.byref(d))
+        if rc != 0:
+            raise AsdError(rc, f"asd_debug_sim3_ransac: the last call ran no hypothesis {hypothesis} of problem {problem}")
+        return dict(idx=[int(i) for i in d.idx], count=int(d.count), T12=np.array(d.T12, np.float32).reshape(4, 4),
+                    T21=np.array(d.T21, np.float32).reshape(4, 4), s=np.float32(d.s), q=np.array(d.q, np.float64))
 
     def _ba_pack(self, prob, its_first, its_second):
         poses = _c(prob["poses"], np.float64).copy()

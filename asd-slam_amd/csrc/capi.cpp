@@ -157,6 +157,7 @@ int asd_ctx_destroy(asd_ctx* ctx) {
   mapping_free(ctx);
   bow_free(ctx);
   sim3_free(ctx);
+  sim3_ransac_free(ctx);
   kfdb_free(ctx);
   ctx->scratch.release();
   ctx->stereo_scratch.release();
@@ -256,6 +257,7 @@ int asd_last_stage_ms(const asd_ctx* ctx, const char* stage, float* ms) {
   else if (!strcmp(stage, "match")) *ms = ctx->ms_match;
   else if (!strcmp(stage, "ba")) *ms = ctx->ms_ba;
   else if (!strcmp(stage, "sim3")) *ms = ctx->ms_sim3;
+  else if (!strcmp(stage, "sim3_ransac")) *ms = ctx->ms_sim3_ransac;
   else if (!strcmp(stage, "kfdb")) *ms = ctx->ms_kfdb;
   else return ASD_ERR_INVALID;
   return ASD_OK;
@@ -359,6 +361,18 @@ int asd_sync(asd_ctx* ctx) {
   if (!ctx) return ASD_ERR_INVALID;
   ASD_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
   return ctx->h_range ? asd_range_status(ctx, ctx->h_range, "asd_describe_device") : ASD_OK;
+}
+
+// Sim3Solver::SetRansacParameters (Sim3Solver.cc:114-138), literally
+int32_t asd_sim3_ransac_max_iterations(int32_t n, double probability, int32_t min_inliers, int32_t max_iterations) {
+  float epsilon = (float)min_inliers / n;                                             // :125
+  int nIterations;
+  if (min_inliers == n) nIterations = 1;                                              // :130-131
+  else {
+    const double v = std::ceil(std::log(1 - probability) / std::log(1 - std::pow((double)epsilon, 3)));   // :133
+    nIterations = (v > -2147483649.0 && v < 2147483648.0) ? (int)v : INT32_MIN;       // what cvttsd2si gives the reference's implicit conversion
+  }
+  return std::max(1, std::min(nIterations, max_iterations));                          // :135
 }
 
 // Converter::toSE3Quat (Converter.cc:37-47) + SE3Quat(R,t) ctor (se3quat.h:58-60): Eigen

@@ -15,6 +15,9 @@
 // failure) except construction, which throws std::runtime_error if no HIP device is usable.
 #pragma once
 #include <cstdint>
+#include <cstdlib>
+#include <deque>
+#include <functional>
 #include <stdexcept>
 #include <string>
 #include <utility>
@@ -533,9 +536,188 @@ class KeyFrameDatabase {
   int scoring_ = -1;
 };
 
-// LoopClosing::ComputeSim3, the numeric body for ONE loop candidate (LoopClosing.cc:304, :346-375, :415): every search and the
-// refinement run behind the C ABI; what stays with the caller is Sim3Solver (:312-337, a three-point closed form inside RANSAC),
-// handed in as a callback that turns the BoW matches into (s, R row-major 3x3, t) of pKF2 -> mpCurrentKF, or returns false.
+// ---- DUtils::Random as Sim3Solver uses it (src/dbow2/DUtils/Random.cpp:47-50) ----------------------------------------------
+// A stream of raw rand() values.  The reference calls rand() three times per RANSAC iteration, at the moment the iteration runs; a
+// batched iterate() has to draw 3 x nIterations values ahead and, on an early return after iteration k, has used only 3 x (k + 1)
+// of them.  The stream therefore takes the unused values back (GiveBack) and hands them out first next time: the sequence of raw
+// values the solvers consume is the reference's for the same seed.  The source defaults to ::rand and can be replaced.
+class DrawStream {
+ public:
+  explicit DrawStream(std::function<int()> source = [] { return std::rand(); }, double rand_max = (double)RAND_MAX)
+      : source_(std::move(source)), rand_max_(rand_max) {}
+  int Next() {
+    if (pending_.empty()) return source_();
+    const int v = pending_.front();
+    pending_.pop_front();
+    return v;
+  }
+  // int RandomInt(int min, int max) of the raw value r: int(((double)r / ((double)RAND_MAX + 1.0)) * d) + min
+  int RandomInt(int raw, int min, int max) const {
+    const int d = max - min + 1;
+    return int(((double)raw / (rand_max_ + 1.0)) * d) + min;
+  }
+  // raw values taken with Next() and not used, in the order they were taken; they must be the LAST values handed out
+  void GiveBack(const int* raw, size_t n) { pending_.insert(pending_.begin(), raw, raw + n); }
+  size_t Pending() const { return pending_.size(); }
+ private:
+  std::function<int()> source_;
+  double rand_max_;
+  std::deque<int> pending_;
+};
+
+// ---- Sim3Solver (Sim3Solver.h:36-128; src/vslam/src/Sim3Solver.cc) -----------------------------------------------------------
+// The RANSAC iterations run on the device (asd_sim3_ransac); this class keeps what the reference's object keeps between iterate()
+// calls: the gathered correspondences, mnIterations, mnBestInliers and the best model.  iterate() = Begin + asd_sim3_ransac + End;
+// the two halves are public so that several solvers can share one call (LoopClosing::ComputeSim3 below).
+class Sim3Solver {
+ public:
+  // Sim3Solver(KeyFrame* pKF1, KeyFrame* pKF2, const vector<MapPoint*>& vpMatched12, bool bFixScale)  (:37-112).  vpMatched12[i1] = pKF2's
+  // map point id matched to pKF1's keypoint i1 (-1 = NULL), vnIdx2[i1] = its keypoint in pKF2 (pMP2->GetIndexInKeyFrame(pKF2)), as
+  // SearchByBoW(KF, KF) leaves them; mvpMapPoints[i] >= 0 stands for "a map point that is not bad", and pMP1->GetIndexInKeyFrame(pKF1) is
+  // i1.  vLevelSigma2_1 / _2 = mvLevelSigma2.  mvnMaxError1 / 2 are vector<size_t> in the reference (Sim3Solver.h:78-79), so the
+  // 9.210 * sigma2 of :87-88 is stored truncated to an integer and compared as a float (:356): that is what is stored here.
+  Sim3Solver(Context& c, const FrameView& KF1, const FrameView& KF2, const std::vector<int32_t>& vpMatched12, const std::vector<int32_t>& vnIdx2,
+             const std::vector<MapPointView>& points, const Camera& K1, const Camera& K2, const std::vector<float>& vLevelSigma2_1,
+             const std::vector<float>& vLevelSigma2_2, bool bFixScale, DrawStream& draws)
+      : ctx_(c.get()), draws_(&draws), mbFixScale(bFixScale), mK1(K1), mK2(K2) {
+    mN1 = (int)vpMatched12.size();
+    auto to_camera = [](const float* T, const float* X, std::vector<float>& out) {   // Rcw * X3Dw + tcw in f32 (:95, :98)
+      for (int r = 0; r < 3; ++r) out.push_back((T[r * 4] * X[0] + T[r * 4 + 1] * X[1] + T[r * 4 + 2] * X[2]) + T[r * 4 + 3]);
+    };
+    for (int i1 = 0; i1 < mN1; ++i1) {                                                // :62-103
+      if (vpMatched12[i1] < 0) continue;
+      const int id1 = KF1.mvpMapPoints.size() == (size_t)KF1.N() ? KF1.mvpMapPoints[i1] : -1;
+      if (id1 < 0) continue;                                                          // :69-73
+      const int indexKF2 = vnIdx2[i1];
+      if (indexKF2 < 0) continue;                                                     // :78-79
+      const float sigmaSquare1 = vLevelSigma2_1[KF1.mvKeysUn[i1].octave], sigmaSquare2 = vLevelSigma2_2[KF2.mvKeysUn[indexKF2].octave];
+      mvnMaxError1.push_back((float)(size_t)(9.210 * sigmaSquare1));                  // :87-88 into vector<size_t>
+      mvnMaxError2.push_back((float)(size_t)(9.210 * sigmaSquare2));
+      mvnIndices1.push_back((size_t)i1);
+      to_camera(KF1.mTcw, points[id1].Xw, mvX3Dc1);
+      to_camera(KF2.mTcw, points[vpMatched12[i1]].Xw, mvX3Dc2);
+    }
+    SetRansacParameters();                                                            // :111
+  }
+  // the gathered vectors directly (tests, or a caller that gathers itself).  ctx may be null for a solver that is only stepped through
+  // Begin / End
+  Sim3Solver(asd_ctx* ctx, int N1, std::vector<size_t> vnIndices1, std::vector<float> vX3Dc1, std::vector<float> vX3Dc2,
+             std::vector<float> vnMaxError1, std::vector<float> vnMaxError2, const Camera& K1, const Camera& K2, bool bFixScale, DrawStream& draws)
+      : ctx_(ctx), draws_(&draws), mbFixScale(bFixScale), mK1(K1), mK2(K2), mN1(N1), mvnIndices1(std::move(vnIndices1)),
+        mvX3Dc1(std::move(vX3Dc1)), mvX3Dc2(std::move(vX3Dc2)), mvnMaxError1(std::move(vnMaxError1)), mvnMaxError2(std::move(vnMaxError2)) {
+    SetRansacParameters();
+  }
+
+  // void SetRansacParameters(double probability = 0.99, int minInliers = 6, int maxIterations = 300)  (:114-138)
+  void SetRansacParameters(double probability = 0.99, int minInliers = 6, int maxIterations = 300) {
+    mRansacProb = probability;
+    mRansacMinInliers = minInliers;
+    N = (int)mvnIndices1.size();
+    mRansacMaxIts = asd_sim3_ransac_max_iterations(N, probability, minInliers, maxIterations);
+    mnIterations = 0;
+  }
+
+  // cv::Mat iterate(int nIterations, bool& bNoMore, vector<bool>& vbInliers, int& nInliers)  (:140-207).  Returns true where the reference
+  // returns a non-empty mBestT12 (GetEstimatedT12); false with an empty matrix.  A failed device call counts as bNoMore.
+  bool iterate(int nIterations, bool& bNoMore, std::vector<bool>& vbInliers, int& nInliers) {
+    asd_sim3_ransac_problem p;
+    if (!Begin(nIterations, p)) { bNoMore = true; vbInliers.assign(mN1, false); nInliers = 0; return false; }
+    if (asd_sim3_ransac(ctx_, 1, &p) != ASD_OK) { Cancel(); bNoMore = true; vbInliers.assign(mN1, false); nInliers = 0; return false; }
+    return End(p, bNoMore, vbInliers, nInliers);
+  }
+  // cv::Mat find(vector<bool>& vbInliers12, int& nInliers)  (:209-213)
+  bool find(std::vector<bool>& vbInliers12, int& nInliers) {
+    bool bFlag;
+    return iterate(mRansacMaxIts, bFlag, vbInliers12, nInliers);
+  }
+  const float* GetEstimatedRotation() const { return mBestRotation; }        // row-major 3x3 (:367-370)
+  const float* GetEstimatedTranslation() const { return mBestTranslation; }  // (:372-375)
+  float GetEstimatedScale() const { return mBestScale; }                     // (:377-380)
+  const float* GetEstimatedT12() const { return mBestT12; }                  // mBestT12, row-major 4x4
+  const std::vector<size_t>& GetIndices1() const { return mvnIndices1; }
+  int GetIterations() const { return mnIterations; }
+  int GetBestInliers() const { return mnBestInliers; }
+  int GetMaxIterations() const { return mRansacMaxIts; }
+  int GetN() const { return N; }
+
+  // The first half of iterate(): fills `p` for asd_sim3_ransac with the iterations the reference's loop would start (:158) and draws
+  // their 3 random numbers each from the stream (:168).  false: N < mRansacMinInliers (:146-150, bNoMore), nothing was drawn.
+  // p points into this object: it must not be moved or destroyed, nor Begin called again, before End or Cancel.
+  bool Begin(int nIterations, asd_sim3_ransac_problem& p) {
+    p = asd_sim3_ransac_problem{};
+    if (N < mRansacMinInliers) return false;
+    const int n_iter = std::max(0, std::min(nIterations, mRansacMaxIts - mnIterations));
+    raw_.resize((size_t)3 * n_iter);
+    randi_.resize((size_t)3 * n_iter);
+    for (int k = 0; k < n_iter; ++k)
+      for (int i = 0; i < 3; ++i) {
+        raw_[3 * k + i] = draws_->Next();
+        randi_[3 * k + i] = draws_->RandomInt(raw_[3 * k + i], 0, N - 1 - i);   // RandomInt(0, vAvailableIndices.size() - 1)
+      }
+    inliers_.assign((size_t)N + 1, 0);
+    p.n = N;
+    p.X1c = mvX3Dc1.data(); p.X2c = mvX3Dc2.data(); p.max_err1 = mvnMaxError1.data(); p.max_err2 = mvnMaxError2.data();
+    const float k1[4] = {mK1.fx, mK1.fy, mK1.cx, mK1.cy}, k2[4] = {mK2.fx, mK2.fy, mK2.cx, mK2.cy};
+    for (int i = 0; i < 4; ++i) { p.K1[i] = k1[i]; p.K2[i] = k2[i]; }
+    p.fix_scale = mbFixScale; p.min_inliers = mRansacMinInliers; p.n_iter = n_iter;
+    p.draws = randi_.data();
+    p.best_inliers = mnBestInliers;
+    p.inliers = inliers_.data();
+    return true;
+  }
+  // The second half: what the iterations changed in the object, the unused random numbers back to the stream, iterate()'s outputs
+  bool End(const asd_sim3_ransac_problem& p, bool& bNoMore, std::vector<bool>& vbInliers, int& nInliers) {
+    bNoMore = false;
+    vbInliers.assign(mN1, false);
+    nInliers = 0;
+    const size_t used = (size_t)3 * p.iterations_done;
+    draws_->GiveBack(raw_.data() + used, raw_.size() - used);
+    last_raw_.assign(raw_.begin(), raw_.begin() + used);
+    raw_.clear();
+    mnIterations += p.iterations_done;
+    mnBestInliers = p.best_inliers;
+    if (p.best_updated) {                                                             // :185-190
+      for (int i = 0; i < 9; ++i) mBestRotation[i] = p.R12[i];
+      for (int i = 0; i < 3; ++i) mBestTranslation[i] = p.t12[i];
+      for (int i = 0; i < 16; ++i) mBestT12[i] = p.T12[i];
+      mBestScale = p.s12;
+    }
+    if (p.found) {                                                                    // :192-199
+      nInliers = p.n_inliers;
+      for (int i = 0; i < N; ++i)
+        if (inliers_[i]) vbInliers[mvnIndices1[i]] = true;
+      return true;
+    }
+    if (mnIterations >= mRansacMaxIts) bNoMore = true;                                // :203-204
+    return false;
+  }
+  // Begin undone: every random number back to the stream, the object as it was (the reference would not have called iterate())
+  void Cancel() {
+    draws_->GiveBack(raw_.data(), raw_.size());
+    raw_.clear();
+  }
+  const std::vector<int>& LastRawConsumed() const { return last_raw_; }   // the raw values the last End kept (test aid)
+
+ private:
+  asd_ctx* ctx_;
+  DrawStream* draws_;
+  bool mbFixScale;
+  Camera mK1, mK2;
+  int mN1 = 0, N = 0;
+  std::vector<size_t> mvnIndices1;
+  std::vector<float> mvX3Dc1, mvX3Dc2, mvnMaxError1, mvnMaxError2;
+  double mRansacProb = 0.99;
+  int mRansacMinInliers = 6, mRansacMaxIts = 300, mnIterations = 0, mnBestInliers = 0;
+  float mBestRotation[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1}, mBestTranslation[3] = {0, 0, 0}, mBestScale = 1.f;
+  float mBestT12[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};
+  std::vector<int> raw_, last_raw_;
+  std::vector<int32_t> randi_;
+  std::vector<uint8_t> inliers_;
+};
+
+// LoopClosing::ComputeSim3 (LoopClosing.cc:269-423): every search, the RANSAC and the refinement run behind the C ABI.  Two forms:
+// ComputeSim3 over the candidate list with asd::Sim3Solver (:291-377), and ComputeSim3Candidate, the numeric body for ONE candidate with
+// the Sim3 handed in by a callback (a caller that keeps a solver of its own).  Both end in the same tail (Sim3Tail: :359-375, :415).
 struct LoopClosing {
   // LoopClosing::DetectLoop's lowest score to a connected keyframe (LoopClosing.cc:154-168): vConnected = the ids of
   // mpCurrentKF->GetVectorCovisibleKeyFrames() that are not bad (all of them must be in the database); 1 when there is none.
@@ -552,7 +734,7 @@ struct LoopClosing {
     }
     return minScore;
   }
-  struct Result { bool bMatch = false; int nBoW = 0, nSim3 = 0, nInliers = 0, nTotalMatches = 0; double g2oScm[8] = {0, 0, 0, 1, 0, 0, 0, 1}; };
+  struct Result { bool bMatch = false; int iMatched = -1; int nBoW = 0, nSim3 = 0, nInliers = 0, nTotalMatches = 0; double g2oScm[8] = {0, 0, 0, 1, 0, 0, 0, 1}; };
   // `points` = the caller's map point table (ids as in mvpMapPoints); vpLoopMapPoints = ids of the points of the loop keyframe and
   // its neighbours (:393-412); vpCurrentMatchedPoints[i] = id matched to the current keyframe's keypoint i on return.
   template <class Sim3SolverFn>
@@ -567,6 +749,15 @@ struct LoopClosing {
     if (r.nBoW < 20) return r;                                                            // :305
     float s = 1.f, R[9], t[3];
     if (!solver(vpMatches, vnIdx2, &s, R, t)) return r;                                   // :337 (the caller keeps only the RANSAC inliers, :349-354)
+    return Sim3Tail(c, CurrentKF, KF, points, vpLoopMapPoints, K, invLevelSigma2, bFixScale, r, vpMatches, vnIdx2, s, R, t, vpCurrentMatchedPoints);
+  }
+
+  // What follows a Sim3 from RANSAC for one candidate (:359-375, :415): SearchBySim3, OptimizeSim3, and for a match mScw and
+  // SearchByProjection(KF, Scw).  vpMatches / vnIdx2 = the matches the RANSAC kept (:349-354); r carries nBoW.
+  static Result Sim3Tail(Context& c, const FrameView& CurrentKF, const FrameView& KF, const std::vector<MapPointView>& points,
+                         const std::vector<int32_t>& vpLoopMapPoints, const Camera& K, const std::vector<float>& invLevelSigma2, bool bFixScale,
+                         Result r, std::vector<int32_t> vpMatches, std::vector<int32_t> vnIdx2, float s, const float* R, const float* t,
+                         std::vector<int32_t>& vpCurrentMatchedPoints) {
     // matcher.SearchBySim3(mpCurrentKF, pKF, vpMapPointMatches, s, R, t, 7.5)  (:359)
     const int n1 = CurrentKF.N(), n2 = KF.N();
     auto gather = [&](const FrameView& F, std::vector<uint8_t>& has, std::vector<float>& Xw, std::vector<float>& mind, std::vector<float>& maxd,
@@ -648,6 +839,93 @@ struct LoopClosing {
     for (int i = 0; i < n1; ++i)
       if (matched_kp[i] >= 0 && matched_kp[i] < nl) vpCurrentMatchedPoints[i] = vpLoopMapPoints[matched_kp[i]];
     for (int i = 0; i < n1; ++i) r.nTotalMatches += vpCurrentMatchedPoints[i] >= 0;        // :418-423
+    return r;
+  }
+
+  // One round of the loop of :322-377 over the live solvers from position `from` on, as ONE asd_sim3_ransac call: every solver draws its
+  // nIterations in candidate order and iterates.  The reference's round is sequential: when solver i returns a model, the solvers behind
+  // it have not iterated yet -- their random numbers go back to the stream (last solver first, so that the stream hands them out in the
+  // order they were drawn) and their state stays as it was in front of the round.  Returns the position of the first solver that
+  // returned a model (vbInliers / nInliers are its outputs), or -1 when none did.  Solvers that reached their last iteration are
+  // marked discarded (:339-343).
+  static int Sim3Round(Context& c, std::vector<Sim3Solver*>& vpSim3Solvers, std::vector<bool>& vbDiscarded, int from, int nIterations,
+                       std::vector<bool>& vbInliers, int& nInliers) {
+    std::vector<int> who;
+    std::vector<asd_sim3_ransac_problem> probs;
+    for (int i = from; i < (int)vpSim3Solvers.size(); ++i) {
+      if (vbDiscarded[i]) continue;
+      asd_sim3_ransac_problem p;
+      if (!vpSim3Solvers[i]->Begin(nIterations, p)) { vbDiscarded[i] = true; continue; }   // N < mRansacMinInliers: bNoMore at once
+      who.push_back(i);
+      probs.push_back(p);
+    }
+    if (who.empty()) return -1;
+    if (asd_sim3_ransac(c.get(), (int32_t)probs.size(), probs.data()) != ASD_OK) {
+      for (size_t k = who.size(); k-- > 0;) { vpSim3Solvers[who[k]]->Cancel(); vbDiscarded[who[k]] = true; }
+      return -1;
+    }
+    size_t first = who.size();
+    for (size_t k = 0; k < who.size(); ++k)
+      if (probs[k].found) { first = k; break; }
+    for (size_t k = who.size(); k-- > first + 1;) vpSim3Solvers[who[k]]->Cancel();
+    int hit = -1;
+    // (End gives the unused numbers of the solver that returned back LAST: they were drawn in front of those of the solvers behind it)
+    for (size_t k = std::min(first + 1, who.size()); k-- > 0;) {
+      bool bNoMore = false;
+      std::vector<bool> inl;
+      int nInl = 0;
+      const bool got = vpSim3Solvers[who[k]]->End(probs[k], bNoMore, inl, nInl);
+      if (bNoMore) vbDiscarded[who[k]] = true;
+      if (got) { hit = who[k]; vbInliers = inl; nInliers = nInl; }
+    }
+    return hit;
+  }
+
+  // bool LoopClosing::ComputeSim3()  (:269-423) over mvpEnoughConsistentCandidates = vpCandidates (with their FeatureVectors).  A Sim3Solver
+  // with SetRansacParameters(0.99, 20, 300) per candidate with 20 BoW matches or more (:304-315); rounds of 5 iterations per live
+  // candidate (:337) until one gives a Sim3 that survives SearchBySim3 + OptimizeSim3 with 20 inliers (:364) or every candidate is
+  // discarded.  loopPoints(i) = the ids of the map points of candidate i and its neighbours (:393-412), asked for the matched candidate only.
+  // Result::iMatched = position of mpMatchedKF in vpCandidates (-1: no match).
+  template <class LoopPointsFn>
+  static Result ComputeSim3(Context& c, const FrameView& CurrentKF, const ORBmatcher::FeatVec& fvCur, const std::vector<const FrameView*>& vpCandidates,
+                            const std::vector<const ORBmatcher::FeatVec*>& vfvCandidates, const std::vector<MapPointView>& points,
+                            LoopPointsFn loopPoints, const Camera& K, const std::vector<float>& levelSigma2, const std::vector<float>& invLevelSigma2,
+                            bool bFixScale, DrawStream& draws, std::vector<int32_t>& vpCurrentMatchedPoints) {
+    const int nInitialCandidates = (int)vpCandidates.size();
+    ORBmatcher matcher(c, 0.85f, true);                                                   // :277
+    std::vector<Sim3Solver*> vpSim3Solvers(nInitialCandidates, nullptr);
+    std::vector<std::vector<int32_t>> vvpMapPointMatches(nInitialCandidates), vvnIdx2(nInitialCandidates);
+    std::vector<int> vnBoW(nInitialCandidates, 0);
+    std::vector<bool> vbDiscarded(nInitialCandidates, false);
+    for (int i = 0; i < nInitialCandidates; ++i) {                                        // :291-318
+      vnBoW[i] = matcher.SearchByBoW(CurrentKF, fvCur, *vpCandidates[i], *vfvCandidates[i], vvpMapPointMatches[i], vvnIdx2[i]);
+      if (vnBoW[i] < 20) { vbDiscarded[i] = true; continue; }
+      vpSim3Solvers[i] = new Sim3Solver(c, CurrentKF, *vpCandidates[i], vvpMapPointMatches[i], vvnIdx2[i], points, K, K, levelSigma2, levelSigma2,
+                                        bFixScale, draws);
+      vpSim3Solvers[i]->SetRansacParameters(0.99, 20, 300);
+    }
+    Result r;
+    auto live = [&] { int n = 0; for (int i = 0; i < nInitialCandidates; ++i) n += !vbDiscarded[i]; return n; };
+    while (live() > 0 && !r.bMatch) {                                                     // :322
+      for (int from = 0; from < nInitialCandidates && !r.bMatch;) {                       // :324: one pass over the candidates
+        std::vector<bool> vbInliers;
+        int nInliers = 0;
+        const int i = Sim3Round(c, vpSim3Solvers, vbDiscarded, from, 5, vbInliers, nInliers);
+        if (i < 0) break;
+        std::vector<int32_t> vpMapPointMatches(vvpMapPointMatches[i].size(), -1), vnIdx2(vvpMapPointMatches[i].size(), -1);   // :349-354
+        for (size_t j = 0; j < vbInliers.size(); ++j)
+          if (vbInliers[j]) { vpMapPointMatches[j] = vvpMapPointMatches[i][j]; vnIdx2[j] = vvnIdx2[i][j]; }
+        Result ri;
+        ri.nBoW = vnBoW[i];
+        ri = Sim3Tail(c, CurrentKF, *vpCandidates[i], points, loopPoints(i), K, invLevelSigma2, bFixScale, ri, vpMapPointMatches, vnIdx2,
+                      vpSim3Solvers[i]->GetEstimatedScale(), vpSim3Solvers[i]->GetEstimatedRotation(), vpSim3Solvers[i]->GetEstimatedTranslation(),
+                      vpCurrentMatchedPoints);
+        ri.iMatched = ri.bMatch ? i : -1;
+        r = ri;
+        from = i + 1;                                                                     // no match (:364): the candidates behind i still iterate this round
+      }
+    }
+    for (Sim3Solver* p : vpSim3Solvers) delete p;
     return r;
   }
 };

@@ -154,6 +154,20 @@ int main(int argc, char** argv) {
                                                                                   false, solver, vpCurrentMatchedPoints);
       printf("loop: bow=%d sim3=%d inliers=%d total=%d match=%d scale=%.6f\n", lc.nBoW, lc.nSim3, lc.nInliers, lc.nTotalMatches, (int)lc.bMatch, lc.g2oScm[7]);
       loop_ok = lc.bMatch && lc.nInliers >= 20;   // LoopClosing.cc:364
+      // the same over the candidate list with asd::Sim3Solver's RANSAC on the device (LoopClosing.cc:291-377): informative only,
+      // the exit status does not depend on it
+      {
+        std::srand(1);
+        asd::DrawStream draws;   // ::rand
+        std::vector<int32_t> matched;
+        const std::vector<const asd::FrameView*> cands = {&F[0]};
+        const std::vector<const asd::ORBmatcher::FeatVec*> cand_fv = {&fv0};
+        const asd::LoopClosing::Result ls = asd::LoopClosing::ComputeSim3(ctx, F[1], fv1, cands, cand_fv, mps, [&](int) { return loop_ids; }, K,
+                                                                          extractor.GetScaleSigmaSquares(), extractor.GetInverseScaleSigmaSquares(),
+                                                                          false, draws, matched);
+        printf("loop-solver: candidate=%d bow=%d sim3=%d inliers=%d total=%d match=%d scale=%.6f\n", ls.iMatched, ls.nBoW, ls.nSim3, ls.nInliers,
+               ls.nTotalMatches, (int)ls.bMatch, ls.g2oScm[7]);
+      }
     }
     printf("kp0=%d kp1=%d matches=%d inliers=%d fused=%d bow=%d t=(%.4f %.4f %.4f)\n", F[0].N(), F[1].N(), nmatches, ninl, nfused, nbow,
            F[1].mTcw[3], F[1].mTcw[7], F[1].mTcw[11]);

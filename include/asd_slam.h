@@ -672,6 +672,7 @@ int asd_pose7_to_tcw(const double* pose7, float* Tcw16);
 /* ---- instrumentation ----------------------------------------------------------------- */
 /* Device-side duration of the kernels enqueued by the most recent call of the named stage,
  * measured with hipEvents on the ctx stream.  stage: "asdnet", "extract", "match", "ba", "sim3" (asd_optimize_sim3),
+ * "sim3_ransac" (both kernels of asd_sim3_ransac, its upload included),
  * "kfdb" (the scoring pass of the last asd_kfdb_score / asd_kfdb_query_*, its upload included). */
 int asd_last_stage_ms(const asd_ctx* ctx, const char* stage, float* ms);
 /* Per-kernel device time of the ASDNet forward, accumulated with hipEvents recorded on the ctx
@@ -765,6 +766,73 @@ int asd_optimize_sim3(asd_ctx* ctx, double* sim3, int32_t n, const double* P1c, 
  * out[11] = n.  Written by one thread into the block the call copies back anyway.  All -1 before any run. */
 #define ASD_SIM3_OPT_DEBUG_INTS 12
 int32_t asd_debug_optimize_sim3(const asd_ctx* ctx, int32_t out[ASD_SIM3_OPT_DEBUG_INTS]);
+/* Sim3Solver (src/vslam/src/Sim3Solver.cc): the RANSAC loop of Sim3Solver::iterate (:140-207) for a batch of solvers, the hypotheses of
+ * every solver in parallel.  One problem = one Sim3Solver and one iterate() call on it:
+ *  in      n                       N = mvX3Dc1.size(), the correspondences the constructor gathered (:62-103)
+ *          X1c[n][3], X2c[n][3]    mvX3Dc1 / mvX3Dc2 = Rcw * Xw + tcw per keyframe (:94-98), f32
+ *          max_err1[n], max_err2[n] mvnMaxError1 / 2: 9.210 * sigma2 of the keypoint's level (:87-88) as the caller's vectors hold it -- the
+ *                                  reference's are vector<size_t> (Sim3Solver.h:78-79), so it compares with the integer part (:356)
+ *          K1[4], K2[4]            fx fy cx cy of mK1 / mK2 (:105-106)
+ *          fix_scale               mbFixScale (:292, :311)
+ *          min_inliers             mRansacMinInliers (:118)
+ *          n_iter                  the iterations this call may run: min(nIterations, mRansacMaxIts - mnIterations) (:158)
+ *          draws[n_iter][3]        draws[k][i] = what RandomInt(0, n - 1 - i) returned for draw i of iteration k (:168); the swap-with-back
+ *                                  bookkeeping of vAvailableIndices (:163-177) is done by the device
+ *  in/out  best_inliers            mnBestInliers (:183-186)
+ *  out     best_updated            1 when an iteration of this call took over the best model (:183); only then are written
+ *          R12[9], t12[3], s12,    mBestRotation, mBestTranslation, mBestScale, mBestT12 (:187-190), row major
+ *          T12[16]
+ *          found                   1 when iterate() returns a model (:192-199), 0 when it returns cv::Mat() (:206)
+ *          iterations_done         how many of the n_iter supplied iterations the reference would have run: k + 1 when iteration k
+ *                                  returns, n_iter otherwise -- what the caller adds to mnIterations, and 3 x that many draws were consumed
+ *          n_inliers               nInliers (:194), 0 unless found
+ *          inliers[n]              mvbInliersi of the returned iteration (:195-197, indexed by correspondence: the caller maps through
+ *                                  mvnIndices1), all 0 unless found (:143)
+ * A problem with n < min_inliers runs nothing (:146-150): found = 0, iterations_done = 0 and nothing else of it is written.
+ * The model of an iteration (ComputeSim3, :226-337) is evaluated in f64 from the f32 points -- centroids, M = Pr2 * Pr1^T, Horn's N (:251-260),
+ * its top eigenvector by cyclic Jacobi, the rotation directly from that unit quaternion (the reference's atan2 / angle-axis / cv::Rodrigues
+ * chain, :274-284, gives the same rotation for either sign of the eigenvector), scale (:292-311), translation (:316), T12 and T21 (:321-336) --
+ * and every output is rounded to f32 once, since the reference keeps them as CV_32F.  It is the reference's formula, not cv::eigen's bits:
+ * an entry is within 0.5 ulp + 32 * eps64 * cond of the exact value, cond = |N|_2 / (lambda1 - lambda2) (tests/sim3solver_ref.py).
+ * CheckInliers / Project (:340-403) and FromCameraToImage (:405-423) run in un-fused f32 in the reference's operation order on those f32
+ * matrices; a non-finite model or projection is never an inlier (both comparisons of :356 are false), as in the reference.
+ * Limits (ASD_ERR_CAPACITY beyond them): ASD_SIM3_RANSAC_MAX_N correspondences per problem, ASD_SIM3_RANSAC_MAX_PROBLEMS problems per call,
+ * ASD_SIM3_RANSAC_MAX_HYPOTHESES iterations per call summed over its problems.  ASD_ERR_INVALID: a draw outside [0, n - 1 - i], n < 3 in a
+ * problem that has iterations to run, a null array, negative n / n_iter; asd_last_error names the problem.  Two kernel launches and one
+ * synchronisation per call, no atomics: a call is one bit pattern.  Legal wherever asd_optimize_sim3 is. */
+#define ASD_SIM3_RANSAC_MAX_N 8192
+#define ASD_SIM3_RANSAC_MAX_PROBLEMS 64
+#define ASD_SIM3_RANSAC_MAX_HYPOTHESES 4096
+typedef struct asd_sim3_ransac_problem {
+  int32_t n;
+  const float* X1c;
+  const float* X2c;
+  const float* max_err1;
+  const float* max_err2;
+  float K1[4], K2[4];
+  int32_t fix_scale, min_inliers, n_iter;
+  const int32_t* draws;
+  int32_t best_inliers;
+  int32_t best_updated;
+  float R12[9], t12[3], s12, T12[16];
+  int32_t found, iterations_done, n_inliers;
+  uint8_t* inliers;
+} asd_sim3_ransac_problem;
+int asd_sim3_ransac(asd_ctx* ctx, int32_t n_problems, asd_sim3_ransac_problem* problems);
+/* Sim3Solver::SetRansacParameters (:114-138), the value it leaves in mRansacMaxIts: epsilon = (float)min_inliers / n as a float,
+ * pow(epsilon, 3) and both log() in double, ceil, the conversion to int (a value that does not fit an int -- epsilon = 0 or > 1 -- converts
+ * as x86-64 does, to INT_MIN), max(1, min(., max_iterations)); 1 iteration when min_inliers == n (:130-131).  Host only, no context. */
+int32_t asd_sim3_ransac_max_iterations(int32_t n, double probability, int32_t min_inliers, int32_t max_iterations);
+/* Test aid: one iteration of the context's last asd_sim3_ransac: the three sampled correspondences (:163-177), mnInliersi (:346-363),
+ * mT12i / mT21i / ms12i as f32 (:308-336) and the f64 unit quaternion (w x y z) the rotation was made from.  Copied back with the
+ * block the call reads anyway.  ASD_ERR_INVALID for a (problem, hypothesis) the last call did not run. */
+typedef struct asd_sim3_ransac_debug {
+  int32_t idx[3];
+  int32_t count;
+  float T12[16], T21[16], s;
+  double q[4];
+} asd_sim3_ransac_debug;
+int32_t asd_debug_sim3_ransac(const asd_ctx* ctx, int32_t problem, int32_t hypothesis, asd_sim3_ransac_debug* out);
 /* ---- keyframe database and BoW score ------------------------------------------------------
  * TemplatedVocabulary::score (TemplatedVocabulary.h:1264-1269) -> L1Scoring / L2Scoring / DotProductScoring::score
  * (src/dbow2/DBoW2/ScoringObject.cpp:23-68, :73-120, :271-311) of two BowVectors given as (word id strictly ascending, value).  Host
