@@ -1,6 +1,7 @@
 """Relocalisation / loop-closing variants of the projection searches:
 SearchByProjection(Frame, KeyFrame, set, th, ORBdist), SearchByProjection(KeyFrame, Scw, ...), Fuse(KeyFrame, Scw, ...),
-SearchBySim3 -- HIP vs the CPU restatement, bit-exact ids and distances."""
+SearchBySim3 -- HIP vs the CPU restatement, bit-exact ids and distances.
+Every exit, bound, threshold and claim chain of the four, against a restatement written from the source: tests/test_loop_search_exits.py."""
 import numpy as np
 import pytest
 
