@@ -311,7 +311,8 @@ __device__ __forceinline__ void resolve2_body(A& a) {
         if (k >= ka) break;
         const int q = qid[k];
         int pk = p[k];
-        if (pk >= 0 && (!(best[k] <= TH_HIGH) || (lvl[k] == lvl2[k] && best[k] > a.nn_ratio * best2[k]))) pk = -1;
+        // (`else if(dist<bestDist2)` from 256, :77 and :102: a second entry at 256 or beyond is no second best and its level never enters the test)
+        if (pk >= 0 && (!(best[k] <= TH_HIGH) || (lvl[k] == lvl2[k] && best2[k] < 256.f && best[k] > a.nn_ratio * best2[k]))) pk = -1;
         changed |= pk != pick[k];
         pick[k] = pk;
         if (pk >= 0 && (posmask >> k & 1)) atomicMin(&lds_c[wr + pk], (tag_wr << 16) | (unsigned)q);

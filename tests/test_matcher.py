@@ -3,6 +3,8 @@ bit-exact (indices, match ids, distances) on the GPU."""
 import numpy as np
 import pytest
 
+from tests.loop_ref import three_maxima
+
 BOUNDS = (0.0, 1241.0, 0.0, 376.0)
 SCALES = np.float32(1.2) ** np.arange(8)
 
@@ -185,14 +187,7 @@ def _m1_python(oracle, cur, last_kps, cur_kps, has, Xw, mp_desc, dc, T, K, th, c
                     b = 0
                 hist[b].append(bj)
     if check_ori:
-        cnt = [len(h) for h in hist]
-        order = sorted(range(30), key=lambda b: -cnt[b])
-        m1, m2, m3 = cnt[order[0]], cnt[order[1]], cnt[order[2]]
-        keep = {order[0]}
-        if m2 >= 0.1 * m1:
-            keep.add(order[1])
-            if m3 >= 0.1 * m1:
-                keep.add(order[2])
+        keep = three_maxima([len(h) for h in hist])
         for b in range(30):
             if b not in keep:
                 for j in hist[b]:
@@ -204,8 +199,7 @@ def _m1_python(oracle, cur, last_kps, cur_kps, has, Xw, mp_desc, dc, T, K, th, c
 @pytest.mark.parametrize("ori", [False, True])
 def test_oracle_m1_overwrites_map_points_without_observations(oracle, synth, ori):
     """ORBmatcher.cc:1392-1395: a keypoint holding a map point with Observations() == 0 is not skipped; the later map
-    point overwrites it and both writes count.  The oracle against the loop written out in Python (ties in the top-3
-    histogram bins would be order dependent: the seed has none)."""
+    point overwrites it and both writes count.  The oracle against the loop written out in Python."""
     n = 160
     kl, dl, kc, dc, Xw, has, mp_desc, T, K, obs = _contested_m1_case(synth, n, 300)
     cur, last = oracle.frame(kc, dc, BOUNDS), oracle.frame(kl, dl, BOUNDS)
