@@ -96,6 +96,19 @@ class asd_sim3_ransac_debug(C.Structure):
                 ("q", C.c_double * 4)]
 
 
+class asd_pnp_ransac_problem(C.Structure):
+    _fields_ = [("n", C.c_int32), ("P3Dw", C.c_void_p), ("P2D", C.c_void_p), ("max_err", C.c_void_p), ("K", C.c_float * 4),
+                ("min_inliers", C.c_int32), ("n_iter", C.c_int32), ("draws", C.c_void_p), ("best_inliers", C.c_int32),
+                ("best_updated", C.c_int32), ("best_Tcw", C.c_float * 16), ("best_mask", C.c_void_p), ("found", C.c_int32),
+                ("iterations_done", C.c_int32), ("n_inliers", C.c_int32), ("Tcw", C.c_float * 16), ("inliers", C.c_void_p)]
+
+
+class asd_pnp_ransac_debug(C.Structure):
+    _fields_ = [("idx", C.c_int32 * 4), ("count", C.c_int32), ("n_refines", C.c_int32), ("N", C.c_int32), ("hypothesis", C.c_int32),
+                ("R", C.c_double * 9), ("t", C.c_double * 3), ("cws", C.c_double * 12), ("v", C.c_double * 48), ("eig", C.c_double * 4),
+                ("rep_errors", C.c_double * 3), ("betas", C.c_double * 4)]
+
+
 def _p(a):
     return None if a is None else a.ctypes.data_as(C.c_void_p)
 
@@ -143,6 +156,18 @@ def sim3_ransac_max_iterations(n, probability, min_inliers, max_iterations):
     lib = load_library()
     lib.asd_sim3_ransac_max_iterations.restype = C.c_int32
     return int(lib.asd_sim3_ransac_max_iterations(C.c_int32(n), C.c_double(probability), C.c_int32(min_inliers), C.c_int32(max_iterations)))
+
+
+def pnp_ransac_parameters(n, probability=0.99, min_inliers=8, max_iterations=300, min_set=4, epsilon=0.4):
+    """asd_pnp_ransac_parameters: PnPsolver::SetRansacParameters (PnPsolver.cc:121-152; host only, no context) ->
+    (mRansacMinInliers, mRansacMaxIts)"""
+    lib = load_library()
+    a, b = C.c_int32(0), C.c_int32(0)
+    rc = lib.asd_pnp_ransac_parameters(C.c_int32(n), C.c_double(probability), C.c_int32(min_inliers), C.c_int32(max_iterations),
+                                       C.c_int32(min_set), C.c_float(epsilon), C.byref(a), C.byref(b))
+    if rc != 0:
+        raise AsdError(rc, "asd_pnp_ransac_parameters: invalid arguments")
+    return int(a.value), int(b.value)
 
 
 class AsdHip:
@@ -954,6 +979,53 @@ class AsdHip:
             raise AsdError(rc, f"asd_debug_sim3_ransac: the last call ran no hypothesis {hypothesis} of problem {problem}")
         return dict(idx=[int(i) for i in d.idx], count=int(d.count), T12=np.array(d.T12, np.float32).reshape(4, 4),
                     T21=np.array(d.T21, np.float32).reshape(4, 4), s=np.float32(d.s), q=np.array(d.q, np.float64))
+
+    def pnp_ransac(self, problems, null=None):
+        """asd_pnp_ransac: PnPsolver::iterate (PnPsolver.cc:165-258) for a batch of solvers.  problems = dicts with n, P3Dw, P2D, max_err,
+        K, min_inliers, n_iter, draws [n_iter][4], best_inliers (further keys are ignored) -> one dict per problem: best_inliers,
+        best_updated, best_Tcw, best_mask (as they went in -- NaN / 0xff here -- unless best_updated), found, iterations_done, n_inliers,
+        Tcw (NaN unless found), inliers [n] uint8 (0xff-filled going in).  null = (problem, field): that pointer is passed as NULL."""
+        arr = (asd_pnp_ransac_problem * max(len(problems), 1))()
+        keep = []
+        nan = float("nan")
+        for j, q in enumerate(problems):
+            n = int(q["n"])
+            a = [_c(q["P3Dw"], np.float32), _c(q["P2D"], np.float32), _c(q["max_err"], np.float32), _c(q["draws"], np.int32),
+                 np.full(max(n, 1), 0xff, np.uint8), np.full(max(n, 1), 0xff, np.uint8)]
+            keep.append(a)
+            P = arr[j]
+            P.n = n
+            P.P3Dw, P.P2D, P.max_err, P.draws, P.best_mask, P.inliers = (x.ctypes.data for x in a)
+            if null is not None and null[0] == j:
+                setattr(P, null[1], None)
+            P.K = (C.c_float * 4)(*[float(k) for k in q["K"]])
+            P.min_inliers, P.n_iter, P.best_inliers = int(q["min_inliers"]), int(q["n_iter"]), int(q["best_inliers"])
+            P.best_updated, P.found, P.iterations_done, P.n_inliers = -1, -1, -1, -1
+            P.best_Tcw = (C.c_float * 16)(*[nan] * 16)
+            P.Tcw = (C.c_float * 16)(*[nan] * 16)
+        self._chk(self.lib.asd_pnp_ransac(self.ctx, len(problems), arr))
+        out = []
+        for j, q in enumerate(problems):
+            P = arr[j]
+            n = int(q["n"])
+            out.append(dict(best_inliers=int(P.best_inliers), best_updated=int(P.best_updated),
+                            best_Tcw=np.array(P.best_Tcw, np.float32).reshape(4, 4), best_mask=keep[j][4][:n].copy(), found=int(P.found),
+                            iterations_done=int(P.iterations_done), n_inliers=int(P.n_inliers), Tcw=np.array(P.Tcw, np.float32).reshape(4, 4),
+                            inliers=keep[j][5][:n].copy()))
+        return out
+
+    def debug_pnp_ransac(self, problem, which):
+        """one compute_pose of the last pnp_ransac (which >= 0: that iteration; -1 - r: the r-th Refine): dict(idx [4], count, n_refines, N,
+        hypothesis, R (3x3), t, cws (4x3), v (4x12), eig [4], rep_errors [3], betas [4], all f64) -- asd_debug_pnp_ransac"""
+        d = asd_pnp_ransac_debug()
+        self.lib.asd_debug_pnp_ransac.restype = C.c_int32
+        rc = self.lib.asd_debug_pnp_ransac(self.ctx, int(problem), int(which), C.byref(d))
+        if rc != 0:
+            raise AsdError(rc, f"asd_debug_pnp_ransac: the last call ran no compute_pose {which} of problem {problem}")
+        f = lambda a, *shape: np.array(a, np.float64).reshape(*shape)
+        return dict(idx=[int(i) for i in d.idx], count=int(d.count), n_refines=int(d.n_refines), N=int(d.N), hypothesis=int(d.hypothesis),
+                    R=f(d.R, 3, 3), t=f(d.t, 3), cws=f(d.cws, 4, 3), v=f(d.v, 4, 12), eig=f(d.eig, 4), rep_errors=f(d.rep_errors, 3),
+                    betas=f(d.betas, 4))
 
     def _ba_pack(self, prob, its_first, its_second):
         poses = _c(prob["poses"], np.float64).copy()

@@ -158,6 +158,7 @@ int asd_ctx_destroy(asd_ctx* ctx) {
   bow_free(ctx);
   sim3_free(ctx);
   sim3_ransac_free(ctx);
+  pnp_ransac_free(ctx);
   kfdb_free(ctx);
   ctx->scratch.release();
   ctx->stereo_scratch.release();
@@ -258,6 +259,7 @@ int asd_last_stage_ms(const asd_ctx* ctx, const char* stage, float* ms) {
   else if (!strcmp(stage, "ba")) *ms = ctx->ms_ba;
   else if (!strcmp(stage, "sim3")) *ms = ctx->ms_sim3;
   else if (!strcmp(stage, "sim3_ransac")) *ms = ctx->ms_sim3_ransac;
+  else if (!strcmp(stage, "pnp_ransac")) *ms = ctx->ms_pnp_ransac;
   else if (!strcmp(stage, "kfdb")) *ms = ctx->ms_kfdb;
   else return ASD_ERR_INVALID;
   return ASD_OK;
@@ -373,6 +375,26 @@ int32_t asd_sim3_ransac_max_iterations(int32_t n, double probability, int32_t mi
     nIterations = (v > -2147483649.0 && v < 2147483648.0) ? (int)v : INT32_MIN;       // what cvttsd2si gives the reference's implicit conversion
   }
   return std::max(1, std::min(nIterations, max_iterations));                          // :135
+}
+
+// PnPsolver::SetRansacParameters (PnPsolver.cc:121-152), literally
+int asd_pnp_ransac_parameters(int32_t n, double probability, int32_t min_inliers, int32_t max_iterations, int32_t min_set, float epsilon,
+                              int32_t* min_inliers_out, int32_t* max_its_out) {
+  if (!min_inliers_out || !max_its_out) return ASD_ERR_INVALID;
+  const float prod = (float)n * epsilon;                                                // :134: int * float is a float product
+  int nMinInliers = (prod > -2147483904.0f && prod < 2147483648.0f) ? (int)prod : INT32_MIN;   // cvttss2si
+  if (nMinInliers < min_inliers) nMinInliers = min_inliers;                            // :135-136
+  if (nMinInliers < min_set) nMinInliers = min_set;                                    // :137-138
+  if (epsilon < (float)nMinInliers / n) epsilon = (float)nMinInliers / n;              // :141-142
+  int nIterations;
+  if (nMinInliers == n) nIterations = 1;                                               // :147-148
+  else {
+    const double v = std::ceil(std::log(1 - probability) / std::log(1 - std::pow((double)epsilon, 3)));   // :150
+    nIterations = (v > -2147483649.0 && v < 2147483648.0) ? (int)v : INT32_MIN;        // cvttsd2si, as asd_sim3_ransac_max_iterations
+  }
+  *min_inliers_out = nMinInliers;
+  *max_its_out = std::max(1, std::min(nIterations, max_iterations));                   // :152
+  return ASD_OK;
 }
 
 // Converter::toSE3Quat (Converter.cc:37-47) + SE3Quat(R,t) ctor (se3quat.h:58-60): Eigen

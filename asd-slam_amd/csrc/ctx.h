@@ -339,6 +339,9 @@ struct asd_ctx {
   // ---- Sim3Solver's RANSAC: the last call's hypothesis records for asd_debug_sim3_ransac (state private to sim3_ransac.hip)
   void* sim3_ransac = nullptr;
 
+  // ---- PnPsolver's RANSAC: the last call's hypothesis and Refine records for asd_debug_pnp_ransac (state private to pnp_ransac.hip)
+  void* pnp_ransac = nullptr;
+
   // ---- keyframe database (state private to kfdb.hip)
   void* kfdb = nullptr;
 
@@ -356,7 +359,7 @@ struct asd_ctx {
 
   // ---- timing
   hipEvent_t ev0 = nullptr, ev1 = nullptr, ev2 = nullptr;
-  float ms_asdnet = 0, ms_extract = 0, ms_match = 0, ms_ba = 0, ms_sim3 = 0, ms_kfdb = 0, ms_sim3_ransac = 0;
+  float ms_asdnet = 0, ms_extract = 0, ms_match = 0, ms_ba = 0, ms_sim3 = 0, ms_kfdb = 0, ms_sim3_ransac = 0, ms_pnp_ransac = 0;
 
   // the extraction worker thread reports errors too: the message is written under a lock, and asd_last_error hands
   // out a copy that stays put until the next call of asd_last_error on this context
@@ -404,6 +407,7 @@ void mapping_free(asd_ctx* ctx);
 void bow_free(asd_ctx* ctx);
 void sim3_free(asd_ctx* ctx);
 void sim3_ransac_free(asd_ctx* ctx);
+void pnp_ransac_free(asd_ctx* ctx);
 void kfdb_free(asd_ctx* ctx);
 const char* kfdb_host_error();   // the message of this thread's last asd_bow_score (a call without a context)
 // The claim replay that makes d_src, to run in FRONT of the solver inside its workgroup (k_resolve_pose, ba.hip) instead of as a kernel of

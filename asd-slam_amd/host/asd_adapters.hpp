@@ -381,7 +381,12 @@ struct Optimizer {
 // The reference runs matcher.SearchByProjection and Optimizer::PoseOptimization back to back in TrackWithMotionModel (:664-723)
 // and in TrackLocalMap (:725-736 with SearchLocalPoints :803-851); asd_track_motion_model / asd_track_local_points do the pair
 // behind one synchronisation and return the same bits as the two calls (tests/test_track_chain.py).
+class PnPsolver;
 struct Tracking {
+  // One pass of the loop of Tracking::Relocalization (:1156-1249) over the live PnPsolvers; defined behind asd::PnPsolver below.
+  template <class TailFn>
+  static int RelocalizationRound(Context& c, std::vector<PnPsolver*>& vpPnPsolvers, std::vector<bool>& vbDiscarded, int nIterations, TailFn tail);
+
   // bool Tracking::TrackWithMotionModel(): Cur.mTcw holds the motion-model prediction on entry (mVelocity * mLastFrame.mTcw, :677).
   // `points` = LastFrame's map points indexed like LastFrame.mvKeysUn (null where there is none).  Writes Cur.mvpMapPoints,
   // Cur.mvbOutlier and Cur.mTcw, discards outliers like :704-719 and returns nmatchesMap >= 10 (:723); *nmatches_out gets the
@@ -714,6 +719,255 @@ class Sim3Solver {
   std::vector<int32_t> randi_;
   std::vector<uint8_t> inliers_;
 };
+
+// ---- PnPsolver (PnPsolver.h; src/vslam/src/PnPsolver.cc) -----------------------------------------------------------------------
+// The EPnP RANSAC iterations run on the device (asd_pnp_ransac); this class keeps what the reference's object keeps between iterate()
+// calls: the gathered correspondences, mnIterations, mnBestInliers, mvbBestInliers and mBestTcw.  iterate() = Begin + asd_pnp_ransac +
+// End; the two halves are public so that several solvers can share one call (Tracking::RelocalizationRound below).  Four random numbers
+// per iteration come from the DrawStream; the unused ones go back in front of the generator.
+class PnPsolver {
+ public:
+  // PnPsolver(const Frame& F, const vector<MapPoint*>& vpMapPointMatches)  (:67-110).  vpMapPointMatches[i] = the map point id matched to
+  // F's keypoint i (-1 = NULL; a bad map point is the caller's to leave out, :85), vLevelSigma2 = F.mvLevelSigma2.
+  PnPsolver(Context& c, const FrameView& F, const std::vector<int32_t>& vpMapPointMatches, const std::vector<MapPointView>& points, const Camera& K,
+            const std::vector<float>& vLevelSigma2, DrawStream& draws)
+      : ctx_(c.get()), draws_(&draws), mK(K) {
+    mNF = (int)vpMapPointMatches.size();
+    for (int i = 0; i < mNF; ++i) {                                                   // :79-101
+      if (vpMapPointMatches[i] < 0) continue;
+      const asd_keypoint& kp = F.mvKeysUn[i];
+      mvP2D.push_back(kp.x); mvP2D.push_back(kp.y);                                   // :89
+      mvSigma2.push_back(vLevelSigma2[kp.octave]);                                    // :90
+      for (int k = 0; k < 3; ++k) mvP3Dw.push_back(points[vpMapPointMatches[i]].Xw[k]);   // :92-93
+      mvKeyPointIndices.push_back((size_t)i);                                         // :95
+    }
+    SetRansacParameters();                                                            // :109
+  }
+  // the gathered vectors directly (tests, or a caller that gathers itself).  ctx may be null for a solver that is only stepped through
+  // Begin / End
+  PnPsolver(asd_ctx* ctx, int NF, std::vector<size_t> vKeyPointIndices, std::vector<float> vP3Dw, std::vector<float> vP2D, std::vector<float> vSigma2,
+            const Camera& K, DrawStream& draws)
+      : ctx_(ctx), draws_(&draws), mK(K), mNF(NF), mvKeyPointIndices(std::move(vKeyPointIndices)), mvP3Dw(std::move(vP3Dw)), mvP2D(std::move(vP2D)),
+        mvSigma2(std::move(vSigma2)) {
+    SetRansacParameters();
+  }
+
+  // void SetRansacParameters(double probability = 0.99, int minInliers = 8, int maxIterations = 300, int minSet = 4, float epsilon = 0.4,
+  //                          float th2 = 5.991)  (:121-157).  minSet must be 4 (ASD_PNP_MIN_SET): the only value the reference passes
+  void SetRansacParameters(double probability = 0.99, int minInliers = 8, int maxIterations = 300, int minSet = 4, float epsilon = 0.4f,
+                           float th2 = 5.991f) {
+    N = (int)mvKeyPointIndices.size();
+    int32_t mi = minInliers, its = 1;
+    asd_pnp_ransac_parameters(N, probability, minInliers, maxIterations, minSet, epsilon, &mi, &its);
+    mRansacMinInliers = mi;
+    mRansacMaxIts = its;
+    mvMaxError.resize(mvSigma2.size());
+    for (size_t i = 0; i < mvSigma2.size(); ++i) mvMaxError[i] = mvSigma2[i] * th2;   // :156, an f32 product
+  }
+
+  // cv::Mat iterate(int nIterations, bool& bNoMore, vector<bool>& vbInliers, int& nInliers)  (:165-258).  Returns true where the reference
+  // returns a non-empty matrix, Tcw (row-major 4x4) = mRefinedTcw (:235) or, at the last iteration, mBestTcw (:253).  A failed device call
+  // counts as bNoMore.
+  bool iterate(int nIterations, bool& bNoMore, std::vector<bool>& vbInliers, int& nInliers, float* Tcw) {
+    asd_pnp_ransac_problem p;
+    if (!Begin(nIterations, p)) { bNoMore = true; vbInliers.clear(); nInliers = 0; return false; }
+    if (asd_pnp_ransac(ctx_, 1, &p) != ASD_OK) { Cancel(); bNoMore = true; vbInliers.clear(); nInliers = 0; return false; }
+    return End(p, bNoMore, vbInliers, nInliers, Tcw);
+  }
+  // cv::Mat find(vector<bool>& vbInliers, int& nInliers)  (:159-163)
+  bool find(std::vector<bool>& vbInliers, int& nInliers, float* Tcw) {
+    bool bFlag;
+    return iterate(mRansacMaxIts, bFlag, vbInliers, nInliers, Tcw);
+  }
+  int GetIterations() const { return mnIterations; }
+  int GetBestInliers() const { return mnBestInliers; }
+  int GetMaxIterations() const { return mRansacMaxIts; }
+  int GetMinInliers() const { return mRansacMinInliers; }
+  int GetN() const { return N; }
+  const float* GetBestTcw() const { return mBestTcw; }
+  const std::vector<size_t>& GetKeyPointIndices() const { return mvKeyPointIndices; }
+
+  // The first half of iterate(): fills `p` for asd_pnp_ransac and draws the 4 random numbers of every iteration the call may run from the
+  // stream (:193).  The loop condition of :182 joins its two limits with OR -- mnIterations < mRansacMaxIts || nCurrentIterations <
+  // nIterations -- so a call that returns no refined model runs max(nIterations, mRansacMaxIts - mnIterations) iterations.  false:
+  // N < mRansacMinInliers (:173-177, bNoMore), nothing was drawn.  p points into this object: it must not be moved or destroyed, nor Begin
+  // called again, before End or Cancel.
+  bool Begin(int nIterations, asd_pnp_ransac_problem& p) {
+    p = asd_pnp_ransac_problem{};
+    if (N < mRansacMinInliers) return false;
+    const int n_iter = std::max(0, std::max(nIterations, mRansacMaxIts - mnIterations));
+    raw_.resize((size_t)4 * n_iter);
+    randi_.resize((size_t)4 * n_iter);
+    for (int k = 0; k < n_iter; ++k)
+      for (int i = 0; i < 4; ++i) {
+        raw_[4 * k + i] = draws_->Next();
+        randi_[4 * k + i] = draws_->RandomInt(raw_[4 * k + i], 0, N - 1 - i);   // RandomInt(0, vAvailableIndices.size() - 1)
+      }
+    inliers_.assign((size_t)N + 1, 0);
+    best_mask_.assign((size_t)N + 1, 0);
+    p.n = N;
+    p.P3Dw = mvP3Dw.data(); p.P2D = mvP2D.data(); p.max_err = mvMaxError.data();
+    p.K[0] = mK.fx; p.K[1] = mK.fy; p.K[2] = mK.cx; p.K[3] = mK.cy;
+    p.min_inliers = mRansacMinInliers; p.n_iter = n_iter;
+    p.draws = randi_.data();
+    p.best_inliers = mnBestInliers;
+    p.best_mask = best_mask_.data();
+    p.inliers = inliers_.data();
+    return true;
+  }
+  // The second half: what the iterations changed in the object, the unused random numbers back to the stream, iterate()'s outputs.
+  // `problem` = the position of p in the asd_pnp_ransac call that ran it.
+  // A solver that is iterated again after it returned its refined model (Relocalization does that when the tail turns the pose down and
+  // bNoMore is not set): the reference calls Refine() at the next iteration that passes :209; where that iteration does not beat the best
+  // model, Refine() runs on the same mvbBestInliers, succeeds again and the same refined model comes back at that iteration.  The device's
+  // walk knows no Refine of an earlier call, so this case is settled here from the iteration counts of the call (asd_debug_pnp_ransac).
+  bool End(const asd_pnp_ransac_problem& p, bool& bNoMore, std::vector<bool>& vbInliers, int& nInliers, float* Tcw, int problem = 0) {
+    bNoMore = false;
+    vbInliers.clear();
+    nInliers = 0;
+    int done = p.iterations_done;
+    bool again = false;
+    if (refined_ok_ && ctx_)
+      for (int k = 0; k < p.iterations_done; ++k) {
+        asd_pnp_ransac_debug d;
+        if (asd_debug_pnp_ransac(ctx_, problem, k, &d) != ASD_OK) break;
+        if (d.count < mRansacMinInliers) continue;                                    // :209
+        if (d.count <= mnBestInliers) { again = true; done = k + 1; }                 // :212 not taken, :226 on the same set
+        break;
+      }
+    const size_t used = (size_t)4 * done;
+    draws_->GiveBack(raw_.data() + used, raw_.size() - used);
+    last_raw_.assign(raw_.begin(), raw_.begin() + used);
+    raw_.clear();
+    mnIterations += done;
+    if (again) {
+      nInliers = mnRefinedInliers;
+      vbInliers.assign(mNF, false);
+      for (int i = 0; i < N; ++i)
+        if (mvbRefinedInliers[i]) vbInliers[mvKeyPointIndices[i]] = true;
+      for (int i = 0; i < 16; ++i) Tcw[i] = mRefinedTcw[i];
+      return true;
+    }
+    mnBestInliers = p.best_inliers;
+    if (p.best_updated) {                                                             // :214-223; otherwise the previous mask and matrix stay
+      mvbBestInliers.assign(best_mask_.begin(), best_mask_.begin() + N);
+      for (int i = 0; i < 16; ++i) mBestTcw[i] = p.best_Tcw[i];
+      refined_ok_ = false;                                                            // its Refine failed, unless found says otherwise
+    }
+    if (p.found) {                                                                    // :226-236
+      refined_ok_ = true;
+      mnRefinedInliers = p.n_inliers;
+      mvbRefinedInliers.assign(inliers_.begin(), inliers_.begin() + N);
+      for (int i = 0; i < 16; ++i) mRefinedTcw[i] = p.Tcw[i];
+      nInliers = p.n_inliers;
+      vbInliers.assign(mNF, false);
+      for (int i = 0; i < N; ++i)
+        if (inliers_[i]) vbInliers[mvKeyPointIndices[i]] = true;
+      for (int i = 0; i < 16; ++i) Tcw[i] = p.Tcw[i];
+      return true;
+    }
+    if (mnIterations >= mRansacMaxIts) {                                              // :241-255 (always true behind the loop of :182)
+      bNoMore = true;
+      if (mnBestInliers >= mRansacMinInliers && (int)mvbBestInliers.size() == N) {
+        nInliers = mnBestInliers;
+        vbInliers.assign(mNF, false);
+        for (int i = 0; i < N; ++i)
+          if (mvbBestInliers[i]) vbInliers[mvKeyPointIndices[i]] = true;
+        for (int i = 0; i < 16; ++i) Tcw[i] = mBestTcw[i];
+        return true;
+      }
+    }
+    return false;
+  }
+  // whether End(p, ..., problem) will consume fewer iterations than p supplied (the solvers behind it in a shared call then drew numbers
+  // that are not theirs)
+  bool ReturnsEarly(const asd_pnp_ransac_problem& p, int problem = 0) const {
+    if (p.found && p.iterations_done < p.n_iter) return true;
+    if (refined_ok_ && ctx_)
+      for (int k = 0; k < p.iterations_done; ++k) {
+        asd_pnp_ransac_debug d;
+        if (asd_debug_pnp_ransac(ctx_, problem, k, &d) != ASD_OK) break;
+        if (d.count < mRansacMinInliers) continue;
+        return d.count <= mnBestInliers && k + 1 < p.n_iter;
+      }
+    return false;
+  }
+  // Begin undone: every random number back to the stream, the object as it was (the reference would not have called iterate())
+  void Cancel() {
+    draws_->GiveBack(raw_.data(), raw_.size());
+    raw_.clear();
+  }
+  const std::vector<int>& LastRawConsumed() const { return last_raw_; }   // the raw values the last End kept (test aid)
+
+ private:
+  asd_ctx* ctx_;
+  DrawStream* draws_;
+  Camera mK;
+  int mNF = 0, N = 0;
+  std::vector<size_t> mvKeyPointIndices;
+  std::vector<float> mvP3Dw, mvP2D, mvSigma2, mvMaxError;
+  int mRansacMinInliers = 8, mRansacMaxIts = 300, mnIterations = 0, mnBestInliers = 0;
+  std::vector<uint8_t> mvbBestInliers, mvbRefinedInliers;
+  float mBestTcw[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1}, mRefinedTcw[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};
+  int mnRefinedInliers = 0;
+  bool refined_ok_ = false;   // Refine() on the present mvbBestInliers succeeded (an earlier call returned its model)
+  std::vector<int> raw_, last_raw_;
+  std::vector<int32_t> randi_;
+  std::vector<uint8_t> inliers_, best_mask_;
+};
+
+// One pass of the loop of Tracking::Relocalization (Tracking.cc:1156-1249): every live solver fills its problem in candidate order, ONE
+// asd_pnp_ransac runs them all, and the results are applied in candidate order: iterate()'s outputs (:1169), bNoMore -> discarded
+// (:1172-1176), and where a pose came back the tail :1176-1247 -- tail(i, Tcw, vbInliers, nInliers) -> bMatch, the caller's
+// PoseOptimization / SearchByProjection rounds.  At the first candidate whose tail reports bMatch the solvers behind it are cancelled,
+// last first, so that the stream hands their random numbers out again in the order they were drawn; its position is returned (-1: no
+// match in this pass).  The reference's pass is sequential: a solver that returned its refined model before its last supplied iteration
+// has numbers left that the solver behind it would have consumed, so behind such a candidate whose tail says no the pass goes on with a
+// call of its own for the rest.
+template <class TailFn>
+int Tracking::RelocalizationRound(Context& c, std::vector<PnPsolver*>& vpPnPsolvers, std::vector<bool>& vbDiscarded, int nIterations, TailFn tail) {
+  const int nKFs = (int)vpPnPsolvers.size();
+  for (int from = 0; from < nKFs;) {
+    std::vector<int> who;
+    std::vector<asd_pnp_ransac_problem> probs;
+    for (int i = from; i < nKFs; ++i) {
+      if (vbDiscarded[i]) continue;
+      asd_pnp_ransac_problem p;
+      if (!vpPnPsolvers[i]->Begin(nIterations, p)) { vbDiscarded[i] = true; continue; }   // N < mRansacMinInliers: bNoMore at once
+      who.push_back(i);
+      probs.push_back(p);
+    }
+    if (who.empty()) return -1;
+    if (asd_pnp_ransac(c.get(), (int32_t)probs.size(), probs.data()) != ASD_OK) {
+      for (size_t k = who.size(); k-- > 0;) { vpPnPsolvers[who[k]]->Cancel(); vbDiscarded[who[k]] = true; }
+      return -1;
+    }
+    // results in candidate order.  A solver that returned before its last supplied iteration has numbers left that the solver behind it
+    // would have consumed: everything behind it is cancelled (last first), then its own End hands its unused numbers back in front
+    size_t stop = who.size();
+    for (size_t k = 0; k < who.size(); ++k) {
+      if (vpPnPsolvers[who[k]]->ReturnsEarly(probs[k], (int)k)) {
+        stop = k;
+        for (size_t b = who.size(); b-- > k + 1;) vpPnPsolvers[who[b]]->Cancel();
+      }
+      bool bNoMore = false;
+      std::vector<bool> vbInliers;
+      int nInliers = 0;
+      float Tcw[16];
+      const bool got = vpPnPsolvers[who[k]]->End(probs[k], bNoMore, vbInliers, nInliers, Tcw, (int)k);
+      if (bNoMore) vbDiscarded[who[k]] = true;
+      if (got && tail(who[k], (const float*)Tcw, vbInliers, nInliers)) {
+        if (stop == who.size())
+          for (size_t b = who.size(); b-- > k + 1;) vpPnPsolvers[who[b]]->Cancel();
+        return who[k];
+      }
+      if (stop < who.size()) break;
+    }
+    if (stop >= who.size()) return -1;
+    from = who[stop] + 1;
+  }
+  return -1;
+}
 
 // LoopClosing::ComputeSim3 (LoopClosing.cc:269-423): every search, the RANSAC and the refinement run behind the C ABI.  Two forms:
 // ComputeSim3 over the candidate list with asd::Sim3Solver (:291-377), and ComputeSim3Candidate, the numeric body for ONE candidate with

@@ -168,6 +168,29 @@ int main(int argc, char** argv) {
         printf("loop-solver: candidate=%d bow=%d sim3=%d inliers=%d total=%d match=%d scale=%.6f\n", ls.iMatched, ls.nBoW, ls.nSim3, ls.nInliers,
                ls.nTotalMatches, (int)ls.bMatch, ls.g2oScm[7]);
       }
+      // Tracking::Relocalization's solver step (Tracking.cc:1128-1174) with frame 0 as the one candidate keyframe: the BoW matches above,
+      // asd::PnPsolver's EPnP RANSAC on the device, passes of 5 iterations until a pose comes back; the tail (:1176-1247) is left to a
+      // callback that accepts the first pose.  Informative only, the exit status does not depend on it
+      {
+        std::srand(1);
+        asd::DrawStream draws;   // ::rand
+        asd::PnPsolver pnp(ctx, F[1], vpMapPointMatches, mps, K, extractor.GetScaleSigmaSquares(), draws);
+        pnp.SetRansacParameters(0.99, 10, 300, 4, 0.5f, 5.991f);                  // :1141
+        std::vector<asd::PnPsolver*> solvers = {&pnp};
+        std::vector<bool> discarded = {false};
+        int matched = -1, n_pnp = 0, passes = 0;
+        float Tpnp[16] = {};
+        while (!discarded[0] && matched < 0) {
+          ++passes;
+          matched = asd::Tracking::RelocalizationRound(ctx, solvers, discarded, 5, [&](int, const float* Tcw, const std::vector<bool>&, int nInl) {
+            n_pnp = nInl;
+            for (int i = 0; i < 16; ++i) Tpnp[i] = Tcw[i];
+            return true;
+          });
+        }
+        printf("reloc-solver: candidate=%d n=%d min=%d passes=%d iterations=%d inliers=%d t=(%.4f %.4f %.4f)\n", matched, pnp.GetN(), pnp.GetMinInliers(),
+               passes, pnp.GetIterations(), n_pnp, Tpnp[3], Tpnp[7], Tpnp[11]);
+      }
     }
     printf("kp0=%d kp1=%d matches=%d inliers=%d fused=%d bow=%d t=(%.4f %.4f %.4f)\n", F[0].N(), F[1].N(), nmatches, ninl, nfused, nbow,
            F[1].mTcw[3], F[1].mTcw[7], F[1].mTcw[11]);

@@ -672,7 +672,7 @@ int asd_pose7_to_tcw(const double* pose7, float* Tcw16);
 /* ---- instrumentation ----------------------------------------------------------------- */
 /* Device-side duration of the kernels enqueued by the most recent call of the named stage,
  * measured with hipEvents on the ctx stream.  stage: "asdnet", "extract", "match", "ba", "sim3" (asd_optimize_sim3),
- * "sim3_ransac" (both kernels of asd_sim3_ransac, its upload included),
+ * "sim3_ransac" (both kernels of asd_sim3_ransac, its upload included), "pnp_ransac" (likewise for asd_pnp_ransac),
  * "kfdb" (the scoring pass of the last asd_kfdb_score / asd_kfdb_query_*, its upload included). */
 int asd_last_stage_ms(const asd_ctx* ctx, const char* stage, float* ms);
 /* Per-kernel device time of the ASDNet forward, accumulated with hipEvents recorded on the ctx
@@ -833,6 +833,101 @@ typedef struct asd_sim3_ransac_debug {
   double q[4];
 } asd_sim3_ransac_debug;
 int32_t asd_debug_sim3_ransac(const asd_ctx* ctx, int32_t problem, int32_t hypothesis, asd_sim3_ransac_debug* out);
+/* PnPsolver (src/vslam/src/PnPsolver.cc): the EPnP RANSAC loop of PnPsolver::iterate (:165-258) for a batch of solvers, the hypotheses of
+ * every solver in parallel -- the step of Tracking::Relocalization (Tracking.cc:1156-1174) between SearchByBoW and PoseOptimization.  One
+ * problem = one PnPsolver and one iterate() call on it:
+ *  in      n                       N = mvP2D.size(), the correspondences the constructor gathered (:67-101, :129)
+ *          P3Dw[n][3]              mvP3Dw (:93), f32
+ *          P2D[n][2]               mvP2D = mvKeysUn[i].pt (:89), f32
+ *          max_err[n]              mvMaxError = mvSigma2[i] * th2, the product taken in f32 (:156)
+ *          K[4]                    fu fv uc vc (:104-107)
+ *          min_inliers             mRansacMinInliers AFTER SetRansacParameters (:139; asd_pnp_ransac_parameters)
+ *          n_iter                  the iterations this call may run.  The loop condition of :182 joins its two limits with OR, so a call that
+ *                                  does not return a refined model runs max(nIterations, mRansacMaxIts - mnIterations) iterations
+ *          draws[n_iter][4]        draws[k][i] = what RandomInt(0, n - 1 - i) returned for draw i of iteration k (:193); the swap-with-back
+ *                                  bookkeeping of vAvailableIndices (:188-201) is done by the device.  The minimal set is ASD_PNP_MIN_SET = 4,
+ *                                  the only value the reference passes (Tracking.cc:1141)
+ *  in/out  best_inliers            mnBestInliers (:212-215)
+ *  out     best_updated            1 when an iteration of this call took over the best model (:212); only then are written
+ *          best_Tcw[16]            mBestTcw (:217-223), row major
+ *          best_mask[n]            mvbBestInliers (:214), by correspondence
+ *          found                   1 when iterate() returns the refined model (:226-236)
+ *          iterations_done         k + 1 when iteration k returns, n_iter otherwise: what the caller adds to mnIterations; 4 x that many
+ *                                  draws were consumed
+ *          n_inliers               mnRefinedInliers (:228), 0 unless found
+ *          Tcw[16]                 mRefinedTcw (:294-300), written only when found
+ *          inliers[n]              mvbRefinedInliers (:229-234, by correspondence: the caller maps through mvKeyPointIndices), all 0 unless found
+ * A problem with n < min_inliers runs nothing (:173-177): found = 0, iterations_done = 0 and nothing else of it is written.
+ * The rule over the iterations is a literal sequential run of :182-257: an iteration with mnInliersi >= min_inliers (:209) that beats
+ * best_inliers (:212, strict) becomes the best model and Refine (:260-305) runs on its inlier set; Refine is a function of mvbBestInliers
+ * alone, so the calls the reference repeats on an unchanged set (:226 for an iteration that passes :209 without beating the best) are known to
+ * fail and are not run; a Refine with more than min_inliers inliers (:292, strict) ends the call.  What :241-255 does afterwards (bNoMore,
+ * returning mBestTcw) is the caller's (asd::PnPsolver, host/asd_adapters.hpp).  So is one case the rule above leaves out: a best model that
+ * comes in with best_inliers is taken to be one whose Refine failed, which holds unless the caller iterates a solver again AFTER it returned
+ * its refined model; the reference then returns the same refined model at the next iteration that passes :209 without beating the best one,
+ * and asd::PnPsolver::End restores that from the iteration counts (asd_debug_pnp_ransac).
+ * The model (compute_pose, :477-525) is EPnP in f64 from the f32 inputs widened: control points by PCA (:375-409), barycentric coordinates
+ * (:411-434), M^T M (:436-451, :492), its four smallest eigenvectors, L_6x10 / rho (:760-810), the three approximations (:667-758) each followed
+ * by five Gauss-Newton steps (:840-950), R and t by Procrustes (:569-627) with the reference's sign rule (:636-649, the first correspondence
+ * only) and determinant fix (:618-622, row 2 of R), the candidate of least reprojection error with strict < from candidate 1 (:518-520).
+ * Where the reference calls OpenCV's legacy C API the library states its own rules; they are the formula, not OpenCV's bits:
+ *  - cvSVD of the symmetric matrices (:400, :493) is a cyclic Jacobi eigen-decomposition; the eigenvalues are ordered and the vectors are
+ *    orthonormal to rounding.  With four correspondences M^T M has a four-dimensional null space and EPnP's result depends on the basis the
+ *    solver returns for it: the pose of a minimal set is not a function of the input alone, in the reference as here.
+ *  - cvInvert(CV_SVD) (:421) and cvSolve(CV_SVD) (:681, :712, :746) are the pseudo-inverse and the minimum-norm least-squares solution by a
+ *    one-sided Jacobi SVD; singular values at or below 2 * DBL_EPSILON * (sum of the singular values) count as zero.
+ *  - cvSVD of ABt (:608): the same SVD; the left vector of a zero singular value is the cross product of the other two left vectors.
+ *  - qr_solve on a zero column (:887-891) returns without writing X in the reference, and gauss_newton then adds an indeterminate x
+ *    (uninitialised on the first pass): the one place the reference's behaviour is undefined.  The library's rule is x = 0 for that step.
+ * CheckInliers (:308-339) is the reference's mixed arithmetic without fusing: Xc, Yc = the f64 expression over the f64 pose and the f32 point
+ * rounded to f32, invZc = 1 / (f64 sum) rounded to f32, ue = uc + fu * Xc * invZc in f64, distX = P2D.x - ue rounded to f32, error2 in f32,
+ * compared < with max_err.  A non-finite pose or projection is never an inlier.  best_Tcw / Tcw are the f64 R, t rounded to f32 once, last row
+ * 0 0 0 1.
+ * Limits (ASD_ERR_CAPACITY beyond them): ASD_PNP_RANSAC_MAX_N correspondences per problem, ASD_PNP_RANSAC_MAX_PROBLEMS problems per call,
+ * ASD_PNP_RANSAC_MAX_HYPOTHESES iterations per call summed over its problems.  ASD_ERR_INVALID: a draw outside [0, n - 1 - i], n < 4 in a
+ * problem that has iterations to run, a null array, negative n / n_iter; asd_last_error names the problem.  Two kernel launches and one
+ * synchronisation per call, no atomics, reductions of one fixed shape: a call is one bit pattern.  Legal wherever asd_sim3_ransac is. */
+#define ASD_PNP_MIN_SET 4
+#define ASD_PNP_RANSAC_MAX_N 8192
+#define ASD_PNP_RANSAC_MAX_PROBLEMS 64
+#define ASD_PNP_RANSAC_MAX_HYPOTHESES 4096
+typedef struct asd_pnp_ransac_problem {
+  int32_t n;
+  const float* P3Dw;
+  const float* P2D;
+  const float* max_err;
+  float K[4];
+  int32_t min_inliers;
+  int32_t n_iter;
+  const int32_t* draws;
+  int32_t best_inliers;
+  int32_t best_updated;
+  float best_Tcw[16];
+  uint8_t* best_mask;
+  int32_t found, iterations_done, n_inliers;
+  float Tcw[16];
+  uint8_t* inliers;
+} asd_pnp_ransac_problem;
+int asd_pnp_ransac(asd_ctx* ctx, int32_t n_problems, asd_pnp_ransac_problem* problems);
+/* PnPsolver::SetRansacParameters (:121-152) in the reference's types: int nMinInliers = N * (float)epsilon, raised to min_inliers and to
+ * min_set (:134-139) -> *min_inliers_out; epsilon = max(epsilon, (float)nMinInliers / N) as a float (:141-142); 1 iteration when
+ * nMinInliers == N, else ceil(log(1 - probability) / log(1 - pow(epsilon, 3))) in double (:147-150); *max_its_out = max(1, min(.,
+ * max_iterations)) (:152).  A value that does not fit an int converts as x86-64 does, to INT_MIN (as asd_sim3_ransac_max_iterations).
+ * Host only, no context. */
+int asd_pnp_ransac_parameters(int32_t n, double probability, int32_t min_inliers, int32_t max_iterations, int32_t min_set, float epsilon,
+                              int32_t* min_inliers_out, int32_t* max_its_out);
+/* Test aid: one compute_pose of the context's last asd_pnp_ransac.  which >= 0: iteration `which`; which = -1 - r: the r-th Refine the walk
+ * ran (r < n_refines).  idx = the four sampled correspondences (:188-201; -1 for a Refine), hypothesis = the iteration (for a Refine: the one
+ * whose inlier set it refined), count = mnInliersi of the CheckInliers behind it, n_refines = how many Refines the problem's walk ran, then in
+ * f64: R (row major), t, the control points cws (:375-409), the four basis vectors v (ut rows 11, 10, 9, 8 of :493) with their eigenvalues
+ * (ascending), rep_errors of candidates 1-3 (:508-516), the chosen N (:518-520) and its betas after gauss_newton.  Copied back with the
+ * block the call reads anyway.  ASD_ERR_INVALID for a (problem, which) the last call did not run. */
+typedef struct asd_pnp_ransac_debug {
+  int32_t idx[4];
+  int32_t count, n_refines, N, hypothesis;
+  double R[9], t[3], cws[12], v[48], eig[4], rep_errors[3], betas[4];
+} asd_pnp_ransac_debug;
+int32_t asd_debug_pnp_ransac(const asd_ctx* ctx, int32_t problem, int32_t which, asd_pnp_ransac_debug* out);
 /* ---- keyframe database and BoW score ------------------------------------------------------
  * TemplatedVocabulary::score (TemplatedVocabulary.h:1264-1269) -> L1Scoring / L2Scoring / DotProductScoring::score
  * (src/dbow2/DBoW2/ScoringObject.cpp:23-68, :73-120, :271-311) of two BowVectors given as (word id strictly ascending, value).  Host
