@@ -109,6 +109,22 @@ class asd_pnp_ransac_debug(C.Structure):
                 ("rep_errors", C.c_double * 3), ("betas", C.c_double * 4)]
 
 
+class asd_initializer_problem(C.Structure):
+    _fields_ = [("n1", C.c_int32), ("keys1", C.c_void_p), ("n2", C.c_int32), ("keys2", C.c_void_p), ("matches12", C.c_void_p),
+                ("K", C.c_float * 4), ("sigma", C.c_float), ("n_iter", C.c_int32), ("draws", C.c_void_p), ("min_parallax", C.c_float),
+                ("min_triangulated", C.c_int32), ("n_matches", C.c_int32), ("SH", C.c_float), ("SF", C.c_float), ("model", C.c_int32),
+                ("ok", C.c_int32), ("R21", C.c_float * 9), ("t21", C.c_float * 3), ("P3D", C.c_void_p), ("triangulated", C.c_void_p),
+                ("H21", C.c_float * 9), ("F21", C.c_float * 9), ("inliers_H", C.c_void_p), ("inliers_F", C.c_void_p)]
+
+
+class asd_initializer_debug(C.Structure):
+    _fields_ = [("idx", C.c_int32 * 8), ("nullv", C.c_double * 9), ("U", C.c_double * 9), ("w", C.c_double * 3), ("Vt", C.c_double * 9),
+                ("M1", C.c_float * 9), ("M2", C.c_float * 9), ("score", C.c_float), ("best_H", C.c_int32), ("best_F", C.c_int32),
+                ("n_inliers", C.c_int32), ("n_hyp", C.c_int32), ("winner", C.c_int32), ("second_good", C.c_int32),
+                ("R", C.c_float * 72), ("t", C.c_float * 24), ("parallax", C.c_float * 8), ("cos_sel", C.c_float * 8),
+                ("n_good", C.c_int32 * 8), ("mask", C.c_void_p), ("points", C.c_void_p), ("flags", C.c_void_p)]
+
+
 def _p(a):
     return None if a is None else a.ctypes.data_as(C.c_void_p)
 
@@ -168,6 +184,19 @@ def pnp_ransac_parameters(n, probability=0.99, min_inliers=8, max_iterations=300
     if rc != 0:
         raise AsdError(rc, "asd_pnp_ransac_parameters: invalid arguments")
     return int(a.value), int(b.value)
+
+
+def initializer_normalize(keys):
+    """asd_initializer_normalize: Initializer::Normalize (Initializer.cc:791-837; host only, no context) over ALL keys [n][2] ->
+    (vNormalizedPoints [n][2] f32, T [3][3] f32)"""
+    lib = load_library()
+    k = _c(keys, np.float32).reshape(-1, 2)
+    pts = np.empty_like(k)
+    T = np.empty(9, np.float32)
+    rc = lib.asd_initializer_normalize(C.c_int32(len(k)), _p(k), _p(pts), _p(T))
+    if rc != 0:
+        raise AsdError(rc, "asd_initializer_normalize: invalid arguments")
+    return pts, T.reshape(3, 3)
 
 
 class AsdHip:
@@ -1026,6 +1055,77 @@ class AsdHip:
         return dict(idx=[int(i) for i in d.idx], count=int(d.count), n_refines=int(d.n_refines), N=int(d.N), hypothesis=int(d.hypothesis),
                     R=f(d.R, 3, 3), t=f(d.t, 3), cws=f(d.cws, 4, 3), v=f(d.v, 4, 12), eig=f(d.eig, 4), rep_errors=f(d.rep_errors, 3),
                     betas=f(d.betas, 4))
+
+    def initialize(self, problems, null=None):
+        """asd_initialize: Initializer::Initialize (Initializer.cc:43-120) for a batch of frame pairs.  problems = dicts with keys1 [n1][2],
+        keys2 [n2][2], matches12 [n1], K, sigma, n_iter, draws [n_iter][8], min_parallax, min_triangulated (further keys are ignored; n1 /
+        n2 override the array lengths) -> one dict per problem: n_matches, SH, SF, model, ok, R21, t21, P3D [n1][3], triangulated [n1], H21,
+        F21, inliers_H, inliers_F [n_matches].  What the call does not write stays as it went in: NaN in R21 / t21 / P3D / H21 / F21, 0xff
+        in triangulated.  null = (problem, field): that pointer is passed as NULL."""
+        arr = (asd_initializer_problem * max(len(problems), 1))()
+        keep = []
+        nan = float("nan")
+        for j, q in enumerate(problems):
+            k1, k2 = _c(q["keys1"], np.float32).reshape(-1, 2), _c(q["keys2"], np.float32).reshape(-1, 2)
+            n1, n2 = int(q.get("n1", len(k1))), int(q.get("n2", len(k2)))
+            a = [k1, k2, _c(q["matches12"], np.int32), _c(q["draws"], np.int32), np.full((max(n1, 1), 3), nan, np.float32),
+                 np.full(max(n1, 1), 0xff, np.uint8), np.full(max(n1, 1), 0xff, np.uint8), np.full(max(n1, 1), 0xff, np.uint8)]
+            keep.append(a)
+            P = arr[j]
+            P.n1, P.n2 = n1, n2
+            P.keys1, P.keys2, P.matches12, P.draws, P.P3D, P.triangulated, P.inliers_H, P.inliers_F = (x.ctypes.data for x in a)
+            if null is not None and null[0] == j:
+                setattr(P, null[1], None)
+            P.K = (C.c_float * 4)(*[float(k) for k in q["K"]])
+            P.sigma, P.n_iter = float(q["sigma"]), int(q["n_iter"])
+            P.min_parallax, P.min_triangulated = float(q["min_parallax"]), int(q["min_triangulated"])
+            P.n_matches, P.model, P.ok = -1, -1, -1
+            P.SH = P.SF = nan
+            P.R21 = (C.c_float * 9)(*[nan] * 9)
+            P.t21 = (C.c_float * 3)(*[nan] * 3)
+            P.H21 = (C.c_float * 9)(*[nan] * 9)
+            P.F21 = (C.c_float * 9)(*[nan] * 9)
+        self._chk(self.lib.asd_initialize(self.ctx, len(problems), arr))
+        out = []
+        for j, q in enumerate(problems):
+            P = arr[j]
+            a = keep[j]
+            n1, N = int(P.n1), int(P.n_matches)
+            f = lambda x, *shape: np.array(x, np.float32).reshape(*shape)
+            out.append(dict(n_matches=N, SH=np.float32(P.SH), SF=np.float32(P.SF), model=int(P.model), ok=int(P.ok), R21=f(P.R21, 3, 3),
+                            t21=f(P.t21, 3), P3D=a[4][:n1].copy(), triangulated=a[5][:n1].copy(), H21=f(P.H21, 3, 3), F21=f(P.F21, 3, 3),
+                            inliers_H=a[6][:N].copy(), inliers_F=a[7][:N].copy()))
+        return out
+
+    def debug_initialize(self, problem, which, n_matches=0):
+        """asd_debug_initialize of the last initialize.  which = 2 k + m (m = 0 H, 1 F): dict(idx [8], nullv [9] f64, U, w, Vt f64 (F: the
+        rank-2 step), M1 = H21i / F21i, M2 = H12i, score, mask [n_matches]); which = -1: the reconstruction: dict(U, w, Vt f64, best_H,
+        best_F, n_inliers, n_hyp, winner, second_good, R [8][3][3], t [8][3], parallax [8], cos_sel [8], n_good [8]); which = -2 - h: the
+        same plus points [n_matches][3] and flags [n_matches] of hypothesis h.  n_matches sizes the per-match arrays (0: not asked for)."""
+        d = asd_initializer_debug()
+        n = int(n_matches)
+        mask = np.zeros(max(n, 1), np.uint8)
+        pts = np.zeros((max(n, 1), 3), np.float32)
+        flags = np.zeros(max(n, 1), np.uint8)
+        if n > 0:
+            d.mask, d.points, d.flags = mask.ctypes.data, pts.ctypes.data, flags.ctypes.data
+        self.lib.asd_debug_initialize.restype = C.c_int32
+        rc = self.lib.asd_debug_initialize(self.ctx, int(problem), int(which), C.byref(d))
+        if rc != 0:
+            raise AsdError(rc, f"asd_debug_initialize: the last call has no record {which} of problem {problem}")
+        f8 = lambda a, *shape: np.array(a, np.float64).reshape(*shape)
+        f4 = lambda a, *shape: np.array(a, np.float32).reshape(*shape)
+        out = dict(U=f8(d.U, 3, 3), w=f8(d.w, 3), Vt=f8(d.Vt, 3, 3), best_H=int(d.best_H), best_F=int(d.best_F), n_inliers=int(d.n_inliers),
+                   n_hyp=int(d.n_hyp), winner=int(d.winner), second_good=int(d.second_good))
+        if which >= 0:
+            out.update(idx=[int(i) for i in d.idx], nullv=f8(d.nullv, 9), M1=f4(d.M1, 3, 3), M2=f4(d.M2, 3, 3), score=np.float32(d.score),
+                       mask=mask[:n].copy())
+        else:
+            out.update(R=f4(d.R, 8, 3, 3), t=f4(d.t, 8, 3), parallax=f4(d.parallax, 8), cos_sel=f4(d.cos_sel, 8),
+                       n_good=np.array(d.n_good, np.int32))
+            if which < -1:
+                out.update(points=pts[:n].copy(), flags=flags[:n].copy())
+        return out
 
     def _ba_pack(self, prob, its_first, its_second):
         poses = _c(prob["poses"], np.float64).copy()

@@ -159,6 +159,7 @@ int asd_ctx_destroy(asd_ctx* ctx) {
   sim3_free(ctx);
   sim3_ransac_free(ctx);
   pnp_ransac_free(ctx);
+  initializer_free(ctx);
   kfdb_free(ctx);
   ctx->scratch.release();
   ctx->stereo_scratch.release();
@@ -260,6 +261,8 @@ int asd_last_stage_ms(const asd_ctx* ctx, const char* stage, float* ms) {
   else if (!strcmp(stage, "sim3")) *ms = ctx->ms_sim3;
   else if (!strcmp(stage, "sim3_ransac")) *ms = ctx->ms_sim3_ransac;
   else if (!strcmp(stage, "pnp_ransac")) *ms = ctx->ms_pnp_ransac;
+  else if (!strcmp(stage, "initializer")) *ms = ctx->ms_initializer;
+  else if (!strcmp(stage, "initializer_hyp")) *ms = ctx->ms_initializer_hyp;
   else if (!strcmp(stage, "kfdb")) *ms = ctx->ms_kfdb;
   else return ASD_ERR_INVALID;
   return ASD_OK;

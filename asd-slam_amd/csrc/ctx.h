@@ -342,6 +342,9 @@ struct asd_ctx {
   // ---- PnPsolver's RANSAC: the last call's hypothesis and Refine records for asd_debug_pnp_ransac (state private to pnp_ransac.hip)
   void* pnp_ransac = nullptr;
 
+  // ---- Initializer: the last call's records for asd_debug_initialize (state private to initializer.hip)
+  void* initializer = nullptr;
+
   // ---- keyframe database (state private to kfdb.hip)
   void* kfdb = nullptr;
 
@@ -359,7 +362,7 @@ struct asd_ctx {
 
   // ---- timing
   hipEvent_t ev0 = nullptr, ev1 = nullptr, ev2 = nullptr;
-  float ms_asdnet = 0, ms_extract = 0, ms_match = 0, ms_ba = 0, ms_sim3 = 0, ms_kfdb = 0, ms_sim3_ransac = 0, ms_pnp_ransac = 0;
+  float ms_asdnet = 0, ms_extract = 0, ms_match = 0, ms_ba = 0, ms_sim3 = 0, ms_kfdb = 0, ms_sim3_ransac = 0, ms_pnp_ransac = 0, ms_initializer = 0, ms_initializer_hyp = 0;
 
   // the extraction worker thread reports errors too: the message is written under a lock, and asd_last_error hands
   // out a copy that stays put until the next call of asd_last_error on this context
@@ -408,6 +411,7 @@ void bow_free(asd_ctx* ctx);
 void sim3_free(asd_ctx* ctx);
 void sim3_ransac_free(asd_ctx* ctx);
 void pnp_ransac_free(asd_ctx* ctx);
+void initializer_free(asd_ctx* ctx);
 void kfdb_free(asd_ctx* ctx);
 const char* kfdb_host_error();   // the message of this thread's last asd_bow_score (a call without a context)
 // The claim replay that makes d_src, to run in FRONT of the solver inside its workgroup (k_resolve_pose, ba.hip) instead of as a kernel of

@@ -1233,4 +1233,81 @@ inline int TriangulateMatches(Context& c, const FrameView& KF1, const FrameView&
   return nnew;
 }
 
+// ---- Initializer (Initializer.h:36-100; src/vslam/src/Initializer.cc) --------------------------------------------------------------
+// DUtils::Random::SeedRandOnce(0) (Random.cpp:38-45, called at Initializer.cc:84): one flag for the whole process; the first Initialize
+// calls srand(0), every later one -- of this or of another Initializer -- goes on with the sequence.
+inline void SeedRandOnce(int seed) {
+  static bool already_seeded = false;
+  if (!already_seeded) {
+    std::srand((unsigned)seed);
+    already_seeded = true;
+  }
+}
+
+struct Point3f { float x, y, z; };
+
+// The whole of Initialize runs on the device (asd_initialize); this class keeps what the reference's object keeps (mvKeys1, mK, mSigma,
+// mMaxIterations) and makes the draws: 8 x mMaxIterations calls of rand() per Initialize, in the reference's order (:86-101).
+class Initializer {
+ public:
+  // Initializer(const Frame& ReferenceFrame, float sigma = 1.0, int iterations = 200)  (:33-42); mK is the frame's in the reference
+  Initializer(asd_ctx* ctx, const FrameView& ReferenceFrame, const Camera& K, float sigma = 1.0f, int iterations = 200)
+      : ctx_(ctx), mK(K), mSigma(sigma), mMaxIterations(iterations) {
+    mvKeys1.reserve(2 * ReferenceFrame.mvKeysUn.size());
+    for (const asd_keypoint& k : ReferenceFrame.mvKeysUn) { mvKeys1.push_back(k.x); mvKeys1.push_back(k.y); }
+  }
+  // the draws of one Initialize over N matches (:84-100): RandomInt(0, vAvailableIndices.size() - 1) eight times per iteration
+  std::vector<int32_t> Draw(int N) {
+    SeedRandOnce(0);
+    std::vector<int32_t> draws((size_t)8 * mMaxIterations);
+    for (int it = 0; it < mMaxIterations; ++it)
+      for (int j = 0; j < 8; ++j) draws[(size_t)8 * it + j] = stream_.RandomInt(stream_.Next(), 0, N - 1 - j);
+    return draws;
+  }
+  // bool Initialize(const Frame& CurrentFrame, const vector<int>& vMatches12, cv::Mat& R21, cv::Mat& t21, vector<cv::Point3f>& vP3D,
+  //                 vector<bool>& vbTriangulated)  (:43-120).  R21 (row major) and t21 are written only when it returns true; vP3D and
+  // vbTriangulated are then indexed by the keypoint of the reference frame.  Fewer than eight matches return false without drawing
+  // (the reference's sampling is undefined there; Tracking.cc:428 asks for 100).
+  bool Initialize(const FrameView& CurrentFrame, const std::vector<int>& vMatches12, float R21[9], float t21[3], std::vector<Point3f>& vP3D,
+                  std::vector<bool>& vbTriangulated) {
+    std::vector<float> keys2;
+    keys2.reserve(2 * CurrentFrame.mvKeysUn.size());
+    for (const asd_keypoint& k : CurrentFrame.mvKeysUn) { keys2.push_back(k.x); keys2.push_back(k.y); }
+    const int n1 = (int)(mvKeys1.size() / 2);
+    std::vector<int32_t> m12(n1, -1);
+    int N = 0;
+    for (int i = 0; i < n1 && i < (int)vMatches12.size(); ++i) { m12[i] = vMatches12[i]; N += vMatches12[i] >= 0; }
+    if (N < 8) return false;
+    mvDraws = Draw(N);
+    std::vector<float> P3D((size_t)3 * n1);
+    std::vector<uint8_t> tri(n1), inlH(N), inlF(N);
+    asd_initializer_problem p{};
+    p.n1 = n1; p.keys1 = mvKeys1.data(); p.n2 = (int)(keys2.size() / 2); p.keys2 = keys2.data(); p.matches12 = m12.data();
+    p.K[0] = mK.fx; p.K[1] = mK.fy; p.K[2] = mK.cx; p.K[3] = mK.cy;
+    p.sigma = mSigma; p.n_iter = mMaxIterations; p.draws = mvDraws.data();
+    p.min_parallax = 1.0f; p.min_triangulated = 50;   // :115-117
+    p.P3D = P3D.data(); p.triangulated = tri.data(); p.inliers_H = inlH.data(); p.inliers_F = inlF.data();
+    if (asd_initialize(ctx_, 1, &p) != ASD_OK) throw std::runtime_error(asd_last_error(ctx_));
+    mLast = p;
+    if (!p.ok) return false;
+    for (int i = 0; i < 9; ++i) R21[i] = p.R21[i];
+    for (int i = 0; i < 3; ++i) t21[i] = p.t21[i];
+    vP3D.resize(n1);
+    vbTriangulated.assign(n1, false);
+    for (int i = 0; i < n1; ++i) { vP3D[i] = Point3f{P3D[3 * i], P3D[3 * i + 1], P3D[3 * i + 2]}; vbTriangulated[i] = tri[i] != 0; }
+    return true;
+  }
+  const std::vector<int32_t>& LastDraws() const { return mvDraws; }
+  const asd_initializer_problem& Last() const { return mLast; }   // SH, SF, model, n_matches of the last Initialize (its pointers are stale)
+ private:
+  asd_ctx* ctx_;
+  Camera mK;
+  float mSigma;
+  int mMaxIterations;
+  std::vector<float> mvKeys1;
+  std::vector<int32_t> mvDraws;
+  asd_initializer_problem mLast{};
+  DrawStream stream_;   // ::rand
+};
+
 }  // namespace asd

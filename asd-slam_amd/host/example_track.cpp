@@ -192,6 +192,25 @@ int main(int argc, char** argv) {
                passes, pnp.GetIterations(), n_pnp, Tpnp[3], Tpnp[7], Tpnp[11]);
       }
     }
+    // Tracking::MonocularInitialization (Tracking.cc:385-438) on the same pair: SearchForInitialization, then Initializer(frame, 1.0, 200)
+    // and Initialize -- both RANSACs and the reconstruction in one asd_initialize call.  CreateInitialMapMonocular and
+    // GlobalBundleAdjustemnt(20) on the two-keyframe map are the caller's.  Informative only, the exit status does not depend on it
+    {
+      asd::ORBmatcher ini_matcher(ctx, 0.9f, true);                                                          // :425
+      std::vector<float> vbPrevMatched;                                                                      // :399-402
+      for (const asd_keypoint& k : F[0].mvKeysUn) { vbPrevMatched.push_back(k.x); vbPrevMatched.push_back(k.y); }
+      std::vector<int> vIniMatches;
+      const int nini = ini_matcher.SearchForInitialization(F[0], F[1], vbPrevMatched, vIniMatches, 100);     // :426
+      asd::Initializer initializer(ctx.get(), F[0], K, 1.0f, 200);                                           // :407
+      float R21[9] = {}, t21[3] = {};
+      std::vector<asd::Point3f> vIniP3D;
+      std::vector<bool> vbTriangulated;
+      const bool ini_ok = initializer.Initialize(F[1], vIniMatches, R21, t21, vIniP3D, vbTriangulated);      // :438
+      int ntri = 0;
+      for (bool b : vbTriangulated) ntri += b;
+      printf("initializer: matches=%d ok=%d model=%s SH=%.1f SF=%.1f triangulated=%d t21=(%.4f %.4f %.4f)\n", nini, (int)ini_ok,
+             initializer.Last().model == 0 ? "H" : "F", initializer.Last().SH, initializer.Last().SF, ntri, t21[0], t21[1], t21[2]);
+    }
     printf("kp0=%d kp1=%d matches=%d inliers=%d fused=%d bow=%d t=(%.4f %.4f %.4f)\n", F[0].N(), F[1].N(), nmatches, ninl, nfused, nbow,
            F[1].mTcw[3], F[1].mTcw[7], F[1].mTcw[11]);
     return (nmatches > 100 && ninl > 50 && nfused > 0 && nbow > 0 && chain_ok && loop_ok) ? 0 : 1;

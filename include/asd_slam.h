@@ -672,7 +672,7 @@ int asd_pose7_to_tcw(const double* pose7, float* Tcw16);
 /* ---- instrumentation ----------------------------------------------------------------- */
 /* Device-side duration of the kernels enqueued by the most recent call of the named stage,
  * measured with hipEvents on the ctx stream.  stage: "asdnet", "extract", "match", "ba", "sim3" (asd_optimize_sim3),
- * "sim3_ransac" (both kernels of asd_sim3_ransac, its upload included), "pnp_ransac" (likewise for asd_pnp_ransac),
+ * "sim3_ransac" (both kernels of asd_sim3_ransac, its upload included), "pnp_ransac" (likewise for asd_pnp_ransac), "initializer" (likewise for asd_initialize; "initializer_hyp": its upload and k_init_hyp alone),
  * "kfdb" (the scoring pass of the last asd_kfdb_score / asd_kfdb_query_*, its upload included). */
 int asd_last_stage_ms(const asd_ctx* ctx, const char* stage, float* ms);
 /* Per-kernel device time of the ASDNet forward, accumulated with hipEvents recorded on the ctx
@@ -928,6 +928,125 @@ typedef struct asd_pnp_ransac_debug {
   double R[9], t[3], cws[12], v[48], eig[4], rep_errors[3], betas[4];
 } asd_pnp_ransac_debug;
 int32_t asd_debug_pnp_ransac(const asd_ctx* ctx, int32_t problem, int32_t which, asd_pnp_ransac_debug* out);
+/* Initializer (src/vslam/src/Initializer.cc): Initializer::Initialize (:43-120) for a batch of frame pairs -- the step of
+ * Tracking::MonocularInitialization (Tracking.cc:385-438, Initializer(frame, 1.0, 200)) between SearchForInitialization (asd_match_init) and
+ * the first map.  GlobalBundleAdjustemnt(20) on the two-keyframe map, which the reference runs next, is not part of the library.  One problem
+ * = one Initialize call:
+ *  in      n1, keys1[n1][2]        mvKeys1 = the reference frame's mvKeysUn pt (:37), f32
+ *          n2, keys2[n2][2]        mvKeys2 = the current frame's mvKeysUn pt (:49), f32
+ *          matches12[n1]           vMatches12: the keypoint of frame 2 matched to keypoint i of frame 1, -1 for none.  mvMatches12 (:55-64) is
+ *                                  built by the library in index order
+ *          K[4]                    fx fy cx cy of mK (:35)
+ *          sigma                   mSigma (:39); mSigma2 = sigma * sigma in f32 (:40)
+ *          n_iter                  mMaxIterations (:41)
+ *          draws[n_iter][8]        draws[k][j] = what RandomInt(0, N - 1 - j) returned for draw j of iteration k (:93); the swap-with-back
+ *                                  bookkeeping of vAvailableIndices (:88-100) is done by the device
+ *          min_parallax,           what Initialize passes to ReconstructH / ReconstructF: 1 and 50 in the reference (:115-117)
+ *          min_triangulated
+ *  out     n_matches               N = mvMatches12.size() (:66)
+ *          SH, SF                  the scores FindHomography / FindFundamental leave (:164-169, :215-220)
+ *          model                   0 = ReconstructH was called, 1 = ReconstructF (:113-116): RH = SH / (SH + SF) in f32, compared as a double
+ *                                  with 0.40; a NaN (SH = SF = 0) goes to F, as in the reference
+ *          ok                      what Initialize returns
+ *          R21[9], t21[3]          row major, f32; written only when ok
+ *          P3D[n1][3],             vP3D / vbTriangulated, indexed by the keypoint of frame 1 (CheckRT :850-851, :931-935): zero / 0 for a
+ *          triangulated[n1]        keypoint whose match is not one of the winning hypothesis' good points; written only when ok
+ *          H21[9], F21[9]          the best models of :166 and :217, f32; each is written only when an iteration of its model scored above 0
+ *          inliers_H[n_matches],   vbMatchesInliers of :167 and :218, by match (the k-th match is the k-th keypoint of frame 1 that has one);
+ *          inliers_F[n_matches]    always written, all 0 for a model no iteration of which scored above 0
+ * When ok == 0 nothing is written to R21, t21, P3D and triangulated (the reference leaves vP3D / vbTriangulated alone and R21 / t21 empty).
+ * A problem in which no iteration of the chosen model scores above 0 makes the reference read an empty H21 / F21; the library's rule is
+ * ok = 0.
+ *
+ * Arithmetic.  Every cv::Mat the reference stores as CV_32F is f32 here.  Where it leaves the evaluation to OpenCV the library states its
+ * own rules; they are the formula, not OpenCV's bits:
+ *  - a matrix product is evaluated in f64 on the widened elements, the terms of an element added in index order, and rounded to f32 once
+ *    when stored; a chain runs left to right as written (T2inv * Hn * T1 is two products and two roundings).  A scalar in front of a chain
+ *    (s * U * Rp * Vt, :638) scales the first matrix first (one rounding); R * p3dC1 + t (:903) and K * [R | t] (:866) are one sum per element
+ *    with the addend last; -R.t() * t (:868) is the negated product.  t / cv::norm(t) (:648, :957) divides each element by the f64 norm.
+ *  - inv() (:133, :160, :595) is the adjugate over the determinant in f64, rounded once; a zero determinant gives the zero matrix, as
+ *    cv::invert leaves it.  determinant and norm are f64 on the widened elements; dot and norm return double to the expression around them.
+ *  - scalar float expressions (:604-627, :662-665, all of CheckHomography, CheckFundamental, CheckRT and Normalize) are the reference's
+ *    C++ literally, un-fused, with the types C++ gives them: th = (float)5.991, invSigmaSquare = (float)(1.0 / (double)(sigma * sigma)),
+ *    1.0 / x divides in double and rounds once, comparisons with 0.99998 / 1.0000001 / 0.40 / 0.7 / 0.75 / 0.9 are made in double, sqrt of a
+ *    float is the f32 square root.  The score is the sequential f32 sum over the matches in order, test 1 before test 2 of each match.
+ *  - the null vector of A (ComputeH21 :229-264, 16 x 9; ComputeF21 :279-303, 8 x 9; every entry the f32 product the reference forms) is the
+ *    right singular vector of the smallest singular value by a one-sided Jacobi in f64 on the widened entries, of unit norm to rounding, then
+ *    rounded to f32.  For F, A has 8 rows and that singular value is zero.  The SIGN is the library's choice -- the component of largest
+ *    magnitude (the first of equal ones) is positive: H21i, H12i and F21i change sign with it, and so does the order of the motion hypotheses;
+ *    the scores, the masks and the outcome of ReconstructF do not (CheckHomography and CheckFundamental are homogeneous of degree 0 in the
+ *    model, E21's singular vectors are defined up to sign either way).
+ *  - the 3 x 3 SVDs (Fpre :305, E21 :954, A = invK * H21 * K :599): the same Jacobi in f64 on the widened elements; V is the product of the
+ *    rotations applied to the identity, u_j = (A v_j) / w_j, and the sign of each pair is set so that the component of v_j of largest magnitude
+ *    (the first of equal ones) is positive; a u_j whose w_j is at or below 2 * DBL_EPSILON * (w_0 + w_1
+ *    + w_2) is the cross product of the other two; the triplets are ordered by descending w (the first of equal ones first); U, w and Vt are
+ *    then rounded to f32.  ReconstructH's eight hypotheses are ordered by the signs of U and V (:621-628 pair x1, x3 with fixed signs), so
+ *    their ORDER, and with it which of two hypotheses tied for best is kept (:717, strict), depends on this convention.
+ *  - Triangulate (:774-787) is asd_svd4_null's computation (OpenCV 3.2.0's JacobiSVDImpl_ on the 4 x 4 f32 matrix, rows formed as
+ *    x * P.row(2) - P.row(0) by asd_triangulate_pairs' rule) and x3D = vt.row(3)[0..2] * (float)(1.0 / vt.row(3)[3]) + 0.0f.
+ *  - parallax (:940-943): vCosParallax[min(50, size - 1)] of the sorted list is selected by rank (-0 and +0 rank as equal; a NaN cosine,
+ *    for which the reference's sort is undefined, orders after every number); parallax = (float)(acos((double)cos) * 180 / CV_PI).
+ * Limits (ASD_ERR_CAPACITY beyond them): ASD_INIT_MAX_KEYS keypoints per frame, ASD_INIT_MAX_ITERATIONS iterations per problem,
+ * ASD_INIT_MAX_PROBLEMS problems per call.  ASD_ERR_INVALID: N < 8 (the reference's sampling is undefined; Tracking.cc:428 never goes below
+ * 100), a draw outside [0, N - 1 - j], a match index outside [-1, n2), a null array, negative n1 / n2, n_iter < 1; asd_last_error names the
+ * problem.  Two kernel launches (k_init_hyp: one workgroup per problem, iteration and model; k_init_reconstruct: one per problem) and one
+ * synchronisation per call, no atomics, every reduction of one fixed shape: a call is one bit pattern.  Timer: "initializer".  Legal wherever
+ * asd_pnp_ransac is. */
+#define ASD_INIT_MAX_KEYS 8192
+#define ASD_INIT_MAX_ITERATIONS 1024
+#define ASD_INIT_MAX_PROBLEMS 8
+typedef struct asd_initializer_problem {
+  int32_t n1;
+  const float* keys1;
+  int32_t n2;
+  const float* keys2;
+  const int32_t* matches12;
+  float K[4];
+  float sigma;
+  int32_t n_iter;
+  const int32_t* draws;
+  float min_parallax;
+  int32_t min_triangulated;
+  int32_t n_matches;
+  float SH, SF;
+  int32_t model, ok;
+  float R21[9], t21[3];
+  float* P3D;
+  uint8_t* triangulated;
+  float H21[9], F21[9];
+  uint8_t* inliers_H;
+  uint8_t* inliers_F;
+} asd_initializer_problem;
+int asd_initialize(asd_ctx* ctx, int32_t n_problems, asd_initializer_problem* problems);
+/* Initializer::Normalize (:791-837) in the reference's f32 order: the means and the mean absolute deviations are sequential f32 sums over
+ * ALL n keys (the frame's, not only the matched ones), sX = (float)(1.0 / meanDevX); pts_out[n][2] = vNormalizedPoints, T_out[9] = T row
+ * major.  asd_initialize normalises with this function on the host, in front of its upload.  n == 0 gives the reference's 0 / 0.  Host only,
+ * no context. */
+int asd_initializer_normalize(int32_t n, const float* keys, float* pts_out, float* T_out);
+/* Test aid: the context's last asd_initialize.
+ *  which = 2 k + m, 0 <= k < n_iter, m = 0 (H) / 1 (F): iteration k of that model.  idx = the eight sampled matches (:88-100), nullv = the
+ *    unit null vector in f64, for F also U, w, Vt of the rank-2 step (:305) in f64 (w descending, before the rounding to f32), M1 = H21i or F21i,
+ *    M2 = H12i (H only), score, and mask (when not NULL: [n_matches] bytes) = vbCurrentInliers.
+ *  which = -1: the reconstruction.  U, w, Vt = the 3 x 3 decomposition (:599 or :954) in f64; best_H / best_F = the iterations the walks kept
+ *    (-1: none scored above 0); n_inliers = N of :485-488 / :586-589; n_hyp = 8 / 4 motion hypotheses, or 0 where none was checked (:607-611,
+ *    or no model); R, t, n_good, parallax and cos_sel (the selected cosine, NaN when n_good = 0) of each; winner = the hypothesis returned or
+ *    -1; second_good (H path).
+ *  which = -2 - h: the same, and points (when not NULL: [n_matches][3] f32) = hypothesis h's triangulated points by match, NaN where the
+ *    point was never triangulated (the match is not in the inlier set), flags (when not NULL: [n_matches] bytes): bit 0 = counted in nGood
+ *    (:930-932), bit 1 = vbGood (:934-935).
+ * ASD_ERR_INVALID for a (problem, which) the last call did not run. */
+typedef struct asd_initializer_debug {
+  int32_t idx[8];
+  double nullv[9], U[9], w[3], Vt[9];
+  float M1[9], M2[9], score;
+  int32_t best_H, best_F, n_inliers, n_hyp, winner, second_good;
+  float R[8][9], t[8][3], parallax[8], cos_sel[8];
+  int32_t n_good[8];
+  uint8_t* mask;
+  float* points;
+  uint8_t* flags;
+} asd_initializer_debug;
+int32_t asd_debug_initialize(const asd_ctx* ctx, int32_t problem, int32_t which, asd_initializer_debug* out);
 /* ---- keyframe database and BoW score ------------------------------------------------------
  * TemplatedVocabulary::score (TemplatedVocabulary.h:1264-1269) -> L1Scoring / L2Scoring / DotProductScoring::score
  * (src/dbow2/DBoW2/ScoringObject.cpp:23-68, :73-120, :271-311) of two BowVectors given as (word id strictly ascending, value).  Host
