@@ -83,6 +83,17 @@ class asd_ba_result(C.Structure):
                 ("iters_first", C.c_int32), ("iters_second", C.c_int32)]
 
 
+class asd_gba_problem(C.Structure):
+    _fields_ = [("n_poses", C.c_int32), ("n_points", C.c_int32), ("n_edges", C.c_int32),
+                ("poses", C.c_void_p), ("fixed", C.c_void_p), ("points", C.c_void_p),
+                ("e_point", C.c_void_p), ("e_pose", C.c_void_p), ("e_obs", C.c_void_p), ("e_info", C.c_void_p),
+                ("K", C.c_double * 4), ("n_iterations", C.c_int32), ("robust", C.c_int32), ("stop", C.c_void_p)]
+
+
+class asd_gba_result(C.Structure):
+    _fields_ = [("edge_chi2", C.c_void_p), ("chi2", C.c_double), ("iterations", C.c_int32), ("trials", C.c_int32)]
+
+
 class asd_sim3_ransac_problem(C.Structure):
     _fields_ = [("n", C.c_int32), ("X1c", C.c_void_p), ("X2c", C.c_void_p), ("max_err1", C.c_void_p), ("max_err2", C.c_void_p),
                 ("K1", C.c_float * 4), ("K2", C.c_float * 4), ("fix_scale", C.c_int32), ("min_inliers", C.c_int32), ("n_iter", C.c_int32),
@@ -1155,6 +1166,41 @@ class AsdHip:
         p, r, keep = self._ba_pack(prob, its_first, its_second)
         self._chk(self.lib.asd_local_ba(self.ctx, C.byref(p), C.byref(r)))
         return self._ba_unpack(r, keep)
+
+    def bundle_adjustment(self, prob, n_iterations=20, robust=True, stop=None):
+        """Optimizer::BundleAdjustment (Optimizer.cc:51-237) -- asd_bundle_adjustment.  prob: the flat arrays of synth.gba_map /
+        synth.ba_problem; stop: None or an int32 array of one element (pbStopFlag).  Returns dict(poses, points, edge_chi2, chi2,
+        iterations, trials)."""
+        poses = _c(prob["poses"], np.float64).reshape(-1, 7).copy()
+        points = _c(prob["points"], np.float64).reshape(-1, 3).copy()
+        fixed = _c(prob["fixed"], np.uint8)
+        e_point, e_pose = _c(prob["e_point"], np.int32), _c(prob["e_pose"], np.int32)
+        e_obs, e_info = _c(prob["e_obs"], np.float64), _c(prob["e_info"], np.float64)
+        E = len(e_point)
+        chi2 = np.zeros(max(E, 1), np.float64)
+        if stop is not None:
+            assert stop.dtype == np.int32 and stop.size == 1
+        p = asd_gba_problem(len(poses), len(points), E, poses.ctypes.data, fixed.ctypes.data, points.ctypes.data,
+                            e_point.ctypes.data, e_pose.ctypes.data, e_obs.ctypes.data, e_info.ctypes.data,
+                            (C.c_double * 4)(*[float(k) for k in prob["K"]]), int(n_iterations), int(bool(robust)),
+                            stop.ctypes.data if stop is not None else None)
+        r = asd_gba_result(chi2.ctypes.data, 0.0, 0, 0)
+        self._chk(self.lib.asd_bundle_adjustment(self.ctx, C.byref(p), C.byref(r)))
+        return dict(poses=poses, points=points, edge_chi2=chi2[:E], chi2=r.chi2, iterations=int(r.iterations), trials=int(r.trials))
+
+    def gba_forms(self):
+        """[dense solve 0 solve_lds / 1 chol_lds / 2 chol / 3 tiled / -1 none, nPf, nLa, Ea, tiles] -- asd_debug_gba_forms"""
+        out = np.zeros(5, np.int32)
+        self.lib.asd_debug_gba_forms.restype = C.c_int32
+        self._chk(self.lib.asd_debug_gba_forms(self.ctx, _p(out)))
+        return [int(v) for v in out]
+
+    def gba_trials(self, cap=256):
+        """trials per iteration of the last bundle_adjustment -- asd_debug_gba_trials"""
+        out = np.zeros(cap, np.int32)
+        self.lib.asd_debug_gba_trials.restype = C.c_int32
+        n = int(self.lib.asd_debug_gba_trials(self.ctx, _p(out), C.c_int32(cap)))
+        return [int(v) for v in out[:min(n, cap)]]
 
     def local_ba_submit(self, prob, its_first=5, its_second=10):
         """LocalBundleAdjustment on the library's OPTIONAL lane: returns at once; local_ba_wait() returns the result dict.  One run

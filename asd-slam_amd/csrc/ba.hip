@@ -38,6 +38,7 @@
 #include <condition_variable>
 
 #include "ctx.h"
+#include "gba.h"
 #include "resolve2.h"
 #include "se3.h"
 
@@ -46,6 +47,19 @@ namespace {
 // "const float deltaMono = sqrt(5.991)" (Optimizer.cc:271,530): the kernel delta is a float
 constexpr float kChi2Mono = 5.991f;
 __host__ __device__ inline double huber_delta() { return (double)(float)2.4476519360399936; }  // (float)sqrt(5.991)
+// "const float thHuber2D = sqrt(5.99)" (Optimizer.cc:91): BundleAdjustment's width is NOT LocalBA's.  The LocalBA kernels take
+// `robust` = 0 (no kernel), 1 (huber_delta) or 2 (this one); each width stays a compile-time constant in its own call of huber(), so
+// LocalBA's instructions are what they were
+__host__ __device__ inline double huber_delta_gba() { return (double)(float)2.4474476501040834; }  // (float)sqrt(5.99)
+// g2o's RobustKernelHuber keeps delta as a double and delta^2 as a FLOAT ("float dsqr", robust_kernel_impl.h:84, set by setDelta,
+// robust_kernel_impl.cpp:65-69): both the inlier test and rho(e) = 2 sqrt(e) delta - dsqr read the rounded square.  BundleAdjustment is
+// pinned to 4 x the distance between two builds of g2o (1e-13 on the chi2), where that rounding -- 1e-8 relative on the chi2 of a
+// problem with outliers -- shows; LocalBA's huber() (se3.h) squares in double and is pinned at 1e-6.
+__host__ __device__ inline void huber_gba(double e2, double& rho0, double& rho1) {
+  const double delta = huber_delta_gba(), dsqr = (double)(float)(delta * delta);
+  if (e2 <= dsqr) { rho0 = e2; rho1 = 1.0; }
+  else { const double s = sqrt(e2); rho0 = 2 * s * delta - dsqr; rho1 = delta / s; }
+}
 
 // ---------------------------------------------------------------- deterministic block reductions
 // Wave-level sum of up to 32 values per lane as a reduce-scatter: each butterfly step exchanges only
@@ -978,6 +992,8 @@ struct BaDev {
                       // kPoseSplit workgroups of pose h.  The workgroup that draws the last ticket does what a kernel of its own did up to
                       // round 4 (the Levenberg control behind k_ba_error, the second stage of the pose sums) and puts the counter back to 0
   int scale_off, gE, gL, gP;
+  int* it_trials;   // device, [iterations] or null: the trials each iteration took (asd_debug_gba_trials)
+  int wide;   // asd_bundle_adjustment: more partial sums than kLmMaxPartials -- the control adds them in two stages (lm_wide_sums)
 };
 
 // lambda of the trial being computed: computeLambdaInit (block_solver.hpp:564-580, tau = 1e-5) until the first control step has
@@ -1035,7 +1051,8 @@ __global__ __launch_bounds__(256) void k_ba_error(BaDev d, int robust, int alway
       ba_project_error(d, e, buf);
       const double c = (d.err[2 * e] * d.err[2 * e] + d.err[2 * e + 1] * d.err[2 * e + 1]) * d.info[e];
       double r0 = c, r1;
-      if (robust) huber(c, huber_delta(), r0, r1);
+      if (robust == 2) huber_gba(c, r0, r1);
+      else if (robust) huber(c, huber_delta(), r0, r1);
       part[0] = r0;
     }
   }
@@ -1078,7 +1095,8 @@ __global__ __launch_bounds__(256) void k_ba_linearize(BaDev d, int robust) {
   jac_pose(x, y, z, d.fx, d.fy, Jc);
   const double e0 = d.err[2 * e], e1 = d.err[2 * e + 1];
   double w = 1.0, r0;
-  if (robust) huber((e0 * e0 + e1 * e1) * d.info[e], huber_delta(), r0, w);
+  if (robust == 2) huber_gba((e0 * e0 + e1 * e1) * d.info[e], r0, w);
+  else if (robust) huber((e0 * e0 + e1 * e1) * d.info[e], huber_delta(), r0, w);
   const double om = d.info[e] * w;
   double* hl = d.Hl + (size_t)k * 9;
   int q = 0;
@@ -1257,7 +1275,7 @@ __global__ __launch_bounds__(kSchurThreads) void k_ba_schur(BaDev d, SchurBlocks
     }
     d.A[(size_t)(6 * bi + r) * n + 6 * bj + c] = v;
     if (bi != bj) d.A[(size_t)(6 * bj + c) * n + 6 * bi + r] = v;
-    d.Apack[((size_t)bj * (bj + 1) / 2 + bi) * 36 + c * 6 + r] = v;   // lower block (bj, bi) = this upper block transposed
+    if (d.Apack) d.Apack[((size_t)bj * (bj + 1) / 2 + bi) * 36 + c * 6 + r] = v;   // lower block (bj, bi) = this upper block transposed
   }
 }
 
@@ -1735,13 +1753,36 @@ __device__ inline int lm_stage_partials(const BaDev& d, double* sh) {
   asd_syncthreads();
   return np;
 }
+// d.wide (a map: up to millions of edges): the three sums the control needs -- [0] residual cost, [1] the poses' gain-ratio terms,
+// [2] the landmarks' -- in two stages with a fixed shape: thread t adds its run of consecutive partials in index order, thread 0
+// then adds the kLmThreads results in index order; they are left in sh[3 kLmThreads + 0..2]
+__device__ inline void lm_wide_sums(const BaDev& d, double* sh) {
+  static_assert(4 * kLmThreads <= kLmMaxPartials, "sh holds three rows of thread sums and the totals");
+  const int base[3] = {0, d.scale_off + d.gL, d.scale_off}, len[3] = {d.gE, d.gP, d.gL};
+  for (int q = 0; q < 3; ++q) {
+    const int per = (len[q] + kLmThreads - 1) / kLmThreads;
+    const int b = min((int)threadIdx.x * per, len[q]), e = min(b + per, len[q]);
+    double s = 0;
+    for (int i = b; i < e; ++i) s += ld_agent(d.partial + base[q] + i);
+    sh[q * kLmThreads + threadIdx.x] = s;
+  }
+  asd_syncthreads();
+  if (threadIdx.x != 0) return;
+  for (int q = 0; q < 3; ++q) {
+    double s = 0;
+    for (int i = 0; i < kLmThreads; ++i) s += sh[q * kLmThreads + i];
+    sh[3 * kLmThreads + q] = s;
+  }
+}
 // start of a round: computeActiveErrors + activeRobustChi2 have just run (k_ba_error, always)
 __device__ void lm_begin_body(const BaDev& d, int iterations, double* sh) {
-  lm_stage_partials(d, sh);
+  if (d.wide) lm_wide_sums(d, sh);
+  else lm_stage_partials(d, sh);
   if (threadIdx.x != 0) return;
   LmState S;
   double sum = 0;
-  for (int i = 0; i < d.gE; ++i) sum += sh[i];
+  if (d.wide) sum = sh[3 * kLmThreads];
+  else for (int i = 0; i < d.gE; ++i) sum += sh[i];
   S.lambda = -1; S.ni = 2; S.currentChi = sum; S.iniChi = sum; S.rho = 0;
   S.maxdiag_bits = 0;
   S.it = 0; S.qmax = 0; S.nBad = 0; S.done = iterations <= 0 ? 1 : 0; S.need_lin = 1; S.cur = d.lm->cur & 1; S.trials = 0; S.iters_done = 0;   // (cur carries over from the previous round)
@@ -1754,7 +1795,8 @@ __device__ void lm_begin_body(const BaDev& d, int iterations, double* sh) {
 }
 // behind every trial (solve, update, computeActiveErrors): accept or reject, next lambda, end of iteration / of the round
 __device__ void lm_control_body(const BaDev& d, double* sh) {
-  lm_stage_partials(d, sh);
+  if (d.wide) lm_wide_sums(d, sh);
+  else lm_stage_partials(d, sh);
   if (threadIdx.x != 0) return;
   LmState S = *d.lm;
   if (S.first) {   // computeLambdaInit after the first buildSystem (:86-91)
@@ -1763,9 +1805,15 @@ __device__ void lm_control_body(const BaDev& d, double* sh) {
   }
   S.need_lin = 0;
   double tempChi = 0, scale = 0;
-  for (int i = 0; i < d.gE; ++i) tempChi += sh[i];
-  if (d.nPf > 0) for (int i = 0; i < d.gP; ++i) scale += sh[d.scale_off + d.gL + i];   // poses first, then landmarks
-  for (int i = 0; i < d.gL; ++i) scale += sh[d.scale_off + i];
+  if (d.wide) {
+    tempChi = sh[3 * kLmThreads];
+    if (d.nPf > 0) scale += sh[3 * kLmThreads + 1];
+    scale += sh[3 * kLmThreads + 2];
+  } else {
+    for (int i = 0; i < d.gE; ++i) tempChi += sh[i];
+    if (d.nPf > 0) for (int i = 0; i < d.gP; ++i) scale += sh[d.scale_off + d.gL + i];   // poses first, then landmarks
+    for (int i = 0; i < d.gL; ++i) scale += sh[d.scale_off + i];
+  }
   const bool ok2 = d.nPf == 0 || S.chol_ok == 1;
   if (S.trials < kLmLogCap) d.lm_log[S.trials] = LmLog{S.lambda, S.currentChi, tempChi, scale};
   if (!ok2) tempChi = 1.7976931348623157e308;
@@ -1787,6 +1835,7 @@ __device__ void lm_control_body(const BaDev& d, double* sh) {
   S.qmax++;
   S.trials++;
   if (!(rho < 0 && S.qmax < 10)) {   // the do-while of :98-146 ends: the iteration is over
+    if (d.it_trials) d.it_trials[S.iters_done] = S.qmax;
     S.iters_done++;
     int stop = (S.qmax == 10 || rho == 0) ? 1 : 0;
     if (!stop) {
@@ -1811,7 +1860,8 @@ __global__ __launch_bounds__(256) void k_ba_chi2_stored(BaDev d, int robust, dou
     if (!d.lvl[e]) {
       const double c = (d.err[2 * e] * d.err[2 * e] + d.err[2 * e + 1] * d.err[2 * e + 1]) * d.info[e];
       double r0 = c, r1;
-      if (robust) huber(c, huber_delta(), r0, r1);
+      if (robust == 2) huber_gba(c, r0, r1);
+      else if (robust) huber(c, huber_delta(), r0, r1);
       part[0] = r0;
     }
   }
@@ -2099,6 +2149,8 @@ struct BaState {
   struct BaLane* lane = nullptr;   // asd_local_ba_submit / _wait: the optional LocalBA lane (own thread, stream and events)
   int forms[2][5] = {{-1, -1, -1, -1, -1}, {-1, -1, -1, -1, -1}};   // asd_debug_local_ba_forms: per round of the last LocalBA
   int lm_rounds[2][4] = {{-1, -1, -1, -1}, {-1, -1, -1, -1}};       // asd_debug_local_ba_lm: per round of the last LocalBA
+  int gba_forms[5] = {-1, -1, -1, -1, -1};                          // asd_debug_gba_forms: the last asd_bundle_adjustment
+  std::vector<int> gba_trials;                                      // asd_debug_gba_trials: trials per iteration of the last asd_bundle_adjustment
   int32_t po_trace[kPoseTraceInts];                                 // asd_debug_pose_opt: the last asd_pose_optimize (k_pose_opt's trc)
   BaState() { for (int32_t& v : po_trace) v = -1; }
 };
@@ -2943,6 +2995,345 @@ int asd_local_ba_poll(asd_ctx* ctx) {
   if (!ln) return 0;
   std::lock_guard<std::mutex> l(ln->m);
   return (ln->has_job || ln->busy) ? 1 : (ln->done ? 2 : 0);
+}
+
+}  // extern "C"
+
+// ---------------------------------------------------------------- Optimizer::BundleAdjustment (Optimizer.cc:51-237)
+namespace {
+
+constexpr int kGbaChunk = 4;   // Levenberg trials enqueued between two looks at the stop flag and the mirrored state
+
+int gba_check(asd_ctx* ctx, const asd_gba_problem* pr, const asd_gba_result* res) {
+  if (!ctx || !pr || !res || pr->n_poses < 0 || pr->n_points < 0 || pr->n_edges < 0 || (pr->n_poses > 0 && (!pr->poses || !pr->fixed)) ||
+      (pr->n_points > 0 && !pr->points) || (pr->n_edges > 0 && (!pr->e_point || !pr->e_pose || !pr->e_obs || !pr->e_info || !res->edge_chi2)))
+    return ASD_ERR_INVALID;
+  int F = 0;
+  for (int p = 0; p < pr->n_poses; ++p) F += !pr->fixed[p];
+  if (F > ASD_GBA_MAX_FREE_POSES) { ctx->set_error("asd_bundle_adjustment: %d free poses exceed ASD_GBA_MAX_FREE_POSES = %d", F, ASD_GBA_MAX_FREE_POSES); return ASD_ERR_CAPACITY; }
+  if (pr->n_edges > ASD_GBA_MAX_EDGES) { ctx->set_error("asd_bundle_adjustment: %d edges exceed ASD_GBA_MAX_EDGES = %d", pr->n_edges, ASD_GBA_MAX_EDGES); return ASD_ERR_CAPACITY; }
+  if (pr->n_points > ASD_GBA_MAX_POINTS) { ctx->set_error("asd_bundle_adjustment: %d points exceed ASD_GBA_MAX_POINTS = %d", pr->n_points, ASD_GBA_MAX_POINTS); return ASD_ERR_CAPACITY; }
+  for (int e = 0; e < pr->n_edges; ++e)
+    if (pr->e_point[e] < 0 || pr->e_point[e] >= pr->n_points || pr->e_pose[e] < 0 || pr->e_pose[e] >= pr->n_poses) {
+      ctx->set_error("asd_bundle_adjustment: edge %d references vertex out of range", e);
+      return ASD_ERR_INVALID;
+    }
+  return ASD_OK;
+}
+
+// One round over LocalBA's kernels: the active structure from the host loop (a map is not per-frame work, and the device structure
+// kernels stop at 32 free poses), Schur workgroups only for the blocks that have pairs -- with the rest of A cleared in front of them --
+// and the dense solve in the form the size asks for.
+int gba_impl(asd_ctx* ctx, BaState* s, asd_gba_problem* pr, asd_gba_result* res) {
+  const int P = pr->n_poses, L = pr->n_points, E = pr->n_edges;
+  hipStream_t st = ctx->stream;
+  (void)hipSetDevice(ctx->cfg.device);
+  int rc;
+  for (int& v : s->gba_forms) v = -1;
+  s->gba_trials.clear();
+  res->chi2 = 0; res->iterations = -1; res->trials = 0;
+  std::vector<Pose7> hp(P);
+  for (int p = 0; p < P; ++p) {   // normalised like SE3Quat's constructor does
+    const double* q = pr->poses + 7 * p;
+    hp[p] = Pose7{q[0], q[1], q[2], q[3], q[4], q[5], q[6]};
+    quat_normalize(hp[p].qx, hp[p].qy, hp[p].qz, hp[p].qw);
+  }
+  auto poses_out = [&]() {
+    for (int p = 0; p < P; ++p) {
+      double* q = pr->poses + 7 * p;
+      q[0] = hp[p].qx; q[1] = hp[p].qy; q[2] = hp[p].qz; q[3] = hp[p].qw; q[4] = hp[p].tx; q[5] = hp[p].ty; q[6] = hp[p].tz;
+    }
+  };
+  // no edge: every point is removed again (Optimizer.cc:153-157), "0 vertices to optimize", optimize() returns -1
+  if (E == 0) { poses_out(); s->gba_forms[1] = s->gba_forms[2] = s->gba_forms[3] = s->gba_forms[4] = 0; return ASD_OK; }
+  const bool stop_on_entry = pr->stop && *pr->stop;
+  const int iterations = stop_on_entry ? 0 : pr->n_iterations;
+  const int robust = pr->robust ? 2 : 0;
+
+  // ---- active structure (sparse_optimizer.cpp:206-267, 166-190), as local_ba_impl's host loop builds it
+  std::vector<int> pose_h(P), pt_h(L), pose_of_h, pt_of_h;
+  {
+    std::vector<uint8_t> pa(P, 0), la(L, 0);
+    for (int e = 0; e < E; ++e) { pa[pr->e_pose[e]] = 1; la[pr->e_point[e]] = 1; }
+    for (int p = 0; p < P; ++p) { pose_h[p] = -1; if (pa[p] && !pr->fixed[p]) { pose_h[p] = (int)pose_of_h.size(); pose_of_h.push_back(p); } }
+    for (int l = 0; l < L; ++l) { pt_h[l] = -1; if (la[l]) { pt_h[l] = (int)pt_of_h.size(); pt_of_h.push_back(l); } }
+  }
+  const int nPf = (int)pose_of_h.size(), nLa = (int)pt_of_h.size(), Ea = E;
+  if (nPf == 0) {
+    ctx->set_error("asd_bundle_adjustment: %d edges but no free pose among their keyframes (the reference stops on an assertion of BlockSolver::resize)", E);
+    return ASD_ERR_INVALID;
+  }
+  // edges grouped by landmark (CSR), inside a landmark ordered by pose h-index (fixed poses first), stable
+  std::vector<int> pt_start(nLa + 1, 0), act(Ea), ph_of_k(Ea), cursor;
+  for (int e = 0; e < E; ++e) ++pt_start[pt_h[pr->e_point[e]] + 1];
+  for (int h = 0; h < nLa; ++h) pt_start[h + 1] += pt_start[h];
+  cursor.assign(pt_start.begin(), pt_start.end() - 1);
+  for (int e = 0; e < E; ++e) act[cursor[pt_h[pr->e_point[e]]]++] = e;
+  for (int h = 0; h < nLa; ++h) {
+    const int s0 = pt_start[h], s1 = pt_start[h + 1];
+    for (int a = s0; a < s1; ++a) ph_of_k[a] = pose_h[pr->e_pose[act[a]]];
+    for (int a = s0 + 1; a < s1; ++a) {
+      const int ea = act[a], pa_ = ph_of_k[a];
+      int b = a - 1;
+      while (b >= s0 && ph_of_k[b] > pa_) { act[b + 1] = act[b]; ph_of_k[b + 1] = ph_of_k[b]; --b; }
+      act[b + 1] = ea; ph_of_k[b + 1] = pa_;
+    }
+  }
+  // per free pose: its edges (k indices) in k order, and the landmark of each
+  std::vector<int> ps_start(nPf + 1, 0);
+  for (int k = 0; k < Ea; ++k) if (ph_of_k[k] >= 0) ++ps_start[ph_of_k[k] + 1];
+  for (int h = 0; h < nPf; ++h) ps_start[h + 1] += ps_start[h];
+  std::vector<int> ps_edges(std::max(ps_start[nPf], 1), 0), ps_hv(std::max(ps_start[nPf], 1), 0);
+  cursor.assign(ps_start.begin(), ps_start.end() - 1);
+  for (int h = 0; h < nLa; ++h)
+    for (int k = pt_start[h]; k < pt_start[h + 1]; ++k)
+      if (ph_of_k[k] >= 0) { const int o = cursor[ph_of_k[k]]++; ps_edges[o] = k; ps_hv[o] = h; }
+
+  // the form of the dense solve
+  const bool tiled = ctx->gba_solve == 1 || (ctx->gba_solve == 0 && nPf >= ASD_GBA_TILED_FROM);
+  const int form = tiled ? 3 : nPf <= kSolveMaxBlocks ? 0 : nPf <= 32 ? 1 : 2;
+  const bool all_blocks = form <= 1;   // the LDS solvers read the packed system whole: every upper block gets its workgroup, as in LocalBA
+  // Schur pair lists per upper block (bi <= bj).  A diagonal block always has a workgroup (Hpp + lambda I); an off-diagonal block
+  // only when a landmark connects its two poses -- a map's covisibility is banded, at 1024 free poses the dense triangle would be
+  // 525 k workgroups for a few thousand blocks with pairs.  The blocks left out are cleared by k_gba_clear in front of every Schur pass.
+  const int nblk_all = nPf * (nPf + 1) / 2;
+  std::vector<int> row_off(nPf), cnt(nblk_all, 0);
+  for (int i = 0; i < nPf; ++i) row_off[i] = i * nPf - i * (i - 1) / 2 - i;   // block id = row_off[i] + j
+  size_t npairs_total = 0;
+  for (int h = 0; h < nLa; ++h) {
+    const int s1 = pt_start[h + 1];
+    int a = pt_start[h];
+    while (a < s1 && ph_of_k[a] < 0) ++a;
+    for (; a < s1; ++a) {
+      const int ro = row_off[ph_of_k[a]];
+      for (int b = a; b < s1; ++b) { const int add = 1 + (b != a && ph_of_k[b] == ph_of_k[a]); cnt[ro + ph_of_k[b]] += add; npairs_total += add; }
+    }
+  }
+  if (npairs_total > (size_t)1 << 30) { ctx->set_error("asd_bundle_adjustment: %zu Schur pairs exceed 2^30", npairs_total); return ASD_ERR_CAPACITY; }
+  std::vector<int> cid(nblk_all, -1), blk_i, blk_j, pair_start(1, 0);
+  for (int i = 0; i < nPf; ++i)
+    for (int j = i; j < nPf; ++j) {
+      const int q = row_off[i] + j;
+      if (!all_blocks && i != j && cnt[q] == 0) continue;
+      cid[q] = (int)blk_i.size();
+      blk_i.push_back(i); blk_j.push_back(j);
+      pair_start.push_back(pair_start.back() + cnt[q]);
+    }
+  const int nblk = (int)blk_i.size();
+  const size_t npairs = std::max(npairs_total, (size_t)1);
+
+  // ---- buffers
+#define ENS(buf, bytes) if ((rc = s->buf.ensure(ctx, (bytes))) != ASD_OK) return rc
+  const int n = 6 * nPf;
+  ENS(pose, (size_t)P * sizeof(Pose7)); ENS(pose_bak, (size_t)P * sizeof(Pose7));
+  ENS(pts, (size_t)L * 24); ENS(pts_bak, (size_t)L * 24);
+  ENS(e_pt, (size_t)E * 4); ENS(e_ps, (size_t)E * 4); ENS(obs, (size_t)E * 16); ENS(info, (size_t)E * 8);
+  ENS(err, (size_t)E * 16); ENS(lvl, (size_t)E);
+  ENS(Bk, (size_t)E * 18 * 8); ENS(Hc, (size_t)E * 27 * 8); ENS(Hl, (size_t)E * 9 * 8); ENS(Hpp, (size_t)nPf * 27 * 8); ENS(Hll, (size_t)nLa * 9 * 8);
+  ENS(x, ((size_t)6 * nPf + 3 * nLa) * 8); ENS(A, (size_t)n * n * 8); ENS(bs, (size_t)n * 8);
+  if (all_blocks) ENS(Apack, (size_t)18 * nPf * (nPf + 1) * 8);
+  ENS(chi2, (size_t)E * 8); ENS(dpos, (size_t)E); ENS(HppPart, (size_t)nPf * kPoseSplit * 27 * 8);
+  ENS(misc, (size_t)std::max(iterations, 1) * 4);
+  const int gE = (Ea + 255) / 256, gL = (nLa + 255) / 256, gP = std::max((nPf + 255) / 256, 1);
+  const size_t npartial = (size_t)gE + gL + gP + 8;
+  ENS(partial, npartial * 8);
+  if (s->h_partial_cap < npartial) {
+    if (s->h_partial) (void)hipHostFree(s->h_partial);
+    s->h_partial = nullptr; s->h_partial_cap = 0;
+    ASD_HIP_CHECK(ctx, hipHostMalloc(&s->h_partial, npartial * 2 * 8));
+    s->h_partial_cap = npartial * 2;
+  }
+  if (!s->h_lm) ASD_HIP_CHECK(ctx, hipHostMalloc(reinterpret_cast<void**>(&s->h_lm), sizeof(LmState)));
+  ENS(lm, sizeof(LmState) + 64 + sizeof(LmLog) * kLmLogCap + sizeof(int) * ((size_t)P + 2));
+  // the structure in one pinned block, one upload
+  size_t off = 0;
+  auto place = [&](size_t bytes) { const size_t o = off; off += (bytes + 255) / 256 * 256; return o; };
+  const size_t o_act = place((size_t)Ea * 4), o_pose_h = place((size_t)P * 4), o_pt_h = place((size_t)L * 4), o_pose_of_h = place((size_t)nPf * 4),
+               o_pt_of_h = place((size_t)nLa * 4), o_pt_start = place((size_t)(nLa + 1) * 4), o_ps_start = place((size_t)(nPf + 1) * 4),
+               o_ps_edges = place(ps_edges.size() * 4), o_ps_h = place(ps_edges.size() * 4), o_blk_i = place((size_t)nblk * 4),
+               o_blk_j = place((size_t)nblk * 4), o_pair_start = place((size_t)(nblk + 1) * 4), o_pairs = place(npairs * 8), o_pair_h = place(npairs * 4);
+  ENS(sblk, off);
+#undef ENS
+  if (s->h_sblk_cap < off) {
+    if (s->h_sblk) (void)hipHostFree(s->h_sblk);
+    s->h_sblk = nullptr; s->h_sblk_cap = 0;
+    ASD_HIP_CHECK(ctx, hipHostMalloc(reinterpret_cast<void**>(&s->h_sblk), off + off / 4));
+    s->h_sblk_cap = off + off / 4;
+  }
+  char* hb = s->h_sblk;
+  auto put = [&](size_t o, const std::vector<int>& v) { if (!v.empty()) memcpy(hb + o, v.data(), v.size() * 4); };
+  put(o_act, act); put(o_pose_h, pose_h); put(o_pt_h, pt_h); put(o_pose_of_h, pose_of_h); put(o_pt_of_h, pt_of_h); put(o_pt_start, pt_start);
+  put(o_ps_start, ps_start); put(o_ps_edges, ps_edges); put(o_ps_h, ps_hv); put(o_blk_i, blk_i); put(o_blk_j, blk_j); put(o_pair_start, pair_start);
+  {
+    int2* pp = reinterpret_cast<int2*>(hb + o_pairs);
+    int* ph_ = reinterpret_cast<int*>(hb + o_pair_h);
+    cursor.assign(pair_start.begin(), pair_start.end() - 1);
+    for (int h = 0; h < nLa; ++h) {
+      const int s1 = pt_start[h + 1];
+      int a = pt_start[h];
+      while (a < s1 && ph_of_k[a] < 0) ++a;
+      for (; a < s1; ++a) {
+        const int ro = row_off[ph_of_k[a]];
+        for (int b = a; b < s1; ++b) {
+          const int c = cid[ro + ph_of_k[b]];
+          const int o = cursor[c]++; pp[o] = make_int2(a, b); ph_[o] = h;
+          // two edges of one pose (a duplicate observation): the diagonal block needs both cross terms (see local_ba_impl)
+          if (b != a && ph_of_k[b] == ph_of_k[a]) { const int o2 = cursor[c]++; pp[o2] = make_int2(b, a); ph_[o2] = h; }
+        }
+      }
+    }
+  }
+
+  // ---- upload; both estimate buffers start as the input (vertices no trial writes must read the same in both)
+  ASD_HIP_CHECK(ctx, hipMemcpyAsync(s->pose.p, hp.data(), (size_t)P * sizeof(Pose7), hipMemcpyHostToDevice, st));
+  ASD_HIP_CHECK(ctx, hipMemcpyAsync(s->pts.p, pr->points, (size_t)L * 24, hipMemcpyHostToDevice, st));
+  ASD_HIP_CHECK(ctx, hipMemcpyAsync(s->pose_bak.p, s->pose.p, (size_t)P * sizeof(Pose7), hipMemcpyDeviceToDevice, st));
+  ASD_HIP_CHECK(ctx, hipMemcpyAsync(s->pts_bak.p, s->pts.p, (size_t)L * 24, hipMemcpyDeviceToDevice, st));
+  ASD_HIP_CHECK(ctx, hipMemsetAsync(s->lm.p, 0, sizeof(LmState), st));   // lm->cur = 0
+  ASD_HIP_CHECK(ctx, hipMemcpyAsync(s->e_pt.p, pr->e_point, (size_t)E * 4, hipMemcpyHostToDevice, st));
+  ASD_HIP_CHECK(ctx, hipMemcpyAsync(s->e_ps.p, pr->e_pose, (size_t)E * 4, hipMemcpyHostToDevice, st));
+  ASD_HIP_CHECK(ctx, hipMemcpyAsync(s->obs.p, pr->e_obs, (size_t)E * 16, hipMemcpyHostToDevice, st));
+  ASD_HIP_CHECK(ctx, hipMemcpyAsync(s->info.p, pr->e_info, (size_t)E * 8, hipMemcpyHostToDevice, st));
+  ASD_HIP_CHECK(ctx, hipMemsetAsync(s->err.p, 0, (size_t)E * 16, st));
+  ASD_HIP_CHECK(ctx, hipMemsetAsync(s->lvl.p, 0, (size_t)E, st));   // no levels: every edge takes part
+  ASD_HIP_CHECK(ctx, hipMemcpyAsync(s->sblk.p, hb, off, hipMemcpyHostToDevice, st));
+  ASD_HIP_CHECK(ctx, hipEventRecord(ctx->ev0, st));
+
+  BaDev d{};
+  d.P = P; d.L = L; d.E = E;
+  d.pose[0] = s->pose.as<Pose7>(); d.pose[1] = s->pose_bak.as<Pose7>();
+  d.pts[0] = s->pts.as<double>(); d.pts[1] = s->pts_bak.as<double>();
+  d.e_pt = s->e_pt.as<int>(); d.e_ps = s->e_ps.as<int>(); d.obs = s->obs.as<double>(); d.info = s->info.as<double>();
+  d.err = s->err.as<double>(); d.lvl = s->lvl.as<uint8_t>(); d.HppPart = s->HppPart.as<double>();
+  d.fx = pr->K[0]; d.fy = pr->K[1]; d.cx = pr->K[2]; d.cy = pr->K[3];
+  char* db = s->sblk.as<char>();
+  d.act = reinterpret_cast<const int*>(db + o_act); d.pose_h = reinterpret_cast<const int*>(db + o_pose_h); d.pt_h = reinterpret_cast<const int*>(db + o_pt_h);
+  d.pose_of_h = reinterpret_cast<const int*>(db + o_pose_of_h); d.pt_of_h = reinterpret_cast<const int*>(db + o_pt_of_h);
+  d.pt_start = reinterpret_cast<const int*>(db + o_pt_start); d.ps_start = reinterpret_cast<const int*>(db + o_ps_start);
+  d.ps_edges = reinterpret_cast<const int*>(db + o_ps_edges); d.ps_h = reinterpret_cast<const int*>(db + o_ps_h);
+  const SchurBlocks sb{reinterpret_cast<const int*>(db + o_blk_i), reinterpret_cast<const int*>(db + o_blk_j), reinterpret_cast<const int*>(db + o_pair_start),
+                       reinterpret_cast<const int2*>(db + o_pairs), reinterpret_cast<const int*>(db + o_pair_h)};
+  d.Bk = s->Bk.as<double>(); d.Hc = s->Hc.as<double>(); d.Hl = s->Hl.as<double>(); d.Hpp = s->Hpp.as<double>(); d.Hll = s->Hll.as<double>();
+  d.x = s->x.as<double>(); d.A = s->A.as<double>(); d.Apack = all_blocks ? s->Apack.as<double>() : nullptr; d.bs = s->bs.as<double>();
+  d.lm = s->lm.as<LmState>();
+  d.lm_host = s->h_lm;
+  d.lm_log = reinterpret_cast<LmLog*>(s->lm.as<char>() + sizeof(LmState) + 64 - (sizeof(LmState) % 8));
+  d.partial = s->partial.as<double>();
+  d.tickets = reinterpret_cast<int*>(reinterpret_cast<char*>(d.lm_log) + sizeof(LmLog) * kLmLogCap);
+  ASD_HIP_CHECK(ctx, hipMemsetAsync(d.tickets, 0, sizeof(int) * ((size_t)P + 2), st));
+  d.Ea = Ea; d.nPf = nPf; d.nLa = nLa;
+  d.gE = gE; d.gL = gL; d.gP = gP; d.scale_off = gE;
+  d.wide = 1;
+  d.it_trials = s->misc.as<int>();
+  s->gba_forms[0] = form; s->gba_forms[1] = nPf; s->gba_forms[2] = nLa; s->gba_forms[3] = Ea; s->gba_forms[4] = tiled ? gba_tile_count(nPf) : 0;
+
+  // ---- one Levenberg trial as the device sees it (see local_ba_impl: blocks behind the round's end are no-ops)
+  auto enqueue_block = [&]() -> int {
+    int r2;
+    hipLaunchKernelGGL(k_ba_linearize, dim3(gE), dim3(256), 0, st, d, robust);
+    hipLaunchKernelGGL(k_ba_reduce, dim3(nPf * kPoseSplit + gL), dim3(256), 0, st, d);
+    if (!all_blocks && (r2 = gba_clear_enqueue(ctx, st, d.A, n, &d.lm->done)) != ASD_OK) return r2;
+    hipLaunchKernelGGL(k_ba_schur, dim3(nblk + nPf), dim3(kSchurThreads), 0, st, d, sb, nblk);
+    if (form == 3) {
+      if ((r2 = gba_solve_enqueue(ctx, st, d.A, d.bs, d.x, n, &d.lm->done, &d.lm->chol_ok, !ctx->gba_update_fma)) != ASD_OK) return r2;
+    } else {
+      const size_t nbk = (size_t)(nPf * (nPf + 1) / 2);
+      static AsdPerDeviceOnce attr_set;   // the dynamic-LDS attribute is per device
+      if (attr_set.need(ctx->cfg.device)) {
+        ASD_HIP_CHECK(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(k_ba_chol_lds), hipFuncAttributeMaxDynamicSharedMemorySize, 158 * 1024));
+        ASD_HIP_CHECK(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(k_ba_solve_lds), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+        attr_set.done(ctx->cfg.device);
+      }
+      if (form == 0) {
+        const size_t lds = (nbk * 36 + (size_t)2 * (kSolveMaxBlocks - 1) * 36 + 192 + 72 + 2) * sizeof(double) + nbk * sizeof(short2) + 16;
+        hipLaunchKernelGGL(k_ba_solve_lds, dim3(1), dim3(kSolveThreads), lds, st, d.Apack, d.bs, d.x, n, d.lm);
+      } else if (form == 1) {
+        const size_t lds = nbk * 36 * sizeof(double) + (2 * 192 + 2) * sizeof(double) + nbk * sizeof(short2) + 16;
+        hipLaunchKernelGGL(k_ba_chol_lds, dim3(1), dim3(kCholThreads), lds, st, d.A, d.bs, d.x, n, d.lm);
+      } else {
+        hipLaunchKernelGGL(k_ba_chol, dim3(1), dim3(1024), 0, st, d.A, d.bs, d.x, n, d.lm);
+      }
+    }
+    hipLaunchKernelGGL(k_ba_step, dim3(gL + gP), dim3(256), 0, st, d);
+    hipLaunchKernelGGL(k_ba_error, dim3(gE), dim3(256), 0, st, d, robust, 0, 0);   // + the Levenberg control, in its last workgroup
+    ASD_HIP_CHECK(ctx, hipGetLastError());
+    return ASD_OK;
+  };
+  // computeActiveErrors + activeRobustChi2 at the first estimate (levenberg.cpp:70-76), state reset
+  hipLaunchKernelGGL(k_ba_error, dim3(gE), dim3(256), 0, st, d, robust, 1, iterations);
+  ASD_HIP_CHECK(ctx, hipGetLastError());
+  const int max_trials = iterations * 10 + 2;
+  int enqueued = 0, iters = 0, trials = 0;
+  bool stopped = false, finished = iterations <= 0;
+  while (!finished && enqueued < max_trials) {
+    if (pr->stop && *pr->stop) { stopped = true; break; }
+    for (int b = 0; b < kGbaChunk; ++b) if ((rc = enqueue_block()) != ASD_OK) return rc;
+    enqueued += kGbaChunk;
+    ASD_HIP_CHECK(ctx, hipStreamSynchronize(st));
+    finished = s->h_lm->done != 0;
+  }
+  if (iterations <= 0) ASD_HIP_CHECK(ctx, hipStreamSynchronize(st));   // the first pass's state (h_lm held an earlier run's until then)
+  if (!finished && !stopped) { ctx->set_error("asd_bundle_adjustment: the Levenberg state did not finish"); return ASD_ERR_NUMERIC; }
+  iters = s->h_lm->iters_done; trials = s->h_lm->trials;
+  // stopped between two chunks: the stored errors may be a rejected trial's.  The errors at the accepted estimate once more (the
+  // pass also resets the Levenberg state, which nothing reads any more)
+  if (stopped) hipLaunchKernelGGL(k_ba_error, dim3(gE), dim3(256), 0, st, d, robust, 1, 0);
+  hipLaunchKernelGGL(k_ba_chi2_stored, dim3(gE), dim3(256), 0, st, d, robust, s->h_partial);
+  hipLaunchKernelGGL(k_ba_edge_report, dim3((E + 255) / 256), dim3(256), 0, st, d, s->chi2.as<double>(), s->dpos.as<uint8_t>(), (uint8_t*)nullptr, (uint8_t*)nullptr);
+  ASD_HIP_CHECK(ctx, hipGetLastError());
+  ASD_HIP_CHECK(ctx, hipEventRecord(ctx->ev1, st));
+  ASD_HIP_CHECK(ctx, hipStreamSynchronize(st));
+  const int fin = s->h_lm->cur & 1;   // the buffer that holds the accepted estimate
+  ASD_HIP_CHECK(ctx, hipMemcpyAsync(res->edge_chi2, s->chi2.p, (size_t)E * 8, hipMemcpyDeviceToHost, st));
+  ASD_HIP_CHECK(ctx, hipMemcpyAsync(hp.data(), fin ? s->pose_bak.p : s->pose.p, (size_t)P * sizeof(Pose7), hipMemcpyDeviceToHost, st));
+  ASD_HIP_CHECK(ctx, hipMemcpyAsync(pr->points, fin ? s->pts_bak.p : s->pts.p, (size_t)L * 24, hipMemcpyDeviceToHost, st));
+  s->gba_trials.assign(std::max(iters, 0), 0);
+  if (iters > 0) ASD_HIP_CHECK(ctx, hipMemcpyAsync(s->gba_trials.data(), s->misc.p, (size_t)iters * 4, hipMemcpyDeviceToHost, st));
+  ASD_HIP_CHECK(ctx, hipStreamSynchronize(st));
+  ASD_HIP_CHECK(ctx, hipEventElapsedTime(&ctx->ms_ba, ctx->ev0, ctx->ev1));
+  poses_out();
+  double sum = 0;
+  for (int i = 0; i < gE; ++i) sum += s->h_partial[i];
+  res->chi2 = sum; res->iterations = iters; res->trials = trials;
+  if (getenv("ASD_BA_DEBUG")) {
+    std::vector<LmLog> lg(kLmLogCap);
+    ASD_HIP_CHECK(ctx, hipMemcpy(lg.data(), d.lm_log, sizeof(LmLog) * kLmLogCap, hipMemcpyDeviceToHost));
+    for (int q = 0; q < std::min(trials, kLmLogCap); ++q)
+      fprintf(stderr, "[gba] trial %d lambda=%.6e cur=%.9e temp=%.9e scale=%.6e\n", q, lg[q].lambda, lg[q].cur, lg[q].temp, lg[q].scale);
+    fprintf(stderr, "[gba] form %d nPf=%d nLa=%d Ea=%d blocks=%d of %d: %d iterations, %d trials, %d blocks enqueued\n", form, nPf, nLa, Ea, nblk, nblk_all, iters, trials, enqueued);
+  }
+  return ASD_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int asd_bundle_adjustment(asd_ctx* ctx, asd_gba_problem* pr, asd_gba_result* res) {
+  int rc = gba_check(ctx, pr, res);
+  if (rc != ASD_OK) return rc;
+  if (asd_track_busy(ctx, "asd_bundle_adjustment")) return ASD_ERR_INVALID;
+  BaState* s = ba_state(ctx);
+  if (lane_outstanding(s)) {
+    ctx->set_error("asd_bundle_adjustment: a run submitted with asd_local_ba_submit is outstanding (the solver's device buffers are in use); call asd_local_ba_wait first");
+    return ASD_ERR_INVALID;
+  }
+  return gba_impl(ctx, s, pr, res);
+}
+
+int32_t asd_debug_gba_trials(const asd_ctx* ctx, int32_t* out, int32_t cap) {
+  if (!ctx || (cap > 0 && !out) || cap < 0) return ASD_ERR_INVALID;
+  const BaState* s = static_cast<const BaState*>(ctx->ba);
+  const int n = s ? (int)s->gba_trials.size() : 0;
+  for (int k = 0; k < cap; ++k) out[k] = k < n ? s->gba_trials[k] : -1;
+  return n;
+}
+
+int32_t asd_debug_gba_forms(const asd_ctx* ctx, int32_t out[5]) {
+  if (!ctx || !out) return ASD_ERR_INVALID;
+  const BaState* s = static_cast<const BaState*>(ctx->ba);
+  for (int k = 0; k < 5; ++k) out[k] = s ? s->gba_forms[k] : -1;
+  return ASD_OK;
 }
 
 }  // extern "C"

@@ -117,6 +117,8 @@ int asd_ctx_create(const asd_config* cfg, asd_ctx** out) {
   c->net_split = 0x3f;
   if (const char* e = getenv("ASD_MATCH_REPLAY")) c->match_replay_host = !strcmp(e, "host");   // matcher.hip, replay_on_device
   if (const char* e = getenv("ASD_BA_STRUCT")) c->ba_struct_host = !strcmp(e, "host");          // ba.hip, local_ba_impl
+  if (const char* e = getenv("ASD_GBA_SOLVE")) c->gba_solve = !strcmp(e, "tiled") ? 1 : !strcmp(e, "single") ? 2 : 0;   // ba.hip, gba_impl
+  if (const char* e = getenv("ASD_GBA_UPDATE")) c->gba_update_fma = !strcmp(e, "fma");          // gba.hip, k_gba_syrk
   if (const char* e = getenv("ASD_ASDNET_MATH")) {
     if (!strcmp(e, "f32")) c->net_split = 0;
     else if (!strcmp(e, "f16x2")) c->net_pieces = 2;

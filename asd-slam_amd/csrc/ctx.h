@@ -283,6 +283,8 @@ struct asd_ctx {
   void* d_wx3[7] = {};          // the same weights split into three bf16 terms (asdnet.hip, split-operand kernels)
   bool match_replay_host = false;  // ASD_MATCH_REPLAY=host (read at asd_ctx_create): matcher claim replay on the host
   bool ba_struct_host = false;     // ASD_BA_STRUCT=host (read at asd_ctx_create): LocalBA's active structure built on the host
+  int gba_solve = 0;               // ASD_GBA_SOLVE=tiled|single (read at asd_ctx_create): 1 / 2 force the form of asd_bundle_adjustment's dense solve, 0 = by size
+  bool gba_update_fma = false;     // ASD_GBA_UPDATE=fma: the tiled form's trailing update on plain FMA instead of f64 MFMA (the timing tool's A/B)
   void* d_wx2[7] = {};          // layers 1..5 split into two fp16 terms of (weight * wx2_scale[l]) (ASD_ASDNET_MATH=f16x2)
   float wx2_scale[7] = {1, 1, 1, 1, 1, 1, 1};
   int net_pieces_req = 2;       // the form asked for at asd_ctx_create (ASD_ASDNET_MATH); asd_load_weights starts from it every time

@@ -368,6 +368,108 @@ struct Optimizer {
     return nIn;
   }
 
+  // What Optimizer::BundleAdjustment reads from a KeyFrame and a MapPoint, flat.  A keyframe that a map point observes but that is not
+  // among vpKFs is still listed, with in_set = false: only its mnId and bad are read (the `pKF->mnId > maxKFid` test of :116).
+  struct BAKeyFrame {
+    unsigned long mnId = 0;
+    bool bad = false;                                   // isBad()
+    bool in_set = true;                                 // one of vpKFs
+    float Tcw[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};   // GetPose()
+    const std::vector<asd_keypoint>* mvKeysUn = nullptr;
+    const std::vector<float>* mvInvLevelSigma2 = nullptr;
+  };
+  struct BAMapPoint {
+    unsigned long mnId = 0;
+    bool bad = false;                                   // isBad()
+    float Xw[3] = {0, 0, 0};                            // GetWorldPos()
+    std::vector<std::pair<int, size_t>> observations;   // GetObservations() in the map's order: (index into the keyframe vector, keypoint)
+  };
+  // What :193-235 write back.  kf_written[i]: keyframe i is not bad (SetPose, or mTcwGBA / mnBAGlobalForKF when nLoopKF != 0: that
+  // choice stays the caller's); mp_written[i]: map point i is not bad and was included (vbNotIncludedMP, :153-161).
+  struct BAResult {
+    int rc = ASD_OK, iterations = 0, trials = 0, n_edges = 0;
+    double chi2 = 0;
+    std::vector<uint8_t> kf_written, mp_written, vbNotIncludedMP;
+    std::vector<float> Tcw;   // [keyframes][16]
+    std::vector<float> Xw;    // [points][3]
+  };
+  // void static BundleAdjustment(const vector<KeyFrame*>& vpKFs, const vector<MapPoint*>& vpMP, int nIterations, bool* pbStopFlag,
+  //                              const unsigned long nLoopKF, const bool bRobust)  (Optimizer.cc:51-237) over asd_bundle_adjustment.
+  // The gather is :69-162: bad keyframes and bad map points get no vertex; an observation of a bad keyframe, or of one with
+  // mnId > maxKFid (the largest id among the keyframes that are not bad), gets no edge; a point left without an edge is not included;
+  // keyframe mnId == 0 is fixed.  Vertices go to the device by ascending id, the edges point by point in the observations' order.
+  static BAResult BundleAdjustment(Context& c, const std::vector<BAKeyFrame>& keyframes, const std::vector<BAMapPoint>& points, const Camera& K,
+                                   int nIterations = 5, const volatile int32_t* pbStopFlag = nullptr, bool bRobust = true) {
+    BAResult out;
+    const int nKF = (int)keyframes.size(), nMP = (int)points.size();
+    out.kf_written.assign(nKF, 0); out.mp_written.assign(nMP, 0); out.vbNotIncludedMP.assign(nMP, 0);
+    out.Tcw.assign((size_t)nKF * 16, 0.f); out.Xw.assign((size_t)nMP * 3, 0.f);
+    unsigned long maxKFid = 0;
+    std::vector<int> kf_order, mp_order, kf_row(nKF, -1), mp_row(nMP, -1);
+    for (int i = 0; i < nKF; ++i) {
+      if (!keyframes[i].in_set || keyframes[i].bad) continue;                      // :79-80
+      kf_order.push_back(i);
+      if (keyframes[i].mnId > maxKFid) maxKFid = keyframes[i].mnId;                // :86-87
+    }
+    for (int i = 0; i < nMP; ++i) if (!points[i].bad) mp_order.push_back(i);      // :99-100
+    std::stable_sort(kf_order.begin(), kf_order.end(), [&](int a, int b) { return keyframes[a].mnId < keyframes[b].mnId; });
+    std::stable_sort(mp_order.begin(), mp_order.end(), [&](int a, int b) { return points[a].mnId < points[b].mnId; });
+    std::vector<double> poses(kf_order.size() * 7), X(mp_order.size() * 3), obs, info;
+    std::vector<uint8_t> fixed(kf_order.size(), 0);
+    std::vector<int32_t> e_point, e_pose;
+    for (size_t r = 0; r < kf_order.size(); ++r) {
+      kf_row[kf_order[r]] = (int)r;
+      asd_tcw_to_pose7(keyframes[kf_order[r]].Tcw, poses.data() + 7 * r);         // Converter::toSE3Quat(pKF->GetPose()), :82
+      fixed[r] = keyframes[kf_order[r]].mnId == 0;                                 // :84
+    }
+    for (size_t r = 0; r < mp_order.size(); ++r) {
+      const BAMapPoint& mp = points[mp_order[r]];
+      mp_row[mp_order[r]] = (int)r;
+      for (int k = 0; k < 3; ++k) X[3 * r + k] = mp.Xw[k];
+      int nEdges = 0;
+      for (const std::pair<int, size_t>& ob : mp.observations) {
+        const BAKeyFrame& kf = keyframes[ob.first];
+        if (kf.bad || kf.mnId > maxKFid) continue;                                 // :116-117
+        if (kf_row[ob.first] < 0) throw std::runtime_error("asd::Optimizer::BundleAdjustment: an observation of a keyframe that is not among vpKFs and has no larger id (the reference would set a null vertex)");
+        ++nEdges;
+        const asd_keypoint& kp = (*kf.mvKeysUn)[ob.second];
+        e_point.push_back((int32_t)r); e_pose.push_back(kf_row[ob.first]);
+        obs.push_back(kp.x); obs.push_back(kp.y);
+        info.push_back((*kf.mvInvLevelSigma2)[kp.octave]);
+      }
+      out.vbNotIncludedMP[mp_order[r]] = nEdges == 0;                              // :153-161
+    }
+    asd_gba_problem pr{};
+    pr.n_poses = (int32_t)kf_order.size(); pr.n_points = (int32_t)mp_order.size(); pr.n_edges = (int32_t)e_point.size();
+    pr.poses = poses.data(); pr.fixed = fixed.data(); pr.points = X.data();
+    pr.e_point = e_point.data(); pr.e_pose = e_pose.data(); pr.e_obs = obs.data(); pr.e_info = info.data();
+    pr.K[0] = K.fx; pr.K[1] = K.fy; pr.K[2] = K.cx; pr.K[3] = K.cy;
+    pr.n_iterations = nIterations; pr.robust = bRobust; pr.stop = pbStopFlag;
+    std::vector<double> edge_chi2(e_point.size() + 1);
+    asd_gba_result res{};
+    res.edge_chi2 = edge_chi2.data();
+    out.n_edges = pr.n_edges;
+    out.rc = asd_bundle_adjustment(c.get(), &pr, &res);
+    if (out.rc != ASD_OK) return out;
+    out.iterations = res.iterations; out.trials = res.trials; out.chi2 = res.chi2;
+    for (size_t r = 0; r < kf_order.size(); ++r) {                                 // :193-210
+      out.kf_written[kf_order[r]] = 1;
+      asd_pose7_to_tcw(poses.data() + 7 * r, out.Tcw.data() + (size_t)kf_order[r] * 16);
+    }
+    for (size_t r = 0; r < mp_order.size(); ++r) {                                 // :213-235
+      if (out.vbNotIncludedMP[mp_order[r]]) continue;
+      out.mp_written[mp_order[r]] = 1;
+      for (int k = 0; k < 3; ++k) out.Xw[(size_t)mp_order[r] * 3 + k] = (float)X[3 * r + k];   // Converter::toCvMat(Vector3d): CV_32F
+    }
+    return out;
+  }
+  // void static GlobalBundleAdjustemnt(Map* pMap, int nIterations, bool* pbStopFlag, const unsigned long nLoopKF, const bool bRobust)
+  // (Optimizer.cc:43-48): pMap->GetAllKeyFrames() / GetAllMapPoints() are the caller's two vectors.
+  static BAResult GlobalBundleAdjustemnt(Context& c, const std::vector<BAKeyFrame>& allKeyFrames, const std::vector<BAMapPoint>& allMapPoints,
+                                         const Camera& K, int nIterations = 5, const volatile int32_t* pbStopFlag = nullptr, bool bRobust = true) {
+    return BundleAdjustment(c, allKeyFrames, allMapPoints, K, nIterations, pbStopFlag, bRobust);
+  }
+
   // void static LocalBundleAdjustment(KeyFrame* pKF, bool* pbStopFlag, Map* pMap)  (Optimizer.cc:415): the
   // caller gathers local / fixed keyframes and map points exactly as :423-467 and hands them over flat;
   // on return it applies the erase policy of :652-700 from edge_chi2 / edge_depth_pos.
@@ -386,6 +488,30 @@ struct Tracking {
   // One pass of the loop of Tracking::Relocalization (:1156-1249) over the live PnPsolvers; defined behind asd::PnPsolver below.
   template <class TailFn>
   static int RelocalizationRound(Context& c, std::vector<PnPsolver*>& vpPnPsolvers, std::vector<bool>& vbDiscarded, int nIterations, TailFn tail);
+
+  // The tail of Tracking::CreateInitialMapMonocular behind GlobalBundleAdjustemnt(mpMap, 20) (Tracking.cc:539-565), on the host:
+  // medianDepth = pKFini->ComputeSceneMedianDepth(2) (KeyFrame.cc:909-937: z = Rcw.row(2) . Xw + tz over the keyframe's map points --
+  // cv::Mat::dot accumulates the f32 products in double -- sorted, element (n - 1) / 2); false for the reference's "Wrong
+  // initialization" (medianDepth < 0 or fewer than 50 tracked points in pKFcur, :542 -- upstream ORB-SLAM2 asks for 100, this
+  // reference for 50), else pKFcur's translation and every map point of pKFini times 1 / medianDepth, in f32.  iniPoints[i] = index
+  // into Xw of pKFini's map point at keypoint i, -1 = none (GetMapPointMatches: a point listed twice is scaled twice, as there).
+  static bool InitialMapScale(const float TcwIni[16], float TcwCur[16], const std::vector<int32_t>& iniPoints, std::vector<float>& Xw,
+                              int nTrackedCur, float* medianDepth_out = nullptr, int minTracked = 50) {
+    std::vector<float> vDepths;
+    for (int32_t l : iniPoints)
+      if (l >= 0)
+        vDepths.push_back((float)(((double)TcwIni[8] * Xw[3 * l] + (double)TcwIni[9] * Xw[3 * l + 1] + (double)TcwIni[10] * Xw[3 * l + 2]) + (double)TcwIni[11]));
+    if (vDepths.empty()) return false;   // (the reference reads vDepths[0] of an empty vector)
+    std::sort(vDepths.begin(), vDepths.end());
+    const float medianDepth = vDepths[(vDepths.size() - 1) / 2];
+    const float invMedianDepth = 1.0f / medianDepth;
+    if (medianDepth_out) *medianDepth_out = medianDepth;
+    if (medianDepth < 0 || nTrackedCur < minTracked) return false;                                  // :542-548
+    for (int r = 0; r < 3; ++r) TcwCur[r * 4 + 3] = TcwCur[r * 4 + 3] * invMedianDepth;             // :551-554
+    for (int32_t l : iniPoints)
+      if (l >= 0) for (int k = 0; k < 3; ++k) Xw[3 * l + k] = Xw[3 * l + k] * invMedianDepth;       // :557-565
+    return true;
+  }
 
   // bool Tracking::TrackWithMotionModel(): Cur.mTcw holds the motion-model prediction on entry (mVelocity * mLastFrame.mTcw, :677).
   // `points` = LastFrame's map points indexed like LastFrame.mvKeysUn (null where there is none).  Writes Cur.mvpMapPoints,

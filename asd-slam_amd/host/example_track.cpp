@@ -193,8 +193,7 @@ int main(int argc, char** argv) {
       }
     }
     // Tracking::MonocularInitialization (Tracking.cc:385-438) on the same pair: SearchForInitialization, then Initializer(frame, 1.0, 200)
-    // and Initialize -- both RANSACs and the reconstruction in one asd_initialize call.  CreateInitialMapMonocular and
-    // GlobalBundleAdjustemnt(20) on the two-keyframe map are the caller's.  Informative only, the exit status does not depend on it
+    // and Initialize -- both RANSACs and the reconstruction in one asd_initialize call.  Informative only, the exit status does not depend on it
     {
       asd::ORBmatcher ini_matcher(ctx, 0.9f, true);                                                          // :425
       std::vector<float> vbPrevMatched;                                                                      // :399-402
@@ -210,6 +209,38 @@ int main(int argc, char** argv) {
       for (bool b : vbTriangulated) ntri += b;
       printf("initializer: matches=%d ok=%d model=%s SH=%.1f SF=%.1f triangulated=%d t21=(%.4f %.4f %.4f)\n", nini, (int)ini_ok,
              initializer.Last().model == 0 ? "H" : "F", initializer.Last().SH, initializer.Last().SF, ntri, t21[0], t21[1], t21[2]);
+      // Tracking::CreateInitialMapMonocular (Tracking.cc:472-570) on that result: the two keyframes, a map point per triangulated match,
+      // Optimizer::GlobalBundleAdjustemnt(mpMap, 20) (:535) and the median-depth rescaling (:539-565)
+      if (ini_ok) {
+        const std::vector<float> invSigma2 = extractor.GetInverseScaleSigmaSquares();
+        std::vector<asd::Optimizer::BAKeyFrame> kfs(2);
+        for (int q = 0; q < 2; ++q) { kfs[q].mnId = q; kfs[q].mvKeysUn = &F[q].mvKeysUn; kfs[q].mvInvLevelSigma2 = &invSigma2; }
+        for (int r = 0; r < 3; ++r) { for (int q = 0; q < 3; ++q) kfs[1].Tcw[r * 4 + q] = R21[r * 3 + q]; kfs[1].Tcw[r * 4 + 3] = t21[r]; }   // :449-453
+        std::vector<asd::Optimizer::BAMapPoint> map;
+        std::vector<int32_t> iniPoints(F[0].N(), -1);
+        for (size_t i = 0; i < vIniMatches.size(); ++i) {
+          if (vIniMatches[i] < 0 || !vbTriangulated[i]) continue;                                          // :489-491
+          asd::Optimizer::BAMapPoint mp;
+          mp.mnId = map.size();
+          mp.Xw[0] = vIniP3D[i].x; mp.Xw[1] = vIniP3D[i].y; mp.Xw[2] = vIniP3D[i].z;
+          mp.observations = {{0, i}, {1, (size_t)vIniMatches[i]}};                                         // :501-502
+          iniPoints[i] = (int32_t)map.size();
+          map.push_back(mp);
+        }
+        const asd::Optimizer::BAResult ba = asd::Optimizer::GlobalBundleAdjustemnt(ctx, kfs, map, K, 20);  // :535
+        float median = 0;
+        bool scaled = false;
+        if (ba.rc == ASD_OK) {
+          float Tcur[16];
+          for (int q = 0; q < 16; ++q) Tcur[q] = ba.Tcw[16 + q];
+          std::vector<float> Xw = ba.Xw;
+          scaled = asd::Tracking::InitialMapScale(ba.Tcw.data(), Tcur, iniPoints, Xw, (int)map.size(), &median);
+          printf("initial-map: points=%d edges=%d gba_iterations=%d trials=%d chi2=%.3f median_depth=%.4f scaled=%d t=(%.4f %.4f %.4f)\n", (int)map.size(),
+                 ba.n_edges, ba.iterations, ba.trials, ba.chi2, median, (int)scaled, Tcur[3], Tcur[7], Tcur[11]);
+        } else {
+          printf("initial-map: points=%d asd_bundle_adjustment failed (%d): %s\n", (int)map.size(), ba.rc, ctx.error());
+        }
+      }
     }
     printf("kp0=%d kp1=%d matches=%d inliers=%d fused=%d bow=%d t=(%.4f %.4f %.4f)\n", F[0].N(), F[1].N(), nmatches, ninl, nfused, nbow,
            F[1].mTcw[3], F[1].mTcw[7], F[1].mTcw[11]);

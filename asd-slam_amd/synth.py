@@ -196,6 +196,70 @@ def ba_problem(n_free=24, n_fixed=12, n_points=6000, obs_per_point=5, seed=1,
     )
 
 
+def gba_map(n_kf=18, pts_per_kf=40, seed=1, loop_points=0, pix_noise=0.5, outlier_frac=0.0, outlier_px=(15.0, 40.0),
+            pose_sigma=0.005, point_sigma=0.03, min_obs=3, max_obs=6, n_free_points=None):
+    """A whole map for asd_bundle_adjustment (reference Optimizer.cc:51-237): keyframes on a sideways track 0.5 m apart (parallax
+    on every point, depths 4-14 m: the free monocular scale is held by the data), keyframe 0 fixed as the reference fixes mnId == 0,
+    banded covisibility -- every point is seen by min_obs..max_obs consecutive keyframes, about pts_per_kf observations per
+    keyframe -- and optionally loop_points points shared by the first two free keyframes and the last two (a corner block of the
+    reduced system).  n_kf == 2: the initial map of Tracking::CreateInitialMapMonocular, n_free_points points seen by both.
+    Edges are grouped by point, as the reference's loop over the map points adds them.  Same layout as ba_problem()."""
+    rng = np.random.default_rng(seed)
+    fx, fy, cx, cy = KITTI_K
+    Rs, cs = [], []
+    for i in range(n_kf):
+        Rs.append(_rot(rng.standard_normal(3) * 0.02))
+        cs.append(np.array([0.5 * i, rng.standard_normal() * 0.03, rng.standard_normal() * 0.03]))
+    ts = [-R @ c for R, c in zip(Rs, cs)]
+    windows = []
+    if n_kf == 2:
+        windows = [(0, 2)] * int(n_free_points if n_free_points is not None else 120)
+    else:
+        mean_obs = 0.5 * (min_obs + max_obs)
+        n_pts = int(round(pts_per_kf * n_kf / mean_obs))
+        for _ in range(n_pts):
+            w = int(rng.integers(min_obs, max_obs + 1))
+            w = min(w, n_kf)
+            windows.append((int(rng.integers(0, n_kf - w + 1)), w))
+    seen = [list(range(s, s + w)) for s, w in windows]
+    for _ in range(loop_points):
+        seen.append([1, 2, n_kf - 2, n_kf - 1])
+    pts, e_point, e_pose, e_obs, e_info = [], [], [], [], []
+    sig2 = 1.2 ** (2 * np.arange(8))
+    for l, kfs in enumerate(seen):
+        xc = 0.5 * float(np.mean(kfs))
+        X = np.array([xc + rng.uniform(-3, 3), rng.uniform(-1.5, 1.5), rng.uniform(4, 14)])
+        pts.append(X)
+        for p in kfs:
+            Xc = Rs[p] @ X + ts[p]
+            du, dv = rng.normal(0, pix_noise, 2)
+            if rng.uniform() < outlier_frac:
+                du, dv = rng.uniform(outlier_px[0], outlier_px[1], 2) * rng.choice([-1.0, 1.0], 2)
+            lvl = int(rng.integers(0, 8))
+            e_point.append(l)
+            e_pose.append(p)
+            e_obs.append((np.float32(fx * Xc[0] / Xc[2] + cx + du), np.float32(fy * Xc[1] / Xc[2] + cy + dv)))
+            e_info.append(np.float32(1.0 / np.float32(sig2[lvl])))
+    pts = np.array(pts).reshape(-1, 3)
+    poses = np.zeros((n_kf, 7))
+    fixed = np.zeros(n_kf, np.uint8)
+    fixed[0] = 1
+    for i in range(n_kf):
+        R, t = Rs[i], ts[i]
+        if not fixed[i]:
+            R = _rot(rng.standard_normal(3) * pose_sigma) @ R
+            t = t + rng.standard_normal(3) * pose_sigma
+        poses[i, :4] = rot_to_quat(R.astype(np.float32).astype(np.float64))
+        poses[i, 4:] = t.astype(np.float32).astype(np.float64)
+    pts_noisy = (pts + rng.standard_normal(pts.shape) * point_sigma).astype(np.float32).astype(np.float64)
+    return dict(
+        poses=poses, fixed=fixed, points=pts_noisy,
+        e_point=np.array(e_point, np.int32), e_pose=np.array(e_pose, np.int32),
+        e_obs=np.array(e_obs, np.float64).reshape(-1, 2), e_info=np.array(e_info, np.float64),
+        K=np.array(KITTI_K, np.float64),
+    )
+
+
 def pose_problem(n=300, seed=2, outlier_frac=0.1, pose_sigma=0.02):
     """Pose-only problem for asd_pose_optimize (reference Optimizer.cc:239-413)."""
     rng = np.random.default_rng(seed)

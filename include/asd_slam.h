@@ -665,6 +665,76 @@ int asd_local_ba_submit(asd_ctx* ctx, asd_ba_problem* problem, asd_ba_result* re
 int asd_local_ba_wait(asd_ctx* ctx);
 int asd_local_ba_poll(asd_ctx* ctx);
 
+/* ---- full bundle adjustment ------------------------------------------------------------ */
+typedef struct asd_gba_problem {
+  int32_t n_poses;          /* keyframes, ordered by ascending KF id (Optimizer.cc:72-89)          */
+  int32_t n_points;         /* map points, ordered by ascending MP id (:96-107)                    */
+  int32_t n_edges;          /* in the caller's insertion order (:112-151: grouped by point)        */
+  double*        poses;     /* [n_poses][7] in/out (qx,qy,qz,qw,tx,ty,tz)                          */
+  const uint8_t* fixed;     /* [n_poses] vSE3->setFixed(pKF->mnId == 0) (:84); any mask is honoured */
+  double*        points;    /* [n_points][3] in/out                                                */
+  const int32_t* e_point;   /* [n_edges] point index                                               */
+  const int32_t* e_pose;    /* [n_edges] pose index                                                */
+  const double*  e_obs;     /* [n_edges][2] kpUn.pt (:121-125)                                     */
+  const double*  e_info;    /* [n_edges] invSigma2 (:133-134)                                      */
+  double K[4];              /* fx, fy, cx, cy                                                      */
+  int32_t n_iterations;     /* nIterations (:173)                                                  */
+  int32_t robust;           /* bRobust (:136-141): 1 = Huber, delta = (float)sqrt(5.99) (:91 --    */
+                            /* NOT LocalBA's 5.991); 0 = no kernel                                 */
+  const volatile int32_t* stop;   /* pbStopFlag (:66-67); NULL = none                              */
+} asd_gba_problem;
+
+typedef struct asd_gba_result {
+  double*  edge_chi2;       /* [n_edges] e->chi2() of the stored errors                            */
+  double   chi2;            /* activeRobustChi2() of the stored errors, as asd_local_ba reports it */
+  int32_t  iterations;      /* what g2o's optimize() returns: iterations run, -1 without an active */
+                            /* vertex (no edge)                                                    */
+  int32_t  trials;          /* solves, accepted and rejected                                       */
+} asd_gba_result;
+
+/* Numeric core of Optimizer::BundleAdjustment (Optimizer.cc:51-237; GlobalBundleAdjustemnt, :43-48, only collects its vectors):
+ * the graph of :57-162, then ONE round, initializeOptimization(); optimize(n_iterations) (:172-173) -- Levenberg with g2o's schedule
+ * (optimization_algorithm_levenberg.cpp:61-189), no outlier gating, no levels.  The caller of Tracking::CreateInitialMapMonocular
+ * (Tracking.cc:472-570: GlobalBundleAdjustemnt(mpMap, 20) behind Initializer::Initialize) and of
+ * LoopClosing::RunGlobalBundleAdjustment needs nothing else from g2o.  Poses and points are written in place.
+ *   - A point without an edge is legal (the reference removes such a vertex, :153-157) and comes back untouched; so does a free pose
+ *     without an edge (its quaternion normalised, as SE3Quat's constructor does for every pose).
+ *   - n_edges == 0: iterations = -1, nothing moves (sparse_optimizer.cpp:356-359).  Edges but no free pose among their keyframes:
+ *     ASD_ERR_INVALID -- the reference does not return, it stops on an assertion of BlockSolver::resize (block_solver.hpp:75).
+ *   - stop: read by the HOST before each chunk of four Levenberg trials is enqueued, never by the device.  Set on entry: the call is
+ *     that of n_iterations = 0 -- iterations = 0, the estimates as given (quaternions normalised), chi2 / edge_chi2 of the errors at
+ *     them.  Set later: the trials already enqueued finish, the iteration in progress is abandoned, the last ACCEPTED estimate
+ *     comes back with the errors at it and the iterations completed so far.  (g2o looks at the flag in front of every iteration,
+ *     sparse_optimizer.cpp:376; this reference is single-threaded, so there the flag cannot change during a call.)
+ *   - The reduced pose system (n = 6 x free poses with an edge) is solved densely in f64.  Up to ASD_GBA_TILED_FROM - 1 such poses
+ *     by LocalBA's single-workgroup solvers; from there on by a tiled Cholesky over the whole chip (csrc/gba.hip: tiles of 96 rows =
+ *     16 pose blocks, the trailing update on v_mfma_f64_16x16x4_f64).  Environment ASD_GBA_SOLVE=tiled|single, read at
+ *     asd_ctx_create, forces one form.  A pivot that is not positive fails the trial's solve: the trial is rejected and lambda grows,
+ *     which is what g2o does when LinearSolverEigen / LinearSolverDense report a failed factorisation (linear_solver_eigen.h:
+ *     105-110: solve() returns false when the LLT did not succeed; optimization_algorithm_levenberg.cpp:126-127 sets tempChi to the
+ *     largest double, rho < 0).
+ *   - Pinned against the reference's g2o with its own solver (BlockSolverX + LinearSolverEigen) in tests/test_gba.py: iterations
+ *     and trials per iteration exact, the estimates within 4 x S, S = the distance between three reference runs (two roundings of
+ *     the sparse solver and the dense one; tests/golden/make_gba_golden.py).
+ * Limits (ASD_ERR_CAPACITY beyond them, asd_last_error says which): ASD_GBA_MAX_FREE_POSES free poses, ASD_GBA_MAX_EDGES edges,
+ * ASD_GBA_MAX_POINTS points.  The partial-sum limit of asd_local_ba's control does not apply.
+ * ASD_ERR_INVALID while a run of asd_local_ba_submit or a call started with asd_track_async is outstanding: they share the
+ * solver's device buffers.  asd_local_ba before and after returns the bits it returns without this call. */
+#define ASD_GBA_MAX_FREE_POSES 2048
+#define ASD_GBA_MAX_EDGES (4 * 1024 * 1024)
+#define ASD_GBA_MAX_POINTS (2 * 1024 * 1024)
+#define ASD_GBA_TILED_FROM 40
+int asd_bundle_adjustment(asd_ctx* ctx, asd_gba_problem* problem, asd_gba_result* result);
+/* Test aid: the forms of the context's last asd_bundle_adjustment.  out = {dense solve: 0 = k_ba_solve_lds, 1 = k_ba_chol_lds,
+ * 2 = k_ba_chol (the single-workgroup solvers, by size as in asd_debug_local_ba_forms), 3 = the tiled Cholesky, -1 = none (no edge);
+ * nPf, nLa, Ea: free poses, landmarks and edges of the active structure; tiles per side of the tiled form (ceil(nPf / 16)), 0 for
+ * the other forms}.  All -1 before any call. */
+int32_t asd_debug_gba_forms(const asd_ctx* ctx, int32_t out[5]);
+/* Test aid: the trials (solves, accepted and rejected) each iteration of the context's last asd_bundle_adjustment took, as g2o's
+ * levenbergIteration() reports them behind an iteration.  Writes min(cap, iterations) values, -1 behind them; returns the number
+ * of iterations recorded (0 before any call, and for a call that ran none). */
+int32_t asd_debug_gba_trials(const asd_ctx* ctx, int32_t* out, int32_t cap);
+
 /* Converter::toSE3Quat / toCvMat (Converter.cc:37-71): f32 4x4 <-> f64 quaternion + t. */
 int asd_tcw_to_pose7(const float* Tcw16, double* pose7);
 int asd_pose7_to_tcw(const double* pose7, float* Tcw16);
@@ -930,7 +1000,7 @@ typedef struct asd_pnp_ransac_debug {
 int32_t asd_debug_pnp_ransac(const asd_ctx* ctx, int32_t problem, int32_t which, asd_pnp_ransac_debug* out);
 /* Initializer (src/vslam/src/Initializer.cc): Initializer::Initialize (:43-120) for a batch of frame pairs -- the step of
  * Tracking::MonocularInitialization (Tracking.cc:385-438, Initializer(frame, 1.0, 200)) between SearchForInitialization (asd_match_init) and
- * the first map.  GlobalBundleAdjustemnt(20) on the two-keyframe map, which the reference runs next, is not part of the library.  One problem
+ * the first map.  GlobalBundleAdjustemnt(20) on the two-keyframe map, which the reference runs next, is asd_bundle_adjustment.  One problem
  * = one Initialize call:
  *  in      n1, keys1[n1][2]        mvKeys1 = the reference frame's mvKeysUn pt (:37), f32
  *          n2, keys2[n2][2]        mvKeys2 = the current frame's mvKeysUn pt (:49), f32
