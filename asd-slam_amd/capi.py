@@ -94,6 +94,16 @@ class asd_gba_result(C.Structure):
     _fields_ = [("edge_chi2", C.c_void_p), ("chi2", C.c_double), ("iterations", C.c_int32), ("trials", C.c_int32)]
 
 
+class asd_essgraph_problem(C.Structure):
+    _fields_ = [("n_kf", C.c_int32), ("n_edges", C.c_int32), ("sim3", C.c_void_p), ("fixed", C.c_void_p), ("e_i", C.c_void_p),
+                ("e_j", C.c_void_p), ("e_meas", C.c_void_p), ("fix_scale", C.c_int32), ("n_iterations", C.c_int32),
+                ("Tcw_out", C.c_void_p), ("n_mp", C.c_int32), ("mp_ref", C.c_void_p), ("mp_Xw", C.c_void_p)]
+
+
+class asd_essgraph_result(C.Structure):
+    _fields_ = [("edge_chi2", C.c_void_p), ("chi2", C.c_double), ("iterations", C.c_int32), ("trials", C.c_int32)]
+
+
 class asd_sim3_ransac_problem(C.Structure):
     _fields_ = [("n", C.c_int32), ("X1c", C.c_void_p), ("X2c", C.c_void_p), ("max_err1", C.c_void_p), ("max_err2", C.c_void_p),
                 ("K1", C.c_float * 4), ("K2", C.c_float * 4), ("fix_scale", C.c_int32), ("min_inliers", C.c_int32), ("n_iter", C.c_int32),
@@ -1187,6 +1197,41 @@ class AsdHip:
         r = asd_gba_result(chi2.ctypes.data, 0.0, 0, 0)
         self._chk(self.lib.asd_bundle_adjustment(self.ctx, C.byref(p), C.byref(r)))
         return dict(poses=poses, points=points, edge_chi2=chi2[:E], chi2=r.chi2, iterations=int(r.iterations), trials=int(r.trials))
+
+    def optimize_essential_graph(self, prob, n_iterations=None, tail=True):
+        """Optimizer::OptimizeEssentialGraph (Optimizer.cc:737-1000) -- asd_optimize_essential_graph.  prob: the flat arrays of
+        asd_essgraph_problem (sim3 [K][8], fixed, e_i, e_j, e_meas [E][8], fix_scale, n_iterations, optionally mp_ref, mp_Xw).
+        Returns dict(sim3, Tcw, points, edge_chi2, chi2, iterations, trials)."""
+        sim3 = _c(prob["sim3"], np.float64).reshape(-1, 8).copy()
+        fixed = _c(prob["fixed"], np.uint8)
+        e_i, e_j = _c(prob["e_i"], np.int32), _c(prob["e_j"], np.int32)
+        e_meas = _c(prob["e_meas"], np.float64).reshape(-1, 8)
+        K, E = len(sim3), len(e_i)
+        mp_ref = _c(prob.get("mp_ref", np.zeros(0, np.int32)), np.int32)
+        mp_Xw = _c(prob.get("mp_Xw", np.zeros((0, 3), np.float32)), np.float32).reshape(-1, 3).copy()
+        M = len(mp_ref) if tail else 0
+        Tcw = np.zeros((K, 16), np.float32)
+        chi2 = np.zeros(max(E, 1), np.float64)
+        its = int(prob["n_iterations"] if n_iterations is None else n_iterations)
+        p = asd_essgraph_problem(K, E, sim3.ctypes.data, fixed.ctypes.data, e_i.ctypes.data, e_j.ctypes.data, e_meas.ctypes.data,
+                                 int(prob["fix_scale"]), its, Tcw.ctypes.data if tail else None, M, mp_ref.ctypes.data, mp_Xw.ctypes.data)
+        r = asd_essgraph_result(chi2.ctypes.data, 0.0, 0, 0)
+        self._chk(self.lib.asd_optimize_essential_graph(self.ctx, C.byref(p), C.byref(r)))
+        return dict(sim3=sim3, Tcw=Tcw, points=mp_Xw, edge_chi2=chi2[:E], chi2=r.chi2, iterations=int(r.iterations), trials=int(r.trials))
+
+    def essgraph_forms(self):
+        """[active vertices, free active vertices, active edges, tiles per side] -- asd_debug_essgraph_forms"""
+        out = np.zeros(4, np.int32)
+        self.lib.asd_debug_essgraph_forms.restype = C.c_int32
+        self._chk(self.lib.asd_debug_essgraph_forms(self.ctx, _p(out)))
+        return [int(v) for v in out]
+
+    def essgraph_trials(self, cap=256):
+        """trials per iteration of the last optimize_essential_graph -- asd_debug_essgraph_trials"""
+        out = np.zeros(cap, np.int32)
+        self.lib.asd_debug_essgraph_trials.restype = C.c_int32
+        n = int(self.lib.asd_debug_essgraph_trials(self.ctx, _p(out), C.c_int32(cap)))
+        return [int(v) for v in out[:min(n, cap)]]
 
     def gba_forms(self):
         """[dense solve 0 solve_lds / 1 chol_lds / 2 chol / 3 tiled / -1 none, nPf, nLa, Ea, tiles] -- asd_debug_gba_forms"""

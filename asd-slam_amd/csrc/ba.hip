@@ -2904,11 +2904,8 @@ int asd_local_ba(asd_ctx* ctx, asd_ba_problem* pr, asd_ba_result* res) {
   int rc = local_ba_check(ctx, pr, res);
   if (rc != ASD_OK) return rc;
   if (asd_track_busy(ctx, "asd_local_ba")) return ASD_ERR_INVALID;   // runs on the context's stream behind the outstanding stage: use the lane
+  if (ba_lane_busy(ctx, "asd_local_ba")) return ASD_ERR_INVALID;
   BaState* s = ba_state(ctx);
-  if (lane_outstanding(s)) {
-    ctx->set_error("asd_local_ba: a run submitted with asd_local_ba_submit is outstanding (the solver's device buffers are in use); call asd_local_ba_wait first");
-    return ASD_ERR_INVALID;
-  }
   return local_ba_impl(ctx, s, pr, res, ctx->stream, ctx->ev0, ctx->ev1, &ctx->ms_ba);
 }
 
@@ -3307,17 +3304,20 @@ int gba_impl(asd_ctx* ctx, BaState* s, asd_gba_problem* pr, asd_gba_result* res)
 
 }  // namespace
 
+bool ba_lane_busy(asd_ctx* ctx, const char* who) {
+  if (!ctx->ba || !lane_outstanding(static_cast<BaState*>(ctx->ba))) return false;
+  ctx->set_error("%s: a run submitted with asd_local_ba_submit is outstanding (the solver's device buffers are in use); call asd_local_ba_wait first", who);
+  return true;
+}
+
 extern "C" {
 
 int asd_bundle_adjustment(asd_ctx* ctx, asd_gba_problem* pr, asd_gba_result* res) {
   int rc = gba_check(ctx, pr, res);
   if (rc != ASD_OK) return rc;
   if (asd_track_busy(ctx, "asd_bundle_adjustment")) return ASD_ERR_INVALID;
+  if (ba_lane_busy(ctx, "asd_bundle_adjustment")) return ASD_ERR_INVALID;
   BaState* s = ba_state(ctx);
-  if (lane_outstanding(s)) {
-    ctx->set_error("asd_bundle_adjustment: a run submitted with asd_local_ba_submit is outstanding (the solver's device buffers are in use); call asd_local_ba_wait first");
-    return ASD_ERR_INVALID;
-  }
   return gba_impl(ctx, s, pr, res);
 }
 

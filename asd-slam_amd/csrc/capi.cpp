@@ -160,6 +160,7 @@ int asd_ctx_destroy(asd_ctx* ctx) {
   bow_free(ctx);
   sim3_free(ctx);
   sim3_ransac_free(ctx);
+  essgraph_free(ctx);
   pnp_ransac_free(ctx);
   initializer_free(ctx);
   kfdb_free(ctx);
@@ -262,6 +263,7 @@ int asd_last_stage_ms(const asd_ctx* ctx, const char* stage, float* ms) {
   else if (!strcmp(stage, "ba")) *ms = ctx->ms_ba;
   else if (!strcmp(stage, "sim3")) *ms = ctx->ms_sim3;
   else if (!strcmp(stage, "sim3_ransac")) *ms = ctx->ms_sim3_ransac;
+  else if (!strcmp(stage, "essgraph")) *ms = ctx->ms_essgraph;
   else if (!strcmp(stage, "pnp_ransac")) *ms = ctx->ms_pnp_ransac;
   else if (!strcmp(stage, "initializer")) *ms = ctx->ms_initializer;
   else if (!strcmp(stage, "initializer_hyp")) *ms = ctx->ms_initializer_hyp;

@@ -350,6 +350,9 @@ struct asd_ctx {
   // ---- keyframe database (state private to kfdb.hip)
   void* kfdb = nullptr;
 
+  // ---- OptimizeEssentialGraph: device buffers and the last call's test aids (state private to essgraph.hip)
+  void* essgraph = nullptr;
+
   // ---- per-layer profiling (asd_profile_enable).  The extraction worker enqueues forwards while the caller enables /
   // reads the profile: every access to the prof_* fields below happens under prof_mutex.
   std::mutex prof_mutex;
@@ -364,7 +367,7 @@ struct asd_ctx {
 
   // ---- timing
   hipEvent_t ev0 = nullptr, ev1 = nullptr, ev2 = nullptr;
-  float ms_asdnet = 0, ms_extract = 0, ms_match = 0, ms_ba = 0, ms_sim3 = 0, ms_kfdb = 0, ms_sim3_ransac = 0, ms_pnp_ransac = 0, ms_initializer = 0, ms_initializer_hyp = 0;
+  float ms_asdnet = 0, ms_extract = 0, ms_match = 0, ms_ba = 0, ms_sim3 = 0, ms_kfdb = 0, ms_sim3_ransac = 0, ms_pnp_ransac = 0, ms_initializer = 0, ms_initializer_hyp = 0, ms_essgraph = 0;
 
   // the extraction worker thread reports errors too: the message is written under a lock, and asd_last_error hands
   // out a copy that stays put until the next call of asd_last_error on this context
@@ -415,6 +418,7 @@ void sim3_ransac_free(asd_ctx* ctx);
 void pnp_ransac_free(asd_ctx* ctx);
 void initializer_free(asd_ctx* ctx);
 void kfdb_free(asd_ctx* ctx);
+void essgraph_free(asd_ctx* ctx);
 const char* kfdb_host_error();   // the message of this thread's last asd_bow_score (a call without a context)
 // The claim replay that makes d_src, to run in FRONT of the solver inside its workgroup (k_resolve_pose, ba.hip) instead of as a kernel of
 // its own: args = the Resolve2Args of resolve2.h (both translation units include it), kind 0 / 1, nq = its query count, lds = the

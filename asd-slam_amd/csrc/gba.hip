@@ -307,7 +307,7 @@ int gba_clear_enqueue(asd_ctx* ctx, hipStream_t st, double* A, int n, const int*
 }
 
 int gba_solve_enqueue(asd_ctx* ctx, hipStream_t st, double* A, const double* b, double* x, int n, const int* done, int* chol_ok, bool mfma) {
-  if (n <= 0 || n % 6) { ctx->set_error("gba_solve_enqueue: n = %d is not a positive multiple of 6", n); return ASD_ERR_INVALID; }
+  if (n <= 0) { ctx->set_error("gba_solve_enqueue: n = %d is not positive", n); return ASD_ERR_INVALID; }
   static AsdPerDeviceOnce attr_set;   // the dynamic-LDS attribute is per device
   if (attr_set.need(ctx->cfg.device)) {
     ASD_HIP_CHECK(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(k_gba_potrf), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kPotrfLds));

@@ -9,9 +9,11 @@ struct Sim3d {  // quaternion (x,y,z,w) -- NOT renormalised, as in the reference
   double qx, qy, qz, qw, tx, ty, tz, s;
 };
 
-// Eigen::Quaterniond(Matrix3d) (Eigen/src/Geometry/Quaternion.h, quaternionbase_assign_impl<Other,3,3>), R row-major
+// Eigen::Quaterniond(Matrix3d) (Eigen/src/Geometry/Quaternion.h, quaternionbase_assign_impl<Other,3,3>), R row-major.
+// kEigen: mat.trace() in Eigen's own order -- an unrolled reduction over three elements splits in halves, R00 + (R11 + R22) (see s3_mul)
+template <bool kEigen = false>
 ASD_HD void s3_quat_of_rot(const double R[9], double& x, double& y, double& z, double& w) {
-  double t = R[0] + R[4] + R[8];
+  double t = kEigen ? R[0] + (R[4] + R[8]) : R[0] + R[4] + R[8];
   if (t > 0) {
     t = sqrt(t + 1.0);
     w = 0.5 * t;
@@ -37,10 +39,13 @@ ASD_HD void s3_quat_of_rot(const double R[9], double& x, double& y, double& z, d
   }
 }
 
-// Sim3(const Vector7d& update) (sim3.h:70-142): update = (omega, upsilon, sigma), with the eps = 1e-5 branches as written there
+// Sim3(const Vector7d& update) (sim3.h:70-142): update = (omega, upsilon, sigma), with the eps = 1e-5 branches as written there.
+// kEigen: the sums in the order the reference's Eigen takes them (see s3_mul): omega.norm() of a Vector3d is an unrolled, unvectorised
+// reduction that splits in halves, x^2 + (y^2 + z^2)
+template <bool kEigen = false>
 ASD_HD Sim3d s3_exp(const double u[7]) {
   const double wx = u[0], wy = u[1], wz = u[2], sigma = u[6];
-  const double theta = sqrt(wx * wx + wy * wy + wz * wz);
+  const double theta = kEigen ? sqrt(wx * wx + (wy * wy + wz * wz)) : sqrt(wx * wx + wy * wy + wz * wz);
   const double O[9] = {0, -wz, wy, wz, 0, -wx, -wy, wx, 0};
   double O2[9];
 #pragma unroll
@@ -87,20 +92,32 @@ ASD_HD Sim3d s3_exp(const double u[7]) {
     R[i] = (theta < eps) ? (I + O[i]) + O2[i] : (I + ra * O[i]) + rb * O2[i];
     W[i] = (A * O[i] + B * O2[i]) + Cc * I;
   }
-  s3_quat_of_rot(R, o.qx, o.qy, o.qz, o.qw);
+  s3_quat_of_rot<kEigen>(R, o.qx, o.qy, o.qz, o.qw);
   o.tx = W[0] * u[3] + W[1] * u[4] + W[2] * u[5];
   o.ty = W[3] * u[3] + W[4] * u[4] + W[5] * u[5];
   o.tz = W[6] * u[3] + W[7] * u[4] + W[8] * u[5];
   return o;
 }
 
-// Sim3::operator* (sim3.h:270-276): r = a.r * b.r (Eigen's quaternion product), t = a.s * (a.r * b.t) + a.t, s = a.s * b.s
+// Sim3::operator* (sim3.h:270-276): r = a.r * b.r (Eigen's quaternion product), t = a.s * (a.r * b.t) + a.t, s = a.s * b.s.
+// kEigen: the quaternion product with the association of Eigen's SSE2 kernel for doubles (Geometry_SSE.h:60-109), which is what the
+// reference's x86-64 build runs -- the same eight products, paired differently.  The essential graph differentiates through this
+// product with delta = 1e-9 and then compares chi2 of rejected trials to 1e-7: there the pairing shows (essgraph.hip).
+// OptimizeSim3 (sim3.hip) keeps the plain form it was pinned with.
+template <bool kEigen = false>
 ASD_HD Sim3d s3_mul(const Sim3d& a, const Sim3d& b) {
   Sim3d o;
-  o.qw = a.qw * b.qw - a.qx * b.qx - a.qy * b.qy - a.qz * b.qz;
-  o.qx = a.qw * b.qx + a.qx * b.qw + a.qy * b.qz - a.qz * b.qy;
-  o.qy = a.qw * b.qy + a.qy * b.qw + a.qz * b.qx - a.qx * b.qz;
-  o.qz = a.qw * b.qz + a.qz * b.qw + a.qx * b.qy - a.qy * b.qx;
+  if (kEigen) {
+    o.qx = (a.qw * b.qx + a.qy * b.qz) - (a.qz * b.qy - a.qx * b.qw);
+    o.qy = (a.qw * b.qy + a.qy * b.qw) + (a.qz * b.qx - a.qx * b.qz);
+    o.qz = (a.qw * b.qz - a.qy * b.qx) + (a.qz * b.qw + a.qx * b.qy);
+    o.qw = (a.qw * b.qw - a.qy * b.qy) - (a.qz * b.qz + a.qx * b.qx);
+  } else {
+    o.qw = a.qw * b.qw - a.qx * b.qx - a.qy * b.qy - a.qz * b.qz;
+    o.qx = a.qw * b.qx + a.qx * b.qw + a.qy * b.qz - a.qz * b.qy;
+    o.qy = a.qw * b.qy + a.qy * b.qw + a.qz * b.qx - a.qx * b.qz;
+    o.qz = a.qw * b.qz + a.qz * b.qw + a.qx * b.qy - a.qy * b.qx;
+  }
   const double bt[3] = {b.tx, b.ty, b.tz};
   double r[3];
   quat_rotate(a.qx, a.qy, a.qz, a.qw, bt, r);
@@ -122,13 +139,123 @@ ASD_HD Sim3d s3_inverse(const Sim3d& a) {
   return o;
 }
 
+// Sim3::map (sim3.h:144-146): s * (r * xyz) + t
+ASD_HD void s3_map(const Sim3d& S, const double v[3], double out[3]) {
+  double r[3];
+  quat_rotate(S.qx, S.qy, S.qz, S.qw, v, r);
+  out[0] = S.s * r[0] + S.tx; out[1] = S.s * r[1] + S.ty; out[2] = S.s * r[2] + S.tz;
+}
+
+// Eigen::Quaterniond::toRotationMatrix (the quaternion as it is, not renormalised), R row-major
+ASD_HD void s3_rot_of_quat(const Sim3d& S, double R[9]) {
+  const double tx = 2 * S.qx, ty = 2 * S.qy, tz = 2 * S.qz;
+  const double twx = tx * S.qw, twy = ty * S.qw, twz = tz * S.qw;
+  const double txx = tx * S.qx, txy = ty * S.qx, txz = tz * S.qx, tyy = ty * S.qy, tyz = tz * S.qy, tzz = tz * S.qz;
+  R[0] = 1 - (tyy + tzz); R[1] = txy - twz; R[2] = txz + twy;
+  R[3] = txy + twz; R[4] = 1 - (txx + tzz); R[5] = tyz - twx;
+  R[6] = txz - twy; R[7] = tyz + twx; R[8] = 1 - (txx + tyy);
+}
+
+// W.lu().solve(t) for a 3x3 W (Eigen's PartialPivLU, unblocked: the largest |entry| of the column at or below the diagonal is the
+// pivot, the first one on a tie), W row-major.  Written with static indices only: rows are swapped by value.  As Eigen 3.2.10 does it:
+// `col /= pivot` is a true division (scalar_quotient_op), and the unrolled triangular solves subtract the SUM of a row's products
+// (triangular_solver_unroller), where a hand-written substitution would subtract them one by one.
+ASD_HD void s3_lu_solve3(const double W[9], const double t[3], double x[3]) {
+  double a0[3] = {W[0], W[1], W[2]}, a1[3] = {W[3], W[4], W[5]}, a2[3] = {W[6], W[7], W[8]};
+  double b0 = t[0], b1 = t[1], b2 = t[2];
+#define S3_SWAP_ROWS(p, q, bp, bq) do { for (int c_ = 0; c_ < 3; ++c_) { const double h_ = p[c_]; p[c_] = q[c_]; q[c_] = h_; } const double g_ = bp; bp = bq; bq = g_; } while (0)
+  {
+    int piv = 0;
+    double big = fabs(a0[0]);
+    if (fabs(a1[0]) > big) { big = fabs(a1[0]); piv = 1; }
+    if (fabs(a2[0]) > big) { piv = 2; }
+    if (piv == 1) S3_SWAP_ROWS(a0, a1, b0, b1);
+    if (piv == 2) S3_SWAP_ROWS(a0, a2, b0, b2);
+  }
+  a1[0] /= a0[0]; a2[0] /= a0[0];
+  a1[1] -= a1[0] * a0[1]; a1[2] -= a1[0] * a0[2];
+  a2[1] -= a2[0] * a0[1]; a2[2] -= a2[0] * a0[2];
+  if (fabs(a2[1]) > fabs(a1[1])) S3_SWAP_ROWS(a1, a2, b1, b2);
+#undef S3_SWAP_ROWS
+  a2[1] /= a1[1];
+  a2[2] -= a2[1] * a1[2];
+  // L y = P b (unit lower), U x = y
+  const double y0 = b0;
+  const double y1 = b1 - a1[0] * y0;
+  const double y2 = b2 - (a2[0] * y0 + a2[1] * y1);
+  x[2] = y2 / a2[2];
+  x[1] = (y1 - a1[2] * x[2]) / a1[1];
+  x[0] = (y0 - (a0[1] * x[1] + a0[2] * x[2])) / a0[0];
+}
+
+// Sim3::log (sim3.h:152-234), with the eps = 1e-5 branches as written there: res = (omega, upsilon, sigma)
+ASD_HD void s3_log(const Sim3d& S, double res[7]) {
+  const double sigma = log(S.s);
+  double R[9];
+  s3_rot_of_quat(S, R);
+  const double d = 0.5 * (R[0] + R[4] + R[8] - 1);
+  const double dR[3] = {R[7] - R[5], R[2] - R[6], R[3] - R[1]};   // deltaR (se3_ops.hpp)
+  const double eps = 0.00001;
+  double A, B, Cc, k;
+  if (fabs(sigma) < eps) {
+    Cc = 1;
+    if (d > 1 - eps) {
+      k = 0.5; A = 1. / 2.; B = 1. / 6.;
+    } else {
+      const double theta = acos(d);
+      const double theta2 = theta * theta;
+      k = theta / (2 * sqrt(1 - d * d));
+      A = (1 - cos(theta)) / (theta2);
+      B = (theta - sin(theta)) / (theta2 * theta);
+    }
+  } else {
+    Cc = (S.s - 1) / sigma;
+    if (d > 1 - eps) {
+      const double sigma2 = sigma * sigma;
+      k = 0.5;
+      A = ((sigma - 1) * S.s + 1) / (sigma2);
+      B = ((0.5 * sigma2 - sigma + 1) * S.s) / (sigma2 * sigma);
+    } else {
+      const double theta = acos(d);
+      k = theta / (2 * sqrt(1 - d * d));
+      const double theta2 = theta * theta;
+      const double a = S.s * sin(theta);
+      const double b = S.s * cos(theta);
+      const double c = theta2 + sigma * sigma;
+      A = (a * sigma + (1 - b) * theta) / (theta * c);
+      B = (Cc - ((b - 1) * sigma + a * theta) / (c)) * 1. / (theta2);
+    }
+  }
+  const double wx = k * dR[0], wy = k * dR[1], wz = k * dR[2];
+  const double O[9] = {0, -wz, wy, wz, 0, -wx, -wy, wx, 0};
+  double W[9];
+#pragma unroll
+  for (int i = 0; i < 3; ++i)
+#pragma unroll
+    for (int j = 0; j < 3; ++j) {
+      // B * Omega * Omega is (B * Omega) * Omega in the reference's expression
+      const double bo2 = (B * O[i * 3]) * O[j] + (B * O[i * 3 + 1]) * O[3 + j] + (B * O[i * 3 + 2]) * O[6 + j];
+      W[i * 3 + j] = (A * O[i * 3 + j] + bo2) + Cc * (i == j ? 1.0 : 0.0);
+    }
+  const double t[3] = {S.tx, S.ty, S.tz};
+  double ups[3];
+  s3_lu_solve3(W, t, ups);
+  res[0] = wx; res[1] = wy; res[2] = wz; res[3] = ups[0]; res[4] = ups[1]; res[5] = ups[2]; res[6] = sigma;
+}
+
+// EdgeSim3::computeError (types_seven_dof_expmap.h:106-114): log(C * S_i * S_j^-1)
+ASD_HD void s3_edge_error(const Sim3d& C, const Sim3d& Si, const Sim3d& Sj, double e[7]) {
+  s3_log(s3_mul<true>(s3_mul<true>(C, Si), s3_inverse(Sj)), e);
+}
+
 // VertexSim3Expmap::oplusImpl (types_seven_dof_expmap.h:60-69)
+template <bool kEigen = false>
 ASD_HD Sim3d s3_oplus(const Sim3d& est, const double u[7], bool fix_scale) {
   double v[7];
 #pragma unroll
   for (int k = 0; k < 7; ++k) v[k] = u[k];
   if (fix_scale) v[6] = 0;
-  return s3_mul(s3_exp(v), est);
+  return s3_mul<kEigen>(s3_exp<kEigen>(v), est);
 }
 
 // obs - cam_map(project(S.map(X))): the error of EdgeSim3ProjectXYZ with (S, X = P2c, K1, obs1) and of EdgeInverseSim3ProjectXYZ with

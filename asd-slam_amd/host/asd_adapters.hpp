@@ -14,6 +14,7 @@
 // Error behaviour follows the reference (no exceptions on the data path, "return 0 / -1" on
 // failure) except construction, which throws std::runtime_error if no HIP device is usable.
 #pragma once
+#include <cmath>
 #include <cstdint>
 #include <cstdlib>
 #include <deque>
@@ -468,6 +469,214 @@ struct Optimizer {
   static BAResult GlobalBundleAdjustemnt(Context& c, const std::vector<BAKeyFrame>& allKeyFrames, const std::vector<BAMapPoint>& allMapPoints,
                                          const Camera& K, int nIterations = 5, const volatile int32_t* pbStopFlag = nullptr, bool bRobust = true) {
     return BundleAdjustment(c, allKeyFrames, allMapPoints, K, nIterations, pbStopFlag, bRobust);
+  }
+
+  // g2o::Sim3 as the 8 doubles of the C ABI (qx qy qz qw tx ty tz s), with the three operations the gather of OptimizeEssentialGraph
+  // needs, in f64 on the host: Sim3(R, t, s) (Eigen's Quaterniond(Matrix3d), not renormalised), inverse() and operator* (sim3.h:64-67,
+  // :237-240, :270-276)
+  struct Sim3 {
+    double v[8] = {0, 0, 0, 1, 0, 0, 0, 1};
+    static void rotate(const double* q, const double* p, double* out) {   // Eigen: v + w uv + q x uv, uv = 2 q x v
+      double ux = q[1] * p[2] - q[2] * p[1], uy = q[2] * p[0] - q[0] * p[2], uz = q[0] * p[1] - q[1] * p[0];
+      ux += ux; uy += uy; uz += uz;
+      out[0] = p[0] + q[3] * ux + (q[1] * uz - q[2] * uy);
+      out[1] = p[1] + q[3] * uy + (q[2] * ux - q[0] * uz);
+      out[2] = p[2] + q[3] * uz + (q[0] * uy - q[1] * ux);
+    }
+    static Sim3 fromTcw(const float* T) {   // Converter::toMatrix3d / toVector3d of a float pose, then Sim3(Rcw, tcw, 1.0) (:783-785)
+      double R[9];
+      for (int r = 0; r < 3; ++r) for (int c = 0; c < 3; ++c) R[3 * r + c] = T[4 * r + c];
+      Sim3 o;
+      double* q = o.v;
+      double t = R[0] + R[4] + R[8];
+      if (t > 0) {
+        t = std::sqrt(t + 1.0);
+        q[3] = 0.5 * t;
+        t = 0.5 / t;
+        q[0] = (R[7] - R[5]) * t; q[1] = (R[2] - R[6]) * t; q[2] = (R[3] - R[1]) * t;
+      } else {
+        int i = 0;
+        if (R[4] > R[0]) i = 1;
+        if (R[8] > R[4 * i]) i = 2;
+        const int j = (i + 1) % 3, k = (j + 1) % 3;
+        t = std::sqrt(R[4 * i] - R[4 * j] - R[4 * k] + 1.0);
+        q[i] = 0.5 * t;
+        t = 0.5 / t;
+        q[3] = (R[3 * k + j] - R[3 * j + k]) * t;
+        q[j] = (R[3 * j + i] + R[3 * i + j]) * t;
+        q[k] = (R[3 * k + i] + R[3 * i + k]) * t;
+      }
+      for (int r = 0; r < 3; ++r) o.v[4 + r] = T[4 * r + 3];
+      o.v[7] = 1.0;
+      return o;
+    }
+    Sim3 inverse() const {
+      Sim3 o;
+      o.v[0] = -v[0]; o.v[1] = -v[1]; o.v[2] = -v[2]; o.v[3] = v[3];
+      const double k = -1. / v[7];
+      const double p[3] = {k * v[4], k * v[5], k * v[6]};
+      rotate(o.v, p, o.v + 4);
+      o.v[7] = 1. / v[7];
+      return o;
+    }
+    Sim3 operator*(const Sim3& b) const {
+      Sim3 o;
+      const double *a = v, *c = b.v;
+      o.v[3] = a[3] * c[3] - a[0] * c[0] - a[1] * c[1] - a[2] * c[2];
+      o.v[0] = a[3] * c[0] + a[0] * c[3] + a[1] * c[2] - a[2] * c[1];
+      o.v[1] = a[3] * c[1] + a[1] * c[3] + a[2] * c[0] - a[0] * c[2];
+      o.v[2] = a[3] * c[2] + a[2] * c[3] + a[0] * c[1] - a[1] * c[0];
+      double r[3];
+      rotate(a, c + 4, r);
+      for (int k = 0; k < 3; ++k) o.v[4 + k] = a[7] * r[k] + a[4 + k];
+      o.v[7] = a[7] * c[7];
+      return o;
+    }
+  };
+  // What Optimizer::OptimizeEssentialGraph reads from a KeyFrame and a MapPoint, flat.  Other keyframes are named by their index in
+  // the caller's vector (GetAllKeyFrames(): no bad keyframe -- the reference dereferences a null vertex at :954 for one); the
+  // reference's sets of KeyFrame* are walked in the order the vectors list them.
+  struct EGKeyFrame {
+    unsigned long mnId = 0;
+    float Tcw[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};   // GetPose()
+    int parent = -1;                                    // GetParent()
+    std::vector<int> children;                          // hasChild()
+    std::vector<int> loopEdges;                         // GetLoopEdges()
+    std::vector<std::pair<int, int>> covisibles;        // (keyframe, weight) ordered by weight: mvpOrderedConnectedKeyFrames / mvOrderedWeights
+    bool hasCorrected = false, hasNonCorrected = false; // CorrectedSim3.find(pKF) / NonCorrectedSim3.find(pKF)
+    Sim3 corrected, nonCorrected;
+    int GetWeight(int other) const {                    // KeyFrame::GetWeight: 0 for a keyframe that is not connected
+      for (const std::pair<int, int>& c : covisibles) if (c.first == other) return c.second;
+      return 0;
+    }
+  };
+  struct EGMapPoint {
+    bool bad = false;                                   // isBad()
+    float Xw[3] = {0, 0, 0};                            // GetWorldPos()
+    int refKF = -1;                                     // GetReferenceKeyFrame()
+    unsigned long mnCorrectedByKF = 0, mnCorrectedReference = 0;
+  };
+  typedef std::vector<std::pair<int, std::vector<int>>> EGLoopConnections;   // map<KeyFrame*, set<KeyFrame*>> in the caller's order
+  // The flat problem of asd_optimize_essential_graph; rows by ascending mnId, row_of[i] = the row of keyframes[i]
+  struct EGProblem {
+    std::vector<int> row_of;
+    std::vector<double> sim3, e_meas;
+    std::vector<uint8_t> fixed;
+    std::vector<int32_t> e_i, e_j;
+  };
+  struct EGResult {   // rc: asd_optimize_essential_graph's, or ASD_ERR_INVALID for a map point whose reference keyframe is not listed
+    int rc = ASD_OK, iterations = 0, trials = 0, n_edges = 0;
+    double chi2 = 0;
+    std::vector<double> sim3;        // [keyframes][8], in the caller's order: the optimised CorrectedSiw
+    std::vector<float> Tcw;          // [keyframes][16]: what pKFi->SetPose gets (:963-965)
+    std::vector<uint8_t> mp_written; // map point i is not bad
+    std::vector<float> Xw;           // [points][3]: what pMP->SetWorldPos gets (:995-996); UpdateNormalAndDepth stays the caller's
+  };
+  // The vertices and edges of :765-939, without a device: vScw (CorrectedSim3 where present, else (Rcw, tcw, 1)), pLoopKF fixed, then
+  // the LoopConnections edges (minFeat = 100 with the pCurKF <-> pLoopKF exemption of :819) and per keyframe -- in the vector's order --
+  // its spanning-tree edge, its loop edges towards smaller ids and its covisibility edges (weight >= minFeat, not the parent, not a
+  // child, not a loop edge, smaller id, not in sInsertedEdges).  Each end's pose is the NonCorrectedSim3 where present; Sji = Sjw * Swi.
+  static EGProblem EssentialGraphProblem(const std::vector<EGKeyFrame>& keyframes, int pLoopKF, int pCurKF, const EGLoopConnections& LoopConnections) {
+    const int nKF = (int)keyframes.size();
+    EGProblem p;
+    std::vector<int> order(nKF);
+    for (int i = 0; i < nKF; ++i) order[i] = i;
+    std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return keyframes[a].mnId < keyframes[b].mnId; });
+    p.row_of.assign(nKF, -1);
+    for (int r = 0; r < nKF; ++r) p.row_of[order[r]] = r;
+    std::vector<Sim3> vScw(nKF);
+    p.sim3.assign((size_t)nKF * 8, 0.0); p.fixed.assign(nKF, 0);
+    for (int i = 0; i < nKF; ++i) {
+      vScw[i] = keyframes[i].hasCorrected ? keyframes[i].corrected : Sim3::fromTcw(keyframes[i].Tcw);   // :774-788
+      for (int k = 0; k < 8; ++k) p.sim3[(size_t)p.row_of[i] * 8 + k] = vScw[i].v[k];
+      if (i == pLoopKF) p.fixed[p.row_of[i]] = 1;                                                        // :790-791
+    }
+    auto add = [&](int i, int j, const Sim3& Sji) {
+      p.e_i.push_back(p.row_of[i]); p.e_j.push_back(p.row_of[j]);
+      p.e_meas.insert(p.e_meas.end(), Sji.v, Sji.v + 8);
+    };
+    const int minFeat = 100;
+    std::vector<std::pair<unsigned long, unsigned long>> sInsertedEdges;
+    auto id_pair = [&](int a, int b) { return std::make_pair(std::min(keyframes[a].mnId, keyframes[b].mnId), std::max(keyframes[a].mnId, keyframes[b].mnId)); };
+    for (const std::pair<int, std::vector<int>>& mit : LoopConnections) {                                // :808-836
+      const int i = mit.first;
+      const Sim3 Swi = vScw[i].inverse();
+      for (int j : mit.second) {
+        if ((keyframes[i].mnId != keyframes[pCurKF].mnId || keyframes[j].mnId != keyframes[pLoopKF].mnId) && keyframes[i].GetWeight(j) < minFeat) continue;
+        add(i, j, vScw[j] * Swi);
+        sInsertedEdges.push_back(id_pair(i, j));
+      }
+    }
+    for (int i = 0; i < nKF; ++i) {                                                                      // :839-939
+      const EGKeyFrame& kf = keyframes[i];
+      const Sim3 Swi = (kf.hasNonCorrected ? kf.nonCorrected : vScw[i]).inverse();
+      auto Sw = [&](int j) { return keyframes[j].hasNonCorrected ? keyframes[j].nonCorrected : vScw[j]; };
+      if (kf.parent >= 0) add(i, kf.parent, Sw(kf.parent) * Swi);
+      for (int l : kf.loopEdges)
+        if (keyframes[l].mnId < kf.mnId) add(i, l, Sw(l) * Swi);
+      for (const std::pair<int, int>& c : kf.covisibles) {
+        if (c.second < minFeat) break;                                                                   // GetCovisiblesByWeight(minFeat)
+        const int n = c.first;
+        if (n == kf.parent || std::find(kf.children.begin(), kf.children.end(), n) != kf.children.end() ||
+            std::find(kf.loopEdges.begin(), kf.loopEdges.end(), n) != kf.loopEdges.end())
+          continue;
+        if (!(keyframes[n].mnId < kf.mnId)) continue;
+        if (std::find(sInsertedEdges.begin(), sInsertedEdges.end(), id_pair(i, n)) != sInsertedEdges.end()) continue;
+        add(i, n, Sw(n) * Swi);
+      }
+    }
+    return p;
+  }
+  // void static OptimizeEssentialGraph(Map* pMap, KeyFrame* pLoopKF, KeyFrame* pCurKF, const KeyFrameAndPose& NonCorrectedSim3,
+  //                                    const KeyFrameAndPose& CorrectedSim3, const map<KeyFrame*, set<KeyFrame*>>& LoopConnections,
+  //                                    const bool& bFixScale)  (Optimizer.cc:737-1000) over asd_optimize_essential_graph: the gather
+  // above, the one call, and what :947-999 write back.  The two Sim3 maps are the hasCorrected / hasNonCorrected fields of the views.
+  static EGResult OptimizeEssentialGraph(Context& c, const std::vector<EGKeyFrame>& keyframes, const std::vector<EGMapPoint>& points, int pLoopKF,
+                                         int pCurKF, const EGLoopConnections& LoopConnections, bool bFixScale, int nIterations = 20) {
+    EGResult out;
+    const int nKF = (int)keyframes.size(), nMP = (int)points.size();
+    EGProblem p = EssentialGraphProblem(keyframes, pLoopKF, pCurKF, LoopConnections);
+    std::vector<int32_t> mp_ref;
+    std::vector<float> X;
+    std::vector<int> mp_of;
+    std::vector<std::pair<unsigned long, int>> kf_of_id(nKF);   // mnCorrectedReference is an mnId: sorted once, looked up per point
+    for (int k = 0; k < nKF; ++k) kf_of_id[k] = std::make_pair(keyframes[k].mnId, k);
+    std::sort(kf_of_id.begin(), kf_of_id.end());
+    for (int i = 0; i < nMP; ++i) {                                                                      // :969-985
+      if (points[i].bad) continue;
+      int r = points[i].refKF;
+      if (points[i].mnCorrectedByKF == keyframes[pCurKF].mnId) {
+        const auto it = std::lower_bound(kf_of_id.begin(), kf_of_id.end(), std::make_pair(points[i].mnCorrectedReference, 0));
+        r = it != kf_of_id.end() && it->first == points[i].mnCorrectedReference ? it->second : -1;
+      }
+      if (r < 0 || r >= nKF) { out.rc = ASD_ERR_INVALID; return out; }   // the reference keyframe is not among the keyframes
+      mp_of.push_back(i); mp_ref.push_back(p.row_of[r]);
+      X.insert(X.end(), points[i].Xw, points[i].Xw + 3);
+    }
+    std::vector<float> T((size_t)nKF * 16 + 1);
+    std::vector<double> edge_chi2(p.e_i.size() + 1);
+    asd_essgraph_problem pr{};
+    pr.n_kf = nKF; pr.n_edges = (int32_t)p.e_i.size();
+    pr.sim3 = p.sim3.data(); pr.fixed = p.fixed.data(); pr.e_i = p.e_i.data(); pr.e_j = p.e_j.data(); pr.e_meas = p.e_meas.data();
+    pr.fix_scale = bFixScale; pr.n_iterations = nIterations;
+    pr.Tcw_out = T.data(); pr.n_mp = (int32_t)mp_of.size(); pr.mp_ref = mp_ref.data(); pr.mp_Xw = X.data();
+    asd_essgraph_result res{};
+    res.edge_chi2 = edge_chi2.data();
+    out.n_edges = pr.n_edges;
+    out.rc = asd_optimize_essential_graph(c.get(), &pr, &res);
+    if (out.rc != ASD_OK) return out;
+    out.iterations = res.iterations; out.trials = res.trials; out.chi2 = res.chi2;
+    out.sim3.assign((size_t)nKF * 8, 0.0); out.Tcw.assign((size_t)nKF * 16, 0.f);
+    out.mp_written.assign(nMP, 0); out.Xw.assign((size_t)nMP * 3, 0.f);
+    for (int i = 0; i < nKF; ++i) {
+      for (int k = 0; k < 8; ++k) out.sim3[(size_t)i * 8 + k] = p.sim3[(size_t)p.row_of[i] * 8 + k];
+      for (int k = 0; k < 16; ++k) out.Tcw[(size_t)i * 16 + k] = T[(size_t)p.row_of[i] * 16 + k];
+    }
+    for (size_t q = 0; q < mp_of.size(); ++q) {
+      out.mp_written[mp_of[q]] = 1;
+      for (int k = 0; k < 3; ++k) out.Xw[(size_t)mp_of[q] * 3 + k] = X[3 * q + k];
+    }
+    return out;
   }
 
   // void static LocalBundleAdjustment(KeyFrame* pKF, bool* pbStopFlag, Map* pMap)  (Optimizer.cc:415): the

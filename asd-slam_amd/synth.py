@@ -260,6 +260,133 @@ def gba_map(n_kf=18, pts_per_kf=40, seed=1, loop_points=0, pix_noise=0.5, outlie
     )
 
 
+def _csr(lists):
+    start = np.zeros(len(lists) + 1, np.int32)
+    for i, l in enumerate(lists):
+        start[i + 1] = start[i] + len(l)
+    flat = np.array([v for l in lists for v in l], np.int32)
+    return start, flat
+
+
+def essential_graph(n_kf=8, seed=1, loop=True, covis=0, drift=0.01, fix_scale=0, n_corrected=3, pts_per_kf=3):
+    """What Optimizer::OptimizeEssentialGraph (reference Optimizer.cc:737-1000) reads from the map after a CorrectLoop, as flat
+    keyframe views (row = position in GetAllKeyFrames(), here by ascending mnId = 2 row + 1):
+    a keyframe trajectory on a circle with accumulated Sim3 drift (rotation and translation noise `drift` per step, and a scale
+    drift unless fix_scale), poses as float Tcw; a spanning tree (parent = the row before, every fourth keyframe the one two before);
+    covisibility lists ordered by weight (parent and children strong, `covis` further neighbours with weights on both sides of
+    minFeat = 100); for n_kf >= 12 one old loop edge pair that is also a strong covisible.
+    With loop: the last keyframe is pCurKF, row 0 pLoopKF; the last n_corrected rows carry a CorrectedSim3 (the pose the loop says
+    they have, in the loop keyframe's scale) and a NonCorrectedSim3 (the drifted pose, scale 1); LoopConnections links pCurKF with
+    pLoopKF (weight below minFeat: the exemption of :819), with row 1 (strong, and listed as a covisible of pCurKF: sInsertedEdges)
+    and the keyframe before pCurKF with pLoopKF (weak: dropped) and row 1 (strong).
+    Without loop nothing is corrected and pCurKF / pLoopKF are still the last row / row 0.
+    Map points: pts_per_kf per keyframe in front of it, every fifth one corrected by pCurKF through another keyframe
+    (mnCorrectedByKF / mnCorrectedReference, :976-985)."""
+    rng = np.random.default_rng(seed)
+    K = int(n_kf)
+    radius = 0.5   # every coordinate stays below 2: a float's last bit there is 1.2e-7
+    Twc_true, Twc_est = [], []
+    sigma = 1.0
+    scales = []
+    for k in range(K):
+        a = 2 * np.pi * k / (K + 1 if loop else 3 * K)
+        Rwc = _rot(np.array([0.0, -a, 0.0])) @ _rot(rng.standard_normal(3) * 0.01)
+        c = np.array([radius * np.sin(a), 0.01 * rng.standard_normal(), radius * (1 - np.cos(a))])
+        T = np.eye(4)
+        T[:3, :3], T[:3, 3] = Rwc, c
+        Twc_true.append(T)
+        if k == 0:
+            Twc_est.append(T.copy())
+        else:
+            rel = np.linalg.inv(Twc_true[k - 1]) @ T
+            if not fix_scale:
+                sigma *= float(np.exp(rng.standard_normal() * drift))
+            rel[:3, :3] = rel[:3, :3] @ _rot(rng.standard_normal(3) * drift)
+            rel[:3, 3] = sigma * rel[:3, 3] + rng.standard_normal(3) * drift * float(np.linalg.norm(rel[:3, 3]))
+            Twc_est.append(Twc_est[k - 1] @ rel)
+        scales.append(sigma)
+    Tcw = np.stack([np.linalg.inv(T) for T in Twc_est]).astype(np.float32)
+    mnId = (2 * np.arange(K) + 1).astype(np.int64)
+    parent = np.array([-1] + [k - 2 if (k % 4 == 0 and k >= 2) else k - 1 for k in range(1, K)], np.int32)
+    children = [[c for c in range(K) if parent[c] == k] for k in range(K)]
+    loops = [[] for _ in range(K)]
+    weights = [dict() for _ in range(K)]
+
+    def connect(a, b, w):
+        weights[a][b] = int(w)
+        weights[b][a] = int(w)
+
+    for k in range(1, K):
+        connect(k, int(parent[k]), 300 + int(rng.integers(0, 100)))
+        if parent[k] != k - 1:
+            connect(k, k - 1, 250 + int(rng.integers(0, 40)))
+        for q in range(covis):
+            o = k - 2 - q
+            if o >= 0 and o not in weights[k]:
+                connect(k, o, int(rng.integers(60, 170)))
+    if K >= 12:
+        a, b = 2, K // 2
+        loops[a].append(b)
+        loops[b].append(a)
+        connect(a, b, 140)
+    cur, lp = K - 1, 0
+    corrected = np.zeros(K, np.uint8)
+    corrected_sim3 = np.zeros((K, 8))
+    noncorrected_sim3 = np.zeros((K, 8))
+    corrected_sim3[:, 3] = corrected_sim3[:, 7] = noncorrected_sim3[:, 3] = noncorrected_sim3[:, 7] = 1.0
+    lc = {}
+    if loop:
+        for r in range(max(K - n_corrected, 1), K):
+            corrected[r] = 1
+            Tt = np.linalg.inv(Twc_true[r])
+            s = scales[r]
+            corrected_sim3[r, :4] = rot_to_quat(Tt[:3, :3])
+            corrected_sim3[r, 4:7] = s * Tt[:3, 3] + rng.standard_normal(3) * 2e-4
+            corrected_sim3[r, 7] = s
+            R32 = Tcw[r, :3, :3].astype(np.float64)
+            noncorrected_sim3[r, :4] = rot_to_quat(R32)
+            noncorrected_sim3[r, 4:7] = Tcw[r, :3, 3].astype(np.float64)
+        lc[cur] = [lp]
+        connect(cur, lp, 70)
+        if K >= 4:
+            lc[cur].append(1)
+            connect(cur, 1, 150)
+            lc[cur - 1] = [lp, 1]
+            connect(cur - 1, lp, 80)
+            connect(cur - 1, 1, 120)
+    cov, cov_w = [], []
+    for k in range(K):
+        order = sorted(weights[k].items(), key=lambda kv: (-kv[1], kv[0]))
+        cov.append([o for o, _ in order])
+        cov_w.append([w for _, w in order])
+    mp_Xw, mp_ref, mp_by, mp_cref = [], [], [], []
+    for k in range(K):
+        for q in range(pts_per_kf):
+            Xc = np.array([rng.uniform(-0.3, 0.3), rng.uniform(-0.2, 0.2), rng.uniform(0.3, 0.8), 1.0])
+            mp_Xw.append((Twc_est[k] @ Xc)[:3])
+            mp_ref.append(k)
+            if loop and len(mp_ref) % 5 == 0:
+                mp_by.append(int(mnId[cur]))
+                mp_cref.append(int(mnId[(k + 1) % K]))
+            else:
+                mp_by.append(0)
+                mp_cref.append(0)
+    child_start, child = _csr(children)
+    loop_start, loop_flat = _csr(loops)
+    cov_start, cov_flat = _csr(cov)
+    _, cov_w_flat = _csr(cov_w)
+    lc_kf = np.array(sorted(lc), np.int32)
+    lc_start, lc_flat = _csr([lc[k] for k in sorted(lc)])
+    return dict(
+        mnId=mnId, Tcw=Tcw.reshape(K, 16), parent=parent, child_start=child_start, child=child, loop_start=loop_start, loop=loop_flat,
+        cov_start=cov_start, cov=cov_flat, cov_w=cov_w_flat, corrected=corrected, corrected_sim3=corrected_sim3,
+        noncorrected=corrected.copy(), noncorrected_sim3=noncorrected_sim3, lc_kf=lc_kf, lc_start=lc_start, lc=lc_flat,
+        loop_kf=np.int32(lp), cur_kf=np.int32(cur), fix_scale=np.int32(fix_scale),
+        mp_Xw=np.array(mp_Xw, np.float32).reshape(-1, 3), mp_ref=np.array(mp_ref, np.int32),
+        mp_corrected_by=np.array(mp_by, np.int64), mp_corrected_ref=np.array(mp_cref, np.int64),
+    )
+
+
 def pose_problem(n=300, seed=2, outlier_frac=0.1, pose_sigma=0.02):
     """Pose-only problem for asd_pose_optimize (reference Optimizer.cc:239-413)."""
     rng = np.random.default_rng(seed)

@@ -735,6 +735,71 @@ int32_t asd_debug_gba_forms(const asd_ctx* ctx, int32_t out[5]);
  * of iterations recorded (0 before any call, and for a call that ran none). */
 int32_t asd_debug_gba_trials(const asd_ctx* ctx, int32_t* out, int32_t cap);
 
+/* ---- essential graph (Sim3 pose graph of a loop closure) --------------------------------- */
+typedef struct asd_essgraph_problem {
+  int32_t n_kf;             /* keyframes, ordered by ascending mnId (Optimizer.cc:765-800)                          */
+  int32_t n_edges;          /* in the caller's insertion order (:808-939)                                          */
+  double*        sim3;      /* [n_kf][8] in/out (qx,qy,qz,qw,tx,ty,tz,s).  On entry vScw: CorrectedSim3 where the   */
+                            /* keyframe has one, else (Rcw, tcw, 1) (:774-788)                                     */
+  const uint8_t* fixed;     /* [n_kf] pKF == pLoopKF (:790); any mask is honoured                                  */
+  const int32_t* e_i;       /* [n_edges] row of vertex 0 (:827)                                                    */
+  const int32_t* e_j;       /* [n_edges] row of vertex 1 (:826)                                                    */
+  const double*  e_meas;    /* [n_edges][8] Sji (:823, :870, :897, :928); the information is the identity (:805)   */
+  int32_t fix_scale;        /* bFixScale (:795)                                                                    */
+  int32_t n_iterations;     /* the reference: 20 (:943)                                                            */
+  /* optional tail (:947-999) */
+  float*         Tcw_out;   /* [n_kf][16] or NULL: [R t/s; 0 1] as float, row major (:957-963)                     */
+  int32_t n_mp;             /* map points to correct (0: none)                                                     */
+  const int32_t* mp_ref;    /* [n_mp] row of the keyframe the point is corrected through: the caller applies the   */
+                            /* mnCorrectedByKF rule of :976-985                                                    */
+  float*         mp_Xw;     /* [n_mp][3] in/out: correctedSwr.map(Srw.map(X)) in f64, stored as float (:988-996)   */
+} asd_essgraph_problem;
+
+typedef struct asd_essgraph_result {
+  double*  edge_chi2;       /* [n_edges] e->chi2() of the stored errors                                            */
+  double   chi2;            /* activeChi2() of the stored errors                                                   */
+  int32_t  iterations;      /* what g2o's optimize() returns: iterations run, -1 without an active vertex (no edge) */
+  int32_t  trials;          /* solves, accepted and rejected                                                       */
+} asd_essgraph_result;
+
+/* Numeric core of Optimizer::OptimizeEssentialGraph (Optimizer.cc:737-1000), which LoopClosing::CorrectLoop calls at
+ * LoopClosing.cc:587: a VertexSim3Expmap per keyframe, an EdgeSim3 per edge, initializeOptimization(); optimize(n_iterations), then
+ * the pose recovery and the map-point correction.  Which edges there are and what they measure (:808-939) is the caller's part
+ * (host/asd_adapters.hpp: asd::Optimizer::OptimizeEssentialGraph); with this call nothing in the reference's Tracking, LocalMapping
+ * or LoopClosing needs g2o.
+ *   - Error: EdgeSim3::computeError, log(C * S_i * S_j^-1) (types_seven_dof_expmap.h:106-114), f64.
+ *   - Jacobians: g2o's numeric ones (base_binary_edge.hpp:130-206): central differences, delta = 1e-9, through oplusImpl =
+ *     Sim3(update) * estimate with update[6] = 0 under fix_scale (types_seven_dof_expmap.h:60-69).  No Jacobian for a fixed vertex.
+ *   - Levenberg: setUserLambdaInit(1e-16) (:750) and g2o's schedule (optimization_algorithm_levenberg.cpp:61-189); no robust kernel,
+ *     no stop flag.  The system of the free vertices that have an edge (n = 7 x their number) is factored densely in f64 by the
+ *     tiled Cholesky of asd_bundle_adjustment (csrc/gba.hip) at every size; a pivot that is not positive rejects the trial.
+ *   - A keyframe without an edge is not an active vertex and comes back untouched (the Sim3 constructors of the reference, sim3.h:
+ *     59-67, store the quaternion as given: no vertex is renormalised on entry).  Fixed vertices come back untouched as well.
+ *   - n_edges == 0: iterations = -1, nothing moves (sparse_optimizer.cpp:356-359); the tail still runs, with the entry estimates.
+ *     Edges but no free vertex among them: ASD_ERR_INVALID.  An edge naming a row outside [0, n_kf), or i == j: ASD_ERR_INVALID.
+ *     Duplicate (i, j) pairs are legal and both count (the reference produces them when a spanning-tree or loop edge coincides with
+ *     a LoopConnections edge: sInsertedEdges only guards the covisibility edges).
+ *   - chi2 / edge_chi2 are those of the stored errors, i.e. of the last computeActiveErrors: after a run that ended on a rejected
+ *     trial, the rejected trial's (the estimates are the accepted ones).  n_iterations = 0: the errors at the entry estimates.
+ *   - Everything is f64 without float atomics: two calls on one problem return the same bits.
+ *   - Pinned against the reference's g2o (BlockSolver_7_3 + LinearSolverEigen) in tests/test_essgraph.py: iterations and trials per
+ *     iteration exact, the estimates within 4 x S (tests/golden/make_essgraph_golden.py).
+ * Limits (ASD_ERR_CAPACITY beyond them, asd_last_error says which): ASD_ESSGRAPH_MAX_KEYFRAMES keyframes, ASD_ESSGRAPH_MAX_EDGES
+ * edges, ASD_ESSGRAPH_MAX_POINTS map points, ASD_ESSGRAPH_MAX_ITERATIONS iterations (a count below 0 is taken as 0).  ASD_ERR_INVALID while a run of asd_local_ba_submit or a call started with
+ * asd_track_async is outstanding.  asd_local_ba and asd_bundle_adjustment before and after return the bits they return without
+ * this call. */
+#define ASD_ESSGRAPH_MAX_KEYFRAMES 2048
+#define ASD_ESSGRAPH_MAX_EDGES (64 * 1024)
+#define ASD_ESSGRAPH_MAX_POINTS (4 * 1024 * 1024)
+#define ASD_ESSGRAPH_MAX_ITERATIONS 1000
+int asd_optimize_essential_graph(asd_ctx* ctx, asd_essgraph_problem* problem, asd_essgraph_result* result);
+/* Test aid: the structure of the context's last asd_optimize_essential_graph.  out = {active vertices (keyframes with an edge, fixed
+ * ones included), free active vertices (n / 7), active edges, tiles per side of the Cholesky (ceil(n / 96), 0 without a solve)}.
+ * All -1 before any call. */
+int32_t asd_debug_essgraph_forms(const asd_ctx* ctx, int32_t out[4]);
+/* Test aid: the trials each iteration of the context's last asd_optimize_essential_graph took, as asd_debug_gba_trials. */
+int32_t asd_debug_essgraph_trials(const asd_ctx* ctx, int32_t* out, int32_t cap);
+
 /* Converter::toSE3Quat / toCvMat (Converter.cc:37-71): f32 4x4 <-> f64 quaternion + t. */
 int asd_tcw_to_pose7(const float* Tcw16, double* pose7);
 int asd_pose7_to_tcw(const double* pose7, float* Tcw16);
@@ -743,7 +808,8 @@ int asd_pose7_to_tcw(const double* pose7, float* Tcw16);
 /* Device-side duration of the kernels enqueued by the most recent call of the named stage,
  * measured with hipEvents on the ctx stream.  stage: "asdnet", "extract", "match", "ba", "sim3" (asd_optimize_sim3),
  * "sim3_ransac" (both kernels of asd_sim3_ransac, its upload included), "pnp_ransac" (likewise for asd_pnp_ransac), "initializer" (likewise for asd_initialize; "initializer_hyp": its upload and k_init_hyp alone),
- * "kfdb" (the scoring pass of the last asd_kfdb_score / asd_kfdb_query_*, its upload included). */
+ * "kfdb" (the scoring pass of the last asd_kfdb_score / asd_kfdb_query_*, its upload included), "essgraph" (asd_optimize_essential_graph:
+ * every kernel of the call, the tail included; the host's looks at the Levenberg state lie inside). */
 int asd_last_stage_ms(const asd_ctx* ctx, const char* stage, float* ms);
 /* Per-kernel device time of the ASDNet forward, accumulated with hipEvents recorded on the ctx
  * stream between the layer launches of every forward while enabled.  layer 0 = input_norm+conv1,
