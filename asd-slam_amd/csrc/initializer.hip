@@ -3,8 +3,8 @@
 // Initializer::Initialize (:43-120) is two RANSACs over the same minimal sets -- FindHomography (:123-171) and FindFundamental (:174-222),
 // each iteration a small SVD and one pass over all matches -- followed by ReconstructH (:583-749) or ReconstructF (:482-581), which
 // triangulate every inlier under 8 or 4 motion hypotheses (CheckRT, :840-949).  The two halves are the two kernels:
-//  * k_init_hyp, one workgroup per (problem, iteration, model).  Thread 0 replays the swap-with-back sampling, builds A from the normalised
-//    points (every entry the f32 product the reference forms), takes its null vector by a one-sided Jacobi in f64 and forms H21i / H12i or
+//  * k_init_hyp, one workgroup per (problem, iteration, model).  Thread 0 replays the sampling (ransac_sample), builds A from the normalised
+//    points (every entry the f32 product the reference forms), takes its null vector by a one-sided Jacobi (jacobi_svd) in f64 and forms H21i / H12i or
 //    F21i in the rules the header states; the workgroup then evaluates CheckHomography / CheckFundamental for all matches in the reference's
 //    f32 operations (this file is compiled with -ffp-contract=off).  The per-match terms are computed in parallel and added by one lane in
 //    match order, test 1 before test 2: the score is the reference's sequential f32 sum.  Each wave stores its 64 decisions as a ballot word.
@@ -16,7 +16,9 @@
 //    hypothesis would add launches without shortening the longest lane.)
 // Normalize (:791-837) runs on the host in front of the upload (asd_initializer_normalize: sequential f32 sums).  No atomics; everything the
 // host reads travels in the context's one result block.  The small matrices live in LDS: no dynamically indexed private array.
+// The sampling, the one-sided Jacobi SVD, the ballot words and the host half of the call are ransac.h's.
 #include "ctx.h"
+#include "ransac.h"
 #include "svd4.h"
 
 #include <cfloat>
@@ -24,7 +26,7 @@
 
 namespace {
 
-constexpr int kInitThreads = 256, kInitWaves = kInitThreads / 64;
+constexpr int kInitThreads = kRansacThreads, kInitWaves = kRansacWaves;
 constexpr int kInitSvdSweeps = 60;   // one-sided Jacobi on at most 16x9: done after 6-10 sweeps; the cap bounds a NaN input
 constexpr unsigned kKeyNaN = 0xfffffffeu, kKeyNone = 0xffffffffu;
 
@@ -90,53 +92,11 @@ __host__ __device__ inline void init_inv33(const float* M, float* out) {
   out[6] = (float)(c02 / det); out[7] = (float)((b * g - a * h) / det); out[8] = (float)((a * e - b * d) / det);
 }
 
-// one-sided (Hestenes) Jacobi SVD of W [m][n]: on return W = U Sigma (orthogonal columns), V [n][n] the right vectors, sig[j] = |W[:, j]|
-__device__ inline void init_svd(double* W, double* V, double* sig, const int m, const int n) {
-  for (int i = 0; i < n; ++i)
-    for (int j = 0; j < n; ++j) V[i * n + j] = i == j ? 1.0 : 0.0;
-  double fro2 = 0.0;
-  for (int i = 0; i < m * n; ++i) fro2 += W[i] * W[i];
-  const double floor2 = (8.0 * DBL_EPSILON) * (8.0 * DBL_EPSILON) * fro2;   // a column at rounding level is a null column (F: A has 8 rows)
-  for (int sweep = 0; sweep < kInitSvdSweeps; ++sweep) {
-    bool rotated = false;
-    for (int p = 0; p < n - 1; ++p)
-      for (int q = p + 1; q < n; ++q) {
-        double alpha = 0.0, beta = 0.0, gamma = 0.0;
-        for (int i = 0; i < m; ++i) {
-          const double wp = W[i * n + p], wq = W[i * n + q];
-          alpha += wp * wp; beta += wq * wq; gamma += wp * wq;
-        }
-        if (alpha <= floor2 || beta <= floor2) continue;                   // nothing to orthogonalise against noise
-        if (!(fabs(gamma) > DBL_EPSILON * sqrt(alpha * beta))) continue;   // orthogonal to rounding (or NaN)
-        rotated = true;
-        const double zeta = (beta - alpha) / (2.0 * gamma);
-        const double t = (zeta >= 0.0 ? 1.0 : -1.0) / (fabs(zeta) + sqrt(zeta * zeta + 1.0));
-        const double c = 1.0 / sqrt(t * t + 1.0), s = t * c;
-        for (int i = 0; i < m; ++i) {
-          const double wp = W[i * n + p], wq = W[i * n + q];
-          W[i * n + p] = c * wp - s * wq;
-          W[i * n + q] = s * wp + c * wq;
-        }
-        for (int i = 0; i < n; ++i) {
-          const double vp = V[i * n + p], vq = V[i * n + q];
-          V[i * n + p] = c * vp - s * vq;
-          V[i * n + q] = s * vp + c * vq;
-        }
-      }
-    if (!rotated) break;
-  }
-  for (int j = 0; j < n; ++j) {
-    double s2 = 0.0;
-    for (int i = 0; i < m; ++i) s2 += W[i * n + j] * W[i * n + j];
-    sig[j] = sqrt(s2);
-  }
-}
-
 // the 3x3 decomposition of the f32 matrix M by the header's rule: U, w (descending), Vt in f64.  ws: 9 + 9 + 3
 __device__ inline void init_svd3(const float* M, double* U, double* w, double* Vt, double* ws) {
   double *W = ws, *V = ws + 9, *sig = ws + 18;
   for (int i = 0; i < 9; ++i) W[i] = (double)M[i];
-  init_svd(W, V, sig, 3, 3);
+  jacobi_svd<true>(W, V, sig, 3, 3, kInitSvdSweeps);
   int o0 = 0, o1 = 1, o2 = 2;   // descending, the first of equal ones first
   if (sig[o1] > sig[o0]) { const int x = o0; o0 = o1; o1 = x; }
   if (sig[o2] > sig[o1]) { const int x = o1; o1 = o2; o2 = x; }
@@ -176,26 +136,12 @@ struct InitHypShared {
 
 __global__ __launch_bounds__(kInitThreads) void k_init_hyp(const InitProb* probs, const int32_t* hyp_prob, InitHypRec* recs) {
   __shared__ InitHypShared S;
-  const int h = blockIdx.x, t = threadIdx.x, lane = t & 63, wave = t >> 6;
+  const int h = blockIdx.x, t = threadIdx.x;
   const InitProb& P = probs[hyp_prob[h]];
   const int local = h - P.hyp_first, k = local >> 1, model = local & 1;
   const int N = P.N;
   if (t == 0) {
-    // vAvailableIndices starts as 0 .. N-1; a draw takes position r and moves the back element there: the identity plus overrides
-    int opos[8], oval[8];
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      const int r = P.draws[8 * k + j], size = N - j;
-      int v = r, b = size - 1;
-#pragma unroll
-      for (int m = 0; m < 8; ++m)
-        if (m < j) {
-          if (opos[m] == r) v = oval[m];
-          if (opos[m] == size - 1) b = oval[m];
-        }
-      S.idx[j] = v;
-      opos[j] = r; oval[j] = b;
-    }
+    ransac_sample<8>(P.draws + 8 * k, N, S.idx);
     const int rows = model == 0 ? 16 : 8;
     for (int j = 0; j < 8; ++j) {
       const int i1 = P.m1[S.idx[j]], i2 = P.m2[S.idx[j]];
@@ -213,7 +159,7 @@ __global__ __launch_bounds__(kInitThreads) void k_init_hyp(const InitProb* probs
         a[6] = (double)u1; a[7] = (double)v1; a[8] = 1.0;
       }
     }
-    init_svd(S.W, S.V, S.sig, rows, 9);
+    jacobi_svd<true>(S.W, S.V, S.sig, rows, 9, kInitSvdSweeps);
     int best = 0;
     for (int j = 1; j < 9; ++j)
       if (S.sig[j] <= S.sig[best]) best = j;
@@ -295,9 +241,7 @@ __global__ __launch_bounds__(kInitThreads) void k_init_hyp(const InitProb* probs
     }
     S.terms[2 * t] = term1;
     S.terms[2 * t + 1] = term2;
-    const unsigned long long bal = __ballot(in);
-    const int word = (base >> 6) + wave;
-    if (lane == 0 && word < P.words) mask[word] = bal;
+    ransac_ballot_word(in, base, P.words, mask);
     asd_syncthreads();
     if (t == 0) {
       const int cnt = 2 * min(kInitThreads, N - base);
@@ -534,7 +478,7 @@ __global__ __launch_bounds__(kInitThreads) void k_init_reconstruct(const InitPro
     const int h = p / N, i = p - h * N;
     float X[3] = {qnan, qnan, qnan}, c = 0.f;
     unsigned fl = 0;
-    if ((bm[i >> 6] >> (i & 63)) & 1ull) {   // :874
+    if (ransac_mask_bit(bm, i)) {   // :874
       const int i1 = P.m1[i], i2 = P.m2[i];
       init_check_rt(P.K, S.R[h], S.t[h], S.P2[h], S.O2[h], P.keys1[2 * i1], P.keys1[2 * i1 + 1], P.keys2[2 * i2], P.keys2[2 * i2 + 1], th2, X, c, fl);
     }
@@ -614,8 +558,8 @@ __global__ __launch_bounds__(kInitThreads) void k_init_reconstruct(const InitPro
   const unsigned long long* mH = S.best_H >= 0 ? P.masks + (size_t)(2 * S.best_H) * P.words : nullptr;
   const unsigned long long* mF = S.best_F >= 0 ? P.masks + (size_t)(2 * S.best_F + 1) * P.words : nullptr;
   for (int i = t; i < N; i += kInitThreads) {
-    P.inl_H[i] = mH ? (uint8_t)((mH[i >> 6] >> (i & 63)) & 1ull) : (uint8_t)0;
-    P.inl_F[i] = mF ? (uint8_t)((mF[i >> 6] >> (i & 63)) & 1ull) : (uint8_t)0;
+    P.inl_H[i] = mH ? ransac_mask_bit(mH, i) : (uint8_t)0;
+    P.inl_F[i] = mF ? ransac_mask_bit(mF, i) : (uint8_t)0;
   }
   for (int i = t; i < P.n1; i += kInitThreads) {   // vP3D.resize / vbGood(false) (:850-851)
     P.P3D[3 * i] = 0.f; P.P3D[3 * i + 1] = 0.f; P.P3D[3 * i + 2] = 0.f;
@@ -635,14 +579,14 @@ __global__ __launch_bounds__(kInitThreads) void k_init_reconstruct(const InitPro
 }
 
 struct InitProbState {
-  int32_t N = 0, n_iter = 0, first = 0, words = 0;
+  int32_t N = 0, words = 0;
   InitReconRec rec;
   std::vector<unsigned long long> masks;
   std::vector<float> pts;
   std::vector<uint8_t> flags;
 };
 struct InitState {
-  std::vector<InitHypRec> recs;
+  RansacRecords<InitHypRec> hyp;   // per problem 2 n_iter records: iteration k of model m at 2 k + m
   std::vector<InitProbState> probs;
 };
 
@@ -690,14 +634,9 @@ int asd_initializer_normalize(int32_t n, const float* keys, float* pts_out, floa
 }
 
 int asd_initialize(asd_ctx* ctx, int32_t n_problems, asd_initializer_problem* p) {
-  if (ctx && asd_track_busy(ctx, "asd_initialize")) return ASD_ERR_INVALID;
-  if (!ctx || n_problems < 0 || (n_problems > 0 && !p)) return ASD_ERR_INVALID;
-  if (n_problems > ASD_INIT_MAX_PROBLEMS) {
-    ctx->set_error("asd_initialize: %d problems in one call, the limit is %d", n_problems, ASD_INIT_MAX_PROBLEMS);
-    return ASD_ERR_CAPACITY;
-  }
+  if (const int e = ransac_check_call(ctx, "asd_initialize", n_problems, p, ASD_INIT_MAX_PROBLEMS)) return e;
   // ---- validation: nothing is written before every problem has passed
-  std::vector<int32_t> Ns(n_problems, 0);
+  std::vector<int32_t> Ns(n_problems, 0), hyps(n_problems, 0);   // matches; (iteration, model) pairs
   size_t total = 0, up_bytes = 0, down_bytes = 0, key_count = 0;
   for (int32_t j = 0; j < n_problems; ++j) {
     const asd_initializer_problem& q = p[j];
@@ -721,15 +660,9 @@ int asd_initialize(asd_ctx* ctx, int32_t n_problems, asd_initializer_problem* p)
       N += m >= 0;
     }
     if (N < 8) { ctx->set_error("asd_initialize: problem %d: %d matches, an iteration samples eight", j, N); return ASD_ERR_INVALID; }
-    for (int32_t k = 0; k < q.n_iter; ++k)
-      for (int i = 0; i < 8; ++i) {
-        const int32_t r = q.draws[8 * k + i];
-        if (r < 0 || r > N - 1 - i) {
-          ctx->set_error("asd_initialize: problem %d: draws[%d][%d] = %d is outside [0, %d]", j, k, i, r, N - 1 - i);
-          return ASD_ERR_INVALID;
-        }
-      }
+    if (!ransac_check_draws(ctx, "asd_initialize", j, q.draws, q.n_iter, 8, N)) return ASD_ERR_INVALID;
     Ns[j] = N;
+    hyps[j] = 2 * q.n_iter;
     const size_t words = ((size_t)N + 63) / 64;
     total += 2 * (size_t)q.n_iter;
     up_bytes += ((size_t)q.n1 + q.n2) * 16 + (size_t)N * 8 + (size_t)q.n_iter * 32 + 8 * 256;
@@ -738,28 +671,17 @@ int asd_initialize(asd_ctx* ctx, int32_t n_problems, asd_initializer_problem* p)
   }
   if (!ctx->initializer) ctx->initializer = new InitState();
   InitState* S = static_cast<InitState*>(ctx->initializer);
-  S->recs.clear();
+  S->hyp.reset(n_problems);
   S->probs.clear();
   ctx->ms_initializer = ctx->ms_initializer_hyp = 0;
   if (n_problems == 0) return ASD_OK;
-  (void)hipSetDevice(ctx->cfg.device);
-  hipStream_t st = ctx->stream;
-  ASD_HIP_CHECK(ctx, ctx->up.begin(st, up_bytes + (size_t)n_problems * sizeof(InitProb) + total * 4 + 1024));
-  ASD_HIP_CHECK(ctx, ctx->down.begin(st, down_bytes + total * sizeof(InitHypRec) + 1024));
-  ASD_HIP_CHECK(ctx, ctx->scratch.reserve(key_count * 4 + 256 * (size_t)n_problems + 256));
-  const size_t off_probs = ctx->up.reserve((size_t)n_problems * sizeof(InitProb)), off_map = ctx->up.reserve(total * 4);
-  const size_t off_recs = ctx->down.reserve(total * sizeof(InitHypRec));
   struct Offs { size_t masks, pts, flags, P3D, tri, inlH, inlF, rec; };
   std::vector<Offs> offs(n_problems);
-  InitProb* hp = ctx->up.host<InitProb>(off_probs);
-  int32_t* hmap = ctx->up.host<int32_t>(off_map);
-  size_t hyp = 0;
-  for (int32_t j = 0; j < n_problems; ++j) {
+  hipStream_t st = ctx->stream;
+  const auto pack = [&](const int32_t j, InitProb& d) {
     const asd_initializer_problem& q = p[j];
-    InitProb& d = hp[j];
-    memset(&d, 0, sizeof d);
     const size_t N = (size_t)Ns[j], n1 = (size_t)q.n1, n2 = (size_t)q.n2;
-    d.n1 = q.n1; d.n2 = q.n2; d.N = Ns[j]; d.n_iter = q.n_iter; d.hyp_first = (int32_t)hyp;
+    d.n1 = q.n1; d.n2 = q.n2; d.N = Ns[j]; d.n_iter = q.n_iter;
     d.words = (int32_t)((N + 63) / 64);
     d.min_tri = q.min_triangulated;
     memcpy(d.K, q.K, 16);
@@ -797,32 +719,25 @@ int asd_initialize(asd_ctx* ctx, int32_t n_problems, asd_initializer_problem* p)
     d.inl_H = ctx->down.dev<uint8_t>(o.inlH);
     d.inl_F = ctx->down.dev<uint8_t>(o.inlF);
     d.rec = ctx->down.dev<InitReconRec>(o.rec);
-    for (int32_t k = 0; k < 2 * q.n_iter; ++k) hmap[hyp + k] = j;
-    hyp += 2 * (size_t)q.n_iter;
-  }
-  ASD_HIP_CHECK(ctx, hipEventRecord(ctx->ev0, st));
-  ASD_HIP_CHECK(ctx, ctx->up.upload(st));
-  hipLaunchKernelGGL(k_init_hyp, dim3((unsigned)total), dim3(kInitThreads), 0, st, ctx->up.dev<InitProb>(off_probs),
-                     ctx->up.dev<int32_t>(off_map), ctx->down.dev<InitHypRec>(off_recs));
-  ASD_HIP_CHECK(ctx, hipGetLastError());
-  ASD_HIP_CHECK(ctx, hipEventRecord(ctx->ev2, st));
-  hipLaunchKernelGGL(k_init_reconstruct, dim3((unsigned)n_problems), dim3(kInitThreads), 0, st, ctx->up.dev<InitProb>(off_probs),
-                     ctx->down.dev<InitHypRec>(off_recs));
-  ASD_HIP_CHECK(ctx, hipGetLastError());
-  ASD_HIP_CHECK(ctx, hipEventRecord(ctx->ev1, st));
-  ASD_HIP_CHECK(ctx, ctx->down.download(st));
-  ASD_HIP_CHECK(ctx, hipStreamSynchronize(st));
-  ASD_HIP_CHECK(ctx, hipEventElapsedTime(&ctx->ms_initializer, ctx->ev0, ctx->ev1));
-  ASD_HIP_CHECK(ctx, hipEventElapsedTime(&ctx->ms_initializer_hyp, ctx->ev0, ctx->ev2));
-  const InitHypRec* recs = ctx->down.host<InitHypRec>(off_recs);
-  S->recs.assign(recs, recs + total);
+  };
+  const int e = ransac_run<InitProb>(
+      ctx, hyps, up_bytes, down_bytes, key_count * 4 + 256 * (size_t)n_problems + 256, total, &ctx->ms_initializer, &ctx->ms_initializer_hyp,
+      S->hyp, pack,
+      [&](unsigned grid, const InitProb* probs, const int32_t* map, InitHypRec* recs) {
+        hipLaunchKernelGGL(k_init_hyp, dim3(grid), dim3(kInitThreads), 0, st, probs, map, recs);
+      },
+      [&](unsigned grid, const InitProb* probs, const InitHypRec* recs) {
+        hipLaunchKernelGGL(k_init_reconstruct, dim3(grid), dim3(kInitThreads), 0, st, probs, recs);
+      });
+  if (e != ASD_OK) return e;
+  const std::vector<InitHypRec>& recs = S->hyp.recs;
   S->probs.resize(n_problems);
   for (int32_t j = 0; j < n_problems; ++j) {
     asd_initializer_problem& q = p[j];
     const Offs& o = offs[j];
-    const size_t N = (size_t)Ns[j];
+    const size_t N = (size_t)Ns[j], first = (size_t)S->hyp.first[j];
     InitProbState& ps = S->probs[j];
-    ps.N = Ns[j]; ps.n_iter = q.n_iter; ps.first = hp[j].hyp_first; ps.words = hp[j].words;
+    ps.N = Ns[j]; ps.words = (int32_t)((N + 63) / 64);
     ps.rec = *ctx->down.host<InitReconRec>(o.rec);
     const unsigned long long* mk = ctx->down.host<unsigned long long>(o.masks);
     ps.masks.assign(mk, mk + 2 * (size_t)q.n_iter * ps.words);
@@ -833,8 +748,8 @@ int asd_initialize(asd_ctx* ctx, int32_t n_problems, asd_initializer_problem* p)
     const InitReconRec& r = ps.rec;
     q.n_matches = Ns[j];
     q.SH = r.SH; q.SF = r.SF; q.model = r.model; q.ok = r.ok;
-    if (r.best_H >= 0) memcpy(q.H21, recs[ps.first + 2 * r.best_H].M1, 36);       // :166
-    if (r.best_F >= 0) memcpy(q.F21, recs[ps.first + 2 * r.best_F + 1].M1, 36);   // :217
+    if (r.best_H >= 0) memcpy(q.H21, recs[first + 2 * r.best_H].M1, 36);       // :166
+    if (r.best_F >= 0) memcpy(q.F21, recs[first + 2 * r.best_F + 1].M1, 36);   // :217
     memcpy(q.inliers_H, ctx->down.host<uint8_t>(o.inlH), N);
     memcpy(q.inliers_F, ctx->down.host<uint8_t>(o.inlF), N);
     if (r.ok) {
@@ -854,8 +769,8 @@ int32_t asd_debug_initialize(const asd_ctx* ctx, int32_t problem, int32_t which,
   const InitProbState& ps = S->probs[problem];
   const InitReconRec& rr = ps.rec;
   if (which >= 0) {
-    if (which >= 2 * ps.n_iter) return ASD_ERR_INVALID;
-    const InitHypRec& r = S->recs[(size_t)ps.first + which];
+    if (which >= S->hyp.count[problem]) return ASD_ERR_INVALID;
+    const InitHypRec& r = S->hyp.recs[(size_t)S->hyp.first[problem] + which];
     memcpy(out->idx, r.idx, sizeof out->idx);
     memcpy(out->nullv, r.nullv, sizeof out->nullv);
     memcpy(out->U, r.U, sizeof out->U);
@@ -866,7 +781,7 @@ int32_t asd_debug_initialize(const asd_ctx* ctx, int32_t problem, int32_t which,
     out->score = r.score;
     if (out->mask) {
       const unsigned long long* m = ps.masks.data() + (size_t)which * ps.words;
-      for (int32_t i = 0; i < ps.N; ++i) out->mask[i] = (uint8_t)((m[i >> 6] >> (i & 63)) & 1ull);
+      for (int32_t i = 0; i < ps.N; ++i) out->mask[i] = ransac_mask_bit(m, i);
     }
   } else {
     const int32_t h = -2 - which;

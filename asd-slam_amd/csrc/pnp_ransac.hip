@@ -3,24 +3,26 @@
 // PnPsolver::iterate (:165-258) is a loop of independent hypotheses -- sample four correspondences (:188-201), EPnP on them (compute_pose,
 // :477-525), score all N correspondences (CheckInliers, :308-339) -- followed by a sequential rule over the scores that calls Refine (:260-305,
 // EPnP on the inlier set of the best model) whenever the best model changes.  The two halves are the two kernels:
-//  * k_pnp_hyp, one workgroup per hypothesis of every problem of the call.  Thread 0 replays the swap-with-back sampling and evaluates EPnP in
+//  * k_pnp_hyp, one workgroup per hypothesis of every problem of the call.  Thread 0 replays the sampling (ransac_sample) and evaluates EPnP in
 //    f64 (the small solves work in LDS: no dynamically indexed private array; the 12x12 Jacobi is spread over the lanes of thread 0's wave,
 //    bit for bit what one lane would compute), the workgroup scores the correspondences in
-//    the reference's mixed f32/f64 operation order (this file is compiled with -ffp-contract=off).  Each wave stores its 64 decisions as one
-//    ballot word; the count is reduced in one fixed shape (wave butterfly, then the waves in order).
+//    the reference's mixed f32/f64 operation order (this file is compiled with -ffp-contract=off).
 //  * k_pnp_select, one workgroup per problem.  It walks the counts in hypothesis order with the reference's rule; a Refine is the same
 //    compute_pose with the whole workgroup over the points of the best mask -- six workgroup-wide sums of fixed shape through LDS (centroid,
 //    PW0^T PW0, the 78 entries of M^T M, pc0 / pw0, ABt, the reprojection sums of the three candidates), the small algebra between them on
 //    thread 0 -- and the same CheckInliers.  alphas and pcs are recomputed per point where they are needed: no per-point scratch.
 // One templated compute_pose serves both: <false> is the first wave over the four sampled points, <true> the workgroup over a mask.
+// The sampling, the one-sided Jacobi SVD, the scoring loop with its ballot words and count, the workgroup sums and the host half of the
+// call are ransac.h's.
 // No atomics: a call is one bit pattern.  Everything the host reads travels in the context's one result block.
 #include "ctx.h"
+#include "ransac.h"
 
 #include <cfloat>
 
 namespace {
 
-constexpr int kPnpThreads = 256, kPnpWaves = kPnpThreads / 64;
+constexpr int kPnpThreads = kRansacThreads, kPnpWaves = kRansacWaves;
 constexpr int kPnpSymSweeps = 30;   // cyclic Jacobi, 12x12: the off-diagonal part is exactly zero after 8-12 sweeps; the cap bounds a NaN input
 constexpr int kPnpSvdSweeps = 40;   // one-sided Jacobi on at most 6x5
 constexpr int kPnpMaxSums = 78;     // the upper triangle of M^T M
@@ -72,11 +74,11 @@ __device__ inline void pnp_for_each(const PnpPts& pts, F f) {
     for (int j = 0; j < 4; ++j) f(pts.idx[j]);
   } else {
     for (int i = threadIdx.x; i < pts.n; i += kPnpThreads)
-      if ((pts.mask[i >> 6] >> (i & 63)) & 1ull) f(i);
+      if (ransac_mask_bit(pts.mask, i)) f(i);
   }
 }
 
-// S.sums[0 .. N) = the sum of acc over the correspondences: <false> thread 0 has them all; <true> wave butterfly, then the waves in order
+// S.sums[0 .. N) = the sum of acc over the correspondences: <false> thread 0 has them all; <true> the workgroup sum of fixed shape
 template <bool BLOCK, int N>
 __device__ inline void pnp_sum(double (&acc)[N], PnpShared& S) {
   if (!BLOCK) {
@@ -86,22 +88,7 @@ __device__ inline void pnp_sum(double (&acc)[N], PnpShared& S) {
     }
     return;
   }
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-  for (int k = 0; k < N; ++k) {
-    double v = acc[k];
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off);
-    if (lane == 0) S.red[wave][k] = v;
-  }
-  asd_syncthreads();
-  if (threadIdx.x < N) {
-    double s = S.red[0][threadIdx.x];
-#pragma unroll
-    for (int w = 1; w < kPnpWaves; ++w) s += S.red[w][threadIdx.x];   // fixed order
-    S.sums[threadIdx.x] = s;
-  }
-  asd_syncthreads();
+  wg_sum(acc, S.red, S.sums);
 }
 
 template <bool BLOCK>
@@ -164,44 +151,6 @@ __device__ inline void pnp_jacobi_sym(double* a, double* v, const int n, const i
   }
 }
 
-// one-sided (Hestenes) Jacobi SVD of W [m][n]: on return W = U Sigma (orthogonal columns), V [n][n] the right vectors, sig[j] = |W[:, j]|
-__device__ inline void pnp_svd(double* W, double* V, double* sig, const int m, const int n) {
-  for (int i = 0; i < n; ++i)
-    for (int j = 0; j < n; ++j) V[i * n + j] = i == j ? 1.0 : 0.0;
-  for (int sweep = 0; sweep < kPnpSvdSweeps; ++sweep) {
-    bool rotated = false;
-    for (int p = 0; p < n - 1; ++p)
-      for (int q = p + 1; q < n; ++q) {
-        double alpha = 0.0, beta = 0.0, gamma = 0.0;
-        for (int i = 0; i < m; ++i) {
-          const double wp = W[i * n + p], wq = W[i * n + q];
-          alpha += wp * wp; beta += wq * wq; gamma += wp * wq;
-        }
-        if (!(fabs(gamma) > DBL_EPSILON * sqrt(alpha * beta))) continue;   // orthogonal to rounding (or NaN)
-        rotated = true;
-        const double zeta = (beta - alpha) / (2.0 * gamma);
-        const double t = (zeta >= 0.0 ? 1.0 : -1.0) / (fabs(zeta) + sqrt(zeta * zeta + 1.0));
-        const double c = 1.0 / sqrt(t * t + 1.0), s = t * c;
-        for (int i = 0; i < m; ++i) {
-          const double wp = W[i * n + p], wq = W[i * n + q];
-          W[i * n + p] = c * wp - s * wq;
-          W[i * n + q] = s * wp + c * wq;
-        }
-        for (int i = 0; i < n; ++i) {
-          const double vp = V[i * n + p], vq = V[i * n + q];
-          V[i * n + p] = c * vp - s * vq;
-          V[i * n + q] = s * vp + c * vq;
-        }
-      }
-    if (!rotated) break;
-  }
-  for (int j = 0; j < n; ++j) {
-    double s2 = 0.0;
-    for (int i = 0; i < m; ++i) s2 += W[i * n + j] * W[i * n + j];
-    sig[j] = sqrt(s2);
-  }
-}
-
 __device__ inline double pnp_svd_threshold(const double* sig, const int n) {
   double sum = 0.0;
   for (int j = 0; j < n; ++j) sum += sig[j];
@@ -213,7 +162,7 @@ __device__ inline void pnp_solve_svd(const double* L, const int* cols, const int
   double *W = w, *V = w + 30, *sig = w + 55;
   for (int i = 0; i < 6; ++i)
     for (int j = 0; j < n; ++j) W[i * n + j] = L[10 * i + cols[j]];
-  pnp_svd(W, V, sig, 6, n);
+  jacobi_svd<false>(W, V, sig, 6, n, kPnpSvdSweeps);
   const double thr = pnp_svd_threshold(sig, n);
   for (int k = 0; k < n; ++k) x[k] = 0.0;
   for (int j = 0; j < n; ++j) {
@@ -323,7 +272,7 @@ __device__ inline void pnp_control_points(PnpShared& S, const int m) {
   double *W = S.w, *V = S.w + 9, *sig = S.w + 18;
   for (int i = 0; i < 3; ++i)
     for (int j = 1; j < 4; ++j) W[3 * i + j - 1] = S.cws[j][i] - S.cws[0][i];
-  pnp_svd(W, V, sig, 3, 3);
+  jacobi_svd<false>(W, V, sig, 3, 3, kPnpSvdSweeps);
   const double thr = pnp_svd_threshold(sig, 3);
   for (int k = 0; k < 3; ++k)
     for (int i = 0; i < 3; ++i) {
@@ -434,7 +383,7 @@ __device__ inline void pnp_betas(PnpShared& S, const PnpPts& pts) {
 __device__ inline void pnp_procrustes(PnpShared& S, const int c) {
   double *W = S.w, *V = S.w + 9, *sig = S.w + 18, *U = S.w + 24;
   for (int i = 0; i < 9; ++i) W[i] = S.sums[9 * c + i];
-  pnp_svd(W, V, sig, 3, 3);
+  jacobi_svd<false>(W, V, sig, 3, 3, kPnpSvdSweeps);
   const double thr = pnp_svd_threshold(sig, 3);
   for (int j = 0; j < 3; ++j)
     for (int i = 0; i < 3; ++i) U[3 * i + j] = sig[j] > thr ? W[3 * i + j] / sig[j] : 0.0;
@@ -621,41 +570,24 @@ __device__ inline void pnp_record(const PnpShared& S, PnpRec& r, const int* idx,
 
 // CheckInliers (:308-339) by the whole workgroup on S.R, S.t: ballot words into mask, the count returned to every thread
 __device__ inline int pnp_check_inliers(const PnpRansacProb& P, const PnpShared& S, unsigned long long* mask, int* s_cnt) {
-  const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
   double R[9], tt[3];
 #pragma unroll
   for (int i = 0; i < 9; ++i) R[i] = S.R[i];
 #pragma unroll
   for (int i = 0; i < 3; ++i) tt[i] = S.t[i];
   const double fu = (double)P.K[0], fv = (double)P.K[1], uc = (double)P.K[2], vc = (double)P.K[3];
-  int mine = 0;
-  for (int base = 0; base < P.n; base += kPnpThreads) {   // (uniform trip count: every lane reaches the ballot)
-    const int i = base + t;
-    bool in = false;
-    if (i < P.n) {
-      const double x = (double)P.P3D[3 * i], y = (double)P.P3D[3 * i + 1], z = (double)P.P3D[3 * i + 2];
-      const float Xc = (float)(R[0] * x + R[1] * y + R[2] * z + tt[0]);           // :317-319
-      const float Yc = (float)(R[3] * x + R[4] * y + R[5] * z + tt[1]);
-      const float invZc = (float)(1.0 / (R[6] * x + R[7] * y + R[8] * z + tt[2]));
-      const double ue = uc + fu * (double)Xc * (double)invZc;                      // :321-322
-      const double ve = vc + fv * (double)Yc * (double)invZc;
-      const float distX = (float)((double)P.P2D[2 * i] - ue);                      // :324-325
-      const float distY = (float)((double)P.P2D[2 * i + 1] - ve);
-      const float error2 = distX * distX + distY * distY;                          // :327
-      in = error2 < P.maxe[i];                                                     // :329
-    }
-    const unsigned long long bal = __ballot(in);
-    const int word = (base >> 6) + wave;
-    if (lane == 0 && word < P.words) mask[word] = bal;
-    mine += in ? 1 : 0;
-  }
-  for (int off = 32; off >= 1; off >>= 1) mine += __shfl_xor(mine, off);
-  asd_syncthreads();   // (the previous count has been read by everyone)
-  if (lane == 0) s_cnt[wave] = mine;
-  asd_syncthreads();
-  int c = s_cnt[0];
-  for (int w = 1; w < kPnpWaves; ++w) c += s_cnt[w];
-  return c;
+  return ransac_score(P.n, P.words, mask, s_cnt, [&](const int i) {
+    const double x = (double)P.P3D[3 * i], y = (double)P.P3D[3 * i + 1], z = (double)P.P3D[3 * i + 2];
+    const float Xc = (float)(R[0] * x + R[1] * y + R[2] * z + tt[0]);           // :317-319
+    const float Yc = (float)(R[3] * x + R[4] * y + R[5] * z + tt[1]);
+    const float invZc = (float)(1.0 / (R[6] * x + R[7] * y + R[8] * z + tt[2]));
+    const double ue = uc + fu * (double)Xc * (double)invZc;                      // :321-322
+    const double ve = vc + fv * (double)Yc * (double)invZc;
+    const float distX = (float)((double)P.P2D[2 * i] - ue);                      // :324-325
+    const float distY = (float)((double)P.P2D[2 * i + 1] - ve);
+    const float error2 = distX * distX + distY * distY;                          // :327
+    return error2 < P.maxe[i];                                                   // :329
+  });
 }
 
 __global__ __launch_bounds__(kPnpThreads) void k_pnp_hyp(const PnpRansacProb* probs, const int32_t* hyp_prob, PnpRec* recs) {
@@ -666,17 +598,8 @@ __global__ __launch_bounds__(kPnpThreads) void k_pnp_hyp(const PnpRansacProb* pr
   const PnpRansacProb P = probs[hyp_prob[h]];
   const int k = h - P.hyp_first;
   if (t < 64) {   // (every lane of the wave replays the sampling: the same values, no hand-over)
-    // vAvailableIndices starts as 0 .. n-1; a draw takes position r and moves the back element there.  Four draws touch at most three
-    // positions before the last read, so the vector is the identity plus three overrides
     PnpPts pts;
-    int opos[3] = {-1, -1, -1}, oval[3] = {0, 0, 0};
-    auto at = [&](int pos) { return pos == opos[2] ? oval[2] : (pos == opos[1] ? oval[1] : (pos == opos[0] ? oval[0] : pos)); };
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      const int r = P.draws[4 * k + i], size = P.n - i;
-      pts.idx[i] = at(r);
-      if (i < 3) { const int back = at(size - 1); opos[i] = r; oval[i] = back; }
-    }
+    ransac_sample<4>(P.draws + 4 * k, P.n, pts.idx);
     pts.P3D = P.P3D; pts.P2D = P.P2D; pts.n = P.n; pts.m = 4; pts.mask = nullptr;
     pts.fu = (double)P.K[0]; pts.fv = (double)P.K[1]; pts.uc = (double)P.K[2]; pts.vc = (double)P.K[3];
     if (t == 0)
@@ -720,14 +643,14 @@ __global__ __launch_bounds__(kPnpThreads) void k_pnp_select(const PnpRansacProb*
   asd_syncthreads();   // the last Refine's ballot words are in memory
   const unsigned long long* const bm = best_h >= 0 ? P.masks + (size_t)best_h * P.words : nullptr;
   for (int i = t; i < P.n; i += kPnpThreads) {
-    P.best_mask[i] = bm ? (uint8_t)((bm[i >> 6] >> (i & 63)) & 1ull) : (uint8_t)0;
-    P.inliers[i] = found ? (uint8_t)((P.refmask[i >> 6] >> (i & 63)) & 1ull) : (uint8_t)0;
+    P.best_mask[i] = bm ? ransac_mask_bit(bm, i) : (uint8_t)0;
+    P.inliers[i] = found ? ransac_mask_bit(P.refmask, i) : (uint8_t)0;
   }
 }
 
 struct PnpRansacState {
-  std::vector<PnpRec> recs;                     // the hypotheses of the call, then the Refine slots in the same layout
-  std::vector<int32_t> first, count, n_ref;     // per problem of the last call
+  RansacRecords<PnpRec> hyp;      // recs: the hypotheses of the call, then the Refine slots in the same layout
+  std::vector<int32_t> n_ref;     // per problem of the last call
   size_t total = 0;
 };
 
@@ -750,15 +673,10 @@ void pnp_ransac_free(asd_ctx* ctx) {
 extern "C" {
 
 int asd_pnp_ransac(asd_ctx* ctx, int32_t n_problems, asd_pnp_ransac_problem* p) {
-  if (ctx && asd_track_busy(ctx, "asd_pnp_ransac")) return ASD_ERR_INVALID;
-  if (!ctx || n_problems < 0 || (n_problems > 0 && !p)) return ASD_ERR_INVALID;
-  if (n_problems > ASD_PNP_RANSAC_MAX_PROBLEMS) {
-    ctx->set_error("asd_pnp_ransac: %d problems in one call, the limit is %d", n_problems, ASD_PNP_RANSAC_MAX_PROBLEMS);
-    return ASD_ERR_CAPACITY;
-  }
+  if (const int e = ransac_check_call(ctx, "asd_pnp_ransac", n_problems, p, ASD_PNP_RANSAC_MAX_PROBLEMS)) return e;
   // ---- validation: nothing is written before every problem has passed
-  std::vector<char> runs(n_problems, 0);
-  size_t total = 0, up_bytes = 0, down_bytes = 0, mask_words = 0;
+  std::vector<int32_t> hyps(n_problems, 0);   // the iterations of a problem that runs
+  size_t total = 0, up_bytes = 0, down_bytes = 0, mask_bytes = 0;
   for (int32_t j = 0; j < n_problems; ++j) {
     const asd_pnp_ransac_problem& q = p[j];
     if (q.n < 0 || q.n_iter < 0) { ctx->set_error("asd_pnp_ransac: problem %d: negative n or n_iter", j); return ASD_ERR_INVALID; }
@@ -772,15 +690,8 @@ int asd_pnp_ransac(asd_ctx* ctx, int32_t n_problems, asd_pnp_ransac_problem* p) 
       ctx->set_error("asd_pnp_ransac: problem %d: null array", j);
       return ASD_ERR_INVALID;
     }
-    for (int32_t k = 0; k < q.n_iter; ++k)
-      for (int i = 0; i < ASD_PNP_MIN_SET; ++i) {
-        const int32_t r = q.draws[ASD_PNP_MIN_SET * k + i];
-        if (r < 0 || r > q.n - 1 - i) {
-          ctx->set_error("asd_pnp_ransac: problem %d: draws[%d][%d] = %d is outside [0, %d]", j, k, i, r, q.n - 1 - i);
-          return ASD_ERR_INVALID;
-        }
-      }
-    runs[j] = 1;
+    if (!ransac_check_draws(ctx, "asd_pnp_ransac", j, q.draws, q.n_iter, ASD_PNP_MIN_SET, q.n)) return ASD_ERR_INVALID;
+    hyps[j] = q.n_iter;
     total += (size_t)q.n_iter;
     if (total > ASD_PNP_RANSAC_MAX_HYPOTHESES) {
       ctx->set_error("asd_pnp_ransac: problem %d brings the call to %zu iterations, the limit is %d", j, total, ASD_PNP_RANSAC_MAX_HYPOTHESES);
@@ -788,41 +699,21 @@ int asd_pnp_ransac(asd_ctx* ctx, int32_t n_problems, asd_pnp_ransac_problem* p) 
     }
     up_bytes += (size_t)q.n * 24 + (size_t)q.n_iter * 16 + 8 * 256;
     down_bytes += (size_t)q.n * 2 + 32 + 3 * 256;
-    mask_words += ((size_t)q.n_iter + 1) * (((size_t)q.n + 63) / 64) + 64;
+    const size_t word_bytes = (((size_t)q.n + 63) / 64) * 8;
+    mask_bytes += AsdDevBuf::padded((size_t)q.n_iter * word_bytes) + AsdDevBuf::padded(word_bytes);
   }
   if (!ctx->pnp_ransac) ctx->pnp_ransac = new PnpRansacState();
   PnpRansacState* S = static_cast<PnpRansacState*>(ctx->pnp_ransac);
-  S->recs.clear();
+  S->hyp.reset(n_problems);
   S->total = total;
-  S->first.assign(n_problems, 0);
-  S->count.assign(n_problems, 0);
   S->n_ref.assign(n_problems, 0);
   for (int32_t j = 0; j < n_problems; ++j)
-    if (!runs[j] && p[j].n >= p[j].min_inliers) {   // no iteration to run: iterate()'s loop body is not entered (:182)
-      p[j].best_updated = 0; p[j].found = 0; p[j].iterations_done = 0; p[j].n_inliers = 0;
-      if (p[j].inliers && p[j].n > 0) memset(p[j].inliers, 0, (size_t)p[j].n);
-    } else if (!runs[j]) {
-      p[j].found = 0; p[j].iterations_done = 0;     // :173-177: nothing else is written
-    }
+    if (!hyps[j]) ransac_runs_nothing(p[j]);   // :173-177, or no iteration to run (:182)
   ctx->ms_pnp_ransac = 0;
   if (total == 0) return ASD_OK;
-  (void)hipSetDevice(ctx->cfg.device);
-  hipStream_t st = ctx->stream;
-  ASD_HIP_CHECK(ctx, ctx->up.begin(st, up_bytes + (size_t)n_problems * sizeof(PnpRansacProb) + total * 4 + 1024));
-  ASD_HIP_CHECK(ctx, ctx->down.begin(st, down_bytes + 2 * total * sizeof(PnpRec) + 1024));
-  ASD_HIP_CHECK(ctx, ctx->scratch.reserve(mask_words * 8 + 256));
-  unsigned long long* d_masks = ctx->scratch.carve<unsigned long long>(mask_words);
-  const size_t off_probs = ctx->up.reserve((size_t)n_problems * sizeof(PnpRansacProb)), off_map = ctx->up.reserve(total * 4);
-  const size_t off_recs = ctx->down.reserve(2 * total * sizeof(PnpRec));
   std::vector<size_t> off_bm(n_problems, 0), off_inl(n_problems, 0), off_res(n_problems, 0);
-  PnpRansacProb* hp = ctx->up.host<PnpRansacProb>(off_probs);
-  int32_t* hmap = ctx->up.host<int32_t>(off_map);
-  size_t hyp = 0, words_used = 0;
-  for (int32_t j = 0; j < n_problems; ++j) {
-    PnpRansacProb& d = hp[j];
-    memset(&d, 0, sizeof d);
-    d.hyp_first = (int32_t)hyp;
-    if (!runs[j]) continue;   // n = n_iter = 0: k_pnp_select's workgroup of this problem touches nothing
+  hipStream_t st = ctx->stream;
+  const auto pack = [&](const int32_t j, PnpRansacProb& d) {
     const asd_pnp_ransac_problem& q = p[j];
     const size_t n = (size_t)q.n;
     d.n = q.n; d.n_iter = q.n_iter; d.min_inliers = q.min_inliers; d.best_in = q.best_inliers;
@@ -832,50 +723,41 @@ int asd_pnp_ransac(asd_ctx* ctx, int32_t n_problems, asd_pnp_ransac_problem* p) 
     d.P2D = ctx->up.dev<float>(ctx->up.add(q.P2D, n * 8));
     d.maxe = ctx->up.dev<float>(ctx->up.add(q.max_err, n * 4));
     d.draws = ctx->up.dev<int32_t>(ctx->up.add(q.draws, (size_t)q.n_iter * 16));
-    d.masks = d_masks + words_used;
-    words_used += (size_t)q.n_iter * d.words;
-    d.refmask = d_masks + words_used;
-    words_used += (size_t)d.words;
+    d.masks = ctx->scratch.carve<unsigned long long>((size_t)q.n_iter * d.words);
+    d.refmask = ctx->scratch.carve<unsigned long long>((size_t)d.words);
     off_bm[j] = ctx->down.reserve(n);
     off_inl[j] = ctx->down.reserve(n);
     off_res[j] = ctx->down.reserve(32);
     d.best_mask = ctx->down.dev<uint8_t>(off_bm[j]);
     d.inliers = ctx->down.dev<uint8_t>(off_inl[j]);
     d.result = ctx->down.dev<int32_t>(off_res[j]);
-    for (int32_t k = 0; k < q.n_iter; ++k) hmap[hyp + k] = j;
-    hyp += (size_t)q.n_iter;
-  }
-  ASD_HIP_CHECK(ctx, hipEventRecord(ctx->ev0, st));
-  ASD_HIP_CHECK(ctx, ctx->up.upload(st));
-  hipLaunchKernelGGL(k_pnp_hyp, dim3((unsigned)total), dim3(kPnpThreads), 0, st, ctx->up.dev<PnpRansacProb>(off_probs),
-                     ctx->up.dev<int32_t>(off_map), ctx->down.dev<PnpRec>(off_recs));
-  ASD_HIP_CHECK(ctx, hipGetLastError());
-  hipLaunchKernelGGL(k_pnp_select, dim3((unsigned)n_problems), dim3(kPnpThreads), 0, st, ctx->up.dev<PnpRansacProb>(off_probs),
-                     ctx->down.dev<PnpRec>(off_recs), (int)total);
-  ASD_HIP_CHECK(ctx, hipGetLastError());
-  ASD_HIP_CHECK(ctx, hipEventRecord(ctx->ev1, st));
-  ASD_HIP_CHECK(ctx, ctx->down.download(st));
-  ASD_HIP_CHECK(ctx, hipStreamSynchronize(st));
-  ASD_HIP_CHECK(ctx, hipEventElapsedTime(&ctx->ms_pnp_ransac, ctx->ev0, ctx->ev1));
-  const PnpRec* recs = ctx->down.host<PnpRec>(off_recs);
-  S->recs.assign(recs, recs + 2 * total);
+  };
+  const int e = ransac_run<PnpRansacProb>(
+      ctx, hyps, up_bytes, down_bytes, mask_bytes + 256, 2 * total, &ctx->ms_pnp_ransac, nullptr, S->hyp, pack,
+      [&](unsigned grid, const PnpRansacProb* probs, const int32_t* map, PnpRec* recs) {
+        hipLaunchKernelGGL(k_pnp_hyp, dim3(grid), dim3(kPnpThreads), 0, st, probs, map, recs);
+      },
+      [&](unsigned grid, const PnpRansacProb* probs, PnpRec* recs) {
+        hipLaunchKernelGGL(k_pnp_select, dim3(grid), dim3(kPnpThreads), 0, st, probs, recs, (int)total);
+      });
+  if (e != ASD_OK) return e;
+  const std::vector<PnpRec>& recs = S->hyp.recs;
   for (int32_t j = 0; j < n_problems; ++j) {
-    S->first[j] = hp[j].hyp_first;
-    if (!runs[j]) continue;
-    S->count[j] = p[j].n_iter;
+    if (!hyps[j]) continue;
+    const size_t first = (size_t)S->hyp.first[j];
     asd_pnp_ransac_problem& q = p[j];
     const int32_t* r = ctx->down.host<int32_t>(off_res[j]);
     S->n_ref[j] = r[6];
     q.best_inliers = r[0];
     q.best_updated = r[1];
     if (r[1]) {   // :214-223
-      pnp_tcw(recs[hp[j].hyp_first + r[2]], q.best_Tcw);
+      pnp_tcw(recs[first + r[2]], q.best_Tcw);
       memcpy(q.best_mask, ctx->down.host<uint8_t>(off_bm[j]), (size_t)q.n);
     }
     q.found = r[3];
     q.iterations_done = r[4];
     q.n_inliers = r[5];
-    if (r[3]) pnp_tcw(recs[total + hp[j].hyp_first + r[6] - 1], q.Tcw);   // the Refine that returned is the last one the walk ran
+    if (r[3]) pnp_tcw(recs[total + first + r[6] - 1], q.Tcw);   // the Refine that returned is the last one the walk ran
     memcpy(q.inliers, ctx->down.host<uint8_t>(off_inl[j]), (size_t)q.n);
   }
   return ASD_OK;
@@ -884,17 +766,17 @@ int asd_pnp_ransac(asd_ctx* ctx, int32_t n_problems, asd_pnp_ransac_problem* p) 
 int32_t asd_debug_pnp_ransac(const asd_ctx* ctx, int32_t problem, int32_t which, asd_pnp_ransac_debug* out) {
   if (!ctx || !out) return ASD_ERR_INVALID;
   const PnpRansacState* S = static_cast<const PnpRansacState*>(ctx->pnp_ransac);
-  if (!S || problem < 0 || problem >= (int32_t)S->count.size()) return ASD_ERR_INVALID;
+  if (!S || problem < 0 || problem >= (int32_t)S->hyp.count.size()) return ASD_ERR_INVALID;
   size_t at;
   if (which >= 0) {
-    if (which >= S->count[problem]) return ASD_ERR_INVALID;
-    at = (size_t)S->first[problem] + which;
+    if (which >= S->hyp.count[problem]) return ASD_ERR_INVALID;
+    at = (size_t)S->hyp.first[problem] + which;
   } else {
     const int32_t r = -1 - which;
     if (r >= S->n_ref[problem]) return ASD_ERR_INVALID;
-    at = S->total + (size_t)S->first[problem] + r;
+    at = S->total + (size_t)S->hyp.first[problem] + r;
   }
-  const PnpRec& r = S->recs[at];
+  const PnpRec& r = S->hyp.recs[at];
   memcpy(out->idx, r.idx, sizeof out->idx);
   out->count = r.count;
   out->n_refines = S->n_ref[problem];

@@ -13,9 +13,10 @@
 //    computeError() (:1146, :1180): the errors of the round's last computeActiveErrors, i.e. of its last pass -- after a round that
 //    ended on a rejected trial, the rejected trial's.  The kernel keeps the Sim3 of the last pass (S.eval) and re-evaluates there
 //    with the pass's own arithmetic, as PoseOptimization's re-classification does.
-// Reductions have one fixed shape (wave butterfly, then the waves in order) and there are no atomics: a call is one bit pattern.
+// Reductions have one fixed shape (wg_sum, ransac.h: wave butterfly, then the waves in order) and there are no atomics: a call is one bit pattern.
 // The edge data stays in global memory (SoA [12][n], read once per pass).
 #include "ctx.h"
+#include "ransac.h"
 #include "sim3_math.h"
 
 namespace {
@@ -48,27 +49,6 @@ struct Sim3Shared {
   int tr[4];   // per round: active edges, iterations (optimize()'s return), trials, ended on a rejected trial
 };
 
-// acc[N] -> S.sums[N]: lanes of a wave by butterfly, then the waves in order.  Two barriers; every thread may read S.sums behind it.
-template <int N>
-__device__ inline void sim3_block_sum(double (&acc)[N], Sim3Shared& S) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-  for (int k = 0; k < N; ++k) {
-    double v = acc[k];
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off);
-    if (lane == 0) S.red[wave][k] = v;
-  }
-  asd_syncthreads();
-  if (threadIdx.x < N) {
-    double s = S.red[0][threadIdx.x];
-#pragma unroll
-    for (int w = 1; w < kSim3Waves; ++w) s += S.red[w][threadIdx.x];   // fixed order
-    S.sums[threadIdx.x] = s;
-  }
-  asd_syncthreads();
-}
-
 struct Sim3Pair {
   double X1, Y1, Z1, X2, Y2, Z2, u1, v1, u2, v2, is1, is2;
 };
@@ -98,7 +78,7 @@ __device__ inline void sim3_pass_errors(const Sim3OptArgs& a, Sim3Shared& S) {
     huber(s3_chi2(e[2], e[3], p.is2), a.huber, r0, r1);
     acc[0] += r0;
   }
-  sim3_block_sum<1>(acc, S);
+  wg_sum(acc, S.red, S.sums);
 }
 
 // H (upper, 28) and b (7) of one edge: J = numeric 2 x 7, weighted Omega = rho' inv_sigma2 I, b += J^T (-(Omega e) rho')
@@ -162,7 +142,7 @@ __device__ inline void sim3_pass_linearise(const Sim3OptArgs& a, Sim3Shared& S) 
     sim3_add_edge(acc, Jc, Jd, e[2], e[3], p.is2, r1);
     acc[36] += 2.0;
   }
-  sim3_block_sum<kSim3Sums>(acc, S);
+  wg_sum(acc, S.red, S.sums);
 }
 
 // thread 0, behind a linearising pass: the head of OptimizationAlgorithmLevenberg::solve (levenberg.cpp:74-101)
@@ -283,7 +263,7 @@ __global__ __launch_bounds__(kSim3Threads) void k_sim3_opt(Sim3OptArgs a) {
       if (s3_chi2(e[0], e[1], p.is1) > a.th2 || s3_chi2(e[2], e[3], p.is2) > a.th2) { a.keep[i] = 0; cnt[0] += 1.0; }
       else cnt[1] += 1.0;
     }
-    sim3_block_sum<2>(cnt, S);
+    wg_sum(cnt, S.red, S.sums);
     if (round == 0) nBad = (int)(S.sums[0] + 0.5); else nIn = (int)(S.sums[1] + 0.5);
     if (t == 0) { trc[4 * round] = S.tr[0]; trc[4 * round + 1] = S.tr[1]; trc[4 * round + 2] = S.tr[2]; trc[4 * round + 3] = S.tr[3]; }
     asd_syncthreads();   // S.sums and S.tr are read: the next round may write them

@@ -3,19 +3,19 @@
 // Sim3Solver::iterate (:140-207) is a loop of independent hypotheses -- sample three correspondences (:163-177), Horn's closed form on
 // them (ComputeSim3, :226-337), score all N correspondences in both directions (CheckInliers, :340-364) -- followed by a sequential rule
 // over the scores (:183-200).  The two halves are the two kernels:
-//  * k_sim3_hyp, one workgroup per hypothesis of every problem of the call.  Thread 0 replays the swap-with-back sampling and evaluates
+//  * k_sim3_hyp, one workgroup per hypothesis of every problem of the call.  Thread 0 replays the sampling (ransac_sample) and evaluates
 //    the model in f64 (a 4x4 cyclic Jacobi is a few hundred operations: not worth spreading), rounds it to f32 once, and the workgroup
-//    scores the correspondences in the reference's un-fused f32 operation order (this file is compiled with -ffp-contract=off).  Each wave
-//    stores its 64 decisions as one ballot word; the count is reduced in one fixed shape (wave butterfly, then the waves in order).
+//    scores the correspondences in the reference's un-fused f32 operation order (this file is compiled with -ffp-contract=off).
 //  * k_sim3_select, one workgroup per problem.  Thread 0 walks the counts in hypothesis order with the reference's rule, the workgroup
 //    expands the returned hypothesis's ballot words into inliers[n].
+// The sampling, the scoring loop with its ballot words and count, and the host half of the call are ransac.h's.
 // No atomics: a call is one bit pattern.  Everything the host reads travels in the context's one result block.
 #include "ctx.h"
+#include "ransac.h"
 
 namespace {
 
-constexpr int kRansacThreads = 256, kRansacWaves = kRansacThreads / 64;
-constexpr int kJacobiSweeps = 24;   // a 4x4 symmetric matrix is diagonal to the last bit after 5-7 sweeps; the cap only bounds a NaN input
+constexpr int kJacobiSweeps = 24;  // a 4x4 symmetric matrix is diagonal to the last bit after 5-7 sweeps; the cap only bounds a NaN input
 
 // what one hypothesis leaves (result block; asd_debug_sim3_ransac reads the host copy)
 struct Sim3HypRec {
@@ -80,15 +80,8 @@ __host__ __device__ inline void sim3_top_eigenvector(double (&a)[4][4], double (
 
 // thread 0 of a hypothesis: sampling (:163-177) and ComputeSim3 (:226-337).  (__host__ too: a CPU build can step through it)
 __host__ __device__ inline void sim3_hypothesis(const Sim3RansacProb& P, const int k, Sim3HypRec& rec, Sim3Model& mdl) {
-  // vAvailableIndices starts as 0 .. n-1; a draw takes position r and moves the back element there.  Three draws touch at most two
-  // positions before the last read, so the vector is the identity plus two overrides
-  int idx[3], opos[2] = {-1, -1}, oval[2] = {0, 0};
-  auto at = [&](int pos) { return pos == opos[1] ? oval[1] : (pos == opos[0] ? oval[0] : pos); };
-  for (int i = 0; i < 3; ++i) {
-    const int r = P.draws[3 * k + i], size = P.n - i;
-    idx[i] = at(r);
-    if (i < 2) { const int back = at(size - 1); opos[i] = r; oval[i] = back; }
-  }
+  int idx[3];
+  ransac_sample<3>(P.draws + 3 * k, P.n, idx);
   double P1[3][3], P2[3][3], O1[3], O2[3];   // [point][xyz]
   for (int i = 0; i < 3; ++i)
     for (int c = 0; c < 3; ++c) { P1[i][c] = (double)P.X1[3 * idx[i] + c]; P2[i][c] = (double)P.X2[3 * idx[i] + c]; }
@@ -175,7 +168,7 @@ __host__ __device__ inline float sim3_reproj_err(const float* T, const float* K,
 __global__ __launch_bounds__(kRansacThreads) void k_sim3_hyp(const Sim3RansacProb* probs, const int32_t* hyp_prob, Sim3HypRec* recs) {
   __shared__ Sim3Model mdl;
   __shared__ int s_cnt[kRansacWaves];
-  const int h = blockIdx.x, t = threadIdx.x, lane = t & 63, wave = t >> 6;
+  const int h = blockIdx.x, t = threadIdx.x;
   const Sim3RansacProb P = probs[hyp_prob[h]];
   const int k = h - P.hyp_first;
   if (t == 0) {
@@ -187,30 +180,13 @@ __global__ __launch_bounds__(kRansacThreads) void k_sim3_hyp(const Sim3RansacPro
   asd_syncthreads();
   float T12[12], T21[12];
   for (int i = 0; i < 12; ++i) { T12[i] = mdl.T12[i]; T21[i] = mdl.T21[i]; }
-  unsigned long long* const mask = P.masks + (size_t)k * P.words;
-  int mine = 0;
-  for (int base = 0; base < P.n; base += kRansacThreads) {   // (uniform trip count: every lane reaches the ballot)
-    const int i = base + t;
-    bool in = false;
-    if (i < P.n) {
-      // dist1 = mvP1im1 - Project(mvX3Dc2, T12, K1), dist2 = Project(mvX3Dc1, T21, K2) - mvP2im2 (:343-351)
-      const float err1 = sim3_reproj_err(T12, P.K1, P.X2[3 * i], P.X2[3 * i + 1], P.X2[3 * i + 2], P.im1[2 * i], P.im1[2 * i + 1], true);
-      const float err2 = sim3_reproj_err(T21, P.K2, P.X1[3 * i], P.X1[3 * i + 1], P.X1[3 * i + 2], P.im2[2 * i], P.im2[2 * i + 1], false);
-      in = err1 < P.e1[i] && err2 < P.e2[i];   // :356
-    }
-    const unsigned long long bal = __ballot(in);
-    const int word = (base >> 6) + wave;
-    if (lane == 0 && word < P.words) mask[word] = bal;
-    mine += in ? 1 : 0;
-  }
-  for (int off = 32; off >= 1; off >>= 1) mine += __shfl_xor(mine, off);
-  if (lane == 0) s_cnt[wave] = mine;
-  asd_syncthreads();
-  if (t == 0) {
-    int c = s_cnt[0];
-    for (int w = 1; w < kRansacWaves; ++w) c += s_cnt[w];
-    recs[h].count = c;
-  }
+  const int c = ransac_score(P.n, P.words, P.masks + (size_t)k * P.words, s_cnt, [&](const int i) {
+    // dist1 = mvP1im1 - Project(mvX3Dc2, T12, K1), dist2 = Project(mvX3Dc1, T21, K2) - mvP2im2 (:343-351)
+    const float err1 = sim3_reproj_err(T12, P.K1, P.X2[3 * i], P.X2[3 * i + 1], P.X2[3 * i + 2], P.im1[2 * i], P.im1[2 * i + 1], true);
+    const float err2 = sim3_reproj_err(T21, P.K2, P.X1[3 * i], P.X1[3 * i + 1], P.X1[3 * i + 2], P.im2[2 * i], P.im2[2 * i + 1], false);
+    return err1 < P.e1[i] && err2 < P.e2[i];   // :356
+  });
+  if (t == 0) recs[h].count = c;
 }
 
 __global__ __launch_bounds__(kRansacThreads) void k_sim3_select(const Sim3RansacProb* probs, const Sim3HypRec* recs) {
@@ -235,13 +211,10 @@ __global__ __launch_bounds__(kRansacThreads) void k_sim3_select(const Sim3Ransac
   asd_syncthreads();
   const int found = s_found;
   const unsigned long long* const mask = found >= 0 ? P.masks + (size_t)found * P.words : nullptr;
-  for (int i = t; i < P.n; i += kRansacThreads) P.inliers[i] = mask ? (uint8_t)((mask[i >> 6] >> (i & 63)) & 1ull) : (uint8_t)0;
+  for (int i = t; i < P.n; i += kRansacThreads) P.inliers[i] = mask ? ransac_mask_bit(mask, i) : (uint8_t)0;
 }
 
-struct Sim3RansacState {
-  std::vector<Sim3HypRec> recs;
-  std::vector<int32_t> first, count;   // per problem of the last call
-};
+using Sim3RansacState = RansacRecords<Sim3HypRec>;
 
 }  // namespace
 
@@ -253,15 +226,10 @@ void sim3_ransac_free(asd_ctx* ctx) {
 extern "C" {
 
 int asd_sim3_ransac(asd_ctx* ctx, int32_t n_problems, asd_sim3_ransac_problem* p) {
-  if (ctx && asd_track_busy(ctx, "asd_sim3_ransac")) return ASD_ERR_INVALID;
-  if (!ctx || n_problems < 0 || (n_problems > 0 && !p)) return ASD_ERR_INVALID;
-  if (n_problems > ASD_SIM3_RANSAC_MAX_PROBLEMS) {
-    ctx->set_error("asd_sim3_ransac: %d problems in one call, the limit is %d", n_problems, ASD_SIM3_RANSAC_MAX_PROBLEMS);
-    return ASD_ERR_CAPACITY;
-  }
+  if (const int e = ransac_check_call(ctx, "asd_sim3_ransac", n_problems, p, ASD_SIM3_RANSAC_MAX_PROBLEMS)) return e;
   // ---- validation: nothing is written before every problem has passed
-  std::vector<char> runs(n_problems, 0);
-  size_t total = 0, up_bytes = 0, down_bytes = 0, mask_words = 0;
+  std::vector<int32_t> hyps(n_problems, 0);   // the iterations of a problem that runs
+  size_t total = 0, up_bytes = 0, down_bytes = 0, mask_bytes = 0;
   for (int32_t j = 0; j < n_problems; ++j) {
     const asd_sim3_ransac_problem& q = p[j];
     if (q.n < 0 || q.n_iter < 0) { ctx->set_error("asd_sim3_ransac: problem %d: negative n or n_iter", j); return ASD_ERR_INVALID; }
@@ -275,15 +243,8 @@ int asd_sim3_ransac(asd_ctx* ctx, int32_t n_problems, asd_sim3_ransac_problem* p
       ctx->set_error("asd_sim3_ransac: problem %d: null array", j);
       return ASD_ERR_INVALID;
     }
-    for (int32_t k = 0; k < q.n_iter; ++k)
-      for (int i = 0; i < 3; ++i) {
-        const int32_t r = q.draws[3 * k + i];
-        if (r < 0 || r > q.n - 1 - i) {
-          ctx->set_error("asd_sim3_ransac: problem %d: draws[%d][%d] = %d is outside [0, %d]", j, k, i, r, q.n - 1 - i);
-          return ASD_ERR_INVALID;
-        }
-      }
-    runs[j] = 1;
+    if (!ransac_check_draws(ctx, "asd_sim3_ransac", j, q.draws, q.n_iter, 3, q.n)) return ASD_ERR_INVALID;
+    hyps[j] = q.n_iter;
     total += (size_t)q.n_iter;
     if (total > ASD_SIM3_RANSAC_MAX_HYPOTHESES) {
       ctx->set_error("asd_sim3_ransac: problem %d brings the call to %zu iterations, the limit is %d", j, total, ASD_SIM3_RANSAC_MAX_HYPOTHESES);
@@ -291,39 +252,18 @@ int asd_sim3_ransac(asd_ctx* ctx, int32_t n_problems, asd_sim3_ransac_problem* p
     }
     up_bytes += (size_t)q.n * 48 + (size_t)q.n_iter * 12 + 8 * 256;
     down_bytes += (size_t)q.n + 32 + 2 * 256;
-    mask_words += (size_t)q.n_iter * (((size_t)q.n + 63) / 64);
+    mask_bytes += AsdDevBuf::padded((size_t)q.n_iter * (((size_t)q.n + 63) / 64) * 8);
   }
   if (!ctx->sim3_ransac) ctx->sim3_ransac = new Sim3RansacState();
   Sim3RansacState* S = static_cast<Sim3RansacState*>(ctx->sim3_ransac);
-  S->recs.clear();
-  S->first.assign(n_problems, 0);
-  S->count.assign(n_problems, 0);
+  S->reset(n_problems);
   for (int32_t j = 0; j < n_problems; ++j)
-    if (!runs[j] && p[j].n >= p[j].min_inliers) {   // no iteration left to run: iterate()'s loop body is not entered (:158)
-      p[j].best_updated = 0; p[j].found = 0; p[j].iterations_done = 0; p[j].n_inliers = 0;
-      if (p[j].inliers && p[j].n > 0) memset(p[j].inliers, 0, (size_t)p[j].n);
-    } else if (!runs[j]) {
-      p[j].found = 0; p[j].iterations_done = 0;     // :146-150: nothing else is written
-    }
+    if (!hyps[j]) ransac_runs_nothing(p[j]);   // :146-150, or no iteration left (:158)
   ctx->ms_sim3_ransac = 0;
   if (total == 0) return ASD_OK;
-  (void)hipSetDevice(ctx->cfg.device);
-  hipStream_t st = ctx->stream;
-  ASD_HIP_CHECK(ctx, ctx->up.begin(st, up_bytes + (size_t)n_problems * sizeof(Sim3RansacProb) + total * 4 + 1024));
-  ASD_HIP_CHECK(ctx, ctx->down.begin(st, down_bytes + total * sizeof(Sim3HypRec) + 1024));
-  ASD_HIP_CHECK(ctx, ctx->scratch.reserve(mask_words * 8 + 256));
-  unsigned long long* d_masks = ctx->scratch.carve<unsigned long long>(mask_words);
-  const size_t off_probs = ctx->up.reserve((size_t)n_problems * sizeof(Sim3RansacProb)), off_map = ctx->up.reserve(total * 4);
-  const size_t off_recs = ctx->down.reserve(total * sizeof(Sim3HypRec));
   std::vector<size_t> off_inl(n_problems, 0), off_res(n_problems, 0);
-  Sim3RansacProb* hp = ctx->up.host<Sim3RansacProb>(off_probs);
-  int32_t* hmap = ctx->up.host<int32_t>(off_map);
-  size_t hyp = 0, words_used = 0;
-  for (int32_t j = 0; j < n_problems; ++j) {
-    Sim3RansacProb& d = hp[j];
-    memset(&d, 0, sizeof d);
-    d.hyp_first = (int32_t)hyp;
-    if (!runs[j]) continue;   // n = n_iter = 0: k_sim3_select's workgroup of this problem touches nothing
+  hipStream_t st = ctx->stream;
+  const auto pack = [&](const int32_t j, Sim3RansacProb& d) {
     const asd_sim3_ransac_problem& q = p[j];
     const size_t n = (size_t)q.n;
     d.n = q.n; d.n_iter = q.n_iter; d.fix_scale = q.fix_scale ? 1 : 0; d.min_inliers = q.min_inliers; d.best_in = q.best_inliers;
@@ -345,39 +285,29 @@ int asd_sim3_ransac(asd_ctx* ctx, int32_t n_problems, asd_sim3_ransac_problem* p
     d.im1 = ctx->up.dev<float>(off_im1);
     d.im2 = ctx->up.dev<float>(off_im2);
     d.draws = ctx->up.dev<int32_t>(ctx->up.add(q.draws, (size_t)q.n_iter * 12));
-    d.masks = d_masks + words_used;
-    words_used += (size_t)q.n_iter * d.words;
+    d.masks = ctx->scratch.carve<unsigned long long>((size_t)q.n_iter * d.words);
     off_inl[j] = ctx->down.reserve(n);
     off_res[j] = ctx->down.reserve(32);
     d.inliers = ctx->down.dev<uint8_t>(off_inl[j]);
     d.result = ctx->down.dev<int32_t>(off_res[j]);
-    for (int32_t k = 0; k < q.n_iter; ++k) hmap[hyp + k] = j;
-    hyp += (size_t)q.n_iter;
-  }
-  ASD_HIP_CHECK(ctx, hipEventRecord(ctx->ev0, st));
-  ASD_HIP_CHECK(ctx, ctx->up.upload(st));
-  hipLaunchKernelGGL(k_sim3_hyp, dim3((unsigned)total), dim3(kRansacThreads), 0, st, ctx->up.dev<Sim3RansacProb>(off_probs),
-                     ctx->up.dev<int32_t>(off_map), ctx->down.dev<Sim3HypRec>(off_recs));
-  ASD_HIP_CHECK(ctx, hipGetLastError());
-  hipLaunchKernelGGL(k_sim3_select, dim3((unsigned)n_problems), dim3(kRansacThreads), 0, st, ctx->up.dev<Sim3RansacProb>(off_probs),
-                     ctx->down.dev<Sim3HypRec>(off_recs));
-  ASD_HIP_CHECK(ctx, hipGetLastError());
-  ASD_HIP_CHECK(ctx, hipEventRecord(ctx->ev1, st));
-  ASD_HIP_CHECK(ctx, ctx->down.download(st));
-  ASD_HIP_CHECK(ctx, hipStreamSynchronize(st));
-  ASD_HIP_CHECK(ctx, hipEventElapsedTime(&ctx->ms_sim3_ransac, ctx->ev0, ctx->ev1));
-  const Sim3HypRec* recs = ctx->down.host<Sim3HypRec>(off_recs);
-  S->recs.assign(recs, recs + total);
+  };
+  const int e = ransac_run<Sim3RansacProb>(
+      ctx, hyps, up_bytes, down_bytes, mask_bytes + 256, total, &ctx->ms_sim3_ransac, nullptr, *S, pack,
+      [&](unsigned grid, const Sim3RansacProb* probs, const int32_t* map, Sim3HypRec* recs) {
+        hipLaunchKernelGGL(k_sim3_hyp, dim3(grid), dim3(kRansacThreads), 0, st, probs, map, recs);
+      },
+      [&](unsigned grid, const Sim3RansacProb* probs, const Sim3HypRec* recs) {
+        hipLaunchKernelGGL(k_sim3_select, dim3(grid), dim3(kRansacThreads), 0, st, probs, recs);
+      });
+  if (e != ASD_OK) return e;
   for (int32_t j = 0; j < n_problems; ++j) {
-    S->first[j] = hp[j].hyp_first;
-    if (!runs[j]) continue;
-    S->count[j] = p[j].n_iter;
+    if (!hyps[j]) continue;
     asd_sim3_ransac_problem& q = p[j];
     const int32_t* r = ctx->down.host<int32_t>(off_res[j]);
     q.best_inliers = r[0];
     q.best_updated = r[1];
     if (r[1]) {   // :185-190
-      const Sim3HypRec& b = recs[hp[j].hyp_first + r[2]];
+      const Sim3HypRec& b = S->recs[S->first[j] + r[2]];
       memcpy(q.R12, b.R12, sizeof q.R12);
       memcpy(q.t12, b.t12, sizeof q.t12);
       memcpy(q.T12, b.T12, sizeof q.T12);

@@ -905,6 +905,41 @@ class DrawStream {
   std::deque<int> pending_;
 };
 
+// The random numbers of one batched call: K per iteration, drawn ahead of the call and handed to it as the RandomInt values; what the
+// call did not consume goes back to the stream.  Sim3Solver, PnPsolver and Initializer draw through it.
+class DrawBatch {
+ public:
+  // n_iter x K calls of stream.Next() in iteration order, draw i of an iteration as RandomInt(0, N - 1 - i) (vAvailableIndices.size() - 1);
+  // returns the [n_iter][K] table for the problem's `draws`
+  const int32_t* Draw(DrawStream& stream, int n_iter, int K, int N) {
+    stream_ = &stream;
+    raw_.resize((size_t)K * n_iter);
+    randi_.resize((size_t)K * n_iter);
+    for (int k = 0; k < n_iter; ++k)
+      for (int i = 0; i < K; ++i) {
+        raw_[(size_t)K * k + i] = stream.Next();
+        randi_[(size_t)K * k + i] = stream.RandomInt(raw_[(size_t)K * k + i], 0, N - 1 - i);
+      }
+    return randi_.data();
+  }
+  // the first `used` raw values were consumed: the tail goes back to the stream
+  void Keep(size_t used) {
+    if (stream_) stream_->GiveBack(raw_.data() + used, raw_.size() - used);
+    last_raw_.assign(raw_.begin(), raw_.begin() + used);
+    raw_.clear();
+  }
+  // Draw undone: every random number back to the stream
+  void Cancel() {
+    if (stream_) stream_->GiveBack(raw_.data(), raw_.size());
+    raw_.clear();
+  }
+  const std::vector<int>& LastRawConsumed() const { return last_raw_; }   // the raw values the last Keep kept (test aid)
+ private:
+  DrawStream* stream_ = nullptr;
+  std::vector<int> raw_, last_raw_;
+  std::vector<int32_t> randi_;
+};
+
 // ---- Sim3Solver (Sim3Solver.h:36-128; src/vslam/src/Sim3Solver.cc) -----------------------------------------------------------
 // The RANSAC iterations run on the device (asd_sim3_ransac); this class keeps what the reference's object keeps between iterate()
 // calls: the gathered correspondences, mnIterations, mnBestInliers and the best model.  iterate() = Begin + asd_sim3_ransac + End;
@@ -987,20 +1022,13 @@ class Sim3Solver {
     p = asd_sim3_ransac_problem{};
     if (N < mRansacMinInliers) return false;
     const int n_iter = std::max(0, std::min(nIterations, mRansacMaxIts - mnIterations));
-    raw_.resize((size_t)3 * n_iter);
-    randi_.resize((size_t)3 * n_iter);
-    for (int k = 0; k < n_iter; ++k)
-      for (int i = 0; i < 3; ++i) {
-        raw_[3 * k + i] = draws_->Next();
-        randi_[3 * k + i] = draws_->RandomInt(raw_[3 * k + i], 0, N - 1 - i);   // RandomInt(0, vAvailableIndices.size() - 1)
-      }
+    p.draws = batch_.Draw(*draws_, n_iter, 3, N);
     inliers_.assign((size_t)N + 1, 0);
     p.n = N;
     p.X1c = mvX3Dc1.data(); p.X2c = mvX3Dc2.data(); p.max_err1 = mvnMaxError1.data(); p.max_err2 = mvnMaxError2.data();
     const float k1[4] = {mK1.fx, mK1.fy, mK1.cx, mK1.cy}, k2[4] = {mK2.fx, mK2.fy, mK2.cx, mK2.cy};
     for (int i = 0; i < 4; ++i) { p.K1[i] = k1[i]; p.K2[i] = k2[i]; }
     p.fix_scale = mbFixScale; p.min_inliers = mRansacMinInliers; p.n_iter = n_iter;
-    p.draws = randi_.data();
     p.best_inliers = mnBestInliers;
     p.inliers = inliers_.data();
     return true;
@@ -1010,10 +1038,7 @@ class Sim3Solver {
     bNoMore = false;
     vbInliers.assign(mN1, false);
     nInliers = 0;
-    const size_t used = (size_t)3 * p.iterations_done;
-    draws_->GiveBack(raw_.data() + used, raw_.size() - used);
-    last_raw_.assign(raw_.begin(), raw_.begin() + used);
-    raw_.clear();
+    batch_.Keep((size_t)3 * p.iterations_done);
     mnIterations += p.iterations_done;
     mnBestInliers = p.best_inliers;
     if (p.best_updated) {                                                             // :185-190
@@ -1032,11 +1057,8 @@ class Sim3Solver {
     return false;
   }
   // Begin undone: every random number back to the stream, the object as it was (the reference would not have called iterate())
-  void Cancel() {
-    draws_->GiveBack(raw_.data(), raw_.size());
-    raw_.clear();
-  }
-  const std::vector<int>& LastRawConsumed() const { return last_raw_; }   // the raw values the last End kept (test aid)
+  void Cancel() { batch_.Cancel(); }
+  const std::vector<int>& LastRawConsumed() const { return batch_.LastRawConsumed(); }   // the raw values the last End kept (test aid)
 
  private:
   asd_ctx* ctx_;
@@ -1050,8 +1072,7 @@ class Sim3Solver {
   int mRansacMinInliers = 6, mRansacMaxIts = 300, mnIterations = 0, mnBestInliers = 0;
   float mBestRotation[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1}, mBestTranslation[3] = {0, 0, 0}, mBestScale = 1.f;
   float mBestT12[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};
-  std::vector<int> raw_, last_raw_;
-  std::vector<int32_t> randi_;
+  DrawBatch batch_;
   std::vector<uint8_t> inliers_;
 };
 
@@ -1131,20 +1152,13 @@ class PnPsolver {
     p = asd_pnp_ransac_problem{};
     if (N < mRansacMinInliers) return false;
     const int n_iter = std::max(0, std::max(nIterations, mRansacMaxIts - mnIterations));
-    raw_.resize((size_t)4 * n_iter);
-    randi_.resize((size_t)4 * n_iter);
-    for (int k = 0; k < n_iter; ++k)
-      for (int i = 0; i < 4; ++i) {
-        raw_[4 * k + i] = draws_->Next();
-        randi_[4 * k + i] = draws_->RandomInt(raw_[4 * k + i], 0, N - 1 - i);   // RandomInt(0, vAvailableIndices.size() - 1)
-      }
+    p.draws = batch_.Draw(*draws_, n_iter, 4, N);
     inliers_.assign((size_t)N + 1, 0);
     best_mask_.assign((size_t)N + 1, 0);
     p.n = N;
     p.P3Dw = mvP3Dw.data(); p.P2D = mvP2D.data(); p.max_err = mvMaxError.data();
     p.K[0] = mK.fx; p.K[1] = mK.fy; p.K[2] = mK.cx; p.K[3] = mK.cy;
     p.min_inliers = mRansacMinInliers; p.n_iter = n_iter;
-    p.draws = randi_.data();
     p.best_inliers = mnBestInliers;
     p.best_mask = best_mask_.data();
     p.inliers = inliers_.data();
@@ -1170,10 +1184,7 @@ class PnPsolver {
         if (d.count <= mnBestInliers) { again = true; done = k + 1; }                 // :212 not taken, :226 on the same set
         break;
       }
-    const size_t used = (size_t)4 * done;
-    draws_->GiveBack(raw_.data() + used, raw_.size() - used);
-    last_raw_.assign(raw_.begin(), raw_.begin() + used);
-    raw_.clear();
+    batch_.Keep((size_t)4 * done);
     mnIterations += done;
     if (again) {
       nInliers = mnRefinedInliers;
@@ -1228,11 +1239,8 @@ class PnPsolver {
     return false;
   }
   // Begin undone: every random number back to the stream, the object as it was (the reference would not have called iterate())
-  void Cancel() {
-    draws_->GiveBack(raw_.data(), raw_.size());
-    raw_.clear();
-  }
-  const std::vector<int>& LastRawConsumed() const { return last_raw_; }   // the raw values the last End kept (test aid)
+  void Cancel() { batch_.Cancel(); }
+  const std::vector<int>& LastRawConsumed() const { return batch_.LastRawConsumed(); }   // the raw values the last End kept (test aid)
 
  private:
   asd_ctx* ctx_;
@@ -1246,8 +1254,7 @@ class PnPsolver {
   float mBestTcw[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1}, mRefinedTcw[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};
   int mnRefinedInliers = 0;
   bool refined_ok_ = false;   // Refine() on the present mvbBestInliers succeeded (an earlier call returned its model)
-  std::vector<int> raw_, last_raw_;
-  std::vector<int32_t> randi_;
+  DrawBatch batch_;
   std::vector<uint8_t> inliers_, best_mask_;
 };
 
@@ -1594,10 +1601,9 @@ class Initializer {
   // the draws of one Initialize over N matches (:84-100): RandomInt(0, vAvailableIndices.size() - 1) eight times per iteration
   std::vector<int32_t> Draw(int N) {
     SeedRandOnce(0);
-    std::vector<int32_t> draws((size_t)8 * mMaxIterations);
-    for (int it = 0; it < mMaxIterations; ++it)
-      for (int j = 0; j < 8; ++j) draws[(size_t)8 * it + j] = stream_.RandomInt(stream_.Next(), 0, N - 1 - j);
-    return draws;
+    const int32_t* draws = batch_.Draw(stream_, mMaxIterations, 8, N);
+    batch_.Keep((size_t)8 * mMaxIterations);   // Initialize runs every iteration
+    return std::vector<int32_t>(draws, draws + (size_t)8 * mMaxIterations);
   }
   // bool Initialize(const Frame& CurrentFrame, const vector<int>& vMatches12, cv::Mat& R21, cv::Mat& t21, vector<cv::Point3f>& vP3D,
   //                 vector<bool>& vbTriangulated)  (:43-120).  R21 (row major) and t21 are written only when it returns true; vP3D and
@@ -1643,6 +1649,7 @@ class Initializer {
   std::vector<int32_t> mvDraws;
   asd_initializer_problem mLast{};
   DrawStream stream_;   // ::rand
+  DrawBatch batch_;
 };
 
 }  // namespace asd
