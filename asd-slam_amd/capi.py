@@ -1247,6 +1247,25 @@ class AsdHip:
         n = int(self.lib.asd_debug_gba_trials(self.ctx, _p(out), C.c_int32(cap)))
         return [int(v) for v in out[:min(n, cap)]]
 
+    def dense_solve(self, A, b, form, done=0, chol_ok_in=1, x0=None):
+        """One dense SPD solve by the kernel of `form` (0 k_ba_solve_lds, 1 k_ba_chol_lds, 2 k_ba_chol, 3 tiled on MFMA, 4 tiled on
+        plain FMA) -- asd_debug_dense_solve.  A: n x n f64, the lower triangle is the matrix; x0: what x holds on entry (default NaN).
+        Returns dict(x, chol_ok, L): L = the matrix as the kernel left it for forms 2 .. 4, else None."""
+        A = _c(A, np.float64)
+        b = _c(b, np.float64).reshape(-1)
+        n = int(A.shape[0]) if A.ndim == 2 else -1
+        if A.ndim != 2 or A.shape[1] != n or len(b) != n:
+            raise ValueError("dense_solve: A must be n x n and b of length n")
+        x = np.full(max(n, 1), np.nan) if x0 is None else _c(x0, np.float64).reshape(-1).copy()
+        if x0 is not None and len(x) != n:
+            raise ValueError("dense_solve: x0 must have length n")
+        L = np.empty((n, n), np.float64) if int(form) >= 2 else None
+        ok = C.c_int32(-1)
+        self.lib.asd_debug_dense_solve.restype = C.c_int32
+        self._chk(self.lib.asd_debug_dense_solve(self.ctx, C.c_int32(int(form)), C.c_int32(n), _p(A), _p(b), C.c_int32(int(done)),
+                                                 C.c_int32(int(chol_ok_in)), _p(L), _p(x), C.byref(ok)))
+        return dict(x=x[:n], chol_ok=int(ok.value), L=L)
+
     def local_ba_submit(self, prob, its_first=5, its_second=10):
         """LocalBundleAdjustment on the library's OPTIONAL lane: returns at once; local_ba_wait() returns the result dict.  One run
         at a time.  Not the reference's order -- Tracking.cc:797 -> LocalMapping.cc:89 runs it in line (local_ba above); frames tracked

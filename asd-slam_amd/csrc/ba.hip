@@ -1679,6 +1679,34 @@ __global__ __launch_bounds__(1024) void k_ba_chol(double* __restrict__ A, const 
   if (t == 0) lm->chol_ok = ok;
 }
 
+// The three one-workgroup solvers as every caller launches them (LocalBA, asd_bundle_adjustment below ASD_GBA_TILED_FROM free poses,
+// asd_debug_dense_solve): which one a size gets, and each one's threads and dynamic LDS -- written down here and nowhere else.
+constexpr int kCholMaxBlocks = 32;   // xs / invd of k_ba_chol_lds hold 192 rows
+constexpr int ba_dense_form(int nPf) { return nPf <= kSolveMaxBlocks ? 0 : nPf <= kCholMaxBlocks ? 1 : 2; }
+inline size_t ba_solve_lds_bytes(int nb) {
+  const size_t nbk = (size_t)(nb * (nb + 1) / 2);
+  return (nbk * 36 + (size_t)2 * (kSolveMaxBlocks - 1) * 36 + 192 + 72 + 2) * sizeof(double) + nbk * sizeof(short2) + 16;
+}
+inline size_t ba_chol_lds_bytes(int nb) {
+  const size_t nbk = (size_t)(nb * (nb + 1) / 2);
+  return nbk * 36 * sizeof(double) + (2 * 192 + 2) * sizeof(double) + nbk * sizeof(short2) + 16;
+}
+constexpr int kSolveLdsAttr = 160 * 1024, kCholLdsAttr = 158 * 1024;
+// form 0: Apack (the packed lower triangle), 1 / 2: A (n x n; form 2 leaves L in its lower triangle); n = 6 x pose blocks
+int ba_dense_enqueue(asd_ctx* ctx, hipStream_t st, int form, const double* Apack, double* A, const double* bs, double* x, int n, LmState* lm) {
+  static AsdPerDeviceOnce attr_set;   // the dynamic-LDS attribute is per device
+  if (attr_set.need(ctx->cfg.device)) {
+    ASD_HIP_CHECK(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(k_ba_chol_lds), hipFuncAttributeMaxDynamicSharedMemorySize, kCholLdsAttr));
+    ASD_HIP_CHECK(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(k_ba_solve_lds), hipFuncAttributeMaxDynamicSharedMemorySize, kSolveLdsAttr));
+    attr_set.done(ctx->cfg.device);
+  }
+  if (form == 0) hipLaunchKernelGGL(k_ba_solve_lds, dim3(1), dim3(kSolveThreads), ba_solve_lds_bytes(n / 6), st, Apack, bs, x, n, lm);
+  else if (form == 1) hipLaunchKernelGGL(k_ba_chol_lds, dim3(1), dim3(kCholThreads), ba_chol_lds_bytes(n / 6), st, A, bs, x, n, lm);
+  else hipLaunchKernelGGL(k_ba_chol, dim3(1), dim3(1024), 0, st, A, bs, x, n, lm);
+  return ASD_OK;
+}
+static_assert(ba_dense_form(kSolveMaxBlocks) == 0 && ba_dense_form(kCholMaxBlocks) == 1 && ba_dense_form(kCholMaxBlocks + 1) == 2, "");
+
 // The step applied: one launch, two kinds of workgroup.  [0, gL): xl = Dinv (bl - B^T xp) and the trial point = accepted point + xl;
 // [gL, gL + gP): the trial pose = exp(xp) * accepted pose (VertexSE3Expmap::oplusImpl).  Both write the TRIAL buffer and leave the
 // accepted estimate alone; each workgroup also leaves its part of the gain-ratio denominator sum_j x_j (lambda x_j + b_j).
@@ -2732,7 +2760,7 @@ int local_ba_impl(asd_ctx* ctx, BaState* s, asd_ba_problem* pr, asd_ba_result* r
     if (round_idx == 0) struct_form = struct_dev ? 0 : 1;
     {
       int* f = s->forms[round_idx];
-      f[0] = Ea == 0 || nPf == 0 ? -1 : nPf <= kSolveMaxBlocks ? 0 : nPf <= 32 ? 1 : 2;   // the dense solve enqueue_block picks
+      f[0] = Ea == 0 || nPf == 0 ? -1 : ba_dense_form(nPf);   // the dense solve enqueue_block picks
       f[1] = struct_form; f[2] = nPf; f[3] = nLa; f[4] = Ea;
     }
     t_prep = std::chrono::steady_clock::now();
@@ -2753,22 +2781,8 @@ int local_ba_impl(asd_ctx* ctx, BaState* s, asd_ba_problem* pr, asd_ba_result* r
       hipLaunchKernelGGL(k_ba_reduce, dim3(nPf * kPoseSplit + gL), dim3(256), 0, st, d);
       if (nPf > 0) {
         hipLaunchKernelGGL(k_ba_schur, dim3(nblk + nPf), dim3(kSchurThreads), 0, st, d, sb, nblk);
-        const size_t nbk = (size_t)(nPf * (nPf + 1) / 2);
-        static AsdPerDeviceOnce attr_set;   // the dynamic-LDS attribute is per device
-        if (attr_set.need(ctx->cfg.device)) {
-          ASD_HIP_CHECK(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(k_ba_chol_lds), hipFuncAttributeMaxDynamicSharedMemorySize, 158 * 1024));
-          ASD_HIP_CHECK(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(k_ba_solve_lds), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-          attr_set.done(ctx->cfg.device);
-        }
-        if (nPf <= kSolveMaxBlocks) {
-          const size_t lds = (nbk * 36 + (size_t)2 * (kSolveMaxBlocks - 1) * 36 + 192 + 72 + 2) * sizeof(double) + nbk * sizeof(short2) + 16;
-          hipLaunchKernelGGL(k_ba_solve_lds, dim3(1), dim3(kSolveThreads), lds, st, d.Apack, d.bs, d.x, n, d.lm);
-        } else if (nPf <= 32) {
-          const size_t lds = nbk * 36 * sizeof(double) + (2 * 192 + 2) * sizeof(double) + nbk * sizeof(short2) + 16;
-          hipLaunchKernelGGL(k_ba_chol_lds, dim3(1), dim3(kCholThreads), lds, st, d.A, d.bs, d.x, n, d.lm);
-        } else {
-          hipLaunchKernelGGL(k_ba_chol, dim3(1), dim3(1024), 0, st, d.A, d.bs, d.x, n, d.lm);
-        }
+        const int r2 = ba_dense_enqueue(ctx, st, ba_dense_form(nPf), d.Apack, d.A, d.bs, d.x, n, d.lm);
+        if (r2 != ASD_OK) return r2;
       }
       hipLaunchKernelGGL(k_ba_step, dim3(gL + gP), dim3(256), 0, st, d);
       hipLaunchKernelGGL(k_ba_error, dim3(gE), dim3(256), 0, st, d, robust ? 1 : 0, 0, 0);   // + the Levenberg control, in its last workgroup
@@ -3088,7 +3102,7 @@ int gba_impl(asd_ctx* ctx, BaState* s, asd_gba_problem* pr, asd_gba_result* res)
 
   // the form of the dense solve
   const bool tiled = ctx->gba_solve == 1 || (ctx->gba_solve == 0 && nPf >= ASD_GBA_TILED_FROM);
-  const int form = tiled ? 3 : nPf <= kSolveMaxBlocks ? 0 : nPf <= 32 ? 1 : 2;
+  const int form = tiled ? 3 : ba_dense_form(nPf);
   const bool all_blocks = form <= 1;   // the LDS solvers read the packed system whole: every upper block gets its workgroup, as in LocalBA
   // Schur pair lists per upper block (bi <= bj).  A diagonal block always has a workgroup (Hpp + lambda I); an off-diagonal block
   // only when a landmark connects its two poses -- a map's covisibility is banded, at 1024 free poses the dense triangle would be
@@ -3234,22 +3248,7 @@ int gba_impl(asd_ctx* ctx, BaState* s, asd_gba_problem* pr, asd_gba_result* res)
     if (form == 3) {
       if ((r2 = gba_solve_enqueue(ctx, st, d.A, d.bs, d.x, n, &d.lm->done, &d.lm->chol_ok, !ctx->gba_update_fma)) != ASD_OK) return r2;
     } else {
-      const size_t nbk = (size_t)(nPf * (nPf + 1) / 2);
-      static AsdPerDeviceOnce attr_set;   // the dynamic-LDS attribute is per device
-      if (attr_set.need(ctx->cfg.device)) {
-        ASD_HIP_CHECK(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(k_ba_chol_lds), hipFuncAttributeMaxDynamicSharedMemorySize, 158 * 1024));
-        ASD_HIP_CHECK(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(k_ba_solve_lds), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        attr_set.done(ctx->cfg.device);
-      }
-      if (form == 0) {
-        const size_t lds = (nbk * 36 + (size_t)2 * (kSolveMaxBlocks - 1) * 36 + 192 + 72 + 2) * sizeof(double) + nbk * sizeof(short2) + 16;
-        hipLaunchKernelGGL(k_ba_solve_lds, dim3(1), dim3(kSolveThreads), lds, st, d.Apack, d.bs, d.x, n, d.lm);
-      } else if (form == 1) {
-        const size_t lds = nbk * 36 * sizeof(double) + (2 * 192 + 2) * sizeof(double) + nbk * sizeof(short2) + 16;
-        hipLaunchKernelGGL(k_ba_chol_lds, dim3(1), dim3(kCholThreads), lds, st, d.A, d.bs, d.x, n, d.lm);
-      } else {
-        hipLaunchKernelGGL(k_ba_chol, dim3(1), dim3(1024), 0, st, d.A, d.bs, d.x, n, d.lm);
-      }
+      if ((r2 = ba_dense_enqueue(ctx, st, form, d.Apack, d.A, d.bs, d.x, n, d.lm)) != ASD_OK) return r2;
     }
     hipLaunchKernelGGL(k_ba_step, dim3(gL + gP), dim3(256), 0, st, d);
     hipLaunchKernelGGL(k_ba_error, dim3(gE), dim3(256), 0, st, d, robust, 0, 0);   // + the Levenberg control, in its last workgroup
@@ -3327,6 +3326,75 @@ int32_t asd_debug_gba_trials(const asd_ctx* ctx, int32_t* out, int32_t cap) {
   const int n = s ? (int)s->gba_trials.size() : 0;
   for (int k = 0; k < cap; ++k) out[k] = k < n ? s->gba_trials[k] : -1;
   return n;
+}
+
+int32_t asd_debug_dense_solve(asd_ctx* ctx, int32_t form, int32_t n, const double* A, const double* b, int32_t done_in, int32_t chol_ok_in,
+                              double* L_out, double* x_out, int32_t* chol_ok_out) {
+  if (!ctx) return ASD_ERR_INVALID;
+  if (!A || !b || !x_out || !chol_ok_out) { ctx->set_error("asd_debug_dense_solve: null argument"); return ASD_ERR_INVALID; }
+  if (form < 0 || form > 4) { ctx->set_error("asd_debug_dense_solve: form %d is not 0 .. 4", form); return ASD_ERR_INVALID; }
+  if (n <= 0) { ctx->set_error("asd_debug_dense_solve: n = %d is not positive", n); return ASD_ERR_INVALID; }
+  if (form <= 2) {
+    const int cap = form == 0 ? kSolveMaxBlocks : form == 1 ? kCholMaxBlocks : ASD_GBA_MAX_FREE_POSES;
+    if (n % 6 != 0 || n / 6 > cap) {
+      ctx->set_error("asd_debug_dense_solve: form %d takes n = 6 x (1 .. %d pose blocks), not %d", form, cap, n);
+      return ASD_ERR_INVALID;
+    }
+  } else if (n > 7 * ASD_GBA_MAX_FREE_POSES) {
+    ctx->set_error("asd_debug_dense_solve: form %d takes at most %d rows, not %d", form, 7 * ASD_GBA_MAX_FREE_POSES, n);
+    return ASD_ERR_INVALID;
+  }
+  if (ba_lane_busy(ctx, "asd_debug_dense_solve")) return ASD_ERR_INVALID;
+  (void)hipSetDevice(ctx->cfg.device);
+  hipStream_t st = ctx->stream;
+  const size_t nn = (size_t)n * (size_t)n;
+  // form 0 reads k_ba_schur's Apack: block (I, J <= I) at (I (I + 1) / 2 + J) * 36, row-major inside; the lower triangle of A is the
+  // matrix (a diagonal block's upper half is its mirror)
+  std::vector<double> pack;
+  if (form == 0) {
+    const int nb = n / 6;
+    pack.resize((size_t)nb * (nb + 1) / 2 * 36);
+    for (int I = 0; I < nb; ++I)
+      for (int J = 0; J <= I; ++J)
+        for (int r = 0; r < 6; ++r)
+          for (int c = 0; c < 6; ++c) {
+            const int gr = 6 * I + r, gc = 6 * J + c;
+            pack[((size_t)I * (I + 1) / 2 + J) * 36 + r * 6 + c] = gc <= gr ? A[(size_t)gr * n + gc] : A[(size_t)gc * n + gr];
+          }
+  }
+  LmState lm0;
+  memset(&lm0, 0, sizeof lm0);
+  lm0.done = done_in; lm0.chol_ok = chol_ok_in;
+  const size_t szA = AsdDevBuf::padded((form == 0 ? pack.size() : nn) * sizeof(double)), szV = AsdDevBuf::padded((size_t)n * sizeof(double));
+  char* dev = nullptr;
+  ASD_HIP_CHECK(ctx, hipMalloc(&dev, szA + 2 * szV + AsdDevBuf::padded(sizeof(LmState))));
+  double* dA = reinterpret_cast<double*>(dev);
+  double* db = reinterpret_cast<double*>(dev + szA);
+  double* dx = reinterpret_cast<double*>(dev + szA + szV);
+  LmState* dlm = reinterpret_cast<LmState*>(dev + szA + 2 * szV);
+  LmState lm1 = lm0;
+  auto body = [&]() -> int {
+    ASD_HIP_CHECK(ctx, hipMemcpyAsync(dA, form == 0 ? pack.data() : A, (form == 0 ? pack.size() : nn) * sizeof(double), hipMemcpyHostToDevice, st));
+    ASD_HIP_CHECK(ctx, hipMemcpyAsync(db, b, (size_t)n * sizeof(double), hipMemcpyHostToDevice, st));
+    ASD_HIP_CHECK(ctx, hipMemcpyAsync(dx, x_out, (size_t)n * sizeof(double), hipMemcpyHostToDevice, st));   // (the caller's sentinel)
+    ASD_HIP_CHECK(ctx, hipMemcpyAsync(dlm, &lm0, sizeof lm0, hipMemcpyHostToDevice, st));
+    int rc;
+    if (form <= 2) rc = ba_dense_enqueue(ctx, st, form, dA, dA, db, dx, n, dlm);
+    else rc = gba_solve_enqueue(ctx, st, dA, db, dx, n, &dlm->done, &dlm->chol_ok, form == 3);
+    if (rc != ASD_OK) return rc;
+    ASD_HIP_CHECK(ctx, hipGetLastError());
+    ASD_HIP_CHECK(ctx, hipMemcpyAsync(x_out, dx, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, st));
+    ASD_HIP_CHECK(ctx, hipMemcpyAsync(&lm1, dlm, sizeof lm1, hipMemcpyDeviceToHost, st));
+    if (L_out && form >= 2) ASD_HIP_CHECK(ctx, hipMemcpyAsync(L_out, dA, nn * sizeof(double), hipMemcpyDeviceToHost, st));
+    ASD_HIP_CHECK(ctx, hipStreamSynchronize(st));
+    return ASD_OK;
+  };
+  const int rc = body();
+  if (rc != ASD_OK) (void)hipStreamSynchronize(st);
+  (void)hipFree(dev);
+  if (rc != ASD_OK) return rc;
+  *chol_ok_out = lm1.chol_ok;
+  return ASD_OK;
 }
 
 int32_t asd_debug_gba_forms(const asd_ctx* ctx, int32_t out[5]) {

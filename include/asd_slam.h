@@ -734,6 +734,18 @@ int32_t asd_debug_gba_forms(const asd_ctx* ctx, int32_t out[5]);
  * levenbergIteration() reports them behind an iteration.  Writes min(cap, iterations) values, -1 behind them; returns the number
  * of iterations recorded (0 before any call, and for a call that ran none). */
 int32_t asd_debug_gba_trials(const asd_ctx* ctx, int32_t* out, int32_t cap);
+/* Test aid: ONE dense symmetric positive-definite solve A x = b in f64 by the kernel every optimiser ends in, launched as the
+ * production call sites launch it (tests/test_dense_solve.py).  form: 0 = k_ba_solve_lds (n = 6 x 1 .. 30 pose blocks; A is packed
+ * on the host the way k_ba_schur leaves it), 1 = k_ba_chol_lds (6 x 1 .. 32), 2 = k_ba_chol (6 x 1 .. ASD_GBA_MAX_FREE_POSES),
+ * 3 = the tiled Cholesky with its trailing update on f64 MFMA, 4 = the same on plain FMA (any n up to 7 x ASD_GBA_MAX_FREE_POSES).
+ * A: host, row-major n x n, the lower triangle is the matrix.  b: [n].  done_in / chol_ok_in: what the kernels find in the
+ * Levenberg state's `done` and `chol_ok` (done_in != 0: every kernel returns at once).  x_out [n]: uploaded as given, comes back
+ * as the kernel left it.  L_out: null, or [n][n] -- forms 2 .. 4: the matrix as the kernel left it (L in the lower triangle);
+ * forms 0 and 1 keep theirs in LDS and do not write it.  *chol_ok_out: the flag afterwards (0: a pivot was not positive; the call
+ * still returns ASD_OK).  ASD_ERR_INVALID for a size the form does not take and while a run of asd_local_ba_submit is outstanding.
+ * Allocates per call; not for a hot path. */
+int32_t asd_debug_dense_solve(asd_ctx* ctx, int32_t form, int32_t n, const double* A, const double* b, int32_t done_in,
+                              int32_t chol_ok_in, double* L_out, double* x_out, int32_t* chol_ok_out);
 
 /* ---- essential graph (Sim3 pose graph of a loop closure) --------------------------------- */
 typedef struct asd_essgraph_problem {
