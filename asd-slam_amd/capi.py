@@ -70,6 +70,13 @@ class asd_track_frame_args(C.Structure):
                 ("match2", C.c_void_p), ("n_matches2", C.c_void_p), ("outlier2", C.c_void_p), ("n_inliers2", C.c_void_p)]
 
 
+class asd_local_map_args(C.Structure):
+    _fields_ = [("n_cur", C.c_int32), ("cur_rows", C.c_void_p), ("n_seen", C.c_int32), ("seen_rows", C.c_void_p), ("n_prev", C.c_int32),
+                ("prev_kfs", C.c_void_p), ("max_kfs", C.c_int32), ("kf_capacity", C.c_int32), ("local_kfs", C.c_void_p),
+                ("n_local_kfs", C.c_int32), ("ref_kf", C.c_int32), ("row_capacity", C.c_int32), ("local_rows", C.c_void_p),
+                ("n_local", C.c_int32), ("search_capacity", C.c_int32), ("search_rows", C.c_void_p), ("n_search", C.c_int32)]
+
+
 class asd_ba_problem(C.Structure):
     _fields_ = [("n_poses", C.c_int32), ("n_points", C.c_int32), ("n_edges", C.c_int32),
                 ("poses", C.c_void_p), ("fixed", C.c_void_p), ("points", C.c_void_p),
@@ -870,6 +877,87 @@ class AsdHip:
         self._chk(self.lib.asd_debug_kfdb_entry(self.ctx, int(kf), _p(out), _p(sc)))
         return dict(loop_stamped=bool(out[0]), loop_words=int(out[1]), reloc_stamped=bool(out[2]), reloc_words=int(out[3]),
                     loop_score=np.float32(sc[0]), reloc_score=np.float32(sc[1]))
+
+    # ---- observation table and the local map (localmap.hip)
+    def map_clear(self):
+        self._chk(self.lib.asd_map_clear(self.ctx))
+
+    def map_put(self, kf, rows):
+        rows = _c(rows, np.int32)
+        self._chk(self.lib.asd_map_put(self.ctx, int(kf), len(rows), _p(rows)))
+
+    def map_set(self, kf, idx, rows):
+        idx, rows = _c(idx, np.int32), _c(rows, np.int32)
+        self._chk(self.lib.asd_map_set(self.ctx, int(kf), len(idx), _p(idx), _p(rows)))
+
+    def map_erase(self, kf):
+        self._chk(self.lib.asd_map_erase(self.ctx, int(kf)))
+
+    def map_kf_links(self, kf, cov, children, parent):
+        cov, children = _c(cov, np.int32), _c(children, np.int32)
+        self._chk(self.lib.asd_map_kf_links(self.ctx, int(kf), len(cov), _p(cov), len(children), _p(children), int(parent)))
+
+    def map_kf_bad(self, kf, flag=True):
+        self._chk(self.lib.asd_map_kf_bad(self.ctx, int(kf), int(bool(flag))))
+
+    def map_point_bad(self, rows, flag=True):
+        rows = _c(rows, np.int32)
+        self._chk(self.lib.asd_map_point_bad(self.ctx, len(rows), _p(rows), int(bool(flag))))
+
+    def update_local_map_raw(self, cur_rows, seen_rows, prev_kfs, max_kfs, kf_capacity, row_capacity, search_capacity):
+        """asd_update_local_map with the caller's capacities -> (rc, dict); the dict's lists are cut to the counts only when rc == 0"""
+        cur, seen, prev = _c(cur_rows, np.int32), _c(seen_rows, np.int32), _c(prev_kfs, np.int32)
+        kfs, rows, srch = (np.full(max(c, 1), -7, np.int32) for c in (kf_capacity, row_capacity, search_capacity))
+        a = asd_local_map_args()
+        a.n_cur, a.cur_rows, a.n_seen, a.seen_rows, a.n_prev, a.prev_kfs = len(cur), cur.ctypes.data, len(seen), seen.ctypes.data, len(prev), prev.ctypes.data
+        a.max_kfs = int(max_kfs)
+        a.kf_capacity, a.local_kfs, a.row_capacity, a.local_rows = int(kf_capacity), kfs.ctypes.data, int(row_capacity), rows.ctypes.data
+        a.search_capacity, a.search_rows = int(search_capacity), srch.ctypes.data
+        rc = self.lib.asd_update_local_map(self.ctx, C.byref(a))
+        out = dict(n_local_kfs=a.n_local_kfs, ref_kf=a.ref_kf, n_local=a.n_local, n_search=a.n_search)
+        if rc == 0:
+            out.update(local_kfs=kfs[:a.n_local_kfs].copy(), local_rows=rows[:a.n_local].copy(), search_rows=srch[:a.n_search].copy())
+        return rc, out
+
+    def update_local_map(self, cur_rows, seen_rows=(), prev_kfs=(), max_kfs=80):
+        """Tracking::UpdateLocalMap + SearchLocalPoints' skip loop -> dict(local_kfs, ref_kf, local_rows, search_rows); repeats once with the
+        counts the library asked for (the ASD_ERR_CAPACITY rule of the call)"""
+        rc, out = self.update_local_map_raw(cur_rows, seen_rows, prev_kfs, max_kfs, 256, 65536, 65536)
+        if rc == -5:   # ASD_ERR_CAPACITY
+            rc, out = self.update_local_map_raw(cur_rows, seen_rows, prev_kfs, max_kfs, out["n_local_kfs"], out["n_local"], out["n_search"])
+        self._chk(rc)
+        return out
+
+    def map_shared_counts(self, kf, capacity=None):
+        """KFcounter of KeyFrame::UpdateConnections -> (keyframe ids ascending, counts)"""
+        cap = int(self.map_debug()[0]) if capacity is None else int(capacity)
+        kfs, cnt, n = np.empty(max(cap, 1), np.int32), np.empty(max(cap, 1), np.int32), C.c_int32(0)
+        rc = self.lib.asd_map_shared_counts(self.ctx, int(kf), cap, _p(kfs), _p(cnt), C.byref(n))
+        if rc != 0:
+            raise AsdError(rc, f"{self.last_error()} [n = {n.value}]")
+        return kfs[:n.value].copy(), cnt[:n.value].copy()
+
+    def map_debug(self):
+        """(live keyframes, live entries, slot capacity, arena capacity, row-table capacity, slot / arena / row-table growths)"""
+        out = np.zeros(8, np.int64)
+        self._chk(self.lib.asd_debug_map(self.ctx, _p(out)))
+        return tuple(int(x) for x in out)
+
+    def track_local_points_map(self, slot_cur, n_cur, Tcw, K, occupied, cur_Xw, th, nn_ratio, pose7, cos_limit=0.5, obs_positive=None, split=False):
+        """asd_track_local_points_map: asd_track_local_points_rows over the search list the last update_local_map left on the device"""
+        Tcw, K, occupied, cur_Xw = _c(Tcw, np.float32), _c(K, np.float32), _c(occupied, np.uint8), _c(cur_Xw, np.float32)
+        match, outl = np.empty(n_cur, np.int32), np.empty(max(n_cur, 1), np.uint8)
+        pose = _c(pose7, np.float64).copy()
+        n, ninl = C.c_int32(), C.c_int32()
+        if split:
+            self._chk(self.lib.asd_track_async(self.ctx))
+        self._chk(self.lib.asd_track_local_points_map(self.ctx, slot_cur, _p(Tcw), _p(K), C.c_float(cos_limit), _p(occupied), _p(cur_Xw), C.c_float(th),
+                                                      C.c_float(nn_ratio), _p(None if obs_positive is None else _c(obs_positive, np.uint8)), _p(pose),
+                                                      _p(match), C.byref(n), _p(outl), C.byref(ninl)))
+        if split:
+            self._track_job = (match, n, pose, outl, ninl, n_cur)
+            return None
+        return match, n.value, pose, outl[:n_cur], ninl.value
 
     def bank_put(self, first_row, desc):
         desc = _c(desc, np.float32)

@@ -164,6 +164,7 @@ int asd_ctx_destroy(asd_ctx* ctx) {
   pnp_ransac_free(ctx);
   initializer_free(ctx);
   kfdb_free(ctx);
+  localmap_free(ctx);
   ctx->scratch.release();
   ctx->stereo_scratch.release();
   ctx->up.release();

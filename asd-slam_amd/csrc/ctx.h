@@ -350,6 +350,9 @@ struct asd_ctx {
   // ---- keyframe database (state private to kfdb.hip)
   void* kfdb = nullptr;
 
+  // ---- observation table and UpdateLocalMap (state private to localmap.hip)
+  void* localmap = nullptr;
+
   // ---- OptimizeEssentialGraph: device buffers and the last call's test aids (state private to essgraph.hip)
   void* essgraph = nullptr;
 
@@ -419,6 +422,10 @@ void pnp_ransac_free(asd_ctx* ctx);
 void initializer_free(asd_ctx* ctx);
 void kfdb_free(asd_ctx* ctx);
 void essgraph_free(asd_ctx* ctx);
+void localmap_free(asd_ctx* ctx);
+// localmap.hip: the search list the last asd_update_local_map left (host copy, device copy, length), or ASD_ERR_INVALID with the message set
+// when there is none, it is empty, or the observation table has changed since
+int localmap_search_list(asd_ctx* ctx, const char* who, const int32_t** h_rows, const int32_t** d_rows, int* n);
 const char* kfdb_host_error();   // the message of this thread's last asd_bow_score (a call without a context)
 // The claim replay that makes d_src, to run in FRONT of the solver inside its workgroup (k_resolve_pose, ba.hip) instead of as a kernel of
 // its own: args = the Resolve2Args of resolve2.h (both translation units include it), kind 0 / 1, nq = its query count, lds = the

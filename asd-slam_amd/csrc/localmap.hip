@@ -1,0 +1,938 @@
+// localmap.hip -- Tracking::UpdateLocalMap (reference src/vslam/src/Tracking.cc:871-1015) with SearchLocalPoints' skip loop (:827-841), and
+// the counting half of KeyFrame::UpdateConnections (src/vslam/src/KeyFrame.cc:541-573), over a resident observation table.
+//
+// Device layout.  The table is keyframe-major: one arena of int32 bank rows (-1 = no map point), a slot table {offset, length, id, bad,
+// covisibles, parent} in front of it (a free slot has length -1; ids map to slots as in kfdb.hip), the children lists as one CSR block
+// and the live ids in ascending order with their slots (both rebuilt by the next query after a call that changed them).  Three tables
+// run by bank row: MapPoint::isBad() as a byte, the frame's marks (the vote multiplicity in the low bits, "carries mnLastFrameSeen" in
+// bit 30) and the claim word of the ordered de-duplication.  Marks and claims are never cleared as a whole: a query undoes exactly what
+// it touched (k_lm_unmark; the surviving claimant resets its claim word).
+//
+// A query.  k_lm_mark (integer atomics on the mark table) -> k_lm_vote (one wave per slot walks the keyframe's row with coalesced loads and
+// adds the marks' multiplicities: every table entry counts, see the header's precondition) -> k_lm_decide (ONE workgroup: the voted
+// keyframes in ascending id, pKFmax, the expansion :958-1008, the prefix of the row lengths over the list) -> the host reads five
+// numbers and sizes the rest -> k_lm_claim (every entry of the concatenated rows claims its point with atomicMin of its global position)
+// -> k_lm_count / k_lm_tilescan / k_lm_scatter (the claimants compacted in position order into mvpLocalMapPoints and the sub-list
+// SearchLocalPoints does not skip).  Every decision is a minimum, a maximum or a scan over integers: the output does not depend on the
+// scheduling.
+//
+// The ordering rule.  Where the reference walks a std::map<KeyFrame*, ...> or a std::set<KeyFrame*> in pointer order, the walk here is
+// in ascending keyframe id: the vote list, the first strict maximum, GetChilds().
+//
+// Streams.  Every copy into these tables and every kernel that reads them is enqueued on ctx->stream, every entry point returns with that
+// stream drained, and all of them are refused while an armed asd_track_* call is unfinished (asd_track_local_points_map reads the search
+// list on that stream).  A growth therefore orders itself against the only stream that can hold a write to the old storage: the copy
+// into the new block is enqueued behind them on ctx->stream, and the old block is freed after that stream has been waited for.  The
+// extractor's streams and asd_prep_async's second stream never touch these tables.
+#include <algorithm>
+#include <climits>
+#include <map>
+#include <unordered_map>
+#include <vector>
+
+#include "ctx.h"
+
+namespace {
+
+constexpr int kInitSlots = 64;            // slot table, arena and row tables start small and double
+constexpr long long kInitEntries = 16384;
+constexpr int kInitRows = 4096;
+constexpr int kMaxSlots = 1 << 18;        // the "included" bit set of k_lm_decide lives in LDS: 32 KB
+constexpr int kMaxKeypoints = 1 << 16;
+constexpr int kMaxRow = 1 << 28;
+constexpr int kMaxCov = 10;               // GetBestCovisibilityKeyFrames(10)
+constexpr int kMaxLocalKfs = 1000;        // bound of max_kfs: the appended ids of the expansion are kept in LDS
+constexpr int kVoteMask = 0x3fffffff, kSkipBit = 0x40000000;
+constexpr int kClaimFree = 0x7f7f7f7f;    // (a byte pattern: hipMemsetAsync fills the claim table)
+constexpr long long kMaxEntriesPerQuery = 0x7f000000;
+constexpr int kTile = 1024;               // entries per workgroup of the compaction: 4 rounds of 256
+
+struct LmSlotDev { long long off; int n; int id; int bad; int n_cov; int parent; int pad; int cov[kMaxCov]; int pad2[2]; };   // n < 0: free slot
+struct LmMove { long long from, to; int n; int pad; };
+
+struct LmDecideArgs {
+  const LmSlotDev* table;
+  const int* sorted_id; const int* sorted_slot; int n_live;   // the live keyframes in ascending id
+  const int* cnt;                                              // [slots] votes
+  const int* child_off; const int* children;                   // CSR by slot
+  const int* prev; int n_prev; int max_kfs; int incl_words;
+  int ids_in_lds;                                              // the ascending id list fits the LDS beside the bit set: the id -> slot searches read it there
+  int* list_id; int* list_slot; long long* list_base;          // out: mvpLocalKeyFrames, their slots (-1: not in the table), prefix of the row lengths
+  int* head;                                                   // out: n_list, ref_kf, any vote, longest row, entries (2 words), 0, 0, n_local, n_search
+};
+
+struct LmPointArgs {
+  const LmSlotDev* table; const int* rows;
+  const int* list_slot; const long long* list_base; int tiles_per_kf;
+  const uint8_t* pbad; const int* mark; int* claim;
+  int* tile_cnt; const int* tile_off;       // [tiles][2]: survivors of the local list and of the search list
+  int* d_local; int* d_search;              // the lists on the device
+  int* h_local; int cap_local; int* h_search; int cap_search;   // and in the pinned result block, as far as the caller's capacities go
+};
+
+__device__ inline int lm_lookup(const int* sorted_id, const int* sorted_slot, int n, int id) {
+  int lo = 0, hi = n;
+  while (lo < hi) { const int mid = (lo + hi) >> 1; if (sorted_id[mid] < id) lo = mid + 1; else hi = mid; }
+  return lo < n && sorted_id[lo] == id ? sorted_slot[lo] : -1;
+}
+
+// frame rows: cur [0, n_cur) vote (unless the point is bad) and are skipped by the search, seen [n_cur, n_cur + n_seen) are skipped only
+__global__ __launch_bounds__(256) void k_lm_mark(const int* __restrict__ cur, int n_cur, const int* __restrict__ seen, int n_seen,
+                                                 const uint8_t* __restrict__ pbad, int* __restrict__ mark) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i < n_cur) {
+    const int r = cur[i];
+    if (r >= 0) { atomicOr(&mark[r], kSkipBit); if (!pbad[r]) atomicAdd(&mark[r], 1); }
+  } else if (i < n_cur + n_seen) {
+    const int r = seen[i - n_cur];
+    if (r >= 0) atomicOr(&mark[r], kSkipBit);
+  }
+}
+__global__ __launch_bounds__(256) void k_lm_unmark(const int* __restrict__ cur, int n_cur, const int* __restrict__ seen, int n_seen, int* __restrict__ mark) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= n_cur + n_seen) return;
+  const int r = i < n_cur ? cur[i] : seen[i - n_cur];
+  if (r >= 0) mark[r] = 0;
+}
+
+// one wave per slot: the sum of the marks' multiplicities over the keyframe's row
+__global__ __launch_bounds__(256) void k_lm_vote(const LmSlotDev* __restrict__ table, int n_slots, const int* __restrict__ rows,
+                                                 const int* __restrict__ mark, int* __restrict__ cnt) {
+  const int lane = threadIdx.x & 63;
+  const int slot = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (slot >= n_slots) return;   // whole waves leave together
+  const long long off = table[slot].off;
+  const int n = table[slot].n;
+  int c = 0;
+  for (int i = lane; i < n; i += 64) {
+    const int r = rows[off + i];
+    if (r >= 0) c += mark[r] & kVoteMask;
+  }
+  for (int s = 32; s > 0; s >>= 1) c += __shfl_xor(c, s, 64);
+  if (lane == 0) cnt[slot] = c;
+}
+
+__global__ __launch_bounds__(256) void k_lm_set(int* __restrict__ row, const int* __restrict__ idx, const int* __restrict__ val, int n) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i < n) row[idx[i]] = val[i];
+}
+__global__ __launch_bounds__(256) void k_lm_point_bad(uint8_t* __restrict__ pbad, const int* __restrict__ rows, int n, int flag) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i < n) pbad[rows[i]] = (uint8_t)flag;
+}
+// growth: one workgroup per live keyframe copies its row from the old arena into the new one
+__global__ __launch_bounds__(256) void k_lm_move(const LmMove* __restrict__ mv, const int* __restrict__ r0, int* __restrict__ r1) {
+  const LmMove m = mv[blockIdx.x];
+  for (int t = threadIdx.x; t < m.n; t += 256) r1[m.to + t] = r0[m.from + t];
+}
+
+// exclusive prefix of one int per thread over the workgroup (256 threads); *total = the sum
+__device__ inline int lm_block_scan(int v, int* s, int* total) {
+  const int t = threadIdx.x;
+  s[t] = v;
+  asd_syncthreads();
+  for (int d = 1; d < 256; d <<= 1) {
+    const int x = t >= d ? s[t - d] : 0;
+    asd_syncthreads();
+    s[t] += x;
+    asd_syncthreads();
+  }
+  const int incl = s[t];
+  *total = s[255];
+  asd_syncthreads();
+  return incl - v;
+}
+// the same for a flag per thread: ballots, and one LDS word per wave
+__device__ inline int lm_block_scan_flag(bool f, int* s_wave, int* total) {
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  const unsigned long long b = __ballot(f);
+  if (lane == 0) s_wave[w] = __popcll(b);
+  asd_syncthreads();
+  int before = 0, all = 0;
+  for (int k = 0; k < 4; ++k) { const int c = s_wave[k]; if (k < w) before += c; all += c; }
+  *total = all;
+  asd_syncthreads();
+  return before + __popcll(b & ((1ull << lane) - 1));
+}
+
+// UpdateLocalKeyFrames' list decisions (:929-1008) in one workgroup
+__global__ __launch_bounds__(256) void k_lm_decide(LmDecideArgs a) {
+  extern __shared__ unsigned s_incl[];   // mnTrackReferenceForFrame == this frame, one bit per slot
+  __shared__ int s_scan[256], s_wave[4], s_app[3 * (kMaxLocalKfs + 1)];
+  __shared__ int s_n, s_any, s_napp, s_first, s_stop, s_maxn;
+  __shared__ unsigned long long s_best;
+  const int t = threadIdx.x;
+  for (int w = t; w < a.incl_words; w += 256) s_incl[w] = 0u;
+  // every id -> slot search below is a chain of dependent loads: from LDS where the list fits, from global memory otherwise
+  int* const s_ids = reinterpret_cast<int*>(s_incl + a.incl_words);
+  if (a.ids_in_lds) for (int i = t; i < a.n_live; i += 256) s_ids[i] = a.sorted_id[i];
+  const int* const ids_sorted = a.ids_in_lds ? s_ids : a.sorted_id;
+  if (t == 0) { s_n = 0; s_any = 0; s_napp = 0; s_stop = 0; s_maxn = 0; s_best = 0ull; }
+  asd_syncthreads();
+  // the voted keyframes in ascending id, bad ones skipped (:939-954); pKFmax = the first strictly larger count
+  for (int base = 0; base < a.n_live; base += 256) {
+    const int p = base + t;
+    bool take = false;
+    int sl = -1, c = 0;
+    if (p < a.n_live) {
+      sl = a.sorted_slot[p];
+      c = a.cnt[sl];
+      if (c > 0) { s_any = 1; take = !a.table[sl].bad; }
+    }
+    int total;
+    const int pos = s_n + lm_block_scan_flag(take, s_wave, &total);
+    if (take) {
+      a.list_id[pos] = a.sorted_id[p];
+      a.list_slot[pos] = sl;
+      atomicOr(&s_incl[sl >> 5], 1u << (sl & 31));
+      atomicMax(&s_best, ((unsigned long long)(unsigned)c << 32) | (unsigned)(0x7fffffff - p));
+    }
+    asd_syncthreads();
+    if (t == 0) s_n += total;
+    asd_syncthreads();
+  }
+  const int n0 = s_n;
+  const bool any = s_any != 0;
+  int ref = -1;
+  if (any && s_best) ref = a.sorted_id[0x7fffffff - (int)(unsigned)(s_best & 0xffffffffull)];
+  if (!any) {   // nobody voted (:929-930): the list stays the caller's
+    for (int i = t; i < a.n_prev; i += 256) {
+      const int id = a.prev[i];
+      a.list_id[i] = id;
+      a.list_slot[i] = lm_lookup(ids_sorted, a.sorted_slot, a.n_live, id);
+    }
+  }
+  asd_syncthreads();
+  // thread 0 appends: the keyframe becomes part of the list and is marked
+  auto append = [&](int id) {
+    const int sl = lm_lookup(ids_sorted, a.sorted_slot, a.n_live, id);
+    const int pos = n0 + s_napp;
+    a.list_id[pos] = id;
+    a.list_slot[pos] = sl;
+    s_app[s_napp] = id;
+    s_napp = s_napp + 1;
+    if (sl >= 0) s_incl[sl >> 5] |= 1u << (sl & 31);
+  };
+  auto included = [&](int id, int sl) -> bool {
+    if (sl >= 0) return (s_incl[sl >> 5] >> (sl & 31)) & 1u;
+    const int na = s_napp;   // an id that is not in the table can only have been appended
+    for (int k = 0; k < na; ++k) if (s_app[k] == id) return true;
+    return false;
+  };
+  // the first not-bad, not-yet-included of ids[0 .. count) is appended; all threads call this together
+  auto first_ok = [&](const int* ids, int count) {
+    for (int base = 0; base < count; base += 256) {
+      if (t == 0) s_first = INT_MAX;
+      asd_syncthreads();
+      const int k = base + t;
+      if (k < count) {
+        const int id = ids[k];
+        const int sl = lm_lookup(ids_sorted, a.sorted_slot, a.n_live, id);
+        if (!(sl >= 0 && a.table[sl].bad) && !included(id, sl)) atomicMin(&s_first, k);
+      }
+      asd_syncthreads();
+      const int f = s_first;
+      if (f != INT_MAX && t == 0) append(ids[f]);
+      asd_syncthreads();
+      if (f != INT_MAX) break;
+    }
+  };
+  if (any) {
+    for (int i = 0; i < n0; ++i) {   // the end iterator was taken before anything was appended
+      const int napp = s_napp;
+      asd_syncthreads();   // (thread 0 appends further down: everybody has read the count first)
+      if (n0 + napp > a.max_kfs) break;   // :961
+      const int sl = a.list_slot[i];
+      const LmSlotDev* S = a.table + sl;
+      first_ok(S->cov, S->n_cov);
+      first_ok(a.children + a.child_off[sl], a.child_off[sl + 1] - a.child_off[sl]);
+      if (t == 0) {   // the parent has no bad test, and taking it ends the expansion (:997-1006)
+        const int id = S->parent;
+        if (id >= 0 && !included(id, lm_lookup(ids_sorted, a.sorted_slot, a.n_live, id))) { append(id); s_stop = 1; }
+      }
+      asd_syncthreads();
+      if (s_stop) break;
+    }
+  }
+  asd_syncthreads();
+  const int n_list = any ? n0 + s_napp : a.n_prev;
+  // the rows of the list laid end to end: the global position of an entry is the order UpdateLocalPoints meets it in
+  long long run = 0;
+  for (int base = 0; base < n_list; base += 256) {
+    const int i = base + t;
+    int n = 0;
+    if (i < n_list) { const int sl = a.list_slot[i]; if (sl >= 0) n = a.table[sl].n; }
+    if (n > 0) atomicMax(&s_maxn, n);
+    int total;
+    const int ex = lm_block_scan(n, s_scan, &total);
+    if (i < n_list) a.list_base[i] = run + ex;
+    run += total;
+  }
+  asd_syncthreads();
+  if (t == 0) {
+    a.head[0] = n_list; a.head[1] = ref; a.head[2] = any; a.head[3] = s_maxn;
+    a.head[4] = (int)(unsigned)(run & 0xffffffffll); a.head[5] = (int)(run >> 32);
+    a.head[6] = 0; a.head[7] = 0; a.head[8] = 0; a.head[9] = 0;
+  }
+}
+
+// the entry of this thread in round k of its tile: row value (or -1) and global position
+__device__ inline int lm_entry(const LmPointArgs& a, int k, long long* pos) {
+  const int sl = a.list_slot[blockIdx.x];   // (x: the list entry, y: the tile inside its row)
+  if (sl < 0) return -1;
+  const LmSlotDev* S = a.table + sl;
+  const int idx = blockIdx.y * kTile + k * 256 + threadIdx.x;
+  if (idx >= S->n) return -1;
+  *pos = a.list_base[blockIdx.x] + idx;
+  const int r = a.rows[S->off + idx];
+  return r >= 0 && !a.pbad[r] ? r : -1;
+}
+__global__ __launch_bounds__(256) void k_lm_claim(LmPointArgs a) {
+  for (int k = 0; k < 4; ++k) {
+    long long pos = 0;
+    const int r = lm_entry(a, k, &pos);
+    if (r >= 0) atomicMin(&a.claim[r], (int)pos);
+  }
+}
+__global__ __launch_bounds__(256) void k_lm_count(LmPointArgs a) {
+  __shared__ int s_wave[4];
+  int nl = 0, ns = 0;
+  for (int k = 0; k < 4; ++k) {
+    long long pos = 0;
+    const int r = lm_entry(a, k, &pos);
+    if (r >= 0 && a.claim[r] == (int)pos) { ++nl; ns += !(a.mark[r] & kSkipBit); }
+  }
+  int packed = nl | (ns << 12);   // (a tile's sums are at most 1024 each)
+  for (int s = 32; s > 0; s >>= 1) packed += __shfl_xor(packed, s, 64);
+  if ((threadIdx.x & 63) == 0) s_wave[threadIdx.x >> 6] = packed;
+  asd_syncthreads();
+  if (threadIdx.x == 0) {
+    const int sum = s_wave[0] + s_wave[1] + s_wave[2] + s_wave[3];
+    const int tile = blockIdx.x * a.tiles_per_kf + blockIdx.y;
+    a.tile_cnt[2 * tile] = sum & 0xfff;
+    a.tile_cnt[2 * tile + 1] = sum >> 12;
+  }
+}
+__global__ __launch_bounds__(256) void k_lm_tilescan(const int* __restrict__ tile_cnt, int* __restrict__ tile_off, int n_tiles, int* __restrict__ head) {
+  __shared__ int s_scan[256];
+  int run[2] = {0, 0};
+  for (int base = 0; base < n_tiles; base += 256) {
+    const int i = base + threadIdx.x;
+    for (int f = 0; f < 2; ++f) {
+      const int v = i < n_tiles ? tile_cnt[2 * i + f] : 0;
+      int total;
+      const int ex = lm_block_scan(v, s_scan, &total);
+      if (i < n_tiles) tile_off[2 * i + f] = run[f] + ex;
+      run[f] += total;
+    }
+  }
+  if (threadIdx.x == 0) { head[8] = run[0]; head[9] = run[1]; }
+}
+__global__ __launch_bounds__(256) void k_lm_scatter(LmPointArgs a) {
+  __shared__ int s_wave[4];
+  const int tile = blockIdx.x * a.tiles_per_kf + blockIdx.y;
+  int ol = a.tile_off[2 * tile], os = a.tile_off[2 * tile + 1];
+  for (int k = 0; k < 4; ++k) {
+    long long pos = 0;
+    const int r = lm_entry(a, k, &pos);
+    const bool win = r >= 0 && a.claim[r] == (int)pos;
+    const bool srch = win && !(a.mark[r] & kSkipBit);
+    int tl, ts;
+    const int pl = lm_block_scan_flag(win, s_wave, &tl);
+    const int ps = lm_block_scan_flag(srch, s_wave, &ts);
+    if (win) {
+      a.d_local[ol + pl] = r;
+      if (ol + pl < a.cap_local) a.h_local[ol + pl] = r;
+      a.claim[r] = kClaimFree;   // every other entry of this point compares its own position, which is never this value
+    }
+    if (srch) {
+      a.d_search[os + ps] = r;
+      if (os + ps < a.cap_search) a.h_search[os + ps] = r;
+    }
+    ol += tl; os += ts;
+  }
+}
+
+struct LmSlot {
+  int kf = -1;   // -1: free slot
+  int n = -1;
+  long long off = 0;
+  bool bad = false;
+  int n_cov = 0, cov[kMaxCov] = {};
+  int parent = -1;
+  std::vector<int> children;
+};
+
+struct LocalMapState {
+  std::vector<LmSlot> slots;
+  std::vector<int> free_slots;
+  std::map<int, int> by_kf;   // ascending id -> slot
+  long long live_entries = 0;
+  uint64_t version = 1;       // bumped by every call that changes what a query reads
+  LmSlotDev* d_table = nullptr; size_t table_cap = 0;
+  int* d_rows = nullptr; long long entry_cap = 0, entry_used = 0;
+  uint8_t* d_pbad = nullptr; int* d_mark = nullptr; int* d_claim = nullptr; size_t row_cap = 0;
+  bool tables_dirty = false;  // a query failed between marking and undoing
+  int* d_sorted = nullptr; size_t sorted_cap = 0; bool sorted_dirty = true;   // ids [live] | slots [live]
+  int* d_child = nullptr; size_t child_cap = 0; bool child_dirty = true;       // offsets [slots + 1] | children
+  size_t child_off_words = 0;
+  int* d_cnt = nullptr; size_t cnt_cap = 0;
+  int* d_list = nullptr; size_t list_cap = 0;           // ids [cap] | slots [cap]
+  long long* d_list_base = nullptr; size_t list_base_cap = 0;
+  int* d_head = nullptr; size_t head_cap = 0;
+  int* h_head = nullptr;   // pinned
+  int* d_tile = nullptr; size_t tile_cap = 0;           // counts [tiles][2] | offsets [tiles][2]
+  int* d_local = nullptr; size_t local_cap = 0;
+  int* d_search = nullptr; size_t search_cap = 0;
+  AsdXfer up, down;
+  int growths[3] = {0, 0, 0};   // slot table, arena, row tables
+  // what the last asd_update_local_map left for asd_track_local_points_map
+  bool last_valid = false;
+  uint64_t last_version = 0;
+  std::vector<int32_t> last_search;
+};
+
+LocalMapState* lstate(asd_ctx* ctx) {
+  if (!ctx->localmap) ctx->localmap = new LocalMapState();
+  return static_cast<LocalMapState*>(ctx->localmap);
+}
+
+// room for `need` elements.  keep: elements of the old block copied over; fill: byte value the new block starts with (-1: none).  The
+// copy goes on ctx->stream behind every write to the old block, which is freed once that stream has drained (see the head of the file).
+template <typename T>
+int lm_reserve(asd_ctx* ctx, T** p, size_t* cap, size_t need, size_t keep, int fill, size_t min_cap, int* growths = nullptr) {
+  if (need <= *cap) return ASD_OK;
+  const size_t nc = std::max(min_cap, std::max(need, 2 * *cap));
+  T* q = nullptr;
+  if (hipMalloc(&q, nc * sizeof(T)) != hipSuccess) { ctx->set_error("local map: out of device memory for %zu bytes", nc * sizeof(T)); return ASD_ERR_HIP; }
+  hipError_t e = hipSuccess;
+  if (fill >= 0) e = hipMemsetAsync(q, fill, nc * sizeof(T), ctx->stream);
+  if (e == hipSuccess && *p && keep) e = hipMemcpyAsync(q, *p, keep * sizeof(T), hipMemcpyDeviceToDevice, ctx->stream);
+  const hipError_t es = hipStreamSynchronize(ctx->stream);
+  if (e == hipSuccess) e = es;
+  if (e != hipSuccess) { (void)hipFree(q); ctx->set_error("local map: growth failed: %s", hipGetErrorString(e)); return ASD_ERR_HIP; }
+  if (*p) { (void)hipFree(*p); if (growths) ++*growths; }
+  *p = q;
+  *cap = nc;
+  return ASD_OK;
+}
+
+void release_device(LocalMapState* S) {
+  void* dev[] = {S->d_table, S->d_rows, S->d_pbad, S->d_mark, S->d_claim, S->d_sorted, S->d_child, S->d_cnt, S->d_list, S->d_list_base, S->d_head,
+                 S->d_tile, S->d_local, S->d_search};
+  for (void* p : dev) if (p) (void)hipFree(p);
+  S->d_table = nullptr; S->d_rows = nullptr; S->d_pbad = nullptr; S->d_mark = nullptr; S->d_claim = nullptr; S->d_sorted = nullptr; S->d_child = nullptr;
+  S->d_cnt = nullptr; S->d_list = nullptr; S->d_list_base = nullptr; S->d_head = nullptr; S->d_tile = nullptr; S->d_local = nullptr; S->d_search = nullptr;
+  S->table_cap = S->row_cap = S->sorted_cap = S->child_cap = S->cnt_cap = S->list_cap = S->list_base_cap = S->head_cap = S->tile_cap = S->local_cap = S->search_cap = 0;
+  S->entry_cap = S->entry_used = 0;
+}
+
+LmSlotDev dev_entry(const LmSlot& s) {
+  LmSlotDev e{};
+  e.off = s.off; e.n = s.kf < 0 ? -1 : s.n; e.id = s.kf; e.bad = s.bad; e.n_cov = s.n_cov; e.parent = s.parent;
+  for (int k = 0; k < kMaxCov; ++k) e.cov[k] = k < s.n_cov ? s.cov[k] : -1;
+  return e;
+}
+
+// the three per-row tables cover rows [0, rows)
+int ensure_rows(asd_ctx* ctx, LocalMapState* S, size_t rows) {
+  if (rows <= S->row_cap) return ASD_OK;
+  size_t c0 = S->row_cap, c1 = S->row_cap, c2 = S->row_cap;
+  int rc;
+  if ((rc = lm_reserve(ctx, &S->d_pbad, &c0, rows, S->row_cap, 0, kInitRows, &S->growths[2])) != ASD_OK) return rc;
+  if ((rc = lm_reserve(ctx, &S->d_mark, &c1, c0, S->row_cap, 0, c0)) != ASD_OK) return rc;
+  if ((rc = lm_reserve(ctx, &S->d_claim, &c2, c0, S->row_cap, 0x7f, c0)) != ASD_OK) return rc;
+  S->row_cap = c0;
+  return ASD_OK;
+}
+
+int check_rows(asd_ctx* ctx, const char* who, const int32_t* rows, int n, int* max_row) {
+  int mx = -1;
+  for (int i = 0; i < n; ++i) {
+    if (rows[i] < -1 || rows[i] >= kMaxRow) { ctx->set_error("%s: bank row %d at %d (rows are -1 or 0 .. %d)", who, rows[i], i, kMaxRow - 1); return rows[i] < -1 ? ASD_ERR_INVALID : ASD_ERR_CAPACITY; }
+    mx = std::max(mx, rows[i]);
+  }
+  *max_row = mx;
+  return ASD_OK;
+}
+
+// one slot's table entry to the device
+int upload_entry(asd_ctx* ctx, LocalMapState* S, int slot) {
+  const LmSlotDev e = dev_entry(S->slots[slot]);
+  ASD_HIP_CHECK(ctx, S->up.begin(ctx->stream, sizeof e));
+  const size_t o = S->up.add(&e, sizeof e);
+  ASD_HIP_CHECK(ctx, hipMemcpyAsync(S->d_table + slot, S->up.h + o, sizeof e, hipMemcpyHostToDevice, ctx->stream));
+  ASD_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
+  return ASD_OK;
+}
+
+int grow_table(asd_ctx* ctx, LocalMapState* S, size_t need) {
+  return lm_reserve(ctx, &S->d_table, &S->table_cap, need, S->table_cap, 0xff, kInitSlots, &S->growths[0]);   // (0xff: n = -1, a free slot)
+}
+
+// room for `need` more entries behind entry_used: a new arena of twice the live entries, the live rows moved into it back to back in slot
+// order (this closes the holes that erase and a longer put leave)
+int grow_arena(asd_ctx* ctx, LocalMapState* S, long long need) {
+  if (S->entry_used + need <= S->entry_cap) return ASD_OK;
+  const long long cap = std::max(kInitEntries, 2 * (S->live_entries + need));
+  int* nr = nullptr;
+  if (hipMalloc(&nr, (size_t)cap * sizeof(int)) != hipSuccess) { ctx->set_error("local map: out of device memory for %lld table entries", cap); return ASD_ERR_HIP; }
+  std::vector<LmMove> mv;
+  std::vector<int> moved;
+  long long used = 0;
+  for (size_t s = 0; s < S->slots.size(); ++s) {
+    LmSlot& L = S->slots[s];
+    if (L.kf < 0 || L.n <= 0) continue;
+    mv.push_back(LmMove{L.off, used, L.n, 0});
+    moved.push_back((int)s);
+    L.off = used;
+    used += L.n;
+  }
+  hipStream_t st = ctx->stream;
+  hipError_t e = hipSuccess;
+  if (!mv.empty() && S->d_rows) {
+    const size_t b_mv = mv.size() * sizeof(LmMove);
+    e = S->up.begin(st, b_mv + moved.size() * AsdDevBuf::padded(sizeof(LmSlotDev)) + 1024);   // (every add is padded to 256 B)
+    if (e == hipSuccess) {
+      const size_t o = S->up.add(mv.data(), b_mv);
+      e = hipMemcpyAsync(S->up.d + o, S->up.h + o, b_mv, hipMemcpyHostToDevice, st);
+      if (e == hipSuccess) { hipLaunchKernelGGL(k_lm_move, dim3((unsigned)mv.size()), dim3(256), 0, st, S->up.dev<LmMove>(o), S->d_rows, nr); e = hipGetLastError(); }
+      for (size_t k = 0; k < moved.size() && e == hipSuccess; ++k) {   // the moved rows' new offsets
+        const LmSlotDev d = dev_entry(S->slots[moved[k]]);
+        const size_t oe = S->up.add(&d, sizeof d);
+        e = hipMemcpyAsync(S->d_table + moved[k], S->up.h + oe, sizeof d, hipMemcpyHostToDevice, st);
+      }
+    }
+  }
+  const hipError_t es = hipStreamSynchronize(st);   // the old arena goes only when the stream that read and wrote it has drained
+  if (e == hipSuccess) e = es;
+  if (S->d_rows) { (void)hipFree(S->d_rows); ++S->growths[1]; }
+  S->d_rows = nr;
+  S->entry_cap = cap; S->entry_used = used;
+  if (e != hipSuccess) { ctx->set_error("local map: arena growth failed: %s", hipGetErrorString(e)); return ASD_ERR_HIP; }
+  return ASD_OK;
+}
+
+// the ascending id list and the children block, where a call since the last query changed them
+int refresh_lists(asd_ctx* ctx, LocalMapState* S) {
+  hipStream_t st = ctx->stream;
+  const size_t live = S->by_kf.size(), n_slots = S->slots.size();
+  if (S->sorted_dirty && live) {
+    int rc = lm_reserve(ctx, &S->d_sorted, &S->sorted_cap, 2 * live, 0, -1, 2 * kInitSlots);
+    if (rc != ASD_OK) return rc;
+    std::vector<int> v(2 * live);
+    size_t k = 0;
+    for (const auto& kv : S->by_kf) { v[k] = kv.first; v[live + k] = kv.second; ++k; }
+    ASD_HIP_CHECK(ctx, S->up.begin(st, v.size() * sizeof(int)));
+    const size_t o = S->up.add(v.data(), v.size() * sizeof(int));
+    ASD_HIP_CHECK(ctx, hipMemcpyAsync(S->d_sorted, S->up.h + o, v.size() * sizeof(int), hipMemcpyHostToDevice, st));
+    ASD_HIP_CHECK(ctx, hipStreamSynchronize(st));
+  }
+  S->sorted_dirty = false;
+  if ((S->child_dirty || S->child_off_words != n_slots + 1) && n_slots) {
+    std::vector<int> v(n_slots + 1, 0);
+    for (size_t s = 0; s < n_slots; ++s) v[s + 1] = v[s] + (S->slots[s].kf >= 0 ? (int)S->slots[s].children.size() : 0);
+    for (size_t s = 0; s < n_slots; ++s) if (S->slots[s].kf >= 0) v.insert(v.end(), S->slots[s].children.begin(), S->slots[s].children.end());
+    int rc = lm_reserve(ctx, &S->d_child, &S->child_cap, v.size() + 1, 0, -1, 4 * kInitSlots);
+    if (rc != ASD_OK) return rc;
+    ASD_HIP_CHECK(ctx, S->up.begin(st, v.size() * sizeof(int)));
+    const size_t o = S->up.add(v.data(), v.size() * sizeof(int));
+    ASD_HIP_CHECK(ctx, hipMemcpyAsync(S->d_child, S->up.h + o, v.size() * sizeof(int), hipMemcpyHostToDevice, st));
+    ASD_HIP_CHECK(ctx, hipStreamSynchronize(st));
+    S->child_off_words = n_slots + 1;
+  }
+  S->child_dirty = false;
+  return ASD_OK;
+}
+
+// a query that failed half way may have left marks and claims behind
+int clean_tables(asd_ctx* ctx, LocalMapState* S) {
+  if (!S->tables_dirty || !S->row_cap) { S->tables_dirty = false; return ASD_OK; }
+  ASD_HIP_CHECK(ctx, hipMemsetAsync(S->d_mark, 0, S->row_cap * sizeof(int), ctx->stream));
+  ASD_HIP_CHECK(ctx, hipMemsetAsync(S->d_claim, 0x7f, S->row_cap * sizeof(int), ctx->stream));
+  ASD_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
+  S->tables_dirty = false;
+  return ASD_OK;
+}
+
+LmSlot* find_kf(asd_ctx* ctx, LocalMapState* S, const char* who, int32_t kf, int* slot) {
+  const auto it = S->by_kf.find(kf);
+  if (it == S->by_kf.end()) { ctx->set_error("%s: keyframe %d is not in the observation table", who, kf); return nullptr; }
+  *slot = it->second;
+  return &S->slots[it->second];
+}
+
+bool refuse(asd_ctx* ctx, const char* who) { return asd_track_busy(ctx, who); }
+
+}  // namespace
+
+void localmap_free(asd_ctx* ctx) {
+  if (!ctx->localmap) return;
+  LocalMapState* S = static_cast<LocalMapState*>(ctx->localmap);
+  release_device(S);
+  if (S->h_head) (void)hipHostFree(S->h_head);
+  S->up.release();
+  S->down.release();
+  delete S;
+  ctx->localmap = nullptr;
+}
+
+int localmap_search_list(asd_ctx* ctx, const char* who, const int32_t** h_rows, const int32_t** d_rows, int* n) {
+  LocalMapState* S = lstate(ctx);
+  if (!S->last_valid) { ctx->set_error("%s: no asd_update_local_map of this context has left a search list", who); return ASD_ERR_INVALID; }
+  if (S->last_version != S->version) { ctx->set_error("%s: the observation table has changed since the last asd_update_local_map", who); return ASD_ERR_INVALID; }
+  if (S->last_search.empty()) { ctx->set_error("%s: the last asd_update_local_map left an empty search list", who); return ASD_ERR_INVALID; }
+  *h_rows = S->last_search.data();
+  *d_rows = S->d_search;
+  *n = (int)S->last_search.size();
+  return ASD_OK;
+}
+
+extern "C" {
+
+int asd_map_clear(asd_ctx* ctx) {
+  if (!ctx) return ASD_ERR_INVALID;
+  if (refuse(ctx, "asd_map_clear")) return ASD_ERR_INVALID;
+  (void)hipSetDevice(ctx->cfg.device);
+  LocalMapState* S = lstate(ctx);
+  ASD_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
+  release_device(S);
+  S->slots.clear(); S->free_slots.clear(); S->by_kf.clear();
+  S->live_entries = 0;
+  S->sorted_dirty = S->child_dirty = true; S->child_off_words = 0; S->tables_dirty = false;
+  S->growths[0] = S->growths[1] = S->growths[2] = 0;
+  S->last_valid = false; S->last_search.clear();
+  ++S->version;
+  return ASD_OK;
+}
+
+int asd_map_put(asd_ctx* ctx, int32_t kf, int32_t n, const int32_t* rows) {
+  if (!ctx) return ASD_ERR_INVALID;
+  if (refuse(ctx, "asd_map_put")) return ASD_ERR_INVALID;
+  if (kf < 0 || n < 0 || (n > 0 && !rows)) { ctx->set_error("asd_map_put: invalid argument (keyframe %d, %d entries)", kf, n); return ASD_ERR_INVALID; }
+  if (n > kMaxKeypoints) { ctx->set_error("asd_map_put: %d entries exceed the %d a keyframe's row holds", n, kMaxKeypoints); return ASD_ERR_CAPACITY; }
+  int max_row = -1;
+  int rc = check_rows(ctx, "asd_map_put", rows, n, &max_row);
+  if (rc != ASD_OK) return rc;
+  (void)hipSetDevice(ctx->cfg.device);
+  LocalMapState* S = lstate(ctx);
+  const auto it = S->by_kf.find(kf);
+  const bool fresh = it == S->by_kf.end();
+  if (fresh && S->free_slots.empty() && (int)S->slots.size() >= kMaxSlots) { ctx->set_error("asd_map_put: the table holds %d keyframes, its limit", kMaxSlots); return ASD_ERR_CAPACITY; }
+  if ((rc = ensure_rows(ctx, S, (size_t)max_row + 1)) != ASD_OK) return rc;
+  int slot;
+  if (!fresh) slot = it->second;
+  else if (!S->free_slots.empty()) { slot = S->free_slots.back(); S->free_slots.pop_back(); }
+  else { slot = (int)S->slots.size(); S->slots.emplace_back(); }
+  auto undo = [&]() { if (fresh) S->free_slots.push_back(slot); };
+  if ((rc = grow_table(ctx, S, S->slots.size())) != ASD_OK) { undo(); return rc; }
+  LmSlot& L = S->slots[slot];
+  const int old_n = fresh ? -1 : L.n;
+  long long off = L.off;
+  if (n > old_n) {   // a new place at the end of the arena (the old one becomes a hole)
+    if (!fresh) { S->live_entries -= L.n; L.n = 0; }
+    if ((rc = grow_arena(ctx, S, n)) != ASD_OK) { undo(); if (!fresh) { L.n = old_n; S->live_entries += old_n; } return rc; }
+    off = S->entry_used;
+    S->entry_used += n;
+    S->live_entries += n;
+  } else {
+    S->live_entries += n - old_n;
+  }
+  if (fresh) { L = LmSlot(); L.kf = kf; S->by_kf[kf] = slot; S->sorted_dirty = true; S->child_dirty = true; }
+  L.n = n; L.off = off;
+  ++S->version;
+  hipStream_t st = ctx->stream;
+  const LmSlotDev e = dev_entry(L);
+  ASD_HIP_CHECK(ctx, S->up.begin(st, (size_t)n * sizeof(int) + sizeof e + 1024));
+  const size_t o_e = S->up.add(&e, sizeof e);
+  if (n > 0) {
+    const size_t o_r = S->up.add(rows, (size_t)n * sizeof(int));
+    ASD_HIP_CHECK(ctx, hipMemcpyAsync(S->d_rows + off, S->up.h + o_r, (size_t)n * sizeof(int), hipMemcpyHostToDevice, st));
+  }
+  ASD_HIP_CHECK(ctx, hipMemcpyAsync(S->d_table + slot, S->up.h + o_e, sizeof e, hipMemcpyHostToDevice, st));
+  ASD_HIP_CHECK(ctx, hipStreamSynchronize(st));
+  return ASD_OK;
+}
+
+int asd_map_set(asd_ctx* ctx, int32_t kf, int32_t count, const int32_t* idx, const int32_t* rows) {
+  if (!ctx) return ASD_ERR_INVALID;
+  if (refuse(ctx, "asd_map_set")) return ASD_ERR_INVALID;
+  if (count < 0 || (count > 0 && (!idx || !rows))) { ctx->set_error("asd_map_set: invalid argument"); return ASD_ERR_INVALID; }
+  LocalMapState* S = lstate(ctx);
+  int slot;
+  LmSlot* L = find_kf(ctx, S, "asd_map_set", kf, &slot);
+  if (!L) return ASD_ERR_INVALID;
+  int max_row = -1;
+  int rc = check_rows(ctx, "asd_map_set", rows, count, &max_row);
+  if (rc != ASD_OK) return rc;
+  for (int i = 0; i < count; ++i)
+    if (idx[i] < 0 || idx[i] >= L->n) { ctx->set_error("asd_map_set: keypoint %d of keyframe %d, whose row has %d entries", idx[i], kf, L->n); return ASD_ERR_INVALID; }
+  if (count == 0) return ASD_OK;
+  (void)hipSetDevice(ctx->cfg.device);
+  if ((rc = ensure_rows(ctx, S, (size_t)max_row + 1)) != ASD_OK) return rc;
+  // the changes apply in the order given: of two for one keypoint the later one stays
+  std::unordered_map<int, int> last;
+  for (int i = 0; i < count; ++i) last[idx[i]] = rows[i];
+  std::vector<int> vi, vr;
+  for (const auto& kv : last) { vi.push_back(kv.first); vr.push_back(kv.second); }
+  const int m = (int)vi.size();
+  ++S->version;
+  hipStream_t st = ctx->stream;
+  ASD_HIP_CHECK(ctx, S->up.begin(st, (size_t)m * 8 + 1024));
+  const size_t o_i = S->up.add(vi.data(), (size_t)m * sizeof(int)), o_r = S->up.add(vr.data(), (size_t)m * sizeof(int));
+  ASD_HIP_CHECK(ctx, S->up.upload(st));
+  hipLaunchKernelGGL(k_lm_set, dim3((m + 255) / 256), dim3(256), 0, st, S->d_rows + L->off, S->up.dev<int>(o_i), S->up.dev<int>(o_r), m);
+  ASD_HIP_CHECK(ctx, hipGetLastError());
+  ASD_HIP_CHECK(ctx, hipStreamSynchronize(st));
+  return ASD_OK;
+}
+
+int asd_map_erase(asd_ctx* ctx, int32_t kf) {
+  if (!ctx) return ASD_ERR_INVALID;
+  if (refuse(ctx, "asd_map_erase")) return ASD_ERR_INVALID;
+  LocalMapState* S = lstate(ctx);
+  const auto it = S->by_kf.find(kf);
+  if (it == S->by_kf.end()) return ASD_OK;
+  (void)hipSetDevice(ctx->cfg.device);
+  const int slot = it->second;
+  S->live_entries -= S->slots[slot].n;
+  S->slots[slot] = LmSlot();   // its row stays in the arena until the next growth compacts it
+  S->free_slots.push_back(slot);
+  S->by_kf.erase(it);
+  S->sorted_dirty = S->child_dirty = true;
+  ++S->version;
+  return upload_entry(ctx, S, slot);
+}
+
+int asd_map_kf_links(asd_ctx* ctx, int32_t kf, int32_t n_cov, const int32_t* cov, int32_t n_children, const int32_t* children, int32_t parent) {
+  if (!ctx) return ASD_ERR_INVALID;
+  if (refuse(ctx, "asd_map_kf_links")) return ASD_ERR_INVALID;
+  if (n_cov < 0 || n_cov > kMaxCov || (n_cov > 0 && !cov) || n_children < 0 || (n_children > 0 && !children) || parent < -1) {
+    ctx->set_error("asd_map_kf_links: invalid argument (%d covisibles of at most %d, %d children, parent %d)", n_cov, kMaxCov, n_children, parent);
+    return ASD_ERR_INVALID;
+  }
+  for (int i = 0; i < n_cov; ++i) if (cov[i] < 0) { ctx->set_error("asd_map_kf_links: covisible id %d", cov[i]); return ASD_ERR_INVALID; }
+  for (int i = 0; i < n_children; ++i)
+    if (children[i] < 0 || (i > 0 && children[i] <= children[i - 1])) { ctx->set_error("asd_map_kf_links: children ids are not non-negative and strictly ascending at %d", i); return ASD_ERR_INVALID; }
+  LocalMapState* S = lstate(ctx);
+  int slot;
+  LmSlot* L = find_kf(ctx, S, "asd_map_kf_links", kf, &slot);
+  if (!L) return ASD_ERR_INVALID;
+  (void)hipSetDevice(ctx->cfg.device);
+  L->n_cov = n_cov;
+  for (int i = 0; i < n_cov; ++i) L->cov[i] = cov[i];
+  L->children.assign(children, children + n_children);
+  L->parent = parent;
+  S->child_dirty = true;
+  ++S->version;
+  return upload_entry(ctx, S, slot);
+}
+
+int asd_map_kf_bad(asd_ctx* ctx, int32_t kf, int32_t flag) {
+  if (!ctx) return ASD_ERR_INVALID;
+  if (refuse(ctx, "asd_map_kf_bad")) return ASD_ERR_INVALID;
+  LocalMapState* S = lstate(ctx);
+  int slot;
+  LmSlot* L = find_kf(ctx, S, "asd_map_kf_bad", kf, &slot);
+  if (!L) return ASD_ERR_INVALID;
+  (void)hipSetDevice(ctx->cfg.device);
+  L->bad = flag != 0;
+  ++S->version;
+  return upload_entry(ctx, S, slot);
+}
+
+int asd_map_point_bad(asd_ctx* ctx, int32_t n, const int32_t* rows, int32_t flag) {
+  if (!ctx) return ASD_ERR_INVALID;
+  if (refuse(ctx, "asd_map_point_bad")) return ASD_ERR_INVALID;
+  if (n < 0 || (n > 0 && !rows)) { ctx->set_error("asd_map_point_bad: invalid argument"); return ASD_ERR_INVALID; }
+  int max_row = -1;
+  int rc = check_rows(ctx, "asd_map_point_bad", rows, n, &max_row);
+  if (rc != ASD_OK) return rc;
+  for (int i = 0; i < n; ++i) if (rows[i] < 0) { ctx->set_error("asd_map_point_bad: bank row %d", rows[i]); return ASD_ERR_INVALID; }
+  if (n == 0) return ASD_OK;
+  (void)hipSetDevice(ctx->cfg.device);
+  LocalMapState* S = lstate(ctx);
+  if ((rc = ensure_rows(ctx, S, (size_t)max_row + 1)) != ASD_OK) return rc;
+  ++S->version;
+  hipStream_t st = ctx->stream;
+  ASD_HIP_CHECK(ctx, S->up.begin(st, (size_t)n * sizeof(int)));
+  const size_t o = S->up.add(rows, (size_t)n * sizeof(int));
+  ASD_HIP_CHECK(ctx, S->up.upload(st));
+  hipLaunchKernelGGL(k_lm_point_bad, dim3((n + 255) / 256), dim3(256), 0, st, S->d_pbad, S->up.dev<int>(o), n, flag != 0);
+  ASD_HIP_CHECK(ctx, hipGetLastError());
+  ASD_HIP_CHECK(ctx, hipStreamSynchronize(st));
+  return ASD_OK;
+}
+
+int asd_update_local_map(asd_ctx* ctx, asd_local_map_args* A) {
+  if (!ctx) return ASD_ERR_INVALID;
+  if (!A || A->n_cur < 0 || A->n_seen < 0 || A->n_prev < 0 || (A->n_cur > 0 && !A->cur_rows) || (A->n_seen > 0 && !A->seen_rows) || (A->n_prev > 0 && !A->prev_kfs) ||
+      A->max_kfs < 0 || A->kf_capacity < 0 || A->row_capacity < 0 || A->search_capacity < 0 || (A->kf_capacity > 0 && !A->local_kfs) ||
+      (A->row_capacity > 0 && !A->local_rows) || (A->search_capacity > 0 && !A->search_rows)) {
+    ctx->set_error("asd_update_local_map: invalid argument");
+    return ASD_ERR_INVALID;
+  }
+  if (refuse(ctx, "asd_update_local_map")) return ASD_ERR_INVALID;
+  if (A->max_kfs > kMaxLocalKfs) { ctx->set_error("asd_update_local_map: max_kfs = %d exceeds %d", A->max_kfs, kMaxLocalKfs); return ASD_ERR_CAPACITY; }
+  if ((long long)A->n_cur + A->n_seen > kVoteMask / 2) { ctx->set_error("asd_update_local_map: %d + %d frame rows", A->n_cur, A->n_seen); return ASD_ERR_CAPACITY; }
+  for (int i = 0; i < A->n_prev; ++i) if (A->prev_kfs[i] < 0) { ctx->set_error("asd_update_local_map: keyframe id %d in prev_kfs", A->prev_kfs[i]); return ASD_ERR_INVALID; }
+  int mx0 = -1, mx1 = -1;
+  int rc;
+  if ((rc = check_rows(ctx, "asd_update_local_map", A->cur_rows, A->n_cur, &mx0)) != ASD_OK) return rc;
+  if ((rc = check_rows(ctx, "asd_update_local_map", A->seen_rows, A->n_seen, &mx1)) != ASD_OK) return rc;
+  (void)hipSetDevice(ctx->cfg.device);
+  LocalMapState* S = lstate(ctx);
+  S->last_valid = false;
+  A->n_local_kfs = 0; A->ref_kf = -1; A->n_local = 0; A->n_search = 0;
+  hipStream_t st = ctx->stream;
+  const int n_slots = (int)S->slots.size(), n_live = (int)S->by_kf.size();
+  const size_t list_need = (size_t)std::max(n_live, A->n_prev) + 3 * ((size_t)A->max_kfs + 1) + 1;
+  if ((rc = ensure_rows(ctx, S, (size_t)std::max(mx0, mx1) + 1)) != ASD_OK) return rc;
+  if ((rc = refresh_lists(ctx, S)) != ASD_OK) return rc;
+  if ((rc = clean_tables(ctx, S)) != ASD_OK) return rc;
+  if ((rc = lm_reserve(ctx, &S->d_cnt, &S->cnt_cap, (size_t)n_slots + 1, 0, -1, kInitSlots)) != ASD_OK) return rc;
+  if ((rc = lm_reserve(ctx, &S->d_list, &S->list_cap, 2 * list_need, 0, -1, 1024)) != ASD_OK) return rc;
+  if ((rc = lm_reserve(ctx, &S->d_list_base, &S->list_base_cap, list_need, 0, -1, 512)) != ASD_OK) return rc;
+  if ((rc = lm_reserve(ctx, &S->d_head, &S->head_cap, 16, 0, 0, 16)) != ASD_OK) return rc;
+  int* d_list_id = S->d_list;
+  int* d_list_slot = S->d_list + S->list_cap / 2;
+
+  const int n_frame = A->n_cur + A->n_seen;
+  ASD_HIP_CHECK(ctx, S->up.begin(st, ((size_t)n_frame + A->n_prev) * sizeof(int) + 1024));
+  const size_t o_cur = S->up.add(A->cur_rows, (size_t)A->n_cur * sizeof(int)), o_seen = S->up.add(A->seen_rows, (size_t)A->n_seen * sizeof(int));
+  const size_t o_prev = S->up.add(A->prev_kfs, (size_t)A->n_prev * sizeof(int));
+  const size_t cap_l = (size_t)A->row_capacity, cap_s = (size_t)A->search_capacity;
+  ASD_HIP_CHECK(ctx, S->up.upload(st));
+  S->tables_dirty = true;
+  if (n_frame > 0) {
+    hipLaunchKernelGGL(k_lm_mark, dim3((n_frame + 255) / 256), dim3(256), 0, st, S->up.dev<int>(o_cur), A->n_cur, S->up.dev<int>(o_seen), A->n_seen, S->d_pbad, S->d_mark);
+    ASD_HIP_CHECK(ctx, hipGetLastError());
+  }
+  if (n_slots > 0) {
+    hipLaunchKernelGGL(k_lm_vote, dim3((n_slots + 3) / 4), dim3(256), 0, st, S->d_table, n_slots, S->d_rows, S->d_mark, S->d_cnt);
+    ASD_HIP_CHECK(ctx, hipGetLastError());
+  }
+  LmDecideArgs da{};
+  da.table = S->d_table; da.sorted_id = S->d_sorted; da.sorted_slot = S->d_sorted ? S->d_sorted + n_live : nullptr; da.n_live = n_live;
+  da.cnt = S->d_cnt; da.child_off = S->d_child; da.children = S->d_child ? S->d_child + S->child_off_words : nullptr;
+  da.prev = S->up.dev<int>(o_prev); da.n_prev = A->n_prev; da.max_kfs = A->max_kfs; da.incl_words = (n_slots + 31) / 32;
+  da.list_id = d_list_id; da.list_slot = d_list_slot; da.list_base = S->d_list_base; da.head = S->d_head;
+  da.ids_in_lds = ((size_t)da.incl_words + n_live) * 4 <= 48 * 1024;   // (+ 14 KB of static LDS: inside the 64 KB a kernel gets without asking)
+  hipLaunchKernelGGL(k_lm_decide, dim3(1), dim3(256), ((size_t)da.incl_words + (da.ids_in_lds ? n_live : 0)) * 4, st, da);
+  ASD_HIP_CHECK(ctx, hipGetLastError());
+  if (!S->h_head) ASD_HIP_CHECK(ctx, hipHostMalloc(&S->h_head, 16 * sizeof(int)));
+  int* const head = S->h_head;
+  ASD_HIP_CHECK(ctx, hipMemcpyAsync(head, S->d_head, 16 * sizeof(int), hipMemcpyDeviceToHost, st));
+  ASD_HIP_CHECK(ctx, hipStreamSynchronize(st));
+  const int n_list = head[0], maxn = head[3];
+  const long long entries = ((long long)head[5] << 32) | (unsigned)head[4];
+  auto unmark = [&]() -> int {
+    if (n_frame > 0) {
+      hipLaunchKernelGGL(k_lm_unmark, dim3((n_frame + 255) / 256), dim3(256), 0, st, S->up.dev<int>(o_cur), A->n_cur, S->up.dev<int>(o_seen), A->n_seen, S->d_mark);
+      ASD_HIP_CHECK(ctx, hipGetLastError());
+    }
+    return ASD_OK;
+  };
+  if (entries >= kMaxEntriesPerQuery) {
+    if ((rc = unmark()) != ASD_OK) return rc;
+    ASD_HIP_CHECK(ctx, hipStreamSynchronize(st));
+    S->tables_dirty = false;
+    ctx->set_error("asd_update_local_map: the %d local keyframes hold %lld table entries, more than one query collects (%lld)", n_list, entries, kMaxEntriesPerQuery);
+    return ASD_ERR_CAPACITY;
+  }
+  const size_t give_l = std::min(cap_l, (size_t)entries), give_s = std::min(cap_s, (size_t)entries), give_k = std::min((size_t)A->kf_capacity, (size_t)n_list);
+  ASD_HIP_CHECK(ctx, S->down.begin(st, (give_l + give_s + give_k) * sizeof(int) + 1024));
+  const size_t o_hl = S->down.reserve(give_l * sizeof(int)), o_hs = S->down.reserve(give_s * sizeof(int)), o_hk = S->down.reserve(give_k * sizeof(int));
+  if (entries > 0) {
+    const int tiles_per_kf = (maxn + kTile - 1) / kTile;
+    const size_t n_tiles = (size_t)tiles_per_kf * n_list;
+    if ((rc = lm_reserve(ctx, &S->d_tile, &S->tile_cap, 4 * n_tiles, 0, -1, 4096)) != ASD_OK) return rc;
+    if ((rc = lm_reserve(ctx, &S->d_local, &S->local_cap, (size_t)entries, 0, -1, 65536)) != ASD_OK) return rc;
+    if ((rc = lm_reserve(ctx, &S->d_search, &S->search_cap, (size_t)entries, 0, -1, 65536)) != ASD_OK) return rc;
+    LmPointArgs pa{};
+    pa.table = S->d_table; pa.rows = S->d_rows; pa.list_slot = d_list_slot; pa.list_base = S->d_list_base; pa.tiles_per_kf = tiles_per_kf;
+    pa.pbad = S->d_pbad; pa.mark = S->d_mark; pa.claim = S->d_claim;
+    pa.tile_cnt = S->d_tile; pa.tile_off = S->d_tile + 2 * n_tiles;
+    pa.d_local = S->d_local; pa.d_search = S->d_search;
+    pa.h_local = S->down.host<int>(o_hl); pa.cap_local = (int)give_l; pa.h_search = S->down.host<int>(o_hs); pa.cap_search = (int)give_s;
+    const dim3 grid((unsigned)n_list, (unsigned)tiles_per_kf);
+    hipLaunchKernelGGL(k_lm_claim, grid, dim3(256), 0, st, pa);
+    ASD_HIP_CHECK(ctx, hipGetLastError());
+    hipLaunchKernelGGL(k_lm_count, grid, dim3(256), 0, st, pa);
+    ASD_HIP_CHECK(ctx, hipGetLastError());
+    hipLaunchKernelGGL(k_lm_tilescan, dim3(1), dim3(256), 0, st, S->d_tile, S->d_tile + 2 * n_tiles, (int)n_tiles, S->d_head);
+    ASD_HIP_CHECK(ctx, hipGetLastError());
+    hipLaunchKernelGGL(k_lm_scatter, grid, dim3(256), 0, st, pa);
+    ASD_HIP_CHECK(ctx, hipGetLastError());
+  }
+  if ((rc = unmark()) != ASD_OK) return rc;
+  ASD_HIP_CHECK(ctx, hipMemcpyAsync(head, S->d_head, 16 * sizeof(int), hipMemcpyDeviceToHost, st));
+  if (give_k) ASD_HIP_CHECK(ctx, hipMemcpyAsync(S->down.h + o_hk, d_list_id, give_k * sizeof(int), hipMemcpyDeviceToHost, st));
+  ASD_HIP_CHECK(ctx, hipStreamSynchronize(st));
+  S->tables_dirty = false;
+  A->n_local_kfs = n_list; A->ref_kf = head[1]; A->n_local = head[8]; A->n_search = head[9];
+  if (n_list > A->kf_capacity || A->n_local > A->row_capacity || A->n_search > A->search_capacity) {
+    ctx->set_error("asd_update_local_map: %d keyframes, %d local points, %d points to search exceed the capacities %d, %d, %d", n_list, A->n_local, A->n_search,
+                   A->kf_capacity, A->row_capacity, A->search_capacity);
+    return ASD_ERR_CAPACITY;
+  }
+  if (n_list) memcpy(A->local_kfs, S->down.h + o_hk, (size_t)n_list * sizeof(int));
+  if (A->n_local) memcpy(A->local_rows, S->down.h + o_hl, (size_t)A->n_local * sizeof(int));
+  if (A->n_search) memcpy(A->search_rows, S->down.h + o_hs, (size_t)A->n_search * sizeof(int));
+  S->last_search.assign(A->search_rows, A->search_rows + A->n_search);
+  S->last_valid = true;
+  S->last_version = S->version;
+  return ASD_OK;
+}
+
+int asd_map_shared_counts(asd_ctx* ctx, int32_t kf, int32_t capacity, int32_t* kfs, int32_t* counts, int32_t* n) {
+  if (!ctx) return ASD_ERR_INVALID;
+  if (!n || capacity < 0 || (capacity > 0 && (!kfs || !counts))) { ctx->set_error("asd_map_shared_counts: invalid argument"); return ASD_ERR_INVALID; }
+  if (refuse(ctx, "asd_map_shared_counts")) return ASD_ERR_INVALID;
+  LocalMapState* S = lstate(ctx);
+  int slot;
+  const LmSlot* L = find_kf(ctx, S, "asd_map_shared_counts", kf, &slot);
+  if (!L) return ASD_ERR_INVALID;
+  *n = 0;
+  (void)hipSetDevice(ctx->cfg.device);
+  hipStream_t st = ctx->stream;
+  const int n_slots = (int)S->slots.size();
+  int rc;
+  if ((rc = clean_tables(ctx, S)) != ASD_OK) return rc;
+  if ((rc = lm_reserve(ctx, &S->d_cnt, &S->cnt_cap, (size_t)n_slots + 1, 0, -1, kInitSlots)) != ASD_OK) return rc;
+  if (L->n > 0) {
+    ASD_HIP_CHECK(ctx, S->down.begin(st, (size_t)n_slots * sizeof(int)));
+    const size_t o = S->down.reserve((size_t)n_slots * sizeof(int));
+    const int* own = S->d_rows + L->off;
+    S->tables_dirty = true;
+    hipLaunchKernelGGL(k_lm_mark, dim3((L->n + 255) / 256), dim3(256), 0, st, own, L->n, own, 0, S->d_pbad, S->d_mark);
+    ASD_HIP_CHECK(ctx, hipGetLastError());
+    hipLaunchKernelGGL(k_lm_vote, dim3((n_slots + 3) / 4), dim3(256), 0, st, S->d_table, n_slots, S->d_rows, S->d_mark, S->d_cnt);
+    ASD_HIP_CHECK(ctx, hipGetLastError());
+    hipLaunchKernelGGL(k_lm_unmark, dim3((L->n + 255) / 256), dim3(256), 0, st, own, L->n, own, 0, S->d_mark);
+    ASD_HIP_CHECK(ctx, hipGetLastError());
+    ASD_HIP_CHECK(ctx, hipMemcpyAsync(S->down.h + o, S->d_cnt, (size_t)n_slots * sizeof(int), hipMemcpyDeviceToHost, st));
+    ASD_HIP_CHECK(ctx, hipStreamSynchronize(st));
+    S->tables_dirty = false;
+    const int* c = S->down.host<int>(o);
+    int k = 0;
+    for (const auto& kv : S->by_kf) {   // KFcounter in ascending id, the keyframe itself left out (:559-565)
+      if (kv.first == kf || c[kv.second] <= 0) continue;
+      if (k < capacity) { kfs[k] = kv.first; counts[k] = c[kv.second]; }
+      ++k;
+    }
+    *n = k;
+    if (k > capacity) { ctx->set_error("asd_map_shared_counts: %d keyframes exceed the capacity %d", k, capacity); return ASD_ERR_CAPACITY; }
+  }
+  return ASD_OK;
+}
+
+int32_t asd_debug_map(asd_ctx* ctx, int64_t out[8]) {
+  if (!ctx || !out) return ASD_ERR_INVALID;
+  const LocalMapState* S = lstate(ctx);
+  out[0] = (int64_t)S->by_kf.size(); out[1] = S->live_entries; out[2] = (int64_t)S->table_cap; out[3] = S->entry_cap; out[4] = (int64_t)S->row_cap;
+  out[5] = S->growths[0]; out[6] = S->growths[1]; out[7] = S->growths[2];
+  return ASD_OK;
+}
+
+}  // extern "C"

@@ -1027,6 +1027,7 @@ struct StageInputs {
   const float* min_dist = nullptr;
   const float* max_dist = nullptr;
   const int32_t* rows = nullptr;        // [nq] bank rows of the queries' descriptors, or null: row = query index
+  const int32_t* d_rows = nullptr;      // ... the same table on the device already (asd_track_local_points_map): `rows` is not uploaded then
 };
 
 // One stage behind one synchronisation: one upload block (queries, the zeroed candidate counter, flags, the chain's tables), the kernels back
@@ -1089,7 +1090,8 @@ int search_and_resolve(asd_ctx* ctx, MatcherState* m, const AsdFrameSlot& F, con
   (void)table(in.normal, (size_t)nq * 12, &q_normal);
   (void)table(in.min_dist, (size_t)nq * 4, &q_min);
   (void)table(in.max_dist, (size_t)nq * 4, &q_max);
-  (void)table(in.rows, (size_t)nq * 4, &q_rows);
+  if (in.d_rows) q_rows = in.d_rows;
+  else (void)table(in.rows, (size_t)nq * 4, &q_rows);
   if (in.source == kQueriesProject) {
     s.project = in.project;
     s.project.Xw = static_cast<const float*>(q_points); s.project.has_mp = static_cast<const uint8_t*>(q_has); s.project.rows = static_cast<const int*>(q_rows);
@@ -1784,7 +1786,8 @@ int track_local_points_impl(asd_ctx* ctx, int32_t slot_cur, int32_t n_mp, const 
 // asd_track_local_points_bank given the same attributes.
 int track_local_points_rows_impl(asd_ctx* ctx, int32_t slot_cur, int32_t n_mp, const int32_t* rows, const float* Tcw, const float* K, float cos_limit,
                                  const uint8_t* occupied, const float* cur_Xw, float th, float nn_ratio, const uint8_t* mp_obs_positive,
-                                 double* pose7, int32_t* match_cur, int32_t* n_matches, uint8_t* outlier, int32_t* n_inliers, std::function<int()>* defer) {
+                                 double* pose7, int32_t* match_cur, int32_t* n_matches, uint8_t* outlier, int32_t* n_inliers, std::function<int()>* defer,
+                                 const int32_t* d_rows = nullptr) {
   AsdFrameSlot* F = slot_of(ctx, slot_cur);
   if (!F || n_mp < 1 || !rows || !Tcw || !K || !pose7 || !match_cur || !n_matches || !outlier || !n_inliers || F->n < 1 || !occupied || !cur_Xw) return ASD_ERR_INVALID;
   (void)hipSetDevice(ctx->cfg.device);
@@ -1814,7 +1817,7 @@ int track_local_points_rows_impl(asd_ctx* ctx, int32_t slot_cur, int32_t n_mp, c
   chain_solver_inputs(&in, pose7, K);
   in.d_points = m->d_cxw;
   in.own = cur_Xw; in.hold = occupied;
-  in.rows = rows;
+  in.rows = rows; in.d_rows = d_rows;
   const double* h_io = nullptr;
   std::function<int()> search_done;
   if ((rc = search_and_resolve(ctx, m, *F, in, match_cur, n_matches, &h_io, defer ? &search_done : nullptr)) != ASD_OK) return rc;
@@ -1899,6 +1902,20 @@ int asd_track_local_points_rows(asd_ctx* ctx, int32_t slot_cur, int32_t n_mp, co
   return run_track(ctx, [&](std::function<int()>* defer) {
     return track_local_points_rows_impl(ctx, slot_cur, n_mp, rows, Tcw, K, viewing_cos_limit, occupied, cur_Xw, th, nn_ratio, mp_obs_positive, pose7, match_cur,
                                         n_matches, outlier, n_inliers, defer); });
+}
+
+// asd_track_local_points_rows over the search list that the last asd_update_local_map left on the device (localmap.hip): the same stage from
+// the same description, with the row table already where k_frustum_queries reads it -- nothing per candidate is uploaded
+int asd_track_local_points_map(asd_ctx* ctx, int32_t slot_cur, const float* Tcw, const float* K, float viewing_cos_limit, const uint8_t* occupied,
+                               const float* cur_Xw, float th, float nn_ratio, const uint8_t* mp_obs_positive, double* pose7, int32_t* match_cur,
+                               int32_t* n_matches, uint8_t* outlier, int32_t* n_inliers) {
+  return run_track(ctx, [&](std::function<int()>* defer) {
+    const int32_t *h_rows = nullptr, *d_rows = nullptr;
+    int n_mp = 0;
+    const int rc = localmap_search_list(ctx, "asd_track_local_points_map", &h_rows, &d_rows, &n_mp);
+    if (rc != ASD_OK) return rc;
+    return track_local_points_rows_impl(ctx, slot_cur, n_mp, h_rows, Tcw, K, viewing_cos_limit, occupied, cur_Xw, th, nn_ratio, mp_obs_positive, pose7, match_cur,
+                                        n_matches, outlier, n_inliers, defer, d_rows); });
 }
 
 

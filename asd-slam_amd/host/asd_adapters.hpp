@@ -801,6 +801,86 @@ struct Tracking {
     }
     return ninl;
   }
+
+  // void Tracking::UpdateLocalMap() (:871-879 = UpdateLocalKeyFrames :907-1015 + UpdateLocalPoints :881-905) together with the skip
+  // loop of SearchLocalPoints (:827-841), over the context's observation table (asd_map_*; INTEGRATION.md says where the map's own
+  // methods keep it current).  All views are flat: map points are bank rows, keyframes their mnId.
+  struct LocalMap {
+    std::vector<int32_t> mvpLocalKeyFrames;     // in: the current list (kept when nobody votes); out: the new one
+    int32_t mpReferenceKF = -1;                 // in / out: replaced by pKFmax when somebody voted (:1010-1014)
+    std::vector<int32_t> mvpLocalMapPoints;     // out, in order
+    std::vector<int32_t> vpSearch;              // out: the points SearchLocalPoints goes on to project, in order; asd_track_local_points_map
+                                                // searches exactly these (its match_cur indexes this list)
+  };
+  // curMapPoints = mCurrentFrame.mvpMapPoints as bank rows after the motion-model stage's outlier drop (-1 = none); seenPoints = the rows
+  // of the points that drop stamped with mnLastFrameSeen (:705-707).  Returns asd_update_local_map's status; the library's capacity
+  // answer is followed by one repetition with the counts it asked for.
+  static int UpdateLocalMap(Context& c, const std::vector<int32_t>& curMapPoints, const std::vector<int32_t>& seenPoints, LocalMap& L,
+                            int maxKeyFrames = 80) {
+    const std::vector<int32_t> prev = L.mvpLocalKeyFrames;
+    std::vector<int32_t> kfs(std::max<size_t>(256, prev.size())), rows(1 << 16), srch(1 << 16);
+    asd_local_map_args a{};
+    a.n_cur = (int32_t)curMapPoints.size(); a.cur_rows = curMapPoints.data();
+    a.n_seen = (int32_t)seenPoints.size(); a.seen_rows = seenPoints.data();
+    a.n_prev = (int32_t)prev.size(); a.prev_kfs = prev.data();
+    a.max_kfs = maxKeyFrames;
+    int rc = ASD_OK;
+    for (int attempt = 0; attempt < 2; ++attempt) {
+      a.kf_capacity = (int32_t)kfs.size(); a.local_kfs = kfs.data();
+      a.row_capacity = (int32_t)rows.size(); a.local_rows = rows.data();
+      a.search_capacity = (int32_t)srch.size(); a.search_rows = srch.data();
+      rc = asd_update_local_map(c.get(), &a);
+      if (rc != ASD_ERR_CAPACITY || (a.n_local_kfs <= 0 && a.n_local <= 0)) break;   // (a capacity answer of another kind carries no counts)
+      kfs.resize(std::max<size_t>(kfs.size(), a.n_local_kfs)); rows.resize(std::max<size_t>(rows.size(), a.n_local)); srch.resize(std::max<size_t>(srch.size(), a.n_search));
+    }
+    if (rc != ASD_OK) return rc;
+    L.mvpLocalKeyFrames.assign(kfs.begin(), kfs.begin() + a.n_local_kfs);
+    if (a.ref_kf >= 0) L.mpReferenceKF = a.ref_kf;
+    L.mvpLocalMapPoints.assign(rows.begin(), rows.begin() + a.n_local);
+    L.vpSearch.assign(srch.begin(), srch.begin() + a.n_search);
+    return ASD_OK;
+  }
+};
+
+// ---- KeyFrame (KeyFrame.h; src/vslam/src/KeyFrame.cc) ---------------------------------------------
+struct KeyFrame {
+  struct Connections {
+    int rc = ASD_OK;
+    std::vector<int32_t> kfs, weights;                       // mConnectedKeyFrameWeights = KFcounter, ascending id
+    std::vector<int32_t> mvpOrderedConnectedKeyFrames, mvOrderedWeights;
+    int32_t pKFmax = -1; int nmax = 0;
+    // GetBestCovisibilityKeyFrames(10) (KeyFrame.cc:372-379): what asd_map_kf_links takes as `cov`
+    std::vector<int32_t> Best(size_t N = 10) const {
+      return std::vector<int32_t>(mvpOrderedConnectedKeyFrames.begin(), mvpOrderedConnectedKeyFrames.begin() + std::min(N, mvpOrderedConnectedKeyFrames.size()));
+    }
+  };
+  // void KeyFrame::UpdateConnections() (KeyFrame.cc:533-637) for keyframe mnId: KFcounter from the device (asd_map_shared_counts: :541-573),
+  // then the reference's rules on the host (:577-636): th = 15, the fall-back to the maximum, sort of (weight, keyframe) pairs ascending
+  // and push_front -- so equal weights come out higher id first --, pKFmax as the first strictly larger count in ascending id.  An
+  // empty KFcounter changes nothing (:577-578: "This should not happen").  The caller applies AddConnection(this, weight) to the listed
+  // keyframes (:605, :617) and the spanning-tree step (:637-646: mpParent = mvpOrderedConnectedKeyFrames.front() on the first connection).
+  static Connections UpdateConnections(Context& c, int32_t mnId, int th = 15) {
+    Connections R;
+    int32_t n = 0;
+    std::vector<int32_t> kfs(256), cnt(256);
+    R.rc = asd_map_shared_counts(c.get(), mnId, (int32_t)kfs.size(), kfs.data(), cnt.data(), &n);
+    if (R.rc == ASD_ERR_CAPACITY && n > (int32_t)kfs.size()) {
+      kfs.resize(n); cnt.resize(n);
+      R.rc = asd_map_shared_counts(c.get(), mnId, n, kfs.data(), cnt.data(), &n);
+    }
+    if (R.rc != ASD_OK || n == 0) return R;
+    R.kfs.assign(kfs.begin(), kfs.begin() + n);
+    R.weights.assign(cnt.begin(), cnt.begin() + n);
+    std::vector<std::pair<int, int32_t>> vPairs;
+    for (int32_t i = 0; i < n; ++i) {
+      if (cnt[i] > R.nmax) { R.nmax = cnt[i]; R.pKFmax = kfs[i]; }
+      if (cnt[i] >= th) vPairs.emplace_back(cnt[i], kfs[i]);
+    }
+    if (vPairs.empty()) vPairs.emplace_back(R.nmax, R.pKFmax);
+    std::sort(vPairs.begin(), vPairs.end());
+    for (size_t i = vPairs.size(); i-- > 0;) { R.mvpOrderedConnectedKeyFrames.push_back(vPairs[i].second); R.mvOrderedWeights.push_back(vPairs[i].first); }
+    return R;
+  }
 };
 
 // OPTIONAL: Optimizer::LocalBundleAdjustment on the library's lane.  The reference calls it IN LINE (Tracking.cc:797 ->

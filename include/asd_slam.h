@@ -353,7 +353,9 @@ int asd_mpbank_put(asd_ctx* ctx, int32_t first_row, int32_t n, const float* Xw, 
  * control flow stays with the caller as before: if the motion-model stage made too few matches (nmatches < 20,
  * Tracking.cc:681-685) it discards match2 / pose7 and runs the retry with the separate calls.  Sizes beyond the one-submission
  * form (more than 4096 last-frame keypoints, more ACTIVE local-map lists than one replay workgroup takes, frames beyond the
- * solver's LDS form) return ASD_ERR_CAPACITY: use the two calls.  Honours asd_track_async / asd_track_finish. */
+ * solver's LDS form) return ASD_ERR_CAPACITY: use the two calls.  Honours asd_track_async / asd_track_finish.
+ * (asd_update_local_map makes that decision on the device from a resident table: running it between the two stages inside this call, which
+ * would meet the precondition, is left to a later change.) */
 typedef struct asd_track_frame_args {
   int32_t slot_cur, slot_last;
   const uint8_t* has_mp;            /* [n_last] motion-model stage: as asd_track_motion_model_bank */
@@ -1262,6 +1264,94 @@ int asd_kfdb_select(asd_ctx* ctx, int32_t mode, int32_t n_scored, const int32_t*
  * score = {loop score, reloc score}; ASD_ERR_INVALID for an id that is not in the database. */
 int32_t asd_debug_kfdb(asd_ctx* ctx, int64_t out[5]);
 int32_t asd_debug_kfdb_entry(asd_ctx* ctx, int32_t kf, int32_t out[4], float score[2]);
+/* ---- observation table and the local map ---------------------------------------------------
+ * The third resident table, one per context (localmap.hip), beside the descriptor / attribute banks and the keyframe database: which
+ * keyframe observes which map point.  It is keyframe-major: every live keyframe (kf = the caller's mnId, any int32 >= 0) has a row of n
+ * int32 entries, entry idx = the bank row of the map point the keyframe observes at keypoint idx, or -1 -- KeyFrame::mvpMapPoints in the
+ * row numbering of asd_bank_put* / asd_mpbank_put.
+ * PRECONDITION, not checked: the table mirrors MapPoint::mObservations -- entry (kf, idx) = r exactly when point r has the observation
+ * kf -> idx, so a point occurs at most once in a keyframe's row.  EVERY TABLE ENTRY COUNTS: a row that names a point twice gives that
+ * keyframe two votes per keypoint of the frame that holds the point.
+ *
+ * asd_map_put        create or replace a keyframe's row (KeyFrame construction; n <= 65536).  Links and bad flag of a replaced row stay.
+ * asd_map_set        change single entries: KeyFrame::AddMapPoint / EraseMapPointMatch / ReplaceMapPointMatch, i.e. the keyframe side of
+ *                    MapPoint::AddObservation / EraseObservation / Replace (KeyFrame.cc:436-459, MapPoint.cc:110-142, :206-244).  Applied
+ *                    in the order given.  An unknown keyframe or an idx outside its row is ASD_ERR_INVALID.
+ * asd_map_erase      the keyframe leaves the table with its links and flag (KeyFrame::SetBadFlag's erase, KeyFrame.cc:723-815).  An
+ *                    unknown id is ASD_OK.
+ * asd_map_clear      empties the table and frees its storage.
+ * asd_map_kf_links   cov[n_cov <= 10] = GetBestCovisibilityKeyFrames(10) as ids in its order, children = GetChilds() as ids strictly
+ *                    ascending, parent = GetParent()'s id or -1.  The ids may name keyframes that are not, or no longer, in the table:
+ *                    such a keyframe contributes no points and counts as not bad, exactly as a keyframe would that the host still holds
+ *                    a pointer to.  kf itself must be in the table (ASD_ERR_INVALID).
+ * asd_map_kf_bad     KeyFrame::isBad() of a keyframe in the table (ASD_ERR_INVALID for an unknown id).
+ * asd_map_point_bad  MapPoint::isBad() for n bank rows, one byte per row; rows never named are not bad.
+ *
+ * Storage starts small and grows; at least 16384 live keyframes (the limit is 262144) of up to 65536 entries and bank rows below 2^28 are
+ * taken, ASD_ERR_CAPACITY with a message beyond.  All work runs on the context's stream and every call returns with its own work drained.
+ * The calls are legal while submissions of asd_extract_submit are outstanding.  While an asd_track_* call armed with asd_track_async is
+ * unfinished EVERY call of this section returns ASD_ERR_INVALID: asd_track_local_points_map reads the search list and the banks on that
+ * stream, and no ordering between a table change and the stage in flight is promised -- asd_track_finish first. */
+int asd_map_put(asd_ctx* ctx, int32_t kf, int32_t n, const int32_t* rows);
+int asd_map_set(asd_ctx* ctx, int32_t kf, int32_t count, const int32_t* idx, const int32_t* rows);
+int asd_map_erase(asd_ctx* ctx, int32_t kf);
+int asd_map_clear(asd_ctx* ctx);
+int asd_map_kf_links(asd_ctx* ctx, int32_t kf, int32_t n_cov, const int32_t* cov, int32_t n_children, const int32_t* children,
+                     int32_t parent);
+int asd_map_kf_bad(asd_ctx* ctx, int32_t kf, int32_t flag);
+int asd_map_point_bad(asd_ctx* ctx, int32_t n, const int32_t* rows, int32_t flag);
+
+/* Tracking::UpdateLocalMap (Tracking.cc:871-879 = UpdateLocalKeyFrames :907-1015 + UpdateLocalPoints :881-905) and the skip loop of
+ * SearchLocalPoints (:827-841) as one call over the table.  The reference is restated literally with ONE rule where it iterates in
+ * pointer order: every walk over a std::map<KeyFrame*, ...> or std::set<KeyFrame*> (keyframeCounter, GetChilds()) is in ASCENDING
+ * KEYFRAME ID (the quadtree's pointer-order tie is documented the same way).
+ *   in   cur_rows[n_cur]   mCurrentFrame.mvpMapPoints as bank rows after the motion-model stage's outlier drop, -1 = none
+ *        seen_rows[n_seen] further rows that carry mnLastFrameSeen == this frame: the dropped outliers' points (:705-707)
+ *        prev_kfs[n_prev]  the caller's current mvpLocalKeyFrames, used only when nobody votes
+ *        max_kfs           80 (:961); at most 1000
+ *   out  local_kfs / n_local_kfs  mvpLocalKeyFrames;  ref_kf  pKFmax, or -1 when nobody voted (mpReferenceKF then stays, :1010-1014)
+ *        local_rows / n_local     mvpLocalMapPoints, in order
+ *        search_rows / n_search   the sub-list SearchLocalPoints does not skip, in order
+ * Votes (:910-927): every keypoint of the frame whose point is not bad gives one vote to every keyframe that observes the point -- per
+ * keypoint, a point the frame holds twice votes twice; bad points do not vote (the caller nulls them itself).  List (:939-954): the voted
+ * keyframes in ascending id, bad ones skipped; pKFmax = the first with a strictly larger count (the lowest id among the maxima, never a bad
+ * keyframe).  Expansion (:958-1008): over the voted keyframes only (the end iterator is taken before anything is appended), stopped when the
+ * list holds more than max_kfs entries at the top of an iteration; per keyframe the first not-bad, not-yet-included covisible, then the
+ * first such child, then the parent (no bad test, :997-1006) if not yet included -- and adding a parent ENDS the expansion (the break at
+ * :1004 leaves the outer loop).  Nobody voted (:929-930): the list is prev_kfs unchanged.  Points (:885-903): the local keyframes in list
+ * order, their entries in ascending keypoint index, a point taken at its first occurrence unless it is bad; a bad keyframe in prev_kfs still
+ * contributes.  Search list: local_rows without the rows named in cur_rows (>= 0) or seen_rows, order kept.
+ * Capacities are the caller's.  When one is too small the call returns ASD_ERR_CAPACITY with ALL counts set to what is needed, and may
+ * simply be repeated.  Both lists also stay on the device for asd_track_local_points_map (after ASD_OK only).  Results are identical from
+ * run to run.  ASD_ERR_CAPACITY also when the local keyframes' rows together exceed 2^31 - 2^24 entries. */
+typedef struct asd_local_map_args {
+  int32_t n_cur;  const int32_t* cur_rows;
+  int32_t n_seen; const int32_t* seen_rows;
+  int32_t n_prev; const int32_t* prev_kfs;
+  int32_t max_kfs;
+  int32_t kf_capacity;     int32_t* local_kfs;   int32_t n_local_kfs; int32_t ref_kf;
+  int32_t row_capacity;    int32_t* local_rows;  int32_t n_local;
+  int32_t search_capacity; int32_t* search_rows; int32_t n_search;
+} asd_local_map_args;
+int asd_update_local_map(asd_ctx* ctx, asd_local_map_args* args);
+
+/* asd_track_local_points_rows over the search_rows that the last asd_update_local_map of this context left on the device: TrackLocalMap's
+ * body (Tracking.cc:725-736) without a row upload.  Same stage, same results bit for bit as the _rows call given the returned list;
+ * match_cur[j] indexes search_rows.  ASD_ERR_INVALID when there is no such list, when any asd_map_* call has changed the table since, or
+ * when n_search == 0; asd_track_local_points_rows' own ASD_ERR_CAPACITY beyond the device replay.  Honours asd_track_async / _finish. */
+int asd_track_local_points_map(asd_ctx* ctx, int32_t slot_cur, const float* Tcw, const float* K, float viewing_cos_limit,
+                               const uint8_t* occupied, const float* cur_Xw, float th, float nn_ratio, const uint8_t* mp_obs_positive,
+                               double* pose7, int32_t* match_cur, int32_t* n_matches, uint8_t* outlier, int32_t* n_inliers);
+
+/* KFcounter of KeyFrame::UpdateConnections (KeyFrame.cc:541-573) for a keyframe in the table: for every OTHER keyframe the number of the
+ * keyframe's not-bad points that it observes too (the vote pass of asd_update_local_map with the keyframe's own row as the frame).  The
+ * keyframe itself is excluded (:561), bad keyframes are not (as in the reference).  Keyframes with a count > 0 come back in ascending id;
+ * ASD_ERR_CAPACITY with *n = the count needed when `capacity` is too small. */
+int asd_map_shared_counts(asd_ctx* ctx, int32_t kf, int32_t capacity, int32_t* kfs, int32_t* counts, int32_t* n);
+/* Test aid: out = {live keyframes, live entries, slot capacity, arena capacity, row-table capacity, growths of the slot table, of the arena,
+ * of the row tables}. */
+int32_t asd_debug_map(asd_ctx* ctx, int64_t out[8]);
+
 /* Runs `reps` back-to-back repetitions of the ASDNet forward on resident buffers and
  * returns the average per-repetition device time (hipEvents on the ctx stream). */
 int asd_describe_timed(asd_ctx* ctx, const uint8_t* d_patches, int32_t n, float* d_desc,
