@@ -227,6 +227,33 @@ def initializer_normalize(keys):
     return pts, T.reshape(3, 3)
 
 
+# asd_debug_prim: op -> (name, doubles in, doubles out), in the order of the enum in include/asd_slam.h
+PRIM_OPS = [("asd_rsqrt", 1, 1), ("quat_normalize", 4, 4), ("quat_rotate", 7, 3), ("pose_map", 10, 3), ("pose_oplus", 13, 7),
+            ("rot_to_quat_eigen", 9, 4), ("huber", 2, 2), ("jac_pose", 5, 12), ("s3_exp", 7, 8), ("s3_exp_eigen", 7, 8), ("s3_log", 8, 7),
+            ("s3_mul", 16, 8), ("s3_mul_eigen", 16, 8), ("s3_inverse", 8, 8), ("s3_map", 11, 3), ("s3_oplus", 16, 8),
+            ("s3_oplus_eigen", 16, 8), ("s3_quat_of_rot", 9, 4), ("s3_quat_of_rot_eigen", 9, 4), ("s3_rot_of_quat", 8, 9),
+            ("s3_lu_solve3", 12, 3), ("s3_edge_error", 24, 7), ("s3_project_error", 17, 2), ("s3_chi2", 3, 1), ("s3_solve7", 57, 8)]
+PRIM_OP = {name: k for k, (name, _i, _o) in enumerate(PRIM_OPS)}
+PRIM_SE3_OPS = 8   # ops below this exist in the contracted build too (fused=True)
+
+
+def debug_prim(op, x, host=False, fused=False, ctx=None):
+    """asd_debug_prim: one primitive of csrc/se3.h / csrc/sim3_math.h per row of x [n, width in] -> [n, width out] f64.  op: a name
+    of PRIM_OPS or its number.  host: through the same header functions on the host (needs no context and no device); fused: the
+    instantiation built with contraction allowed, as ba.o and gba.o (the se3.h ops only)."""
+    k = PRIM_OP[op] if isinstance(op, str) else int(op)
+    _name, w_in, w_out = PRIM_OPS[k]
+    x = _c(x, np.float64).reshape(-1, w_in)
+    out = np.full((len(x), w_out), np.nan)
+    lib = ctx.lib if ctx is not None else load_library()
+    lib.asd_debug_prim.restype = C.c_int32
+    lib.asd_debug_prim.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]
+    rc = lib.asd_debug_prim(ctx.ctx if ctx is not None else None, k, (1 if host else 0) | (2 if fused else 0), len(x), _p(x), _p(out))
+    if rc != 0:
+        raise AsdError(rc, ctx.last_error() if ctx is not None else "asd_debug_prim: invalid arguments")
+    return out
+
+
 class AsdHip:
     """One asd_ctx (= one HIP device + stream)."""
 
@@ -1353,6 +1380,10 @@ class AsdHip:
         self._chk(self.lib.asd_debug_dense_solve(self.ctx, C.c_int32(int(form)), C.c_int32(n), _p(A), _p(b), C.c_int32(int(done)),
                                                  C.c_int32(int(chol_ok_in)), _p(L), _p(x), C.byref(ok)))
         return dict(x=x[:n], chol_ok=int(ok.value), L=L)
+
+    def debug_prim(self, op, x, host=False, fused=False):
+        """one primitive of se3.h / sim3_math.h on every row of x (see debug_prim below) -- asd_debug_prim"""
+        return debug_prim(op, x, host=host, fused=fused, ctx=self)
 
     def local_ba_submit(self, prob, its_first=5, its_second=10):
         """LocalBundleAdjustment on the library's OPTIONAL lane: returns at once; local_ba_wait() returns the result dict.  One run

@@ -748,6 +748,47 @@ int32_t asd_debug_gba_trials(const asd_ctx* ctx, int32_t* out, int32_t cap);
  * Allocates per call; not for a hot path. */
 int32_t asd_debug_dense_solve(asd_ctx* ctx, int32_t form, int32_t n, const double* A, const double* b, int32_t done_in,
                               int32_t chol_ok_in, double* L_out, double* x_out, int32_t* chol_ok_out);
+/* Test aid: ONE call of one fp64 primitive of csrc/se3.h / csrc/sim3_math.h per item (tests/test_prims.py).  in: host, n items of
+ * the op's input width; out: host, n items of its output width (doubles, in the order of the function's arguments; a Pose7 is
+ * qx qy qz qw tx ty tz, a Sim3d is qx qy qz qw tx ty tz s, matrices are row-major).  One launch of a 64-thread-per-block kernel on
+ * the context's stream, one lane per item, then a synchronise.
+ *   op                              in                                            out
+ *    0 asd_rsqrt                     1  x                                          1
+ *    1 quat_normalize                4  x y z w                                    4  x y z w
+ *    2 quat_rotate                   7  qx qy qz qw, v[3]                          3
+ *    3 pose_map                     10  Pose7, X[3]                                3
+ *    4 pose_oplus                   13  Pose7, u[6] = (omega, upsilon)             7  Pose7
+ *    5 rot_to_quat_eigen             9  R                                          4  x y z w
+ *    6 huber                         2  e2, delta                                  2  rho0, rho1
+ *    7 jac_pose                      5  x y z fx fy                               12  J
+ *    8 s3_exp<false>   9 <true>      7  u = (omega, upsilon, sigma)                8  Sim3d
+ *   10 s3_log                        8  Sim3d                                      7
+ *   11 s3_mul<false>  12 <true>     16  Sim3d a, Sim3d b                           8  Sim3d
+ *   13 s3_inverse                    8  Sim3d                                      8  Sim3d
+ *   14 s3_map                       11  Sim3d, v[3]                                3
+ *   15 s3_oplus<false> 16 <true>    16  Sim3d est, u[7], fix_scale (0 or not)      8  Sim3d
+ *   17 s3_quat_of_rot<false> 18 <true> 9  R                                        4  x y z w
+ *   19 s3_rot_of_quat                8  Sim3d (the quaternion is read)             9  R
+ *   20 s3_lu_solve3                 12  W, t[3]                                    3
+ *   21 s3_edge_error                24  Sim3d C, Si, Sj                            7
+ *   22 s3_project_error             17  Sim3d, X Y Z, ou ov, fx fy cx cy           2
+ *   23 s3_chi2                       3  e0 e1 inv_sigma2                           1
+ *   24 s3_solve7                    57  H[49], lambda, b[7]                        8  ok (1 or 0), x[7]
+ * flags: ASD_PRIM_HOST -- run on the host instead, through the same header functions (ctx may then be NULL; no device is touched);
+ * ASD_PRIM_FUSED_BUILD -- the instantiation compiled with the flags of ba.o / gba.o (contraction allowed) instead of
+ * -ffp-contract=off; it holds ops 0 .. 7 only.  ASD_ERR_INVALID for an unknown op or flag bit, n < 0 and null pointers; n = 0
+ * returns ASD_OK and launches nothing.  Allocates per call; not for a hot path. */
+enum {
+  ASD_PRIM_RSQRT = 0, ASD_PRIM_QUAT_NORMALIZE, ASD_PRIM_QUAT_ROTATE, ASD_PRIM_POSE_MAP, ASD_PRIM_POSE_OPLUS, ASD_PRIM_ROT_TO_QUAT_EIGEN,
+  ASD_PRIM_HUBER, ASD_PRIM_JAC_POSE, ASD_PRIM_SE3_OPS,
+  ASD_PRIM_S3_EXP = ASD_PRIM_SE3_OPS, ASD_PRIM_S3_EXP_EIGEN, ASD_PRIM_S3_LOG, ASD_PRIM_S3_MUL, ASD_PRIM_S3_MUL_EIGEN, ASD_PRIM_S3_INVERSE,
+  ASD_PRIM_S3_MAP, ASD_PRIM_S3_OPLUS, ASD_PRIM_S3_OPLUS_EIGEN, ASD_PRIM_S3_QUAT_OF_ROT, ASD_PRIM_S3_QUAT_OF_ROT_EIGEN,
+  ASD_PRIM_S3_ROT_OF_QUAT, ASD_PRIM_S3_LU_SOLVE3, ASD_PRIM_S3_EDGE_ERROR, ASD_PRIM_S3_PROJECT_ERROR, ASD_PRIM_S3_CHI2, ASD_PRIM_S3_SOLVE7,
+  ASD_PRIM_OPS
+};
+#define ASD_PRIM_HOST 1
+#define ASD_PRIM_FUSED_BUILD 2
+int32_t asd_debug_prim(asd_ctx* ctx, int32_t op, int32_t flags, int32_t n, const double* in, double* out);
 
 /* ---- essential graph (Sim3 pose graph of a loop closure) --------------------------------- */
 typedef struct asd_essgraph_problem {
