@@ -77,6 +77,11 @@ class asd_local_map_args(C.Structure):
                 ("n_local", C.c_int32), ("search_capacity", C.c_int32), ("search_rows", C.c_void_p), ("n_search", C.c_int32)]
 
 
+class asd_kf_culling_args(C.Structure):
+    _fields_ = [("n_cand", C.c_int32), ("cand", C.c_void_p), ("cand_flags", C.c_void_p), ("apply", C.c_int32), ("decision", C.c_void_p),
+                ("n_mps", C.c_void_p), ("n_redundant", C.c_void_p), ("bad_capacity", C.c_int32), ("bad_rows", C.c_void_p), ("n_bad", C.c_int32)]
+
+
 class asd_ba_problem(C.Structure):
     _fields_ = [("n_poses", C.c_int32), ("n_points", C.c_int32), ("n_edges", C.c_int32),
                 ("poses", C.c_void_p), ("fixed", C.c_void_p), ("points", C.c_void_p),
@@ -963,6 +968,42 @@ class AsdHip:
         if rc != 0:
             raise AsdError(rc, f"{self.last_error()} [n = {n.value}]")
         return kfs[:n.value].copy(), cnt[:n.value].copy()
+
+    def map_put_octaves(self, kf, octaves):
+        octaves = _c(octaves, np.uint8)
+        self._chk(self.lib.asd_map_put_octaves(self.ctx, int(kf), len(octaves), _p(octaves)))
+
+    def keyframe_culling_raw(self, cand, flags, apply, bad_capacity):
+        """asd_keyframe_culling with the caller's bad_capacity -> (rc, dict); the outputs are in the dict only when rc == 0"""
+        cand, flags = _c(cand, np.int32), _c(flags, np.uint8)
+        n = len(cand)
+        dec, nm, nr = np.full(max(n, 1), 9, np.uint8), np.full(max(n, 1), -7, np.int32), np.full(max(n, 1), -7, np.int32)
+        bad = np.full(max(int(bad_capacity), 1), -7, np.int32)
+        a = asd_kf_culling_args()
+        a.n_cand, a.cand, a.cand_flags, a.apply = n, cand.ctypes.data, flags.ctypes.data, int(bool(apply))
+        a.decision, a.n_mps, a.n_redundant = dec.ctypes.data, nm.ctypes.data, nr.ctypes.data
+        a.bad_capacity, a.bad_rows, a.n_bad = int(bad_capacity), bad.ctypes.data, -1
+        rc = self.lib.asd_keyframe_culling(self.ctx, C.byref(a))
+        out = dict(n_bad=a.n_bad)
+        if rc == 0:
+            out.update(decision=dec[:n].copy(), n_mps=nm[:n].copy(), n_redundant=nr[:n].copy(), bad_rows=bad[:a.n_bad].copy())
+        return rc, out
+
+    def keyframe_culling(self, cand, flags=None, apply=False, bad_capacity=256):
+        """LocalMapping::KeyFrameCulling -> dict(decision, n_mps, n_redundant, bad_rows); repeats once with the capacity the library asked for"""
+        flags = np.zeros(len(cand), np.uint8) if flags is None else flags
+        rc, out = self.keyframe_culling_raw(cand, flags, apply, bad_capacity)
+        if rc == -5 and out["n_bad"] > bad_capacity:   # ASD_ERR_CAPACITY
+            rc, out = self.keyframe_culling_raw(cand, flags, apply, out["n_bad"])
+        self._chk(rc)
+        return out
+
+    def map_observations(self, rows):
+        """MapPoint::Observations() for bank rows"""
+        rows = _c(rows, np.int32)
+        counts = np.full(max(len(rows), 1), -7, np.int32)
+        self._chk(self.lib.asd_map_observations(self.ctx, len(rows), _p(rows), _p(counts)))
+        return counts[:len(rows)].copy()
 
     def map_debug(self):
         """(live keyframes, live entries, slot capacity, arena capacity, row-table capacity, slot / arena / row-table growths)"""

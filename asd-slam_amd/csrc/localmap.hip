@@ -19,6 +19,18 @@
 // The ordering rule.  Where the reference walks a std::map<KeyFrame*, ...> or a std::set<KeyFrame*> in pointer order, the walk here is
 // in ascending keyframe id: the vote list, the first strict maximum, GetChilds().
 //
+// Culling.  LocalMapping::KeyFrameCulling (reference src/vslam/src/LocalMapping.cc:739-809, monocular) and MapPoint::Observations() read the
+// same table; the arena has a second plane, one byte per entry = mvKeysUn[idx].octave, that follows its row through growth and compaction.
+// asd_keyframe_culling: the candidates' rows laid end to end go through the claim / count / tile-scan / scatter compaction above, which
+// leaves their distinct not-bad points in order; k_cull_index writes each point's position into the mark table and zeroes its 16 int32
+// counters; k_cull_count is ONE pass over every live row (one wave per slot, coalesced row and octave loads, integer atomics) that builds
+// the per-octave observation counts of those points only; k_cull_walk is ONE workgroup that takes the candidates in order -- a strided
+// count over the row, a workgroup reduction, the decision 10 nR > 9 nM, then over the same row the decrements, the points that fall to
+// <= 2 observations (appended in keypoint order by a ballot scan) -- so a cull is seen by the next candidate without a host round trip.
+// The walk changes only the call's scratch.  With apply = 1 one more pass over the live rows (k_cull_apply) empties the culled rows and
+// the entries of the points that turned bad; k_cull_finish undoes the marks either way.  asd_map_observations is the same marking and the
+// same pass with one counter per point.
+//
 // Streams.  Every copy into these tables and every kernel that reads them is enqueued on ctx->stream, every entry point returns with that
 // stream drained, and all of them are refused while an armed asd_track_* call is unfinished (asd_track_local_points_map reads the search
 // list on that stream).  A growth therefore orders itself against the only stream that can hold a write to the old storage: the copy
@@ -46,6 +58,9 @@ constexpr int kVoteMask = 0x3fffffff, kSkipBit = 0x40000000;
 constexpr int kClaimFree = 0x7f7f7f7f;    // (a byte pattern: hipMemsetAsync fills the claim table)
 constexpr long long kMaxEntriesPerQuery = 0x7f000000;
 constexpr int kTile = 1024;               // entries per workgroup of the compaction: 4 rounds of 256
+constexpr int kLevels = ASD_MAX_LEVELS;   // counters per point of asd_keyframe_culling
+constexpr int kMaxCand = 4096;
+constexpr long long kMaxCullEntries = 1ll << 26;   // entries of the candidates' rows together: 16 counters each stay below 2^31 words
 
 struct LmSlotDev { long long off; int n; int id; int bad; int n_cov; int parent; int pad; int cov[kMaxCov]; int pad2[2]; };   // n < 0: free slot
 struct LmMove { long long from, to; int n; int pad; };
@@ -121,9 +136,10 @@ __global__ __launch_bounds__(256) void k_lm_point_bad(uint8_t* __restrict__ pbad
   if (i < n) pbad[rows[i]] = (uint8_t)flag;
 }
 // growth: one workgroup per live keyframe copies its row from the old arena into the new one
-__global__ __launch_bounds__(256) void k_lm_move(const LmMove* __restrict__ mv, const int* __restrict__ r0, int* __restrict__ r1) {
+__global__ __launch_bounds__(256) void k_lm_move(const LmMove* __restrict__ mv, const int* __restrict__ r0, int* __restrict__ r1,
+                                                 const uint8_t* __restrict__ o0, uint8_t* __restrict__ o1) {
   const LmMove m = mv[blockIdx.x];
-  for (int t = threadIdx.x; t < m.n; t += 256) r1[m.to + t] = r0[m.from + t];
+  for (int t = threadIdx.x; t < m.n; t += 256) { r1[m.to + t] = r0[m.from + t]; o1[m.to + t] = o0[m.from + t]; }
 }
 
 // exclusive prefix of one int per thread over the workgroup (256 threads); *total = the sum
@@ -353,11 +369,158 @@ __global__ __launch_bounds__(256) void k_lm_scatter(LmPointArgs a) {
   }
 }
 
+// ---- KeyFrameCulling and Observations()
+struct LmCullArgs {
+  const LmSlotDev* table; const int* rows; const uint8_t* oct; const uint8_t* pbad; const int* mark;
+  const int* cand_slot; const uint8_t* cand_flags; int n_cand;   // slot -1: skipped (:751-754)
+  int* cnt; int* gone;         // per compacted point: observations per octave [16]; 1 = EraseObservation turned it bad in this call
+  int* bad_rows;               // out: those points in the order it happened
+  int* culled;                 // [slots] 1 = SetBadFlag took effect
+  int* out;                    // [3][n_cand]: decision, nMPs, nRedundantObservations
+  int* head;                   // head[10] = number of bad_rows
+};
+
+// the compacted points get their position (+ 1) in the mark table and clean counters; head[8] = their number
+__global__ __launch_bounds__(256) void k_cull_index(const int* __restrict__ pts, const int* __restrict__ head, int* __restrict__ mark,
+                                                    int* __restrict__ cnt, int* __restrict__ gone) {
+  const int ci = blockIdx.x * 256 + threadIdx.x;
+  if (ci >= head[8]) return;
+  mark[pts[ci]] = ci + 1;
+  gone[ci] = 0;
+  int4* q = reinterpret_cast<int4*>(cnt + (size_t)ci * kLevels);
+  const int4 z = make_int4(0, 0, 0, 0);
+  for (int k = 0; k < kLevels / 4; ++k) q[k] = z;
+}
+// ONE pass over the table, one wave per slot: every entry that names a marked point counts, at its octave (levels = 16) or at all (1)
+__global__ __launch_bounds__(256) void k_cull_count(const LmSlotDev* __restrict__ table, int n_slots, const int* __restrict__ rows,
+                                                    const uint8_t* __restrict__ oct, const int* __restrict__ mark, int* __restrict__ cnt, int levels) {
+  const int lane = threadIdx.x & 63;
+  const int slot = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (slot >= n_slots) return;
+  const long long off = table[slot].off;
+  const int n = table[slot].n;
+  for (int i = lane; i < n; i += 64) {
+    const int r = rows[off + i];
+    if (r < 0) continue;
+    const int m = mark[r];
+    if (m > 0) atomicAdd(&cnt[(size_t)(m - 1) * levels + (levels > 1 ? (oct[off + i] & (kLevels - 1)) : 0)], 1);
+  }
+}
+// the point of table entry e as the walk sees it now: its compacted position, or -1 (none, bad, or turned bad by an earlier cull)
+__device__ inline int cull_point(const LmCullArgs& a, long long e) {
+  const int r = a.rows[e];
+  if (r < 0 || a.pbad[r]) return -1;
+  const int ci = a.mark[r] - 1;
+  return ci >= 0 && !a.gone[ci] ? ci : -1;
+}
+// the sequential part (:748-808) as ONE workgroup.  A point occurs once per row (the table's precondition), so the threads of a round
+// touch different counters; the barrier at the end of a candidate orders its decrements before the next candidate's reads.
+__global__ __launch_bounds__(256) void k_cull_walk(LmCullArgs a) {
+  __shared__ int s_red[4][2], s_wave[4];
+  const int t = threadIdx.x, lane = t & 63, w = t >> 6;
+  int n_bad = 0;
+  for (int c = 0; c < a.n_cand; ++c) {
+    const int sl = a.cand_slot[c];
+    if (sl < 0) {   // (the same for every thread)
+      if (t == 0) { a.out[c] = 3; a.out[a.n_cand + c] = 0; a.out[2 * a.n_cand + c] = 0; }
+      continue;
+    }
+    const long long off = a.table[sl].off;
+    const int n = a.table[sl].n;
+    int nm = 0, nr = 0;
+    for (int i = t; i < n; i += 256) {
+      const int ci = cull_point(a, off + i);
+      if (ci < 0) continue;
+      ++nm;
+      const int* q = a.cnt + (size_t)ci * kLevels;
+      const int lim = min((a.oct[off + i] & (kLevels - 1)) + 1, kLevels - 1);
+      int total = 0, upto = 0;   // Observations(), and the observations at an octave <= scaleLevel + 1 -- the keyframe's own among them
+      for (int k = 0; k < kLevels; ++k) { const int v = q[k]; total += v; if (k <= lim) upto += v; }
+      if (total > 3 && upto - 1 >= 3) ++nr;
+    }
+    for (int s = 32; s > 0; s >>= 1) { nm += __shfl_xor(nm, s, 64); nr += __shfl_xor(nr, s, 64); }
+    if (lane == 0) { s_red[w][0] = nm; s_red[w][1] = nr; }
+    asd_syncthreads();
+    nm = s_red[0][0] + s_red[1][0] + s_red[2][0] + s_red[3][0];
+    nr = s_red[0][1] + s_red[1][1] + s_red[2][1] + s_red[3][1];
+    const bool cull = 10 * nr > 9 * nm;   // nRedundantObservations > 0.9 * nMPs (:805); rows hold at most 65536 entries
+    const int decision = !cull ? 0 : (a.cand_flags[c] & 2) ? 2 : 1;
+    if (decision == 1) {   // SetBadFlag: the observations leave in ascending keypoint index
+      for (int base = 0; base < n; base += 256) {
+        const int i = base + t;
+        bool turned = false;
+        int r = -1;
+        if (i < n) {
+          const int ci = cull_point(a, off + i);
+          if (ci >= 0) {
+            int* q = a.cnt + (size_t)ci * kLevels;
+            q[a.oct[off + i] & (kLevels - 1)] -= 1;
+            int total = 0;
+            for (int k = 0; k < kLevels; ++k) total += q[k];
+            if (total <= 2) { turned = true; a.gone[ci] = 1; r = a.rows[off + i]; }   // MapPoint.cc:136-141
+          }
+        }
+        int round;
+        const int pos = lm_block_scan_flag(turned, s_wave, &round);
+        if (turned) a.bad_rows[n_bad + pos] = r;
+        n_bad += round;
+      }
+      if (t == 0) a.culled[sl] = 1;
+    }
+    if (t == 0) { a.out[c] = decision; a.out[a.n_cand + c] = nm; a.out[2 * a.n_cand + c] = nr; }
+    asd_syncthreads();
+  }
+  if (t == 0) a.head[10] = n_bad;
+}
+// apply = 1: the culled keyframes' rows and every entry of a point that turned bad become -1; the culled keyframes become bad
+__global__ __launch_bounds__(256) void k_cull_apply(LmSlotDev* __restrict__ table, int n_slots, int* __restrict__ rows, const int* __restrict__ mark,
+                                                    const int* __restrict__ gone, const int* __restrict__ culled) {
+  const int lane = threadIdx.x & 63;
+  const int slot = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (slot >= n_slots) return;
+  const long long off = table[slot].off;
+  const int n = table[slot].n;
+  if (n < 0) return;
+  const bool all = culled[slot] != 0;
+  for (int i = lane; i < n; i += 64) {
+    const int r = rows[off + i];
+    if (r < 0) continue;
+    const int m = mark[r];
+    if (all || (m > 0 && gone[m - 1])) rows[off + i] = -1;
+  }
+  if (all && lane == 0) table[slot].bad = 1;
+}
+// the marks are undone; with apply the points that turned bad get their byte
+__global__ __launch_bounds__(256) void k_cull_finish(const int* __restrict__ pts, const int* __restrict__ head, int* __restrict__ mark,
+                                                     const int* __restrict__ gone, uint8_t* __restrict__ pbad, int apply) {
+  const int ci = blockIdx.x * 256 + threadIdx.x;
+  if (ci >= head[8]) return;
+  const int r = pts[ci];
+  mark[r] = 0;
+  if (apply && gone[ci]) pbad[r] = 1;
+}
+// asd_map_observations: a row asked for twice shares one counter (the larger position wins, whatever the scheduling)
+// (a row beyond the row tables has never been named by an entry: it counts 0 and the tables do not grow for it)
+__global__ __launch_bounds__(256) void k_obs_mark(const int* __restrict__ rows, int n, int row_cap, int* __restrict__ mark) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i < n && rows[i] < row_cap) atomicMax(&mark[rows[i]], i + 1);
+}
+__global__ __launch_bounds__(256) void k_obs_gather(const int* __restrict__ rows, int n, int row_cap, const int* __restrict__ mark, const int* __restrict__ cnt,
+                                                    int* __restrict__ out) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i < n) out[i] = rows[i] < row_cap ? cnt[mark[rows[i]] - 1] : 0;
+}
+__global__ __launch_bounds__(256) void k_obs_unmark(const int* __restrict__ rows, int n, int row_cap, int* __restrict__ mark) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i < n && rows[i] < row_cap) mark[rows[i]] = 0;
+}
+
 struct LmSlot {
   int kf = -1;   // -1: free slot
   int n = -1;
   long long off = 0;
   bool bad = false;
+  bool has_oct = false;   // asd_map_put_octaves has filled the octave plane of this row
   int n_cov = 0, cov[kMaxCov] = {};
   int parent = -1;
   std::vector<int> children;
@@ -371,6 +534,8 @@ struct LocalMapState {
   uint64_t version = 1;       // bumped by every call that changes what a query reads
   LmSlotDev* d_table = nullptr; size_t table_cap = 0;
   int* d_rows = nullptr; long long entry_cap = 0, entry_used = 0;
+  uint8_t* d_oct = nullptr;   // the octave plane of the arena: same offsets, same capacity
+  int live_without_oct = 0;   // live keyframes whose row has no octaves (asd_keyframe_culling refuses unless 0)
   uint8_t* d_pbad = nullptr; int* d_mark = nullptr; int* d_claim = nullptr; size_t row_cap = 0;
   bool tables_dirty = false;  // a query failed between marking and undoing
   int* d_sorted = nullptr; size_t sorted_cap = 0; bool sorted_dirty = true;   // ids [live] | slots [live]
@@ -384,6 +549,8 @@ struct LocalMapState {
   int* d_tile = nullptr; size_t tile_cap = 0;           // counts [tiles][2] | offsets [tiles][2]
   int* d_local = nullptr; size_t local_cap = 0;
   int* d_search = nullptr; size_t search_cap = 0;
+  int* d_cull = nullptr; size_t cull_cap = 0;           // scratch of asd_keyframe_culling / asd_map_observations
+  int* d_culled = nullptr; size_t culled_cap = 0;       // [slots]
   AsdXfer up, down;
   int growths[3] = {0, 0, 0};   // slot table, arena, row tables
   // what the last asd_update_local_map left for asd_track_local_points_map
@@ -419,10 +586,11 @@ int lm_reserve(asd_ctx* ctx, T** p, size_t* cap, size_t need, size_t keep, int f
 
 void release_device(LocalMapState* S) {
   void* dev[] = {S->d_table, S->d_rows, S->d_pbad, S->d_mark, S->d_claim, S->d_sorted, S->d_child, S->d_cnt, S->d_list, S->d_list_base, S->d_head,
-                 S->d_tile, S->d_local, S->d_search};
+                 S->d_tile, S->d_local, S->d_search, S->d_oct, S->d_cull, S->d_culled};
   for (void* p : dev) if (p) (void)hipFree(p);
   S->d_table = nullptr; S->d_rows = nullptr; S->d_pbad = nullptr; S->d_mark = nullptr; S->d_claim = nullptr; S->d_sorted = nullptr; S->d_child = nullptr;
   S->d_cnt = nullptr; S->d_list = nullptr; S->d_list_base = nullptr; S->d_head = nullptr; S->d_tile = nullptr; S->d_local = nullptr; S->d_search = nullptr;
+  S->d_oct = nullptr; S->d_cull = nullptr; S->d_culled = nullptr; S->cull_cap = S->culled_cap = 0;
   S->table_cap = S->row_cap = S->sorted_cap = S->child_cap = S->cnt_cap = S->list_cap = S->list_base_cap = S->head_cap = S->tile_cap = S->local_cap = S->search_cap = 0;
   S->entry_cap = S->entry_used = 0;
 }
@@ -476,7 +644,12 @@ int grow_arena(asd_ctx* ctx, LocalMapState* S, long long need) {
   if (S->entry_used + need <= S->entry_cap) return ASD_OK;
   const long long cap = std::max(kInitEntries, 2 * (S->live_entries + need));
   int* nr = nullptr;
-  if (hipMalloc(&nr, (size_t)cap * sizeof(int)) != hipSuccess) { ctx->set_error("local map: out of device memory for %lld table entries", cap); return ASD_ERR_HIP; }
+  uint8_t* no = nullptr;
+  if (hipMalloc(&nr, (size_t)cap * sizeof(int)) != hipSuccess || hipMalloc(&no, (size_t)cap) != hipSuccess) {
+    if (nr) (void)hipFree(nr);
+    ctx->set_error("local map: out of device memory for %lld table entries", cap);
+    return ASD_ERR_HIP;
+  }
   std::vector<LmMove> mv;
   std::vector<int> moved;
   long long used = 0;
@@ -489,14 +662,14 @@ int grow_arena(asd_ctx* ctx, LocalMapState* S, long long need) {
     used += L.n;
   }
   hipStream_t st = ctx->stream;
-  hipError_t e = hipSuccess;
-  if (!mv.empty() && S->d_rows) {
+  hipError_t e = hipMemsetAsync(no, 0, (size_t)cap, st);   // (rows without octaves read as level 0, never as a level outside the counters)
+  if (e == hipSuccess && !mv.empty() && S->d_rows) {
     const size_t b_mv = mv.size() * sizeof(LmMove);
     e = S->up.begin(st, b_mv + moved.size() * AsdDevBuf::padded(sizeof(LmSlotDev)) + 1024);   // (every add is padded to 256 B)
     if (e == hipSuccess) {
       const size_t o = S->up.add(mv.data(), b_mv);
       e = hipMemcpyAsync(S->up.d + o, S->up.h + o, b_mv, hipMemcpyHostToDevice, st);
-      if (e == hipSuccess) { hipLaunchKernelGGL(k_lm_move, dim3((unsigned)mv.size()), dim3(256), 0, st, S->up.dev<LmMove>(o), S->d_rows, nr); e = hipGetLastError(); }
+      if (e == hipSuccess) { hipLaunchKernelGGL(k_lm_move, dim3((unsigned)mv.size()), dim3(256), 0, st, S->up.dev<LmMove>(o), S->d_rows, nr, S->d_oct, no); e = hipGetLastError(); }
       for (size_t k = 0; k < moved.size() && e == hipSuccess; ++k) {   // the moved rows' new offsets
         const LmSlotDev d = dev_entry(S->slots[moved[k]]);
         const size_t oe = S->up.add(&d, sizeof d);
@@ -506,8 +679,9 @@ int grow_arena(asd_ctx* ctx, LocalMapState* S, long long need) {
   }
   const hipError_t es = hipStreamSynchronize(st);   // the old arena goes only when the stream that read and wrote it has drained
   if (e == hipSuccess) e = es;
-  if (S->d_rows) { (void)hipFree(S->d_rows); ++S->growths[1]; }
+  if (S->d_rows) { (void)hipFree(S->d_rows); (void)hipFree(S->d_oct); ++S->growths[1]; }
   S->d_rows = nr;
+  S->d_oct = no;
   S->entry_cap = cap; S->entry_used = used;
   if (e != hipSuccess) { ctx->set_error("local map: arena growth failed: %s", hipGetErrorString(e)); return ASD_ERR_HIP; }
   return ASD_OK;
@@ -599,6 +773,7 @@ int asd_map_clear(asd_ctx* ctx) {
   release_device(S);
   S->slots.clear(); S->free_slots.clear(); S->by_kf.clear();
   S->live_entries = 0;
+  S->live_without_oct = 0;
   S->sorted_dirty = S->child_dirty = true; S->child_off_words = 0; S->tables_dirty = false;
   S->growths[0] = S->growths[1] = S->growths[2] = 0;
   S->last_valid = false; S->last_search.clear();
@@ -638,7 +813,8 @@ int asd_map_put(asd_ctx* ctx, int32_t kf, int32_t n, const int32_t* rows) {
   } else {
     S->live_entries += n - old_n;
   }
-  if (fresh) { L = LmSlot(); L.kf = kf; S->by_kf[kf] = slot; S->sorted_dirty = true; S->child_dirty = true; }
+  if (fresh) { L = LmSlot(); L.kf = kf; S->by_kf[kf] = slot; S->sorted_dirty = true; S->child_dirty = true; ++S->live_without_oct; }
+  else if (n != old_n && L.has_oct) { L.has_oct = false; ++S->live_without_oct; }   // the octaves are the keypoints': another n is another set of keypoints
   L.n = n; L.off = off;
   ++S->version;
   hipStream_t st = ctx->stream;
@@ -696,6 +872,7 @@ int asd_map_erase(asd_ctx* ctx, int32_t kf) {
   (void)hipSetDevice(ctx->cfg.device);
   const int slot = it->second;
   S->live_entries -= S->slots[slot].n;
+  if (!S->slots[slot].has_oct) --S->live_without_oct;
   S->slots[slot] = LmSlot();   // its row stays in the arena until the next growth compacts it
   S->free_slots.push_back(slot);
   S->by_kf.erase(it);
@@ -924,6 +1101,196 @@ int asd_map_shared_counts(asd_ctx* ctx, int32_t kf, int32_t capacity, int32_t* k
     *n = k;
     if (k > capacity) { ctx->set_error("asd_map_shared_counts: %d keyframes exceed the capacity %d", k, capacity); return ASD_ERR_CAPACITY; }
   }
+  return ASD_OK;
+}
+
+int asd_map_put_octaves(asd_ctx* ctx, int32_t kf, int32_t n, const uint8_t* octave) {
+  if (!ctx) return ASD_ERR_INVALID;
+  if (refuse(ctx, "asd_map_put_octaves")) return ASD_ERR_INVALID;
+  if (n < 0 || (n > 0 && !octave)) { ctx->set_error("asd_map_put_octaves: invalid argument (keyframe %d, %d octaves)", kf, n); return ASD_ERR_INVALID; }
+  LocalMapState* S = lstate(ctx);
+  int slot;
+  LmSlot* L = find_kf(ctx, S, "asd_map_put_octaves", kf, &slot);
+  if (!L) return ASD_ERR_INVALID;
+  if (n != L->n) { ctx->set_error("asd_map_put_octaves: %d octaves for keyframe %d, whose row has %d entries", n, kf, L->n); return ASD_ERR_INVALID; }
+  for (int i = 0; i < n; ++i)
+    if (octave[i] >= ASD_MAX_LEVELS) { ctx->set_error("asd_map_put_octaves: octave %d at keypoint %d of keyframe %d (levels are 0 .. %d)", (int)octave[i], i, kf, ASD_MAX_LEVELS - 1); return ASD_ERR_INVALID; }
+  (void)hipSetDevice(ctx->cfg.device);
+  if (n > 0) {
+    hipStream_t st = ctx->stream;
+    ASD_HIP_CHECK(ctx, S->up.begin(st, (size_t)n));
+    const size_t o = S->up.add(octave, (size_t)n);
+    ASD_HIP_CHECK(ctx, hipMemcpyAsync(S->d_oct + L->off, S->up.h + o, (size_t)n, hipMemcpyHostToDevice, st));
+    ASD_HIP_CHECK(ctx, hipStreamSynchronize(st));
+  }
+  if (!L->has_oct) { L->has_oct = true; --S->live_without_oct; }
+  return ASD_OK;   // (the search list of the last asd_update_local_map stays: nothing it was built from has changed)
+}
+
+int asd_keyframe_culling(asd_ctx* ctx, asd_kf_culling_args* A) {
+  if (!ctx) return ASD_ERR_INVALID;
+  if (!A || A->n_cand < 0 || (A->n_cand > 0 && (!A->cand || !A->cand_flags || !A->decision || !A->n_mps || !A->n_redundant)) || A->bad_capacity < 0 ||
+      (A->bad_capacity > 0 && !A->bad_rows)) {
+    ctx->set_error("asd_keyframe_culling: invalid argument");
+    return ASD_ERR_INVALID;
+  }
+  if (refuse(ctx, "asd_keyframe_culling")) return ASD_ERR_INVALID;
+  A->n_bad = 0;
+  const int n_cand = A->n_cand;
+  if (n_cand > kMaxCand) { ctx->set_error("asd_keyframe_culling: %d candidates exceed %d", n_cand, kMaxCand); return ASD_ERR_CAPACITY; }
+  LocalMapState* S = lstate(ctx);
+  std::vector<int> cand_slot(n_cand);
+  std::vector<long long> base(n_cand);
+  long long entries = 0;
+  int maxn = 0;
+  {
+    std::vector<int> seen(A->cand, A->cand + n_cand);
+    std::sort(seen.begin(), seen.end());
+    for (int i = 1; i < n_cand; ++i) if (seen[i] == seen[i - 1]) { ctx->set_error("asd_keyframe_culling: keyframe %d occurs twice among the candidates", seen[i]); return ASD_ERR_INVALID; }
+  }
+  for (int i = 0; i < n_cand; ++i) {
+    int slot;
+    const LmSlot* L = find_kf(ctx, S, "asd_keyframe_culling", A->cand[i], &slot);
+    if (!L) return ASD_ERR_INVALID;
+    const bool skip = (A->cand_flags[i] & 1) || A->cand[i] == 0;   // GetGlobalMapFlag(), mnId == 0 (:751-754)
+    cand_slot[i] = skip ? -1 : slot;
+    base[i] = entries;
+    if (!skip) { entries += L->n; maxn = std::max(maxn, L->n); }
+  }
+  if (S->live_without_oct > 0) {
+    for (const auto& kv : S->by_kf)
+      if (!S->slots[kv.second].has_oct) { ctx->set_error("asd_keyframe_culling: keyframe %d has no octaves (asd_map_put_octaves); %d live keyframes have none", kv.first, S->live_without_oct); break; }
+    return ASD_ERR_INVALID;
+  }
+  if (n_cand == 0) return ASD_OK;
+  if (entries > kMaxCullEntries) { ctx->set_error("asd_keyframe_culling: the candidates' rows hold %lld entries, more than one call takes (%lld)", entries, kMaxCullEntries); return ASD_ERR_CAPACITY; }
+  (void)hipSetDevice(ctx->cfg.device);
+  hipStream_t st = ctx->stream;
+  const int n_slots = (int)S->slots.size();
+  const size_t E = ((size_t)entries + 3) / 4 * 4 + 4;   // (a multiple of 4: the counters are stored as int4)
+  int rc;
+  if ((rc = clean_tables(ctx, S)) != ASD_OK) return rc;
+  if ((rc = lm_reserve(ctx, &S->d_head, &S->head_cap, 16, 0, 0, 16)) != ASD_OK) return rc;
+  if ((rc = lm_reserve(ctx, &S->d_culled, &S->culled_cap, (size_t)n_slots + 1, 0, -1, kInitSlots)) != ASD_OK) return rc;
+  if ((rc = lm_reserve(ctx, &S->d_cull, &S->cull_cap, (4 + kLevels) * E + 3 * (size_t)n_cand, 0, -1, 65536)) != ASD_OK) return rc;
+  // pts | the compaction's second list (unused) | counters | gone | bad rows | decision, nMPs, nRedundantObservations
+  int* const d_pts = S->d_cull; int* const d_second = d_pts + E; int* const d_ccnt = d_second + E; int* const d_gone = d_ccnt + kLevels * E;
+  int* const d_bad = d_gone + E; int* const d_out = d_bad + E;
+  if (!S->h_head) ASD_HIP_CHECK(ctx, hipHostMalloc(&S->h_head, 16 * sizeof(int)));
+  ASD_HIP_CHECK(ctx, S->up.begin(st, (size_t)n_cand * 13 + 1024));
+  const size_t o_slot = S->up.add(cand_slot.data(), (size_t)n_cand * sizeof(int)), o_base = S->up.add(base.data(), (size_t)n_cand * sizeof(long long));
+  const size_t o_flag = S->up.add(A->cand_flags, (size_t)n_cand);
+  ASD_HIP_CHECK(ctx, S->up.upload(st));
+  ASD_HIP_CHECK(ctx, hipMemsetAsync(S->d_head, 0, 16 * sizeof(int), st));
+  ASD_HIP_CHECK(ctx, hipMemsetAsync(S->d_culled, 0, ((size_t)n_slots + 1) * sizeof(int), st));
+  S->tables_dirty = true;
+  const unsigned pt_blocks = (unsigned)((entries + 255) / 256);
+  if (entries > 0) {   // the distinct not-bad points of the candidates' rows, in order
+    const int tiles_per_kf = (maxn + kTile - 1) / kTile;
+    const size_t n_tiles = (size_t)tiles_per_kf * n_cand;
+    if ((rc = lm_reserve(ctx, &S->d_tile, &S->tile_cap, 4 * n_tiles, 0, -1, 4096)) != ASD_OK) return rc;
+    LmPointArgs pa{};
+    pa.table = S->d_table; pa.rows = S->d_rows; pa.list_slot = S->up.dev<int>(o_slot); pa.list_base = S->up.dev<long long>(o_base); pa.tiles_per_kf = tiles_per_kf;
+    pa.pbad = S->d_pbad; pa.mark = S->d_mark; pa.claim = S->d_claim;
+    pa.tile_cnt = S->d_tile; pa.tile_off = S->d_tile + 2 * n_tiles;
+    pa.d_local = d_pts; pa.d_search = d_second;   // (not the resident search list: that one stays as it is)
+    pa.h_local = nullptr; pa.cap_local = 0; pa.h_search = nullptr; pa.cap_search = 0;
+    const dim3 grid((unsigned)n_cand, (unsigned)tiles_per_kf);
+    hipLaunchKernelGGL(k_lm_claim, grid, dim3(256), 0, st, pa);
+    ASD_HIP_CHECK(ctx, hipGetLastError());
+    hipLaunchKernelGGL(k_lm_count, grid, dim3(256), 0, st, pa);
+    ASD_HIP_CHECK(ctx, hipGetLastError());
+    hipLaunchKernelGGL(k_lm_tilescan, dim3(1), dim3(256), 0, st, S->d_tile, S->d_tile + 2 * n_tiles, (int)n_tiles, S->d_head);
+    ASD_HIP_CHECK(ctx, hipGetLastError());
+    hipLaunchKernelGGL(k_lm_scatter, grid, dim3(256), 0, st, pa);
+    ASD_HIP_CHECK(ctx, hipGetLastError());
+    hipLaunchKernelGGL(k_cull_index, dim3(pt_blocks), dim3(256), 0, st, d_pts, S->d_head, S->d_mark, d_ccnt, d_gone);
+    ASD_HIP_CHECK(ctx, hipGetLastError());
+    hipLaunchKernelGGL(k_cull_count, dim3((n_slots + 3) / 4), dim3(256), 0, st, S->d_table, n_slots, S->d_rows, S->d_oct, S->d_mark, d_ccnt, kLevels);
+    ASD_HIP_CHECK(ctx, hipGetLastError());
+  }
+  LmCullArgs ca{};
+  ca.table = S->d_table; ca.rows = S->d_rows; ca.oct = S->d_oct; ca.pbad = S->d_pbad; ca.mark = S->d_mark;
+  ca.cand_slot = S->up.dev<int>(o_slot); ca.cand_flags = S->up.dev<uint8_t>(o_flag); ca.n_cand = n_cand;
+  ca.cnt = d_ccnt; ca.gone = d_gone; ca.bad_rows = d_bad; ca.culled = S->d_culled; ca.out = d_out; ca.head = S->d_head;
+  hipLaunchKernelGGL(k_cull_walk, dim3(1), dim3(256), 0, st, ca);
+  ASD_HIP_CHECK(ctx, hipGetLastError());
+  const size_t give_bad = std::min((size_t)A->bad_capacity, (size_t)entries);
+  ASD_HIP_CHECK(ctx, S->down.begin(st, (3 * (size_t)n_cand + give_bad) * sizeof(int) + 1024));
+  const size_t o_out = S->down.reserve(3 * (size_t)n_cand * sizeof(int)), o_bad = S->down.reserve(give_bad * sizeof(int));
+  int* const head = S->h_head;
+  ASD_HIP_CHECK(ctx, hipMemcpyAsync(head, S->d_head, 16 * sizeof(int), hipMemcpyDeviceToHost, st));
+  ASD_HIP_CHECK(ctx, hipMemcpyAsync(S->down.h + o_out, d_out, 3 * (size_t)n_cand * sizeof(int), hipMemcpyDeviceToHost, st));
+  if (give_bad) ASD_HIP_CHECK(ctx, hipMemcpyAsync(S->down.h + o_bad, d_bad, give_bad * sizeof(int), hipMemcpyDeviceToHost, st));
+  ASD_HIP_CHECK(ctx, hipStreamSynchronize(st));
+  const int n_bad = head[10];
+  const int* out = S->down.host<int>(o_out);
+  bool any_culled = false;
+  for (int i = 0; i < n_cand; ++i) any_culled = any_culled || out[i] == 1;
+  const bool fits = n_bad <= A->bad_capacity;
+  const bool change = fits && A->apply && any_culled;
+  if (change) {
+    hipLaunchKernelGGL(k_cull_apply, dim3((n_slots + 3) / 4), dim3(256), 0, st, S->d_table, n_slots, S->d_rows, S->d_mark, d_gone, S->d_culled);
+    ASD_HIP_CHECK(ctx, hipGetLastError());
+  }
+  if (entries > 0) {
+    hipLaunchKernelGGL(k_cull_finish, dim3(pt_blocks), dim3(256), 0, st, d_pts, S->d_head, S->d_mark, d_gone, S->d_pbad, change ? 1 : 0);
+    ASD_HIP_CHECK(ctx, hipGetLastError());
+  }
+  ASD_HIP_CHECK(ctx, hipStreamSynchronize(st));
+  S->tables_dirty = false;
+  A->n_bad = n_bad;
+  if (!fits) {
+    ctx->set_error("asd_keyframe_culling: %d points turn bad, bad_capacity is %d", n_bad, A->bad_capacity);
+    return ASD_ERR_CAPACITY;
+  }
+  for (int i = 0; i < n_cand; ++i) { A->decision[i] = (uint8_t)out[i]; A->n_mps[i] = out[n_cand + i]; A->n_redundant[i] = out[2 * n_cand + i]; }
+  if (n_bad) memcpy(A->bad_rows, S->down.h + o_bad, (size_t)n_bad * sizeof(int));
+  if (change) {
+    for (int i = 0; i < n_cand; ++i) if (out[i] == 1) S->slots[cand_slot[i]].bad = true;   // the host mirror of what k_cull_apply wrote
+    ++S->version;
+  }
+  return ASD_OK;
+}
+
+int asd_map_observations(asd_ctx* ctx, int32_t n, const int32_t* rows, int32_t* counts) {
+  if (!ctx) return ASD_ERR_INVALID;
+  if (n < 0 || (n > 0 && (!rows || !counts))) { ctx->set_error("asd_map_observations: invalid argument"); return ASD_ERR_INVALID; }
+  if (refuse(ctx, "asd_map_observations")) return ASD_ERR_INVALID;
+  int max_row = -1;
+  int rc = check_rows(ctx, "asd_map_observations", rows, n, &max_row);
+  if (rc != ASD_OK) return rc;
+  for (int i = 0; i < n; ++i) if (rows[i] < 0) { ctx->set_error("asd_map_observations: bank row %d", rows[i]); return ASD_ERR_INVALID; }
+  if (n == 0) return ASD_OK;
+  (void)hipSetDevice(ctx->cfg.device);
+  LocalMapState* S = lstate(ctx);
+  hipStream_t st = ctx->stream;
+  const int n_slots = (int)S->slots.size();
+  const int row_cap = (int)S->row_cap;   // (at most 2^28)
+  if (row_cap == 0 || n_slots == 0) { for (int i = 0; i < n; ++i) counts[i] = 0; return ASD_OK; }
+  if ((rc = clean_tables(ctx, S)) != ASD_OK) return rc;
+  if ((rc = lm_reserve(ctx, &S->d_cull, &S->cull_cap, 2 * (size_t)n, 0, -1, 65536)) != ASD_OK) return rc;
+  int* const d_ccnt = S->d_cull; int* const d_res = S->d_cull + n;
+  ASD_HIP_CHECK(ctx, S->up.begin(st, (size_t)n * sizeof(int)));
+  const size_t o = S->up.add(rows, (size_t)n * sizeof(int));
+  ASD_HIP_CHECK(ctx, S->up.upload(st));
+  ASD_HIP_CHECK(ctx, S->down.begin(st, (size_t)n * sizeof(int)));
+  const size_t o_res = S->down.reserve((size_t)n * sizeof(int));
+  ASD_HIP_CHECK(ctx, hipMemsetAsync(d_ccnt, 0, (size_t)n * sizeof(int), st));
+  S->tables_dirty = true;
+  const dim3 grid((n + 255) / 256);
+  hipLaunchKernelGGL(k_obs_mark, grid, dim3(256), 0, st, S->up.dev<int>(o), n, row_cap, S->d_mark);
+  ASD_HIP_CHECK(ctx, hipGetLastError());
+  hipLaunchKernelGGL(k_cull_count, dim3((n_slots + 3) / 4), dim3(256), 0, st, S->d_table, n_slots, S->d_rows, S->d_oct, S->d_mark, d_ccnt, 1);
+  ASD_HIP_CHECK(ctx, hipGetLastError());
+  hipLaunchKernelGGL(k_obs_gather, grid, dim3(256), 0, st, S->up.dev<int>(o), n, row_cap, S->d_mark, d_ccnt, d_res);
+  ASD_HIP_CHECK(ctx, hipGetLastError());
+  hipLaunchKernelGGL(k_obs_unmark, grid, dim3(256), 0, st, S->up.dev<int>(o), n, row_cap, S->d_mark);
+  ASD_HIP_CHECK(ctx, hipGetLastError());
+  ASD_HIP_CHECK(ctx, hipMemcpyAsync(S->down.h + o_res, d_res, (size_t)n * sizeof(int), hipMemcpyDeviceToHost, st));
+  ASD_HIP_CHECK(ctx, hipStreamSynchronize(st));
+  S->tables_dirty = false;
+  memcpy(counts, S->down.h + o_res, (size_t)n * sizeof(int));
   return ASD_OK;
 }
 

@@ -26,6 +26,7 @@
 #include <vector>
 
 #include "../../include/asd_slam.h"
+#include "map_point_culling.hpp"
 
 namespace asd {
 
@@ -891,6 +892,46 @@ struct LocalMapping {
   static int LocalBundleAdjustmentSubmit(Context& c, asd_ba_problem* problem, asd_ba_result* result) { return asd_local_ba_submit(c.get(), problem, result); }
   static int LocalBundleAdjustmentWait(Context& c) { return asd_local_ba_wait(c.get()); }
   static bool Busy(Context& c) { return asd_local_ba_poll(c.get()) == 1; }
+
+  // void LocalMapping::KeyFrameCulling() (LocalMapping.cc:739-809, monocular) over the context's observation table, whose rows carry their
+  // keypoints' octaves (asd_map_put_octaves).  cand = mpCurrentKeyFrame->GetVectorCovisibleKeyFrames() as ids in its order; flags per
+  // candidate: bit0 = GetGlobalMapFlag(), bit1 = mbNotErase.  The in-loop SetBadFlag's effect on the observations is part of the call
+  // (include/asd_slam.h); with apply the table is left as the cull leaves the map.  INTEGRATION.md lists what stays the caller's.
+  struct Culling {
+    int rc = ASD_OK;
+    std::vector<uint8_t> decision;                       // 0 kept, 1 SetBadFlag took effect, 2 mbToBeErased only, 3 skipped
+    std::vector<int32_t> nMPs, nRedundantObservations;
+    std::vector<int32_t> badPoints;                      // bank rows of the points EraseObservation turned bad, in the order it happened
+  };
+  static Culling KeyFrameCulling(Context& c, const std::vector<int32_t>& cand, const std::vector<uint8_t>& flags, bool apply) {
+    Culling R;
+    if (flags.size() != cand.size()) { R.rc = ASD_ERR_INVALID; return R; }
+    const size_t n = cand.size();
+    R.decision.assign(n, 0); R.nMPs.assign(n, 0); R.nRedundantObservations.assign(n, 0);
+    R.badPoints.resize(256);
+    asd_kf_culling_args a{};
+    a.n_cand = (int32_t)n; a.cand = cand.data(); a.cand_flags = flags.data(); a.apply = apply ? 1 : 0;
+    a.decision = R.decision.data(); a.n_mps = R.nMPs.data(); a.n_redundant = R.nRedundantObservations.data();
+    for (int attempt = 0; attempt < 2; ++attempt) {
+      a.bad_capacity = (int32_t)R.badPoints.size(); a.bad_rows = R.badPoints.data();
+      R.rc = asd_keyframe_culling(c.get(), &a);
+      if (R.rc != ASD_ERR_CAPACITY || a.n_bad <= a.bad_capacity) break;   // (a capacity answer of another kind carries no count)
+      R.badPoints.resize(a.n_bad);
+    }
+    R.badPoints.resize(R.rc == ASD_OK ? a.n_bad : 0);
+    return R;
+  }
+
+  // void LocalMapping::MapPointCulling() (:261-297) over mlpRecentAddedMapPoints as flat records, Observations() from the table.  Returns
+  // which records to SetBadFlag (the caller does that to its MapPoint and, for the table, asd_map_point_bad and the entries' asd_map_set) and
+  // the surviving list.
+  static MapPointCullingResult MapPointCulling(Context& c, const std::vector<RecentMapPoint>& recent, int32_t nCurrentKFid) {
+    std::vector<int32_t> rows(recent.size()), obs(recent.size());
+    for (size_t i = 0; i < recent.size(); ++i) rows[i] = recent[i].row;
+    const int rc = asd_map_observations(c.get(), (int32_t)rows.size(), rows.data(), obs.data());
+    if (rc != ASD_OK) { MapPointCullingResult R; R.rc = rc; R.recent = recent; return R; }
+    return MapPointCullingRule(recent, obs, nCurrentKFid, 2);
+  }
 };
 
 // DBoW2::BowVector as asd_compute_bow hands it out: word ids ascending, one value per word

@@ -1389,6 +1389,48 @@ int asd_track_local_points_map(asd_ctx* ctx, int32_t slot_cur, const float* Tcw,
  * keyframe itself is excluded (:561), bad keyframes are not (as in the reference).  Keyframes with a count > 0 come back in ascending id;
  * ASD_ERR_CAPACITY with *n = the count needed when `capacity` is too small. */
 int asd_map_shared_counts(asd_ctx* ctx, int32_t kf, int32_t capacity, int32_t* kfs, int32_t* counts, int32_t* n);
+
+/* ---- LocalMapping::KeyFrameCulling and MapPoint::Observations() over the table ----
+ * asd_map_put_octaves sets mvKeysUn[idx].octave for every keypoint of a keyframe that is in the table: n must equal the row's length and
+ * every value must be < ASD_MAX_LEVELS, anything else is ASD_ERR_INVALID.  The octaves are the keypoints', not the point list's: they
+ * follow the row through growth and compaction, an asd_map_put that replaces the row with the same n keeps them, one with another n drops
+ * them, asd_map_erase and asd_map_clear drop them, asd_map_set does not touch them.  Setting them does not invalidate the search list of
+ * asd_track_local_points_map. */
+int asd_map_put_octaves(asd_ctx* ctx, int32_t kf, int32_t n, const uint8_t* octave);
+
+/* LocalMapping::KeyFrameCulling (LocalMapping.cc:739-809), the monocular path, stated literally -- including what pKF->SetBadFlag() inside
+ * the loop does to the observations the NEXT candidates are judged by (KeyFrame.cc:739-741 -> MapPoint::EraseObservation, MapPoint.cc:
+ * 119-142 -> MapPoint::SetBadFlag, :180-197).  Per candidate, in list order:
+ *   skipped (decision 3, counts 0) when bit0 of its flag is set or its id is 0 (:751-754);
+ *   for every entry idx whose point r is >= 0 and not bad: nMPs++; if Observations(r) > 3 and at least 3 OTHER keyframes observe r at an
+ *   octave <= octave(kf, idx) + 1: nRedundantObservations++.  Observations(r) = the number of table entries that name r;
+ *   culled when nRedundantObservations > 0.9 nMPs (decided as 10 nR > 9 nM, the same for every row the table takes; nMPs == 0 never culls);
+ *   a culled candidate with bit1 (mbNotErase) gets decision 2 and changes nothing (KeyFrame.cc:729-733);
+ *   otherwise (decision 1) its observations leave the counts before the next candidate is examined, in ascending keypoint index; a point
+ *   whose count thereby reaches <= 2 becomes bad at that moment, is appended to bad_rows, loses all its observations and counts in no later
+ *   candidate's nMPs.  (A point that is flagged bad and still has entries -- a state the reference does not have -- counts nowhere, is not
+ *   reported again, and keeps its entries in other rows.)
+ * apply = 1 leaves the table as these calls would: for every decision-1 keyframe asd_map_kf_bad(kf, 1) and every entry of its row -1; for
+ * every row of bad_rows asd_map_point_bad(row, 1) and its remaining entries in all other rows -1.  The keyframe keeps its slot, links and
+ * octaves (asd_map_erase stays the caller's step).  When that changed anything the search list of asd_track_local_points_map is invalid.
+ * apply = 0 changes nothing.
+ * ASD_ERR_INVALID: a candidate that is not in the table or occurs twice; any live keyframe without octaves (asd_last_error names one).
+ * ASD_ERR_CAPACITY: more than 4096 candidates; candidates' rows of more than 2^26 entries together; bad_capacity too small -- n_bad then
+ * holds the count needed, the table is untouched whatever apply says, and the call may be repeated.  Results are identical from run to run. */
+typedef struct asd_kf_culling_args {
+  int32_t n_cand; const int32_t* cand;      /* GetVectorCovisibleKeyFrames() as ids, in its order                    */
+  const uint8_t* cand_flags;                /* per candidate: bit0 = GetGlobalMapFlag() (:751), bit1 = mbNotErase    */
+  int32_t apply;                            /* 0: decisions only, the table is left as it was                        */
+  uint8_t* decision;                        /* [n_cand] 0 kept, 1 SetBadFlag took effect, 2 mbToBeErased only, 3 skipped (:751-754) */
+  int32_t* n_mps; int32_t* n_redundant;     /* [n_cand] nMPs, nRedundantObservations as the reference had them at the test (0 when skipped) */
+  int32_t bad_capacity; int32_t* bad_rows; int32_t n_bad;  /* points that EraseObservation turned bad, in the order it happened */
+} asd_kf_culling_args;
+int asd_keyframe_culling(asd_ctx* ctx, asd_kf_culling_args* args);
+
+/* MapPoint::Observations() (nObs, MapPoint.cc:110-117) for n bank rows: counts[i] = the number of table entries that name rows[i].  The
+ * bad byte is not consulted; a row never named gives 0.  Changes neither the table nor the search list. */
+int asd_map_observations(asd_ctx* ctx, int32_t n, const int32_t* rows, int32_t* counts);
+
 /* Test aid: out = {live keyframes, live entries, slot capacity, arena capacity, row-table capacity, growths of the slot table, of the arena,
  * of the row tables}. */
 int32_t asd_debug_map(asd_ctx* ctx, int64_t out[8]);
