@@ -15,18 +15,24 @@
 // LocalBundleAdjustment: g2o walks pointer graphs and hash maps edge by edge; here the problem is
 // flat arrays in HBM and every step is a data-parallel kernel with FIXED reduction shapes (no
 // float atomics), so results are bit-reproducible run to run:
-//   k_ba_error      edge-parallel residual + robust cost            -> per-block partial sums
-//   k_ba_linearize  edge-parallel Jacobians, Huber weight, per-edge blocks (Hpp/Hll/Hpl parts)
-//   k_ba_reduce_*   per-pose / per-landmark segmented sums (CSR built once per round on the host)
-//   (k_ba_edge_y, rounds 1-4: Y = B*Dinv, c = B*db per edge; since round 5 formed inside k_ba_schur)
-//   k_ba_schur      one workgroup per upper 6x6 block: Hpp + lambda I - sum_l (B Dinv) B^T  (dense)
-//   k_ba_chol       blocked Cholesky + triangular solves in one workgroup
+//   k_ba_struct_*   the active structure (h-indices, landmark CSR, per-pose edge lists, Schur pair lists) built on the device; problems
+//                   they do not take, and BundleAdjustment, get the same tables from the host (ba_structure.h)
+//   k_ba_linearize  edge-parallel Jacobians, Huber weight, per-edge blocks (Bk, Hc, Hl)
+//   k_ba_reduce     per-pose / per-landmark segmented sums over the structure's lists -> Hpp, Hll; the diagonal's maximum
+//   k_ba_schur      one workgroup per upper 6x6 block: Hpp + lambda I - sum_l (B Dinv) B^T, Dinv = (Hll + lambda I)^-1 formed per pair;
+//                   further workgroups for the right-hand side
+//   k_ba_solve_lds / k_ba_chol_lds / k_ba_chol   the dense solve by size (ba_dense_form); BundleAdjustment's tiled form is gba.hip's
 //   k_ba_step       landmark-parallel xl = Dinv (bl - B^T xp) + pose-parallel oplus into the TRIAL buffer, gain-ratio partials
-// The Levenberg accept/reject logic (optimization_algorithm_levenberg.cpp:61-189) runs ON THE DEVICE since round 3: the scalars
-// live in LmState, a one-thread kernel (k_ba_lm_control) behind every trial takes the decision the host used to take after a
-// synchronisation, and every other kernel reads lambda / "is this step needed" from that state -- a step whose answer is no
-// exits at once.  The host enqueues whole iterations ("blocks" = linearise group + trial group + control) ahead and
-// synchronises once per chunk of blocks instead of once per trial.
+//   k_ba_error      edge-parallel residual + robust cost -> per-block partial sums; its last workgroup runs the Levenberg control
+//   k_ba_chi2_stored, k_ba_edge_report   the round's chi2 from the stored errors; per-edge chi2, depth sign and the outlier gating
+// The Levenberg accept/reject logic (optimization_algorithm_levenberg.cpp:61-189) runs ON THE DEVICE: the scalars live in LmState,
+// the workgroup of k_ba_error that finishes last (lm_begin_body / lm_control_body) takes the decision the host used to take after
+// a synchronisation, and every other kernel reads lambda / "is this step needed" from that state -- a step whose answer is no
+// exits at once.  The host enqueues whole trials ("blocks" = linearise group + trial group + control) ahead and synchronises
+// once per chunk of blocks instead of once per trial.
+//
+// Host side: local_ba_impl and gba_impl share one setup (ba_setup_upload, ba_setup_bind, ba_bind_structure), one trial enqueue
+// (ba_enqueue_trial) and the round-close helpers; each keeps its own round loop (chunking and stop policy differ).
 #include <algorithm>
 #include <chrono>
 #include <cmath>
@@ -38,6 +44,7 @@
 #include <condition_variable>
 
 #include "ctx.h"
+#include "ba_structure.h"
 #include "gba.h"
 #include "resolve2.h"
 #include "se3.h"
@@ -977,9 +984,7 @@ struct BaDev {
   double* Hpp;  // [nPf][27]
   double* HppPart;  // [nPf][kPoseSplit][27] partial sums of k_ba_reduce_pose
   double* Hll;  // [nLa][9]
-  double* Dinv; // [nLa][6]
-  double* db;   // [nLa][3]
-  double* x;    // [6 nPf + 3 nLa]
+  double* x;   // [6 nPf + 3 nLa]
   // dense system
   double* A;    // [n][n]
   double* Apack; // the same system as the solve kernel keeps it: lower triangle by 6x6 blocks, block (I, J <= I) at (I (I + 1) / 2 + J) * 36
@@ -1931,13 +1936,23 @@ struct DevBuf {
   }
   template <typename T> T* as() { return reinterpret_cast<T*>(p); }
 };
-
+// a pinned host allocation of at least `need` elements, grown to `want`.  Pointer and capacity are cleared BEFORE the allocation:
+// when it fails, nothing dangles for the next call to write through or for ba_free to free a second time
+template <typename T>
+int pinned_ensure(asd_ctx* ctx, T*& p, size_t& cap, size_t need, size_t want) {
+  if (cap >= need) return ASD_OK;
+  if (p) (void)hipHostFree(p);
+  p = nullptr; cap = 0;
+  ASD_HIP_CHECK(ctx, hipHostMalloc(reinterpret_cast<void**>(&p), want * sizeof(T)));
+  cap = want;
+  return ASD_OK;
+}
 
 // ---------------------------------------------------------------- the active structure, built on the device
 // g2o's initializeOptimization + buildStructure (sparse_optimizer.cpp:206-267, 166-190; block_solver.hpp:117-300) as this solver
 // keeps it: h-indices of the free poses / active landmarks, the edges grouped by landmark and ordered by pose inside a landmark,
 // every free pose's edge list, and per upper block (i <= j) of the reduced system the list of edge pairs (a, b) that meet in it.
-// The host loop that made these tables (kept below: ASD_BA_STRUCT=host, and for more than 32 free poses) took 0.35-0.47 ms of the
+// The host loop that made these tables (kept in ba_structure.h: ASD_BA_STRUCT=host, and for more than 32 free poses) took 0.35-0.47 ms of the
 // 2.5 ms LocalBA with the device idle; the same tables come out of four small launches.  Every list is in the order the host
 // loop produces (landmark, then position inside the landmark), so the sums the solver forms over them are the same sums.
 struct BaStructDev {
@@ -2162,9 +2177,7 @@ struct BaState {
   DevBuf out1, Apack, sblk;   // sblk: the round's structure arrays in one block (uploaded from the pinned h_sblk)
   char* h_sblk = nullptr;
   size_t h_sblk_cap = 0;
-  DevBuf pose, pose_bak, pts, pts_bak, e_pt, e_ps, obs, info, err, act, pose_h, pt_h, pose_of_h, pt_of_h, pt_start,
-      ps_start, ps_edges, Bk, Hc, Hl, Yk, ck, Hpp, Hll, Dinv, db, x, A, bs, misc, partial, blk_i, blk_j, pair_start,
-      pairs, chi2, dpos;
+  DevBuf pose, pose_bak, pts, pts_bak, e_pt, e_ps, obs, info, err, Bk, Hc, Hl, Hpp, Hll, x, A, bs, misc, partial, chi2, dpos;
   DevBuf po_Xw, po_obs, po_info, po_err, po_level, po_outlier, po_pose;
   DevBuf pc_n;   // fused chains: edge count made on the device
   double* h_partial = nullptr;  // pinned
@@ -2225,10 +2238,9 @@ void ba_free(asd_ctx* ctx) {
     delete ln;
     s->lane = nullptr;
   }
-  DevBuf* all[] = {&s->pose, &s->pose_bak, &s->pts, &s->pts_bak, &s->e_pt, &s->e_ps, &s->obs, &s->info, &s->err, &s->act,
-                   &s->pose_h, &s->pt_h, &s->pose_of_h, &s->pt_of_h, &s->pt_start, &s->ps_start, &s->ps_edges, &s->Bk,
-                   &s->Hc, &s->Hl, &s->Yk, &s->ck, &s->Hpp, &s->Hll, &s->Dinv, &s->db, &s->x, &s->A, &s->bs, &s->misc, &s->lm, &s->lvl, &s->HppPart, &s->out1, &s->Apack, &s->sblk,
-                   &s->partial, &s->blk_i, &s->blk_j, &s->pair_start, &s->pairs, &s->chi2, &s->dpos, &s->po_Xw,
+  DevBuf* all[] = {&s->pose, &s->pose_bak, &s->pts, &s->pts_bak, &s->e_pt, &s->e_ps, &s->obs, &s->info, &s->err, &s->Bk,
+                   &s->Hc, &s->Hl, &s->Hpp, &s->Hll, &s->x, &s->A, &s->bs, &s->misc, &s->lm, &s->lvl, &s->HppPart, &s->out1, &s->Apack, &s->sblk,
+                   &s->fixed_d, &s->partial, &s->chi2, &s->dpos, &s->po_Xw,
                    &s->po_obs, &s->po_info, &s->po_err, &s->po_level, &s->po_outlier, &s->po_pose, &s->pc_n};
   for (DevBuf* b : all) if (b->p) (void)hipFree(b->p);
   if (s->h_partial) (void)hipHostFree(s->h_partial);
@@ -2351,12 +2363,7 @@ int asd_pose_optimize(asd_ctx* ctx, double* pose7, int32_t n, const double* Xw, 
   if ((rc = s->po_Xw.ensure(ctx, in_bytes)) || (rc = s->po_err.ensure(ctx, (size_t)n * 64)) ||
       (rc = s->po_level.ensure(ctx, (size_t)2 * n)) || (rc = s->po_pose.ensure(ctx, io_bytes)))
     return rc;
-  if (s->h_po_cap < in_bytes + io_bytes) {
-    if (s->h_po) (void)hipHostFree(s->h_po);
-    s->h_po_cap = 0;
-    ASD_HIP_CHECK(ctx, hipHostMalloc(&s->h_po, 2 * (in_bytes + io_bytes)));
-    s->h_po_cap = 2 * (in_bytes + io_bytes);
-  }
+  if ((rc = pinned_ensure(ctx, s->h_po, s->h_po_cap, in_bytes + io_bytes, 2 * (in_bytes + io_bytes))) != ASD_OK) return rc;
   static const bool timing = getenv("ASD_TIMING") != nullptr;
   static double tacc[2][4]; static long tcalls[2];
   auto now = [] { return std::chrono::steady_clock::now(); };
@@ -2454,6 +2461,146 @@ int local_ba_check(asd_ctx* ctx, const asd_ba_problem* pr, const asd_ba_result* 
   return ASD_OK;
 }
 
+// ---------------------------------------------------------------- host side shared by LocalBA and BundleAdjustment
+// What the two size differently: LocalBA by the problem (P, L and its free poses, known before the structure is), BundleAdjustment by
+// the structure's counts (nPf, nLa).
+struct BaSizes {
+  size_t n_pose, n_lm;   // rows of Hpp / HppPart / bs and of Hll; x holds 6 n_pose + 3 n_lm
+  size_t n_dense;        // pose blocks of the dense system A
+  bool apack;            // the packed form of A beside it (the LDS solver forms)
+  size_t misc_bytes, npartial;
+};
+
+// the poses as the kernels keep them, normalised like SE3Quat's constructor does
+std::vector<Pose7> poses_pack(const double* poses, int P) {
+  std::vector<Pose7> hp(P);
+  for (int p = 0; p < P; ++p) {
+    const double* q = poses + 7 * p;
+    hp[p] = Pose7{q[0], q[1], q[2], q[3], q[4], q[5], q[6]};
+    quat_normalize(hp[p].qx, hp[p].qy, hp[p].qz, hp[p].qw);
+  }
+  return hp;
+}
+void poses_unpack(const std::vector<Pose7>& hp, double* poses) {
+  for (size_t p = 0; p < hp.size(); ++p) {
+    double* q = poses + 7 * p;
+    q[0] = hp[p].qx; q[1] = hp[p].qy; q[2] = hp[p].qz; q[3] = hp[p].qw; q[4] = hp[p].tx; q[5] = hp[p].ty; q[6] = hp[p].tz;
+  }
+}
+
+#define ENS(buf, bytes) if ((rc = s->buf.ensure(ctx, (bytes))) != ASD_OK) return rc
+// The buffers both solvers use, then the problem on the device.  Both estimate buffers start as the input: vertices no trial writes
+// -- fixed poses, landmarks without an active edge -- must read the same in both.  (asd_ba_problem and asd_gba_problem name the
+// problem's arrays alike.)
+template <class Problem>
+int ba_setup_upload(asd_ctx* ctx, BaState* s, const Problem* pr, const std::vector<Pose7>& hp, const BaSizes& z, hipStream_t st) {
+  const size_t P = pr->n_poses, L = pr->n_points, E = pr->n_edges;
+  int rc;
+  ENS(pose, P * sizeof(Pose7)); ENS(pose_bak, P * sizeof(Pose7)); ENS(pts, L * 24); ENS(pts_bak, L * 24);
+  ENS(e_pt, E * 4); ENS(e_ps, E * 4); ENS(obs, E * 16); ENS(info, E * 8); ENS(err, E * 16); ENS(lvl, E);
+  ENS(Bk, E * 18 * 8); ENS(Hc, E * 27 * 8); ENS(Hl, E * 9 * 8); ENS(chi2, E * 8); ENS(dpos, E);
+  ENS(Hpp, z.n_pose * 27 * 8); ENS(HppPart, z.n_pose * kPoseSplit * 27 * 8); ENS(Hll, z.n_lm * 9 * 8); ENS(x, (6 * z.n_pose + 3 * z.n_lm) * 8);
+  ENS(bs, 6 * z.n_pose * 8); ENS(A, 36 * z.n_dense * z.n_dense * 8);
+  if (z.apack) ENS(Apack, 18 * z.n_dense * (z.n_dense + 1) * 8);
+  ENS(misc, z.misc_bytes); ENS(partial, z.npartial * 8);
+  if ((rc = pinned_ensure(ctx, s->h_partial, s->h_partial_cap, z.npartial, z.npartial * 2)) != ASD_OK) return rc;
+  if (!s->h_lm) ASD_HIP_CHECK(ctx, hipHostMalloc(reinterpret_cast<void**>(&s->h_lm), sizeof(LmState)));
+  ENS(lm, sizeof(LmState) + 64 + sizeof(LmLog) * kLmLogCap + sizeof(int) * (P + 2));
+  ASD_HIP_CHECK(ctx, hipMemcpyAsync(s->pose.p, hp.data(), P * sizeof(Pose7), hipMemcpyHostToDevice, st));
+  ASD_HIP_CHECK(ctx, hipMemcpyAsync(s->pts.p, pr->points, L * 24, hipMemcpyHostToDevice, st));
+  ASD_HIP_CHECK(ctx, hipMemcpyAsync(s->pose_bak.p, s->pose.p, P * sizeof(Pose7), hipMemcpyDeviceToDevice, st));
+  ASD_HIP_CHECK(ctx, hipMemcpyAsync(s->pts_bak.p, s->pts.p, L * 24, hipMemcpyDeviceToDevice, st));
+  ASD_HIP_CHECK(ctx, hipMemsetAsync(s->lm.p, 0, sizeof(LmState), st));   // lm->cur = 0
+  ASD_HIP_CHECK(ctx, hipMemcpyAsync(s->e_pt.p, pr->e_point, E * 4, hipMemcpyHostToDevice, st));
+  ASD_HIP_CHECK(ctx, hipMemcpyAsync(s->e_ps.p, pr->e_pose, E * 4, hipMemcpyHostToDevice, st));
+  ASD_HIP_CHECK(ctx, hipMemcpyAsync(s->obs.p, pr->e_obs, E * 16, hipMemcpyHostToDevice, st));
+  ASD_HIP_CHECK(ctx, hipMemcpyAsync(s->info.p, pr->e_info, E * 8, hipMemcpyHostToDevice, st));
+  ASD_HIP_CHECK(ctx, hipMemsetAsync(s->err.p, 0, E * 16, st));
+  ASD_HIP_CHECK(ctx, hipMemsetAsync(s->lvl.p, 0, E, st));   // every edge at level 0
+  return ASD_OK;
+}
+
+// The common part of the kernels' argument block, and the workgroup tickets cleared on the stream (a call of its own behind the upload:
+// each caller has a copy and an event record of its own between the two).  The Levenberg scalars and the per-workgroup partial sums they
+// are made of stay on the device; the host sees a pinned mirror of the state, written after every trial, and reads it once per chunk
+template <class Problem>
+int ba_setup_bind(asd_ctx* ctx, BaState* s, const Problem* pr, const BaSizes& z, hipStream_t st, BaDev& d) {
+  d = BaDev{};
+  d.P = pr->n_poses; d.L = pr->n_points; d.E = pr->n_edges;
+  d.pose[0] = s->pose.as<Pose7>(); d.pose[1] = s->pose_bak.as<Pose7>();
+  d.pts[0] = s->pts.as<double>(); d.pts[1] = s->pts_bak.as<double>();
+  d.e_pt = s->e_pt.as<int>(); d.e_ps = s->e_ps.as<int>(); d.obs = s->obs.as<double>(); d.info = s->info.as<double>();
+  d.err = s->err.as<double>(); d.lvl = s->lvl.as<uint8_t>(); d.HppPart = s->HppPart.as<double>();
+  d.fx = pr->K[0]; d.fy = pr->K[1]; d.cx = pr->K[2]; d.cy = pr->K[3];
+  d.Bk = s->Bk.as<double>(); d.Hc = s->Hc.as<double>(); d.Hl = s->Hl.as<double>(); d.Hpp = s->Hpp.as<double>(); d.Hll = s->Hll.as<double>();
+  d.x = s->x.as<double>(); d.A = s->A.as<double>(); d.Apack = z.apack ? s->Apack.as<double>() : nullptr; d.bs = s->bs.as<double>();
+  d.lm = s->lm.as<LmState>();
+  d.lm_host = s->h_lm;
+  d.lm_log = reinterpret_cast<LmLog*>(s->lm.as<char>() + sizeof(LmState) + 64 - (sizeof(LmState) % 8));
+  d.partial = s->partial.as<double>();
+  d.tickets = reinterpret_cast<int*>(reinterpret_cast<char*>(d.lm_log) + sizeof(LmLog) * kLmLogCap);
+  ASD_HIP_CHECK(ctx, hipMemsetAsync(d.tickets, 0, sizeof(int) * ((size_t)d.P + 2), st));
+  return ASD_OK;
+}
+#undef ENS
+
+// the structure's tables at their places in the device block: the layout of a host-built structure, or the device-built path's upper bounds
+void ba_bind_structure(BaDev& d, SchurBlocks& sb, const char* base, const BaStructLayout& lay) {
+  auto tab = [&](size_t o) { return reinterpret_cast<const int*>(base + o); };
+  d.act = tab(lay.act); d.pose_h = tab(lay.pose_h); d.pt_h = tab(lay.pt_h); d.pose_of_h = tab(lay.pose_of_h); d.pt_of_h = tab(lay.pt_of_h);
+  d.pt_start = tab(lay.pt_start); d.ps_start = tab(lay.ps_start); d.ps_edges = tab(lay.ps_edges); d.ps_h = tab(lay.ps_h);
+  sb = SchurBlocks{tab(lay.blk_i), tab(lay.blk_j), tab(lay.pair_start), reinterpret_cast<const int2*>(base + lay.pairs), tab(lay.pair_h)};
+}
+
+// A host-built structure (ba_structure.h) written into the pinned block; the caller enqueues the block's one upload.  (Eleven copies
+// out of pageable vectors cost ~0.2 ms: the per-pose lists and the pair lists -- the largest -- are written straight into it.)
+int ba_structure_stage(asd_ctx* ctx, BaState* s, const BaStructure& hs, const BaStructLayout& lay) {
+  int rc;
+  if ((rc = s->sblk.ensure(ctx, lay.bytes)) != ASD_OK) return rc;
+  if ((rc = pinned_ensure(ctx, s->h_sblk, s->h_sblk_cap, lay.bytes, lay.bytes + lay.bytes / 4)) != ASD_OK) return rc;
+  hs.fill(s->h_sblk, lay);
+  return ASD_OK;
+}
+
+// One "block" = one Levenberg trial as the device sees it: [linearise group -- runs only when the state says a new iteration starts]
+// [solve: Schur complement, dense solve, back-substitution, pose update] [errors at the trial estimate + the control in k_ba_error's last
+// workgroup: accept / reject (= flip the estimate buffers or not), next lambda, end of iteration / round].  Blocks behind the round's
+// end are no-ops.  form: 0-2 = ba_dense_form, 3 = gba.hip's tiled solve; without all_blocks the Schur pass has workgroups only for
+// the blocks with pairs and the rest of A is cleared in front of it.
+struct BaTrial { int form; bool all_blocks; int nblk; SchurBlocks sb; int robust; };
+int ba_enqueue_trial(asd_ctx* ctx, hipStream_t st, const BaDev& d, const BaTrial& t) {
+  const int n = 6 * d.nPf;
+  hipLaunchKernelGGL(k_ba_linearize, dim3(d.gE), dim3(256), 0, st, d, t.robust);
+  hipLaunchKernelGGL(k_ba_reduce, dim3(d.nPf * kPoseSplit + d.gL), dim3(256), 0, st, d);
+  if (d.nPf > 0) {
+    int rc;
+    if (!t.all_blocks && (rc = gba_clear_enqueue(ctx, st, d.A, n, &d.lm->done)) != ASD_OK) return rc;
+    hipLaunchKernelGGL(k_ba_schur, dim3(t.nblk + d.nPf), dim3(kSchurThreads), 0, st, d, t.sb, t.nblk);
+    if (t.form == 3) rc = gba_solve_enqueue(ctx, st, d.A, d.bs, d.x, n, &d.lm->done, &d.lm->chol_ok, !ctx->gba_update_fma);
+    else rc = ba_dense_enqueue(ctx, st, t.form, d.Apack, d.A, d.bs, d.x, n, d.lm);
+    if (rc != ASD_OK) return rc;
+  }
+  hipLaunchKernelGGL(k_ba_step, dim3(d.gL + d.gP), dim3(256), 0, st, d);
+  hipLaunchKernelGGL(k_ba_error, dim3(d.gE), dim3(256), 0, st, d, t.robust, 0, 0);
+  ASD_HIP_CHECK(ctx, hipGetLastError());
+  return ASD_OK;
+}
+
+// ASD_BA_DEBUG: the device's record of every trial, one line each ("[tag] trial ..." + tail)
+int ba_debug_trials(asd_ctx* ctx, const BaDev& d, int trials, const char* tag, const char* tail) {
+  std::vector<LmLog> lg(kLmLogCap);
+  ASD_HIP_CHECK(ctx, hipMemcpy(lg.data(), d.lm_log, sizeof(LmLog) * kLmLogCap, hipMemcpyDeviceToHost));
+  for (int q = 0; q < std::min(trials, kLmLogCap); ++q)
+    fprintf(stderr, "[%s] trial %d lambda=%.6e cur=%.9e temp=%.9e scale=%.6e%s\n", tag, q, lg[q].lambda, lg[q].cur, lg[q].temp, lg[q].scale, tail);
+  return ASD_OK;
+}
+// activeRobustChi2() as k_ba_chi2_stored left it in pinned memory: the workgroups' sums in index order
+double ba_chi2_sum(const BaState* s, int gE) {
+  double sum = 0;
+  for (int i = 0; i < gE; ++i) sum += s->h_partial[i];
+  return sum;
+}
+
 // the whole LocalBundleAdjustment on stream `st` (the context's stream for asd_local_ba, the lane's for asd_local_ba_submit);
 // e0 / e1 bracket the device work, *ms receives its duration
 int local_ba_impl(asd_ctx* ctx, BaState* s, asd_ba_problem* pr, asd_ba_result* res, hipStream_t st, hipEvent_t ev0, hipEvent_t ev1, float* ms) {
@@ -2461,87 +2608,26 @@ int local_ba_impl(asd_ctx* ctx, BaState* s, asd_ba_problem* pr, asd_ba_result* r
   (void)hipSetDevice(ctx->cfg.device);
   int rc;
   const auto t_enter = std::chrono::steady_clock::now();
-#define ENS(buf, bytes) if ((rc = s->buf.ensure(ctx, (bytes))) != ASD_OK) return rc
   // the reduced pose system has n = 6 nPf rows, nPf <= the number of free poses: A and Apack are sized by that, not by P
-  int F = 0;
-  for (int p = 0; p < P; ++p) F += !pr->fixed[p];
-  F = std::max(F, 1);
-  ENS(pose, (size_t)P * sizeof(Pose7)); ENS(pose_bak, (size_t)P * sizeof(Pose7));
-  ENS(pts, (size_t)L * 24); ENS(pts_bak, (size_t)L * 24);
-  ENS(e_pt, (size_t)E * 4); ENS(e_ps, (size_t)E * 4); ENS(obs, (size_t)E * 16); ENS(info, (size_t)E * 8);
-  ENS(err, (size_t)E * 16); ENS(act, (size_t)E * 4); ENS(pose_h, (size_t)P * 4); ENS(pt_h, (size_t)L * 4);
-  ENS(pose_of_h, (size_t)P * 4); ENS(pt_of_h, (size_t)L * 4); ENS(pt_start, (size_t)(L + 1) * 4);
-  ENS(ps_start, (size_t)(P + 1) * 4); ENS(ps_edges, (size_t)E * 4);
-  ENS(Bk, (size_t)E * 18 * 8); ENS(Hc, (size_t)E * 27 * 8); ENS(Hl, (size_t)E * 9 * 8); ENS(Hpp, (size_t)P * 27 * 8); ENS(Hll, (size_t)L * 9 * 8); ENS(Dinv, (size_t)L * 6 * 8);
-  ENS(db, (size_t)L * 3 * 8); ENS(x, ((size_t)6 * P + 3 * L) * 8); ENS(A, (size_t)36 * F * F * 8); ENS(Apack, (size_t)18 * F * (F + 1) * 8); ENS(bs, (size_t)6 * P * 8);
-  ENS(misc, 64); ENS(chi2, (size_t)E * 8); ENS(dpos, (size_t)E); ENS(lvl, (size_t)E); ENS(out1, (size_t)E); ENS(HppPart, (size_t)P * kPoseSplit * 27 * 8);
+  int n_free = 0;
+  for (int p = 0; p < P; ++p) n_free += !pr->fixed[p];
   const int nblk_e = (E + 255) / 256, nblk_l = (L + 255) / 256, nblk_p = (P + 255) / 256;
-  const size_t npartial = (size_t)nblk_e + nblk_l + nblk_p + 8;
-  ENS(partial, npartial * 8);
-  if (s->h_partial_cap < npartial) {
-    if (s->h_partial) (void)hipHostFree(s->h_partial);
-    ASD_HIP_CHECK(ctx, hipHostMalloc(&s->h_partial, npartial * 2 * 8));
-    s->h_partial_cap = npartial * 2;
-  }
-  if (!s->h_lm) ASD_HIP_CHECK(ctx, hipHostMalloc(reinterpret_cast<void**>(&s->h_lm), sizeof(LmState)));
-  ENS(lm, sizeof(LmState) + 64 + sizeof(LmLog) * kLmLogCap + sizeof(int) * ((size_t)P + 2));
-  if (npartial > (size_t)kLmMaxPartials) { ctx->set_error("asd_local_ba: %d edges exceed the control kernel's %d partial sums", E, kLmMaxPartials); return ASD_ERR_CAPACITY; }
-
-  // upload the problem: poses normalised like SE3Quat's constructor does
-  std::vector<Pose7> hp(P);
-  for (int p = 0; p < P; ++p) {
-    const double* q = pr->poses + 7 * p;
-    hp[p] = Pose7{q[0], q[1], q[2], q[3], q[4], q[5], q[6]};
-    quat_normalize(hp[p].qx, hp[p].qy, hp[p].qz, hp[p].qw);
-  }
-  // both estimate buffers start as the input (vertices no trial writes -- fixed poses, landmarks without an active edge -- must read the same in both)
-  ASD_HIP_CHECK(ctx, hipMemcpyAsync(s->pose.p, hp.data(), (size_t)P * sizeof(Pose7), hipMemcpyHostToDevice, st));
-  ASD_HIP_CHECK(ctx, hipMemcpyAsync(s->pts.p, pr->points, (size_t)L * 24, hipMemcpyHostToDevice, st));
-  ASD_HIP_CHECK(ctx, hipMemcpyAsync(s->pose_bak.p, s->pose.p, (size_t)P * sizeof(Pose7), hipMemcpyDeviceToDevice, st));
-  ASD_HIP_CHECK(ctx, hipMemcpyAsync(s->pts_bak.p, s->pts.p, (size_t)L * 24, hipMemcpyDeviceToDevice, st));
-  ASD_HIP_CHECK(ctx, hipMemsetAsync(s->lm.p, 0, sizeof(LmState), st));   // lm->cur = 0
-  ASD_HIP_CHECK(ctx, hipMemcpyAsync(s->e_pt.p, pr->e_point, (size_t)E * 4, hipMemcpyHostToDevice, st));
-  ASD_HIP_CHECK(ctx, hipMemcpyAsync(s->e_ps.p, pr->e_pose, (size_t)E * 4, hipMemcpyHostToDevice, st));
-  ASD_HIP_CHECK(ctx, hipMemcpyAsync(s->obs.p, pr->e_obs, (size_t)E * 16, hipMemcpyHostToDevice, st));
-  ASD_HIP_CHECK(ctx, hipMemcpyAsync(s->info.p, pr->e_info, (size_t)E * 8, hipMemcpyHostToDevice, st));
-  ASD_HIP_CHECK(ctx, hipMemsetAsync(s->err.p, 0, (size_t)E * 16, st));
-  ASD_HIP_CHECK(ctx, hipMemsetAsync(s->lvl.p, 0, (size_t)E, st));
-  ENS(fixed_d, (size_t)std::max(P, 1));
+  const BaSizes z{(size_t)P, (size_t)L, (size_t)std::max(n_free, 1), true, 64, (size_t)nblk_e + nblk_l + nblk_p + 8};
+  if (z.npartial > (size_t)kLmMaxPartials) { ctx->set_error("asd_local_ba: %d edges exceed the control kernel's %d partial sums", E, kLmMaxPartials); return ASD_ERR_CAPACITY; }
+  if ((rc = s->out1.ensure(ctx, (size_t)E)) != ASD_OK || (rc = s->fixed_d.ensure(ctx, (size_t)std::max(P, 1))) != ASD_OK) return rc;
+  std::vector<Pose7> hp = poses_pack(pr->poses, P);
+  if ((rc = ba_setup_upload(ctx, s, pr, hp, z, st)) != ASD_OK) return rc;
   ASD_HIP_CHECK(ctx, hipMemcpyAsync(s->fixed_d.p, pr->fixed, (size_t)P, hipMemcpyHostToDevice, st));
   if (!s->h_counts) ASD_HIP_CHECK(ctx, hipHostMalloc(reinterpret_cast<void**>(&s->h_counts), 64));
   if (!s->ev_counts) ASD_HIP_CHECK(ctx, hipEventCreateWithFlags(&s->ev_counts, hipEventDisableTiming));
   ASD_HIP_CHECK(ctx, hipEventRecord(ev0, st));
-
-  BaDev d{};
-  d.P = P; d.L = L; d.E = E;
-  d.pose[0] = s->pose.as<Pose7>(); d.pose[1] = s->pose_bak.as<Pose7>();
-  d.pts[0] = s->pts.as<double>(); d.pts[1] = s->pts_bak.as<double>();
-  d.e_pt = s->e_pt.as<int>(); d.e_ps = s->e_ps.as<int>(); d.obs = s->obs.as<double>(); d.info = s->info.as<double>();
-  d.err = s->err.as<double>(); d.lvl = s->lvl.as<uint8_t>(); d.HppPart = s->HppPart.as<double>();
-  d.fx = pr->K[0]; d.fy = pr->K[1]; d.cx = pr->K[2]; d.cy = pr->K[3];
-  d.act = s->act.as<int>(); d.pose_h = s->pose_h.as<int>(); d.pt_h = s->pt_h.as<int>();
-  d.pose_of_h = s->pose_of_h.as<int>(); d.pt_of_h = s->pt_of_h.as<int>(); d.pt_start = s->pt_start.as<int>();
-  d.ps_start = s->ps_start.as<int>(); d.ps_edges = s->ps_edges.as<int>();
-  d.Bk = s->Bk.as<double>(); d.Hc = s->Hc.as<double>(); d.Hl = s->Hl.as<double>(); d.Hpp = s->Hpp.as<double>(); d.Hll = s->Hll.as<double>(); d.Dinv = s->Dinv.as<double>();
-  d.db = s->db.as<double>(); d.x = s->x.as<double>(); d.A = s->A.as<double>(); d.Apack = s->Apack.as<double>(); d.bs = s->bs.as<double>();
-  // status and the per-workgroup partial sums are read by the host after every trial: the kernels store them straight into
-  // pinned host memory (a few hundred doubles), which removes two copy commands per trial from the lane's queue
-  // the Levenberg scalars and the per-workgroup partial sums they are made of stay on the device (k_ba_lm_control); the host sees
-  // a pinned mirror of the state, written after every trial, and reads it once per chunk of blocks
-  d.lm = s->lm.as<LmState>();
-  d.lm_host = s->h_lm;
-  d.lm_log = reinterpret_cast<LmLog*>(s->lm.as<char>() + sizeof(LmState) + 64 - (sizeof(LmState) % 8));
-  d.partial = s->partial.as<double>();
-  d.tickets = reinterpret_cast<int*>(reinterpret_cast<char*>(d.lm_log) + sizeof(LmLog) * kLmLogCap);
-  ASD_HIP_CHECK(ctx, hipMemsetAsync(d.tickets, 0, sizeof(int) * ((size_t)P + 2), st));
+  BaDev d;
+  if ((rc = ba_setup_bind(ctx, s, pr, z, st, d)) != ASD_OK) return rc;
+  d.scale_off = nblk_e;
 
   for (auto& f : s->forms) for (int& v : f) v = -1;
   for (auto& f : s->lm_rounds) for (int& v : f) v = -1;
   const auto t_uploaded = std::chrono::steady_clock::now();
-  std::vector<uint8_t> level(E, 0);
-  std::vector<int> act, pose_h(P), pt_h(L), pose_of_h, pt_of_h, pt_start, ps_start, ps_edges, ps_hv, blk_i, blk_j, pair_start, ph_of_k, cursor,
-      row_off;
-  std::vector<int2> pairs;
 
   // one g2o initializeOptimization(level 0) + optimize(iterations) round
   const bool timing = getenv("ASD_TIMING") != nullptr;
@@ -2559,14 +2645,12 @@ int local_ba_impl(asd_ctx* ctx, BaState* s, asd_ba_problem* pr, asd_ba_result* r
     const auto t_round = std::chrono::steady_clock::now();
     int n_trials = 0;
     int r2;
-    int n_free_max = 0;
-    for (int p = 0; p < P; ++p) n_free_max += !pr->fixed[p];
     const bool struct_host = ctx->ba_struct_host;   // per context (a process-wide latch made the first call decide for every context)
-    // a landmark observed twice by one pose (nothing forbids it; the host loop gives its diagonal block both cross terms, the general
+    // a landmark observed twice by one pose (nothing forbids it; ba_structure.h gives its diagonal block both cross terms, the general
     // branch of k_ba_struct_pairs does not) has more pairs than the device tables are sized for -- E (F + 1) / 2 assumes at most one edge per (landmark, free pose): such a
     // problem takes the host-built structure instead of writing past the pair list
     bool dup_edges = false;
-    if (round_idx == 0 && !struct_host && E > 0 && P <= kStructMaxP && n_free_max <= kStructMaxFree) {
+    if (round_idx == 0 && !struct_host && E > 0 && P <= kStructMaxP && n_free <= kStructMaxFree) {
       const size_t words = ((size_t)P + 63) / 64;
       std::vector<uint64_t> seen((size_t)L * words, 0);
       for (int e = 0; e < E && !dup_edges; ++e) {
@@ -2576,40 +2660,32 @@ int local_ba_impl(asd_ctx* ctx, BaState* s, asd_ba_problem* pr, asd_ba_result* r
         w |= bit;
       }
     }
-    const bool struct_dev = !struct_host && !dup_edges && E > 0 && P <= kStructMaxP && n_free_max <= kStructMaxFree;
+    const bool struct_dev = !struct_host && !dup_edges && E > 0 && P <= kStructMaxP && n_free <= kStructMaxFree;
     if (round_idx == 0 && struct_dev) {
-      // ---- active structure, on the device (k_ba_struct_*): the tables are carved out of one block sized by upper bounds
-      const int nblk_max = n_free_max * (n_free_max + 1) / 2;
-      const size_t pairs_cap = (size_t)E * (size_t)(n_free_max + 1) / 2 + 1;
-      size_t off = 0;
-      auto place = [&](size_t bytes) { const size_t o = off; off += (bytes + 255) / 256 * 256; return o; };
-      const size_t o_act = place((size_t)E * 4), o_pose_h = place((size_t)P * 4), o_pt_h = place((size_t)L * 4), o_pose_of_h = place((size_t)P * 4),
-                   o_pt_of_h = place((size_t)L * 4), o_pt_start = place((size_t)(L + 1) * 4), o_ps_start = place((size_t)(P + 1) * 4),
-                   o_ps_edges = place((size_t)E * 4), o_blk_i = place((size_t)std::max(nblk_max, 1) * 4), o_blk_j = place((size_t)std::max(nblk_max, 1) * 4),
-                   o_pair_start = place((size_t)(nblk_max + 1) * 4), o_pairs = place(pairs_cap * 8), o_pair_h = place(pairs_cap * 4), o_ph = place((size_t)E * 4),
-                   o_hk = place((size_t)E * 4), o_ps_h = place((size_t)E * 4),
-                   o_cursor = place((size_t)(L + 1) * 4), o_mask = place((size_t)L * 4), o_pscnt = place(kStructMaxFree * 4),
-                   o_paircnt = place((size_t)std::max(std::max(nblk_max, P), 1) * 4), o_free0 = place((size_t)L * 4);
-      if ((r2 = s->sblk.ensure(ctx, off)) != ASD_OK) return r2;
+      // ---- active structure, on the device (k_ba_struct_*): the common tables at the layout's places with upper bounds for counts,
+      // the kernels' own tables behind them, one block
+      const int nblk_max = n_free * (n_free + 1) / 2;
+      const size_t pairs_cap = (size_t)E * (size_t)(n_free + 1) / 2 + 1;
+      BaStructLayout lay(P, L, P, L, E, E, nblk_max, pairs_cap);
+      const size_t o_ph = lay.place((size_t)E * 4), o_hk = lay.place((size_t)E * 4), o_cursor = lay.place((size_t)(L + 1) * 4), o_mask = lay.place((size_t)L * 4),
+                   o_pscnt = lay.place(kStructMaxFree * 4), o_paircnt = lay.place((size_t)std::max(nblk_max, P) * 4), o_free0 = lay.place((size_t)L * 4);
+      if ((r2 = s->sblk.ensure(ctx, lay.bytes)) != ASD_OK) return r2;
       char* db = s->sblk.as<char>();
+      ba_bind_structure(d, sb, db, lay);
+      auto own = [&](size_t o) { return reinterpret_cast<int*>(db + o); };
       BaStructDev sd{};
       sd.P = P; sd.L = L; sd.E = E;
       sd.e_ps = d.e_ps; sd.e_pt = d.e_pt; sd.fixed = s->fixed_d.as<uint8_t>();
-      sd.pose_h = reinterpret_cast<int*>(db + o_pose_h); sd.pt_h = reinterpret_cast<int*>(db + o_pt_h);
-      sd.pose_of_h = reinterpret_cast<int*>(db + o_pose_of_h); sd.pt_of_h = reinterpret_cast<int*>(db + o_pt_of_h);
-      sd.pt_start = reinterpret_cast<int*>(db + o_pt_start); sd.act = reinterpret_cast<int*>(db + o_act);
-      sd.ph_of_k = reinterpret_cast<int*>(db + o_ph); sd.cursor = reinterpret_cast<int*>(db + o_cursor);
-      sd.pt_free0 = reinterpret_cast<int*>(db + o_free0);
-      sd.pt_mask = reinterpret_cast<unsigned*>(db + o_mask); sd.ps_cnt = reinterpret_cast<int*>(db + o_pscnt);
-      sd.ps_start = reinterpret_cast<int*>(db + o_ps_start); sd.ps_edges = reinterpret_cast<int*>(db + o_ps_edges);
-      sd.blk_i = reinterpret_cast<int*>(db + o_blk_i); sd.blk_j = reinterpret_cast<int*>(db + o_blk_j);
-      sd.pair_cnt = reinterpret_cast<int*>(db + o_paircnt); sd.pair_start = reinterpret_cast<int*>(db + o_pair_start);
-      sd.pairs = reinterpret_cast<int2*>(db + o_pairs); sd.pair_h = reinterpret_cast<int*>(db + o_pair_h);
-      sd.h_of_k = reinterpret_cast<int*>(db + o_hk); sd.ps_h = reinterpret_cast<int*>(db + o_ps_h);
+      sd.pose_h = own(lay.pose_h); sd.pt_h = own(lay.pt_h); sd.pose_of_h = own(lay.pose_of_h); sd.pt_of_h = own(lay.pt_of_h);
+      sd.pt_start = own(lay.pt_start); sd.act = own(lay.act); sd.ps_start = own(lay.ps_start); sd.ps_edges = own(lay.ps_edges); sd.ps_h = own(lay.ps_h);
+      sd.blk_i = own(lay.blk_i); sd.blk_j = own(lay.blk_j); sd.pair_start = own(lay.pair_start);
+      sd.pairs = reinterpret_cast<int2*>(db + lay.pairs); sd.pair_h = own(lay.pair_h);
+      sd.ph_of_k = own(o_ph); sd.h_of_k = own(o_hk); sd.cursor = own(o_cursor); sd.pt_mask = reinterpret_cast<unsigned*>(db + o_mask);
+      sd.ps_cnt = own(o_pscnt); sd.pair_cnt = own(o_paircnt); sd.pt_free0 = own(o_free0);
       sd.counts = s->h_counts;
       s->h_counts[3] = 0;
       {
-        int* pflag = sd.pair_cnt;   // [P] scratch until the pair kernels run (nblk_max >= P whenever a pose is free; else sized below)
+        int* pflag = sd.pair_cnt;   // [P] scratch until the pair kernels run
         const int gEs = (E + 255) / 256;
         ASD_HIP_CHECK(ctx, hipMemsetAsync(sd.pt_h, 0, (size_t)L * 4, st));
         ASD_HIP_CHECK(ctx, hipMemsetAsync(pflag, 0, (size_t)P * 4, st));
@@ -2633,164 +2709,39 @@ int local_ba_impl(asd_ctx* ctx, BaState* s, asd_ba_problem* pr, asd_ba_result* r
         hipLaunchKernelGGL(k_ba_struct_pairs<true>, dim3(nblk), dim3(kPairThreads), 0, st, sd, nPf, nLa, nblk);
         ASD_HIP_CHECK(ctx, hipGetLastError());
       }
-      d.act = sd.act; d.pose_h = sd.pose_h; d.pt_h = sd.pt_h; d.pose_of_h = sd.pose_of_h; d.pt_of_h = sd.pt_of_h;
-      d.pt_start = sd.pt_start; d.ps_start = sd.ps_start; d.ps_edges = sd.ps_edges; d.ps_h = sd.ps_h;
-      sb = SchurBlocks{sd.blk_i, sd.blk_j, sd.pair_start, sd.pairs, sd.pair_h};
       d.Ea = Ea; d.nPf = nPf; d.nLa = nLa;
       n_pairs_total = 0;   // (on the device; read from the pinned counts when the round reports)
-    } else
-    if (round_idx == 0) {
-    // ---- active structure, on the host
-    std::vector<uint8_t> pa(P, 0), la(L, 0);
-    for (int e = 0; e < E; ++e)
-      if (!level[e]) { pa[pr->e_pose[e]] = 1; la[pr->e_point[e]] = 1; }
-    pose_of_h.clear(); pt_of_h.clear();
-    for (int p = 0; p < P; ++p) { pose_h[p] = -1; if (pa[p] && !pr->fixed[p]) { pose_h[p] = (int)pose_of_h.size(); pose_of_h.push_back(p); } }
-    for (int l = 0; l < L; ++l) { pt_h[l] = -1; if (la[l]) { pt_h[l] = (int)pt_of_h.size(); pt_of_h.push_back(l); } }
-    nPf = (int)pose_of_h.size(); nLa = (int)pt_of_h.size();
-    // active edges grouped by landmark (CSR), inside a landmark ordered by pose h-index (fixed poses first)
-    pt_start.assign(nLa + 1, 0);
-    for (int e = 0; e < E; ++e) if (!level[e]) ++pt_start[pt_h[pr->e_point[e]] + 1];
-    for (int h = 0; h < nLa; ++h) pt_start[h + 1] += pt_start[h];
-    Ea = pt_start[nLa];
-    act.assign(Ea, 0);
-    ph_of_k.assign(std::max(Ea, 1), -1);  // pose h-index of the k-th active edge (-1 = fixed pose)
-    {
-      cursor.assign(pt_start.begin(), pt_start.end() - 1);
-      for (int e = 0; e < E; ++e) if (!level[e]) act[cursor[pt_h[pr->e_point[e]]]++] = e;
-      for (int h = 0; h < nLa; ++h) {  // stable insertion sort: a landmark has a handful of observations
-        const int s0 = pt_start[h], s1 = pt_start[h + 1];
-        for (int a = s0; a < s1; ++a) ph_of_k[a] = pose_h[pr->e_pose[act[a]]];
-        for (int a = s0 + 1; a < s1; ++a) {
-          const int ea = act[a], pa_ = ph_of_k[a];
-          int b = a - 1;
-          while (b >= s0 && ph_of_k[b] > pa_) { act[b + 1] = act[b]; ph_of_k[b + 1] = ph_of_k[b]; --b; }
-          act[b + 1] = ea; ph_of_k[b + 1] = pa_;
-        }
-      }
+    } else if (round_idx == 0) {
+      // ---- active structure, on the host.  Every upper block gets a workgroup, also those no landmark connects: the in-place
+      // Cholesky leaves fill-in in A, so blocks without pairs must be rewritten (to zero) on every trial.
+      BaStructure hs;
+      hs.count(P, L, E, pr->e_pose, pr->e_point, pr->fixed);
+      const BaStructLayout lay = hs.layout();
+      if ((r2 = ba_structure_stage(ctx, s, hs, lay)) != ASD_OK) return r2;
+      ASD_HIP_CHECK(ctx, hipMemcpyAsync(s->sblk.p, s->h_sblk, lay.bytes, hipMemcpyHostToDevice, st));
+      ba_bind_structure(d, sb, s->sblk.as<char>(), lay);
+      nPf = hs.nPf; nLa = hs.nLa; Ea = hs.Ea; nblk = hs.nblk;
+      d.Ea = Ea; d.nPf = nPf; d.nLa = nLa;
+      n_pairs_total = std::max(hs.npairs, (size_t)1);
     }
-    // per free pose: its edges (k indices) in k order
-    ps_start.assign(nPf + 1, 0);
-    for (int k = 0; k < Ea; ++k) if (ph_of_k[k] >= 0) ++ps_start[ph_of_k[k] + 1];
-    for (int h = 0; h < nPf; ++h) ps_start[h + 1] += ps_start[h];
-    ps_edges.assign(std::max(ps_start[nPf], 1), 0);
-    ps_hv.assign(ps_edges.size(), 0);
-    {
-      cursor.assign(ps_start.begin(), ps_start.end() - 1);
-      for (int h = 0; h < nLa; ++h)
-        for (int k = pt_start[h]; k < pt_start[h + 1]; ++k)   // (k ascending over the landmarks in order: the same order as a plain loop over k)
-          if (ph_of_k[k] >= 0) { const int o = cursor[ph_of_k[k]]++; ps_edges[o] = k; ps_hv[o] = h; }
-    }
-    // Schur pair lists per upper block (bi <= bj), blocks numbered row-major over the upper triangle.  Every upper
-    // block gets a workgroup, also those no landmark connects: the in-place Cholesky leaves fill-in in A, so blocks
-    // without pairs must be rewritten (to zero) on every trial.
-    const int nblk_all = nPf * (nPf + 1) / 2;
-    row_off.assign(std::max(nPf, 1), 0);
-    for (int i = 0; i < nPf; ++i) row_off[i] = i * nPf - i * (i - 1) / 2 - i;  // block id = row_off[i] + j
-    pair_start.assign(nblk_all + 1, 0);
-    for (int h = 0; h < nLa; ++h) {
-      const int s1 = pt_start[h + 1];
-      int a = pt_start[h];
-      while (a < s1 && ph_of_k[a] < 0) ++a;  // fixed poses sort first
-      for (; a < s1; ++a) {
-        const int ro = row_off[ph_of_k[a]];
-        for (int b = a; b < s1; ++b) pair_start[ro + ph_of_k[b] + 1] += 1 + (b != a && ph_of_k[b] == ph_of_k[a]);
-      }
-    }
-    for (int q = 0; q < nblk_all; ++q) pair_start[q + 1] += pair_start[q];
-    blk_i.resize(nblk_all); blk_j.resize(nblk_all);
-    for (int i = 0, q = 0; i < nPf; ++i)
-      for (int j = i; j < nPf; ++j, ++q) { blk_i[q] = i; blk_j[q] = j; }
-    // ONE pinned block, ONE upload for the whole structure (eleven copies out of pageable vectors cost ~0.2 ms of the 0.45 ms this
-    // pass took): the pair lists -- the largest array -- are written straight into it
-    nblk = nblk_all;
-    const size_t npairs = (size_t)std::max(pair_start[nblk_all], 1);
-    size_t off = 0;
-    auto place = [&](size_t bytes) { const size_t o = off; off += (bytes + 255) / 256 * 256; return o; };
-    const size_t o_act = place((size_t)std::max(Ea, 1) * 4), o_pose_h = place((size_t)P * 4), o_pt_h = place((size_t)L * 4),
-                 o_pose_of_h = place((size_t)std::max(nPf, 1) * 4), o_pt_of_h = place((size_t)std::max(nLa, 1) * 4), o_pt_start = place((size_t)(nLa + 1) * 4),
-                 o_ps_start = place((size_t)(nPf + 1) * 4), o_ps_edges = place(ps_edges.size() * 4), o_blk_i = place((size_t)std::max(nblk, 1) * 4),
-                 o_blk_j = place((size_t)std::max(nblk, 1) * 4), o_pair_start = place((size_t)(nblk + 1) * 4), o_pairs = place(npairs * 8),
-                 o_pair_h = place(npairs * 4), o_ps_h = place(ps_edges.size() * 4);
-    if ((r2 = s->sblk.ensure(ctx, off)) != ASD_OK) return r2;
-    if (s->h_sblk_cap < off) {
-      if (s->h_sblk) (void)hipHostFree(s->h_sblk);
-      s->h_sblk = nullptr; s->h_sblk_cap = 0;
-      ASD_HIP_CHECK(ctx, hipHostMalloc(reinterpret_cast<void**>(&s->h_sblk), off + off / 4));
-      s->h_sblk_cap = off + off / 4;
-    }
-    char* hb = s->h_sblk;
-    auto put = [&](size_t o, const std::vector<int>& v) { if (!v.empty()) memcpy(hb + o, v.data(), v.size() * 4); };
-    put(o_act, act); put(o_pose_h, pose_h); put(o_pt_h, pt_h); put(o_pose_of_h, pose_of_h); put(o_pt_of_h, pt_of_h); put(o_pt_start, pt_start);
-    put(o_ps_start, ps_start); put(o_ps_edges, ps_edges); put(o_pair_start, pair_start); put(o_ps_h, ps_hv);
-    {
-      int* bi_ = reinterpret_cast<int*>(hb + o_blk_i);
-      int* bj_ = reinterpret_cast<int*>(hb + o_blk_j);
-      for (int i = 0, q = 0; i < nPf; ++i)
-        for (int j = i; j < nPf; ++j, ++q) { bi_[q] = i; bj_[q] = j; }
-      int2* pp = reinterpret_cast<int2*>(hb + o_pairs);
-      int* ph_ = reinterpret_cast<int*>(hb + o_pair_h);
-      cursor.assign(pair_start.begin(), pair_start.end() - 1);
-      for (int h = 0; h < nLa; ++h) {
-        const int s1 = pt_start[h + 1];
-        int a = pt_start[h];
-        while (a < s1 && ph_of_k[a] < 0) ++a;
-        for (; a < s1; ++a) {
-          const int ro = row_off[ph_of_k[a]];
-          for (int b = a; b < s1; ++b) {
-            const int o = cursor[ro + ph_of_k[b]]++; pp[o] = make_int2(a, b); ph_[o] = h;
-            // two edges of one pose (a duplicate observation): k_ba_schur adds Y_a B_b^T for a pair, and the diagonal block needs
-            // both cross terms, Y_a B_b^T + Y_b B_a^T -- the transposed block of an off-diagonal pair is written from the same sum
-            if (b != a && ph_of_k[b] == ph_of_k[a]) { const int o2 = cursor[ro + ph_of_k[b]]++; pp[o2] = make_int2(b, a); ph_[o2] = h; }
-          }
-        }
-      }
-    }
-    n_pairs_total = npairs;
-    ASD_HIP_CHECK(ctx, hipMemcpyAsync(s->sblk.p, hb, off, hipMemcpyHostToDevice, st));
-    char* db = s->sblk.as<char>();
-    d.act = reinterpret_cast<const int*>(db + o_act); d.pose_h = reinterpret_cast<const int*>(db + o_pose_h); d.pt_h = reinterpret_cast<const int*>(db + o_pt_h);
-    d.pose_of_h = reinterpret_cast<const int*>(db + o_pose_of_h); d.pt_of_h = reinterpret_cast<const int*>(db + o_pt_of_h);
-    d.pt_start = reinterpret_cast<const int*>(db + o_pt_start); d.ps_start = reinterpret_cast<const int*>(db + o_ps_start);
-    d.ps_edges = reinterpret_cast<const int*>(db + o_ps_edges); d.ps_h = reinterpret_cast<const int*>(db + o_ps_h);
-    sb = SchurBlocks{reinterpret_cast<const int*>(db + o_blk_i), reinterpret_cast<const int*>(db + o_blk_j), reinterpret_cast<const int*>(db + o_pair_start),
-                     reinterpret_cast<const int2*>(db + o_pairs), reinterpret_cast<const int*>(db + o_pair_h)};
-    d.Ea = Ea; d.nPf = nPf; d.nLa = nLa;
-    }   // round_idx == 0
     if (round_idx == 0) struct_form = struct_dev ? 0 : 1;
     {
       int* f = s->forms[round_idx];
-      f[0] = Ea == 0 || nPf == 0 ? -1 : ba_dense_form(nPf);   // the dense solve enqueue_block picks
+      f[0] = Ea == 0 || nPf == 0 ? -1 : ba_dense_form(nPf);   // the dense solve of the trial
       f[1] = struct_form; f[2] = nPf; f[3] = nLa; f[4] = Ea;
     }
     t_prep = std::chrono::steady_clock::now();
     *iters_out = 0;
     *chi_out = 0;
     if (Ea == 0) return ASD_OK;
-    const int gE = (Ea + 255) / 256, gL = (nLa + 255) / 256, gP = std::max((nPf + 255) / 256, 1);
-    const int n = 6 * nPf;
-
-    d.gE = gE; d.gL = gL; d.gP = gP;
-    // ---- the round on the device.  One "block" = one Levenberg trial as the device sees it: [linearise group -- runs only when
-    // the state says a new iteration starts] [solve: Dinv, Y, Schur, dense solve, back-substitution, pose update] [errors at the
-    // trial estimate] [control: accept / reject (= flip the estimate buffers or not), next lambda, end of iteration / round].
-    // Blocks are enqueued ahead; the host reads the mirrored state once per chunk.  The first chunk is as long as the previous
-    // LocalBA's round of the same index took (same map, similar problem), so the usual round needs one synchronisation.
-    auto enqueue_block = [&]() -> int {
-      hipLaunchKernelGGL(k_ba_linearize, dim3(gE), dim3(256), 0, st, d, robust ? 1 : 0);
-      hipLaunchKernelGGL(k_ba_reduce, dim3(nPf * kPoseSplit + gL), dim3(256), 0, st, d);
-      if (nPf > 0) {
-        hipLaunchKernelGGL(k_ba_schur, dim3(nblk + nPf), dim3(kSchurThreads), 0, st, d, sb, nblk);
-        const int r2 = ba_dense_enqueue(ctx, st, ba_dense_form(nPf), d.Apack, d.A, d.bs, d.x, n, d.lm);
-        if (r2 != ASD_OK) return r2;
-      }
-      hipLaunchKernelGGL(k_ba_step, dim3(gL + gP), dim3(256), 0, st, d);
-      hipLaunchKernelGGL(k_ba_error, dim3(gE), dim3(256), 0, st, d, robust ? 1 : 0, 0, 0);   // + the Levenberg control, in its last workgroup
-      ASD_HIP_CHECK(ctx, hipGetLastError());
-      return ASD_OK;
-    };
+    const int gE = (Ea + 255) / 256;
+    d.gE = gE; d.gL = (nLa + 255) / 256; d.gP = std::max((nPf + 255) / 256, 1);
+    // ---- the round on the device.  Blocks (ba_enqueue_trial) are enqueued ahead; the host reads the mirrored state once per chunk.
+    // The first chunk is as long as the previous LocalBA's round of the same index took (same map, similar problem), so the usual
+    // round needs one synchronisation.
+    const BaTrial trial{ba_dense_form(nPf), true, nblk, sb, robust ? 1 : 0};
     // computeActiveErrors + activeRobustChi2 at the round's first estimate (levenberg.cpp:70-76), state reset
-    hipLaunchKernelGGL(k_ba_error, dim3(gE), dim3(256), 0, st, d, robust ? 1 : 0, 1, iterations);
+    hipLaunchKernelGGL(k_ba_error, dim3(gE), dim3(256), 0, st, d, trial.robust, 1, iterations);
     ASD_HIP_CHECK(ctx, hipGetLastError());
     int& predicted = s->lm_blocks[round_idx];
     int chunk = predicted > 0 ? predicted : iterations;
@@ -2800,10 +2751,10 @@ int local_ba_impl(asd_ctx* ctx, BaState* s, asd_ba_problem* pr, asd_ba_result* r
     // fixed number of chunks, bounds the loop -- a slowly converging problem with many iterations is not a numeric failure
     const int max_trials = iterations * 10 + 2;
     while (iterations > 0 && n_trials < max_trials) {
-      for (int b = 0; b < chunk; ++b) if ((r2 = enqueue_block()) != ASD_OK) return r2;
+      for (int b = 0; b < chunk; ++b) if ((r2 = ba_enqueue_trial(ctx, st, d, trial)) != ASD_OK) return r2;
       n_trials += chunk;
       // activeRobustChi2() from the stored edge errors behind every chunk: if the round ended inside it, its report is already there
-      hipLaunchKernelGGL(k_ba_chi2_stored, dim3(gE), dim3(256), 0, st, d, robust ? 1 : 0, s->h_partial);
+      hipLaunchKernelGGL(k_ba_chi2_stored, dim3(gE), dim3(256), 0, st, d, trial.robust, s->h_partial);
       ASD_HIP_CHECK(ctx, hipGetLastError());
       ASD_HIP_CHECK(ctx, hipStreamSynchronize(st));
       if (s->h_lm->done) break;
@@ -2812,7 +2763,7 @@ int local_ba_impl(asd_ctx* ctx, BaState* s, asd_ba_problem* pr, asd_ba_result* r
     // no block ran: wait for k_ba_error's first pass before reading its state (h_lm held the previous round's until then), and
     // report the chi2 of the stored errors as they stand
     if (iterations <= 0) {
-      hipLaunchKernelGGL(k_ba_chi2_stored, dim3(gE), dim3(256), 0, st, d, robust ? 1 : 0, s->h_partial);
+      hipLaunchKernelGGL(k_ba_chi2_stored, dim3(gE), dim3(256), 0, st, d, trial.robust, s->h_partial);
       ASD_HIP_CHECK(ctx, hipGetLastError());
       ASD_HIP_CHECK(ctx, hipStreamSynchronize(st));
     }
@@ -2824,16 +2775,13 @@ int local_ba_impl(asd_ctx* ctx, BaState* s, asd_ba_problem* pr, asd_ba_result* r
       f[0] = done; f[1] = s->h_lm->trials; f[2] = n_trials; f[3] = first_chunk;
     }
     if (getenv("ASD_BA_DEBUG")) {
-      std::vector<LmLog> lg(kLmLogCap);
-      ASD_HIP_CHECK(ctx, hipMemcpy(lg.data(), d.lm_log, sizeof(LmLog) * kLmLogCap, hipMemcpyDeviceToHost));
-      for (int q = 0; q < std::min(s->h_lm->trials, kLmLogCap); ++q)
-        fprintf(stderr, "[ba] trial %d lambda=%.6e cur=%.9e temp=%.9e scale=%.6e nPf=%d nLa=%d Ea=%d nblk=%d\n", q, lg[q].lambda, lg[q].cur, lg[q].temp, lg[q].scale, nPf, nLa, Ea, nblk);
+      char tail[96];
+      snprintf(tail, sizeof tail, " nPf=%d nLa=%d Ea=%d nblk=%d", nPf, nLa, Ea, nblk);
+      if ((r2 = ba_debug_trials(ctx, d, s->h_lm->trials, "ba", tail)) != ASD_OK) return r2;
       fprintf(stderr, "[ba] round %d: %d iterations, %d trials, %d blocks enqueued\n", round_idx, done, s->h_lm->trials, n_trials);
     }
     *iters_out = done;
-    double sum = 0;
-    for (int i = 0; i < gE; ++i) sum += s->h_partial[i];
-    *chi_out = sum;
+    *chi_out = ba_chi2_sum(s, gE);
     if (timing) {
       const auto t_end = std::chrono::steady_clock::now();
       fprintf(stderr, "[ba round] structure %.0f us (Ea=%d nPf=%d nLa=%d pairs=%zu), %d iterations / %d trials in %.0f us\n",
@@ -2843,7 +2791,6 @@ int local_ba_impl(asd_ctx* ctx, BaState* s, asd_ba_problem* pr, asd_ba_result* r
     return ASD_OK;
   };
 
-  d.scale_off = nblk_e;
   // optimizer.initializeOptimization(); optimizer.optimize(its_first)           (Optimizer.cc:601-602)
   rc = run_round(0, pr->its_first, true, &res->chi2_first, &res->iters_first);
   if (rc != ASD_OK) return rc;
@@ -2866,11 +2813,7 @@ int local_ba_impl(asd_ctx* ctx, BaState* s, asd_ba_problem* pr, asd_ba_result* r
   ASD_HIP_CHECK(ctx, hipMemcpyAsync(pr->points, fin ? s->pts_bak.p : s->pts.p, (size_t)L * 24, hipMemcpyDeviceToHost, st));
   ASD_HIP_CHECK(ctx, hipStreamSynchronize(st));
   ASD_HIP_CHECK(ctx, hipEventElapsedTime(ms, ev0, ev1));
-  for (int p = 0; p < P; ++p) {
-    double* q = pr->poses + 7 * p;
-    q[0] = hp[p].qx; q[1] = hp[p].qy; q[2] = hp[p].qz; q[3] = hp[p].qw; q[4] = hp[p].tx; q[5] = hp[p].ty; q[6] = hp[p].tz;
-  }
-#undef ENS
+  poses_unpack(hp, pr->poses);
   if (timing) {
     auto us = [](auto a, auto b) { return std::chrono::duration<double, std::micro>(b - a).count(); };
     fprintf(stderr, "[ba call] buffers + problem upload %.0f us, rounds (structure, trials, gating) %.0f us, results %.0f us\n", us(t_enter, t_uploaded),
@@ -3032,9 +2975,9 @@ int gba_check(asd_ctx* ctx, const asd_gba_problem* pr, const asd_gba_result* res
   return ASD_OK;
 }
 
-// One round over LocalBA's kernels: the active structure from the host loop (a map is not per-frame work, and the device structure
-// kernels stop at 32 free poses), Schur workgroups only for the blocks that have pairs -- with the rest of A cleared in front of them --
-// and the dense solve in the form the size asks for.
+// One round over LocalBA's kernels and its host setup: the active structure from the host (ba_structure.h: a map is not per-frame work,
+// and the device structure kernels stop at 32 free poses), Schur workgroups only for the blocks that have pairs -- with the rest of A
+// cleared in front of them -- and the dense solve in the form the size asks for.
 int gba_impl(asd_ctx* ctx, BaState* s, asd_gba_problem* pr, asd_gba_result* res) {
   const int P = pr->n_poses, L = pr->n_points, E = pr->n_edges;
   hipStream_t st = ctx->stream;
@@ -3043,218 +2986,52 @@ int gba_impl(asd_ctx* ctx, BaState* s, asd_gba_problem* pr, asd_gba_result* res)
   for (int& v : s->gba_forms) v = -1;
   s->gba_trials.clear();
   res->chi2 = 0; res->iterations = -1; res->trials = 0;
-  std::vector<Pose7> hp(P);
-  for (int p = 0; p < P; ++p) {   // normalised like SE3Quat's constructor does
-    const double* q = pr->poses + 7 * p;
-    hp[p] = Pose7{q[0], q[1], q[2], q[3], q[4], q[5], q[6]};
-    quat_normalize(hp[p].qx, hp[p].qy, hp[p].qz, hp[p].qw);
-  }
-  auto poses_out = [&]() {
-    for (int p = 0; p < P; ++p) {
-      double* q = pr->poses + 7 * p;
-      q[0] = hp[p].qx; q[1] = hp[p].qy; q[2] = hp[p].qz; q[3] = hp[p].qw; q[4] = hp[p].tx; q[5] = hp[p].ty; q[6] = hp[p].tz;
-    }
-  };
+  std::vector<Pose7> hp = poses_pack(pr->poses, P);
   // no edge: every point is removed again (Optimizer.cc:153-157), "0 vertices to optimize", optimize() returns -1
-  if (E == 0) { poses_out(); s->gba_forms[1] = s->gba_forms[2] = s->gba_forms[3] = s->gba_forms[4] = 0; return ASD_OK; }
+  if (E == 0) { poses_unpack(hp, pr->poses); s->gba_forms[1] = s->gba_forms[2] = s->gba_forms[3] = s->gba_forms[4] = 0; return ASD_OK; }
   const bool stop_on_entry = pr->stop && *pr->stop;
   const int iterations = stop_on_entry ? 0 : pr->n_iterations;
   const int robust = pr->robust ? 2 : 0;
 
-  // ---- active structure (sparse_optimizer.cpp:206-267, 166-190), as local_ba_impl's host loop builds it
-  std::vector<int> pose_h(P), pt_h(L), pose_of_h, pt_of_h;
-  {
-    std::vector<uint8_t> pa(P, 0), la(L, 0);
-    for (int e = 0; e < E; ++e) { pa[pr->e_pose[e]] = 1; la[pr->e_point[e]] = 1; }
-    for (int p = 0; p < P; ++p) { pose_h[p] = -1; if (pa[p] && !pr->fixed[p]) { pose_h[p] = (int)pose_of_h.size(); pose_of_h.push_back(p); } }
-    for (int l = 0; l < L; ++l) { pt_h[l] = -1; if (la[l]) { pt_h[l] = (int)pt_of_h.size(); pt_of_h.push_back(l); } }
-  }
-  const int nPf = (int)pose_of_h.size(), nLa = (int)pt_of_h.size(), Ea = E;
+  // ---- active structure (sparse_optimizer.cpp:206-267, 166-190)
+  BaStructure hs;
+  hs.count(P, L, E, pr->e_pose, pr->e_point, pr->fixed);
+  const int nPf = hs.nPf, nLa = hs.nLa, Ea = hs.Ea;
   if (nPf == 0) {
     ctx->set_error("asd_bundle_adjustment: %d edges but no free pose among their keyframes (the reference stops on an assertion of BlockSolver::resize)", E);
     return ASD_ERR_INVALID;
   }
-  // edges grouped by landmark (CSR), inside a landmark ordered by pose h-index (fixed poses first), stable
-  std::vector<int> pt_start(nLa + 1, 0), act(Ea), ph_of_k(Ea), cursor;
-  for (int e = 0; e < E; ++e) ++pt_start[pt_h[pr->e_point[e]] + 1];
-  for (int h = 0; h < nLa; ++h) pt_start[h + 1] += pt_start[h];
-  cursor.assign(pt_start.begin(), pt_start.end() - 1);
-  for (int e = 0; e < E; ++e) act[cursor[pt_h[pr->e_point[e]]]++] = e;
-  for (int h = 0; h < nLa; ++h) {
-    const int s0 = pt_start[h], s1 = pt_start[h + 1];
-    for (int a = s0; a < s1; ++a) ph_of_k[a] = pose_h[pr->e_pose[act[a]]];
-    for (int a = s0 + 1; a < s1; ++a) {
-      const int ea = act[a], pa_ = ph_of_k[a];
-      int b = a - 1;
-      while (b >= s0 && ph_of_k[b] > pa_) { act[b + 1] = act[b]; ph_of_k[b + 1] = ph_of_k[b]; --b; }
-      act[b + 1] = ea; ph_of_k[b + 1] = pa_;
-    }
-  }
-  // per free pose: its edges (k indices) in k order, and the landmark of each
-  std::vector<int> ps_start(nPf + 1, 0);
-  for (int k = 0; k < Ea; ++k) if (ph_of_k[k] >= 0) ++ps_start[ph_of_k[k] + 1];
-  for (int h = 0; h < nPf; ++h) ps_start[h + 1] += ps_start[h];
-  std::vector<int> ps_edges(std::max(ps_start[nPf], 1), 0), ps_hv(std::max(ps_start[nPf], 1), 0);
-  cursor.assign(ps_start.begin(), ps_start.end() - 1);
-  for (int h = 0; h < nLa; ++h)
-    for (int k = pt_start[h]; k < pt_start[h + 1]; ++k)
-      if (ph_of_k[k] >= 0) { const int o = cursor[ph_of_k[k]]++; ps_edges[o] = k; ps_hv[o] = h; }
-
   // the form of the dense solve
   const bool tiled = ctx->gba_solve == 1 || (ctx->gba_solve == 0 && nPf >= ASD_GBA_TILED_FROM);
   const int form = tiled ? 3 : ba_dense_form(nPf);
-  const bool all_blocks = form <= 1;   // the LDS solvers read the packed system whole: every upper block gets its workgroup, as in LocalBA
-  // Schur pair lists per upper block (bi <= bj).  A diagonal block always has a workgroup (Hpp + lambda I); an off-diagonal block
-  // only when a landmark connects its two poses -- a map's covisibility is banded, at 1024 free poses the dense triangle would be
-  // 525 k workgroups for a few thousand blocks with pairs.  The blocks left out are cleared by k_gba_clear in front of every Schur pass.
-  const int nblk_all = nPf * (nPf + 1) / 2;
-  std::vector<int> row_off(nPf), cnt(nblk_all, 0);
-  for (int i = 0; i < nPf; ++i) row_off[i] = i * nPf - i * (i - 1) / 2 - i;   // block id = row_off[i] + j
-  size_t npairs_total = 0;
-  for (int h = 0; h < nLa; ++h) {
-    const int s1 = pt_start[h + 1];
-    int a = pt_start[h];
-    while (a < s1 && ph_of_k[a] < 0) ++a;
-    for (; a < s1; ++a) {
-      const int ro = row_off[ph_of_k[a]];
-      for (int b = a; b < s1; ++b) { const int add = 1 + (b != a && ph_of_k[b] == ph_of_k[a]); cnt[ro + ph_of_k[b]] += add; npairs_total += add; }
-    }
-  }
-  if (npairs_total > (size_t)1 << 30) { ctx->set_error("asd_bundle_adjustment: %zu Schur pairs exceed 2^30", npairs_total); return ASD_ERR_CAPACITY; }
-  std::vector<int> cid(nblk_all, -1), blk_i, blk_j, pair_start(1, 0);
-  for (int i = 0; i < nPf; ++i)
-    for (int j = i; j < nPf; ++j) {
-      const int q = row_off[i] + j;
-      if (!all_blocks && i != j && cnt[q] == 0) continue;
-      cid[q] = (int)blk_i.size();
-      blk_i.push_back(i); blk_j.push_back(j);
-      pair_start.push_back(pair_start.back() + cnt[q]);
-    }
-  const int nblk = (int)blk_i.size();
-  const size_t npairs = std::max(npairs_total, (size_t)1);
+  // The LDS solvers read the packed system whole: every upper block gets its workgroup, as in LocalBA.  Otherwise a diagonal block
+  // always has one (Hpp + lambda I), an off-diagonal block only when a landmark connects its two poses -- a map's covisibility is
+  // banded, at 1024 free poses the dense triangle would be 525 k workgroups for a few thousand blocks with pairs.  The blocks left
+  // out are cleared by k_gba_clear in front of every Schur pass.
+  const bool all_blocks = form <= 1;
+  hs.select_blocks(all_blocks);
+  if (hs.npairs > (size_t)1 << 30) { ctx->set_error("asd_bundle_adjustment: %zu Schur pairs exceed 2^30", hs.npairs); return ASD_ERR_CAPACITY; }
+  const int nblk = hs.nblk, nblk_all = nPf * (nPf + 1) / 2;
 
-  // ---- buffers
-#define ENS(buf, bytes) if ((rc = s->buf.ensure(ctx, (bytes))) != ASD_OK) return rc
-  const int n = 6 * nPf;
-  ENS(pose, (size_t)P * sizeof(Pose7)); ENS(pose_bak, (size_t)P * sizeof(Pose7));
-  ENS(pts, (size_t)L * 24); ENS(pts_bak, (size_t)L * 24);
-  ENS(e_pt, (size_t)E * 4); ENS(e_ps, (size_t)E * 4); ENS(obs, (size_t)E * 16); ENS(info, (size_t)E * 8);
-  ENS(err, (size_t)E * 16); ENS(lvl, (size_t)E);
-  ENS(Bk, (size_t)E * 18 * 8); ENS(Hc, (size_t)E * 27 * 8); ENS(Hl, (size_t)E * 9 * 8); ENS(Hpp, (size_t)nPf * 27 * 8); ENS(Hll, (size_t)nLa * 9 * 8);
-  ENS(x, ((size_t)6 * nPf + 3 * nLa) * 8); ENS(A, (size_t)n * n * 8); ENS(bs, (size_t)n * 8);
-  if (all_blocks) ENS(Apack, (size_t)18 * nPf * (nPf + 1) * 8);
-  ENS(chi2, (size_t)E * 8); ENS(dpos, (size_t)E); ENS(HppPart, (size_t)nPf * kPoseSplit * 27 * 8);
-  ENS(misc, (size_t)std::max(iterations, 1) * 4);
+  // ---- buffers, the structure in one pinned block, and the upload: the problem, then the block in one copy
   const int gE = (Ea + 255) / 256, gL = (nLa + 255) / 256, gP = std::max((nPf + 255) / 256, 1);
-  const size_t npartial = (size_t)gE + gL + gP + 8;
-  ENS(partial, npartial * 8);
-  if (s->h_partial_cap < npartial) {
-    if (s->h_partial) (void)hipHostFree(s->h_partial);
-    s->h_partial = nullptr; s->h_partial_cap = 0;
-    ASD_HIP_CHECK(ctx, hipHostMalloc(&s->h_partial, npartial * 2 * 8));
-    s->h_partial_cap = npartial * 2;
-  }
-  if (!s->h_lm) ASD_HIP_CHECK(ctx, hipHostMalloc(reinterpret_cast<void**>(&s->h_lm), sizeof(LmState)));
-  ENS(lm, sizeof(LmState) + 64 + sizeof(LmLog) * kLmLogCap + sizeof(int) * ((size_t)P + 2));
-  // the structure in one pinned block, one upload
-  size_t off = 0;
-  auto place = [&](size_t bytes) { const size_t o = off; off += (bytes + 255) / 256 * 256; return o; };
-  const size_t o_act = place((size_t)Ea * 4), o_pose_h = place((size_t)P * 4), o_pt_h = place((size_t)L * 4), o_pose_of_h = place((size_t)nPf * 4),
-               o_pt_of_h = place((size_t)nLa * 4), o_pt_start = place((size_t)(nLa + 1) * 4), o_ps_start = place((size_t)(nPf + 1) * 4),
-               o_ps_edges = place(ps_edges.size() * 4), o_ps_h = place(ps_edges.size() * 4), o_blk_i = place((size_t)nblk * 4),
-               o_blk_j = place((size_t)nblk * 4), o_pair_start = place((size_t)(nblk + 1) * 4), o_pairs = place(npairs * 8), o_pair_h = place(npairs * 4);
-  ENS(sblk, off);
-#undef ENS
-  if (s->h_sblk_cap < off) {
-    if (s->h_sblk) (void)hipHostFree(s->h_sblk);
-    s->h_sblk = nullptr; s->h_sblk_cap = 0;
-    ASD_HIP_CHECK(ctx, hipHostMalloc(reinterpret_cast<void**>(&s->h_sblk), off + off / 4));
-    s->h_sblk_cap = off + off / 4;
-  }
-  char* hb = s->h_sblk;
-  auto put = [&](size_t o, const std::vector<int>& v) { if (!v.empty()) memcpy(hb + o, v.data(), v.size() * 4); };
-  put(o_act, act); put(o_pose_h, pose_h); put(o_pt_h, pt_h); put(o_pose_of_h, pose_of_h); put(o_pt_of_h, pt_of_h); put(o_pt_start, pt_start);
-  put(o_ps_start, ps_start); put(o_ps_edges, ps_edges); put(o_ps_h, ps_hv); put(o_blk_i, blk_i); put(o_blk_j, blk_j); put(o_pair_start, pair_start);
-  {
-    int2* pp = reinterpret_cast<int2*>(hb + o_pairs);
-    int* ph_ = reinterpret_cast<int*>(hb + o_pair_h);
-    cursor.assign(pair_start.begin(), pair_start.end() - 1);
-    for (int h = 0; h < nLa; ++h) {
-      const int s1 = pt_start[h + 1];
-      int a = pt_start[h];
-      while (a < s1 && ph_of_k[a] < 0) ++a;
-      for (; a < s1; ++a) {
-        const int ro = row_off[ph_of_k[a]];
-        for (int b = a; b < s1; ++b) {
-          const int c = cid[ro + ph_of_k[b]];
-          const int o = cursor[c]++; pp[o] = make_int2(a, b); ph_[o] = h;
-          // two edges of one pose (a duplicate observation): the diagonal block needs both cross terms (see local_ba_impl)
-          if (b != a && ph_of_k[b] == ph_of_k[a]) { const int o2 = cursor[c]++; pp[o2] = make_int2(b, a); ph_[o2] = h; }
-        }
-      }
-    }
-  }
-
-  // ---- upload; both estimate buffers start as the input (vertices no trial writes must read the same in both)
-  ASD_HIP_CHECK(ctx, hipMemcpyAsync(s->pose.p, hp.data(), (size_t)P * sizeof(Pose7), hipMemcpyHostToDevice, st));
-  ASD_HIP_CHECK(ctx, hipMemcpyAsync(s->pts.p, pr->points, (size_t)L * 24, hipMemcpyHostToDevice, st));
-  ASD_HIP_CHECK(ctx, hipMemcpyAsync(s->pose_bak.p, s->pose.p, (size_t)P * sizeof(Pose7), hipMemcpyDeviceToDevice, st));
-  ASD_HIP_CHECK(ctx, hipMemcpyAsync(s->pts_bak.p, s->pts.p, (size_t)L * 24, hipMemcpyDeviceToDevice, st));
-  ASD_HIP_CHECK(ctx, hipMemsetAsync(s->lm.p, 0, sizeof(LmState), st));   // lm->cur = 0
-  ASD_HIP_CHECK(ctx, hipMemcpyAsync(s->e_pt.p, pr->e_point, (size_t)E * 4, hipMemcpyHostToDevice, st));
-  ASD_HIP_CHECK(ctx, hipMemcpyAsync(s->e_ps.p, pr->e_pose, (size_t)E * 4, hipMemcpyHostToDevice, st));
-  ASD_HIP_CHECK(ctx, hipMemcpyAsync(s->obs.p, pr->e_obs, (size_t)E * 16, hipMemcpyHostToDevice, st));
-  ASD_HIP_CHECK(ctx, hipMemcpyAsync(s->info.p, pr->e_info, (size_t)E * 8, hipMemcpyHostToDevice, st));
-  ASD_HIP_CHECK(ctx, hipMemsetAsync(s->err.p, 0, (size_t)E * 16, st));
-  ASD_HIP_CHECK(ctx, hipMemsetAsync(s->lvl.p, 0, (size_t)E, st));   // no levels: every edge takes part
-  ASD_HIP_CHECK(ctx, hipMemcpyAsync(s->sblk.p, hb, off, hipMemcpyHostToDevice, st));
+  const BaSizes z{(size_t)nPf, (size_t)nLa, (size_t)nPf, all_blocks, (size_t)std::max(iterations, 1) * 4, (size_t)gE + gL + gP + 8};
+  const BaStructLayout lay = hs.layout();
+  BaDev d;
+  SchurBlocks sb{};
+  if ((rc = ba_setup_upload(ctx, s, pr, hp, z, st)) != ASD_OK) return rc;
+  if ((rc = ba_structure_stage(ctx, s, hs, lay)) != ASD_OK) return rc;
+  ASD_HIP_CHECK(ctx, hipMemcpyAsync(s->sblk.p, s->h_sblk, lay.bytes, hipMemcpyHostToDevice, st));
   ASD_HIP_CHECK(ctx, hipEventRecord(ctx->ev0, st));
-
-  BaDev d{};
-  d.P = P; d.L = L; d.E = E;
-  d.pose[0] = s->pose.as<Pose7>(); d.pose[1] = s->pose_bak.as<Pose7>();
-  d.pts[0] = s->pts.as<double>(); d.pts[1] = s->pts_bak.as<double>();
-  d.e_pt = s->e_pt.as<int>(); d.e_ps = s->e_ps.as<int>(); d.obs = s->obs.as<double>(); d.info = s->info.as<double>();
-  d.err = s->err.as<double>(); d.lvl = s->lvl.as<uint8_t>(); d.HppPart = s->HppPart.as<double>();
-  d.fx = pr->K[0]; d.fy = pr->K[1]; d.cx = pr->K[2]; d.cy = pr->K[3];
-  char* db = s->sblk.as<char>();
-  d.act = reinterpret_cast<const int*>(db + o_act); d.pose_h = reinterpret_cast<const int*>(db + o_pose_h); d.pt_h = reinterpret_cast<const int*>(db + o_pt_h);
-  d.pose_of_h = reinterpret_cast<const int*>(db + o_pose_of_h); d.pt_of_h = reinterpret_cast<const int*>(db + o_pt_of_h);
-  d.pt_start = reinterpret_cast<const int*>(db + o_pt_start); d.ps_start = reinterpret_cast<const int*>(db + o_ps_start);
-  d.ps_edges = reinterpret_cast<const int*>(db + o_ps_edges); d.ps_h = reinterpret_cast<const int*>(db + o_ps_h);
-  const SchurBlocks sb{reinterpret_cast<const int*>(db + o_blk_i), reinterpret_cast<const int*>(db + o_blk_j), reinterpret_cast<const int*>(db + o_pair_start),
-                       reinterpret_cast<const int2*>(db + o_pairs), reinterpret_cast<const int*>(db + o_pair_h)};
-  d.Bk = s->Bk.as<double>(); d.Hc = s->Hc.as<double>(); d.Hl = s->Hl.as<double>(); d.Hpp = s->Hpp.as<double>(); d.Hll = s->Hll.as<double>();
-  d.x = s->x.as<double>(); d.A = s->A.as<double>(); d.Apack = all_blocks ? s->Apack.as<double>() : nullptr; d.bs = s->bs.as<double>();
-  d.lm = s->lm.as<LmState>();
-  d.lm_host = s->h_lm;
-  d.lm_log = reinterpret_cast<LmLog*>(s->lm.as<char>() + sizeof(LmState) + 64 - (sizeof(LmState) % 8));
-  d.partial = s->partial.as<double>();
-  d.tickets = reinterpret_cast<int*>(reinterpret_cast<char*>(d.lm_log) + sizeof(LmLog) * kLmLogCap);
-  ASD_HIP_CHECK(ctx, hipMemsetAsync(d.tickets, 0, sizeof(int) * ((size_t)P + 2), st));
+  if ((rc = ba_setup_bind(ctx, s, pr, z, st, d)) != ASD_OK) return rc;
+  ba_bind_structure(d, sb, s->sblk.as<char>(), lay);
   d.Ea = Ea; d.nPf = nPf; d.nLa = nLa;
   d.gE = gE; d.gL = gL; d.gP = gP; d.scale_off = gE;
   d.wide = 1;
   d.it_trials = s->misc.as<int>();
   s->gba_forms[0] = form; s->gba_forms[1] = nPf; s->gba_forms[2] = nLa; s->gba_forms[3] = Ea; s->gba_forms[4] = tiled ? gba_tile_count(nPf) : 0;
 
-  // ---- one Levenberg trial as the device sees it (see local_ba_impl: blocks behind the round's end are no-ops)
-  auto enqueue_block = [&]() -> int {
-    int r2;
-    hipLaunchKernelGGL(k_ba_linearize, dim3(gE), dim3(256), 0, st, d, robust);
-    hipLaunchKernelGGL(k_ba_reduce, dim3(nPf * kPoseSplit + gL), dim3(256), 0, st, d);
-    if (!all_blocks && (r2 = gba_clear_enqueue(ctx, st, d.A, n, &d.lm->done)) != ASD_OK) return r2;
-    hipLaunchKernelGGL(k_ba_schur, dim3(nblk + nPf), dim3(kSchurThreads), 0, st, d, sb, nblk);
-    if (form == 3) {
-      if ((r2 = gba_solve_enqueue(ctx, st, d.A, d.bs, d.x, n, &d.lm->done, &d.lm->chol_ok, !ctx->gba_update_fma)) != ASD_OK) return r2;
-    } else {
-      if ((r2 = ba_dense_enqueue(ctx, st, form, d.Apack, d.A, d.bs, d.x, n, d.lm)) != ASD_OK) return r2;
-    }
-    hipLaunchKernelGGL(k_ba_step, dim3(gL + gP), dim3(256), 0, st, d);
-    hipLaunchKernelGGL(k_ba_error, dim3(gE), dim3(256), 0, st, d, robust, 0, 0);   // + the Levenberg control, in its last workgroup
-    ASD_HIP_CHECK(ctx, hipGetLastError());
-    return ASD_OK;
-  };
+  const BaTrial trial{form, all_blocks, nblk, sb, robust};
   // computeActiveErrors + activeRobustChi2 at the first estimate (levenberg.cpp:70-76), state reset
   hipLaunchKernelGGL(k_ba_error, dim3(gE), dim3(256), 0, st, d, robust, 1, iterations);
   ASD_HIP_CHECK(ctx, hipGetLastError());
@@ -3263,7 +3040,7 @@ int gba_impl(asd_ctx* ctx, BaState* s, asd_gba_problem* pr, asd_gba_result* res)
   bool stopped = false, finished = iterations <= 0;
   while (!finished && enqueued < max_trials) {
     if (pr->stop && *pr->stop) { stopped = true; break; }
-    for (int b = 0; b < kGbaChunk; ++b) if ((rc = enqueue_block()) != ASD_OK) return rc;
+    for (int b = 0; b < kGbaChunk; ++b) if ((rc = ba_enqueue_trial(ctx, st, d, trial)) != ASD_OK) return rc;
     enqueued += kGbaChunk;
     ASD_HIP_CHECK(ctx, hipStreamSynchronize(st));
     finished = s->h_lm->done != 0;
@@ -3287,15 +3064,10 @@ int gba_impl(asd_ctx* ctx, BaState* s, asd_gba_problem* pr, asd_gba_result* res)
   if (iters > 0) ASD_HIP_CHECK(ctx, hipMemcpyAsync(s->gba_trials.data(), s->misc.p, (size_t)iters * 4, hipMemcpyDeviceToHost, st));
   ASD_HIP_CHECK(ctx, hipStreamSynchronize(st));
   ASD_HIP_CHECK(ctx, hipEventElapsedTime(&ctx->ms_ba, ctx->ev0, ctx->ev1));
-  poses_out();
-  double sum = 0;
-  for (int i = 0; i < gE; ++i) sum += s->h_partial[i];
-  res->chi2 = sum; res->iterations = iters; res->trials = trials;
+  poses_unpack(hp, pr->poses);
+  res->chi2 = ba_chi2_sum(s, gE); res->iterations = iters; res->trials = trials;
   if (getenv("ASD_BA_DEBUG")) {
-    std::vector<LmLog> lg(kLmLogCap);
-    ASD_HIP_CHECK(ctx, hipMemcpy(lg.data(), d.lm_log, sizeof(LmLog) * kLmLogCap, hipMemcpyDeviceToHost));
-    for (int q = 0; q < std::min(trials, kLmLogCap); ++q)
-      fprintf(stderr, "[gba] trial %d lambda=%.6e cur=%.9e temp=%.9e scale=%.6e\n", q, lg[q].lambda, lg[q].cur, lg[q].temp, lg[q].scale);
+    if ((rc = ba_debug_trials(ctx, d, trials, "gba", "")) != ASD_OK) return rc;
     fprintf(stderr, "[gba] form %d nPf=%d nLa=%d Ea=%d blocks=%d of %d: %d iterations, %d trials, %d blocks enqueued\n", form, nPf, nLa, Ea, nblk, nblk_all, iters, trials, enqueued);
   }
   return ASD_OK;
