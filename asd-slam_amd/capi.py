@@ -29,6 +29,8 @@ class asd_config(C.Structure):
                 ("max_height", C.c_int32), ("max_patches", C.c_int32), ("device", C.c_int32)]
 
 
+BANK_MAX_ROWS = 1 << 22   # ASD_BANK_MAX_ROWS (include/asd_slam.h): rows of the descriptor and attribute banks
+
 KP_DTYPE = np.dtype([("x", np.float32), ("y", np.float32), ("size", np.float32), ("angle", np.float32),
                      ("response", np.float32), ("octave", np.int32)])
 
@@ -1033,6 +1035,15 @@ class AsdHip:
 
     def bank_put_from_frame(self, slot, first_row, n):
         self._chk(self.lib.asd_bank_put_from_frame(self.ctx, slot, first_row, n))
+
+    def bank_get(self, first_row, n, desc=True, attr=True):
+        """asd_debug_bank_get: rows [first_row, first_row + n) of the banks as a consumer reads them (the context's stream only) ->
+        (descriptors [n, 128] f32 or None, attributes [n, 8] f32 = Xw, normal, min_dist, max_dist or None)"""
+        d = np.empty((max(n, 0), 128), np.float32) if desc else None
+        a = np.empty((max(n, 0), 8), np.float32) if attr else None
+        self.lib.asd_debug_bank_get.restype = C.c_int32
+        self._chk(self.lib.asd_debug_bank_get(self.ctx, C.c_int32(first_row), C.c_int32(n), _p(d), _p(a)))
+        return d, a
 
     def match_project_frame_bank(self, slot_cur, slot_last, n_cur, has_mp, Xw, mp_rows, Tcw, K, th, check_ori=True, obs_positive=None):
         has_mp, Xw, mp_rows = _c(has_mp, np.uint8), _c(Xw, np.float32), _c(mp_rows, np.int32)

@@ -134,7 +134,14 @@ void asd_track_set_fused(asd_track_handle* h, int32_t on) { if (h) h->fused = on
 void asd_track_set_async_ba(asd_track_handle* h, int32_t on) { if (h) h->async_ba = on != 0; }
 void asd_track_set_split(asd_track_handle* h, int32_t on) { if (h) h->split = on != 0; }
 void asd_track_set_chain(asd_track_handle* h, int32_t on) { if (h) h->chain = on != 0; }
-void asd_track_set_map_copies(asd_track_handle* h, int32_t copies) { if (h && copies >= 1 && copies <= 16) h->map_copies = copies; }
+// A frame prepared under the old count has the old count's bank rows and tables: it is forgotten, the next step prepares its frame again
+// (from a synchronous extraction: the read-ahead result was consumed when the frame was prepared)
+void asd_track_set_map_copies(asd_track_handle* h, int32_t copies) {
+  if (!h || copies < 1 || copies > 16 || copies == h->map_copies) return;
+  h->map_copies = copies;
+  h->prep_t = -1;
+  h->tables_for = -1;
+}
 // hands every read-ahead submission of this handle back to the library (another handle of the same context can then start)
 int asd_track_drain(asd_track_handle* h) {
   if (!h) return ASD_ERR_INVALID;
@@ -313,7 +320,7 @@ static int prepare_frame(asd_track_handle* h, int t, const std::vector<int>& nex
     }
   }
   seg(1);
-  if (h->have_last && chain) {
+  if (h->have_last) {   // (both callers are split-phase steps: `chain` holds)
     // the map this frame is tracked against, written beside the previous frame's stages: the other bank region (rows the stages in
     // flight do not read) takes the last frame's points -- descriptors device to device, attributes from the host -- and a displaced copy
     const std::vector<asd_keypoint>& lk = h->last_kps;
@@ -341,32 +348,6 @@ static int prepare_frame(asd_track_handle* h, int t, const std::vector<int>& nex
     h->rows.resize(nl); h->last_cand.resize(nl); h->cand_rows.resize(n2p);
     for (int i = 0; i < nl; ++i) { h->rows[i] = base + i; h->last_cand[i] = i; }
     for (int i = 0; i < n2p; ++i) h->cand_rows[i] = base + i;
-    h->tables_for = t;
-    seg(2);
-  } else if (h->have_last) {
-    const std::vector<asd_keypoint>& lk = h->last_kps;
-    const int nl = (int)lk.size();
-    const float fx = h->K32[0], fy = h->K32[1], cx = h->K32[2], cy = h->K32[3];
-    // (default drift: exactly bench.py's predicted_uv -- z = 1.003f, c3 = (float)(3 * 1.003), c02 = (float)(0.2 * 1.003))
-    const float z = h->drift_z, c3 = (float)((double)h->drift_dx * (double)(h->drift_z == 1.003f ? 1.003 : (double)h->drift_z)),
-                c02 = (float)((double)(h->drift_dy == 0.2f ? 0.2 : (double)h->drift_dy) * (double)(h->drift_z == 1.003f ? 1.003 : (double)h->drift_z)), depth = 20.0f;
-    h->Xw.resize((size_t)3 * nl);
-    for (int i = 0; i < nl; ++i) {
-      const float u = (lk[i].x - h->drift_cx) * z + h->drift_cx - c3;
-      const float v = (lk[i].y - h->drift_cy) * z + h->drift_cy - c02;
-      h->Xw[3 * i + 0] = (u - cx) / fx * depth;
-      h->Xw[3 * i + 1] = (v - cy) / fy * depth;
-      h->Xw[3 * i + 2] = depth;
-    }
-    seg(7);
-    for (int c = 0; c < h->map_copies; ++c)
-      if ((rc = asd_bank_put_from_frame(ctx, h->last_slot, c * nl, nl)) != ASD_OK) return rc;
-    h->rows.resize((size_t)h->map_copies * nl);
-    for (int i = 0; i < h->map_copies * nl; ++i) h->rows[i] = i;
-    // the candidates' attributes (MapPoint::mWorldPos, mNormalVector, mfMin/MaxDistance: they exist before the frame is tracked) into the
-    // attribute bank, rows as the descriptors': the local-map stage then names its points by row (asd_track_local_points_rows)
-    build_candidate_tables(h, nl);
-    if ((rc = asd_mpbank_put(ctx, 0, h->map_copies * nl, h->Xw2.data(), h->nrm.data(), h->mind.data(), h->maxd.data())) != ASD_OK) return rc;
     h->tables_for = t;
     seg(2);
   }

@@ -29,10 +29,11 @@ void asd_track_destroy(asd_track_handle* h);
 void asd_track_set_fused(asd_track_handle* h, int32_t on);
 void asd_track_set_async_ba(asd_track_handle* h, int32_t on);   /* 1 = LocalBA on the optional lane (NOT the reference's order) */
 void asd_track_set_split(asd_track_handle* h, int32_t on);
-/* 1 (default, with fused + split): both stages as one submission (asd_track_frame), the next frame constructed on the context's second
- * stream beside them (asd_prep_async); 0 = two submissions with the host in between */
+/* 1 (with fused + split): both stages as one submission (asd_track_frame); 0 (default) = two submissions with the host in between.  Either
+ * way the split-phase step constructs the next frame on the context's second stream beside the stages (asd_prep_async) */
 void asd_track_set_chain(asd_track_handle* h, int32_t on);
-/* the stand-in local map holds `copies` candidates per point of the last frame (default 2; bench.py's local_map_sweep: 2 / 4 / 8 = 4 k / 8 k / 16 k candidates) */
+/* the stand-in local map holds `copies` candidates per point of the last frame (default 2; bench.py's local_map_sweep: 2 / 4 / 8 = 4 k / 8 k / 16 k candidates).
+ * A frame already prepared under the old count is prepared again by the next step. */
 void asd_track_set_map_copies(asd_track_handle* h, int32_t copies);
 /* 1 = the frame pointers given to asd_track_create are page-locked HOST memory: every frame's image goes host -> device inside the step
  * (asd_extract_submit(device_resident = 0)), as kitti.cc:116-155 hands images over; 0 (default) = frames resident in HBM */

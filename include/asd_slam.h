@@ -252,7 +252,13 @@ int asd_match_project_points(asd_ctx* ctx, int32_t slot_cur, int32_t n_mp, const
  * (MapPoint::ComputeDistinctiveDescriptors, MapPoint.cc:330-337).  An integration that gives each
  * MapPoint a bank row uploads a descriptor when it changes and passes row ids per frame instead of
  * 512-byte descriptors: asd_match_project_frame_bank / asd_match_project_points_bank are
- * asd_match_project_frame / _points with `rows` in place of the descriptor table. */
+ * asd_match_project_frame / _points with `rows` in place of the descriptor table.
+ * Rows: both banks (this one and the attribute bank of asd_mpbank_put) grow on demand, from 16384 rows, to hold every row written;
+ * first_row + n is summed in 64 bits and may not exceed ASD_BANK_MAX_ROWS (ASD_ERR_CAPACITY, asd_last_error names the limit; nothing
+ * is allocated or enqueued then).  A negative first_row or n is ASD_ERR_INVALID.  Growth waits for EVERY stream of the context -- the
+ * second stream of an asd_prep_async bracket included -- before the old rows are carried over, so no row written earlier is lost,
+ * whichever stream its write was enqueued on. */
+#define ASD_BANK_MAX_ROWS (1 << 22) /* 2 GiB of descriptors */
 int asd_bank_put(asd_ctx* ctx, int32_t first_row, int32_t n, const float* desc);
 /* bank[first_row + i] = descriptor of keypoint i of frame `slot`, i in [0, n): device to device */
 int asd_bank_put_from_frame(asd_ctx* ctx, int32_t slot, int32_t first_row, int32_t n);
@@ -352,7 +358,7 @@ int asd_mpbank_put(asd_ctx* ctx, int32_t first_row, int32_t n, const float* Xw, 
  * pose7: in = SE3Quat of the predicted pose, out = the local-map stage's optimum; pose1 = the motion-model stage's.  The
  * control flow stays with the caller as before: if the motion-model stage made too few matches (nmatches < 20,
  * Tracking.cc:681-685) it discards match2 / pose7 and runs the retry with the separate calls.  Sizes beyond the one-submission
- * form (more than 4096 last-frame keypoints, more ACTIVE local-map lists than one replay workgroup takes, frames beyond the
+ * form (more than 4096 last-frame points, more than 32768 candidates, frames beyond the
  * solver's LDS form) return ASD_ERR_CAPACITY: use the two calls.  Honours asd_track_async / asd_track_finish.
  * (asd_update_local_map makes that decision on the device from a resident table: running it between the two stages inside this call, which
  * would meet the precondition, is left to a later change.) */
@@ -383,7 +389,14 @@ int asd_track_frame(asd_ctx* ctx, const asd_track_frame_args* args);
  * behind the outstanding asd_track_* stage (the reference's Frame constructor runs before the frame is tracked, not after the
  * previous one: Tracking.cc:96-118); closing the bracket orders everything enqueued on the context AFTERWARDS behind it.  The
  * caller guarantees what ordering on one stream gave for free: nothing written inside the bracket (the frame slot, the bank
- * rows) is read by a stage still in flight. */
+ * rows) is read by a stage still in flight.
+ * What the bracket does NOT order: opening it does not put the second stream behind work already enqueued on the context's stream.
+ * A frame slot written OUTSIDE a bracket must therefore be complete -- some call that waits for the context's stream (a matcher or
+ * asd_track_* call run to completion, asd_track_finish, asd_bank_put, asd_extract_device) or for work ordered behind the slot's copies
+ * (asd_extract_wait* of a submission made after the asd_frame_set: submissions wait for the adoption copy) has returned since -- before
+ * a call inside a bracket reads it (asd_bank_put_from_frame's source slot).  The host loop of host/track_loop.cpp behaves this way:
+ * the only frame it sets outside a bracket is the first of a run, and the bracket that reads that slot first takes the next frame's
+ * extraction, submitted or run after it. */
 int asd_prep_async(asd_ctx* ctx, int32_t on);
 
 /* Split-phase execution of the asd_track_* calls.  asd_track_async(ctx) arms the NEXT asd_track_motion_model[_bank] /
@@ -1434,6 +1447,13 @@ int asd_map_observations(asd_ctx* ctx, int32_t n, const int32_t* rows, int32_t* 
 /* Test aid: out = {live keyframes, live entries, slot capacity, arena capacity, row-table capacity, growths of the slot table, of the arena,
  * of the row tables}. */
 int32_t asd_debug_map(asd_ctx* ctx, int64_t out[8]);
+
+/* Test aid: rows [first_row, first_row + n) of the descriptor bank (desc[n][128], or NULL) and of the attribute bank (attr[n][8] = Xw,
+ * normal, min_dist, max_dist as asd_mpbank_put stored them, or NULL), read as a consumer reads them: the copies are enqueued on the
+ * context's stream and that stream alone is waited for -- NOT the second stream of asd_prep_async, so a bracket that does not order its
+ * writes shows.  ASD_ERR_INVALID for rows outside the respective bank's capacity, while a bracket is open and while a call started with
+ * asd_track_async is outstanding.  A row never written holds whatever the allocation held. */
+int32_t asd_debug_bank_get(asd_ctx* ctx, int32_t first_row, int32_t n, float* desc, float* attr);
 
 /* Runs `reps` back-to-back repetitions of the ASDNet forward on resident buffers and
  * returns the average per-repetition device time (hipEvents on the ctx stream). */

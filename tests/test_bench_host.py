@@ -4,6 +4,7 @@ import importlib.util
 import os
 import sys
 
+import numpy as np
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -65,6 +66,71 @@ def test_cxx_host_equals_python_host(pkg, pipeline, fused, async_ba, split, chai
     finally:
         cx.close()
     assert whole == ref[-1]
+
+
+@pytest.mark.gpu
+def test_cxx_host_bank_growth_and_map_copies(pkg):
+    """The native host in its default split form, 4 frames from t = 0 (no LocalBA among them).
+    Nine copies of ~2010 keypoints are more rows than a bank starts with, so both banks grow while the next frame is constructed inside
+    the asd_prep_async bracket, beside a stage in flight: the per-frame statistics must be those of a context whose banks were grown
+    beforehand (one row put at 140000 into each).  Like the bracket test of tests/test_banks.py this depends on timing: required to pass
+    with the growth that waits for every stream, never run without it.
+    asd_track_set_map_copies between two steps: the frame already prepared under the old count is prepared again -- 2 steps at 2 copies,
+    the count set to 5, 2 more steps, against a handle that had the count set before each step with nothing prepared ahead."""
+    bench = _bench()
+    wl = bench.Workload(pkg.synth)
+    frames = range(4)
+    assert all(t % bench.KF_INTERVAL != bench.KF_INTERVAL - 1 for t in frames)
+
+    def backend(pregrown):
+        be = bench.HipBackend(pkg, wl, 0, pipeline=True)
+        if pregrown:
+            be.hip.bank_put(140000, np.zeros((1, 128), np.float32))
+            be.hip.mpbank_put(140000, np.zeros((1, 3), np.float32), np.zeros((1, 3), np.float32), np.ones(1, np.float32), np.ones(1, np.float32))
+        return be
+
+    def with_handle(be, body):
+        nh = bench.NativeHost(pkg, be, wl, pipeline=True)   # the defaults: fused, split-phase, two submissions per frame
+        try:
+            out = body(nh)
+            nh.lib.asd_track_drain(nh.h)
+            return out
+        finally:
+            nh.close()
+
+    def nine_copies(nh):
+        nh.lib.asd_track_set_map_copies(nh.h, 9)
+        return [nh.run(t, 1, True) for t in frames]
+
+    def copies_changed_between_steps(nh):
+        out = [nh.run(t, 1, True) for t in (0, 1)]          # frame 2 is prepared under 2 copies when this returns
+        nh.lib.asd_track_set_map_copies(nh.h, 5)
+        return out + [nh.run(t, 1, True) for t in (2, 3)]
+
+    def copies_set_before_each_step(nh):
+        out = []
+        for t, copies in zip(frames, (2, 2, 5, 5)):
+            nh.lib.asd_track_set_map_copies(nh.h, copies)
+            out.append(nh.run(t, 1, False))                  # no read-ahead, nothing prepared beyond frame t
+        return out
+
+    be = backend(False)
+    try:
+        fresh = with_handle(be, nine_copies)
+    finally:
+        be.close()
+    be = backend(True)
+    try:
+        grown = with_handle(be, nine_copies)
+        changed = with_handle(be, copies_changed_between_steps)
+        stepwise = with_handle(be, copies_set_before_each_step)
+    finally:
+        be.close()
+    assert fresh == grown
+    assert all(s["m1"] > 500 and s["inliers"] > 500 for s in fresh[1:])
+    assert fresh[-1]["m2"] > 0
+    assert changed == stepwise
+    assert all(s["m1"] > 500 and s["inliers"] > 500 for s in changed[1:])
 
 
 @pytest.mark.gpu
