@@ -1,5 +1,5 @@
 // capi.cpp -- C ABI entry points of libasdhip: context, ASDNet, utilities.
-// (extractor: frontend.hip, matchers: matcher.hip, optimizer: ba.hip)
+// (extractor: frontend.hip, matchers: matcher.hip + matcher_replay.cpp + matcher_banks.cpp, optimizer: ba.hip)
 #include <cmath>
 #include <cstdlib>
 #include <cstring>

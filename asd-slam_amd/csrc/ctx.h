@@ -315,7 +315,7 @@ struct asd_ctx {
   // ---- frames
   AsdFrameSlot frames[ASD_MAX_FRAMES];
 
-  // ---- matcher scratch (state private to matcher.hip)
+  // ---- matcher scratch (MatcherState, matcher.h: shared by matcher.hip, matcher_replay.cpp and matcher_banks.cpp)
   void* matcher = nullptr;
 
   // ---- BA scratch (lazily grown)

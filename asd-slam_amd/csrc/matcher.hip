@@ -1,8 +1,9 @@
-// matcher.hip -- Frame grid (G1) and the per-frame ORBmatcher searches (M0-M2, M4 init, M5).
+// matcher.hip -- Frame grid (G1), every kernel of the ORBmatcher searches and the per-frame tracking stages (M0-M2).  The searches that
+// replay the reference's logic on the host (M4, M5, loop closing) are in matcher_replay.cpp, the banks in matcher_banks.cpp (matcher.h).
 //
 // Reference (src/vslam/src): Frame.cc:123-138,219-286 (grid), Frame.cc:160-217 (isInFrustum),
-// ORBmatcher.cc:1629-1650 (DescriptorDistance), :44-122, :1318-1452, :416-531 (searches),
-// :1584-1625 (ComputeThreeMaxima), MapPoint.cc:271-338 (ComputeDistinctiveDescriptors).
+// ORBmatcher.cc:1629-1650 (DescriptorDistance), :44-122, :1318-1452 (the tracking searches), :825-936 (Fuse),
+// MapPoint.cc:271-338 (ComputeDistinctiveDescriptors).
 //
 // Split of work.  The reference's searches are order-dependent: a keypoint claimed by an earlier
 // map point is skipped by later ones, best/second-best use strict '<' so the first candidate in
@@ -13,8 +14,8 @@
 // order (Frame::GetFeaturesInArea: ix outer, iy inner, insertion order inside a cell), compacts the
 // accepted candidates by ballot/prefix in that order and evaluates each candidate's squared L2 in
 // the reference's exact summation order (sequential f32, no FMA: -ffp-contract=off) from
-// descriptors resident in HBM; the host then replays the claim / ratio / rotation-histogram logic
-// over the per-query (index, distance) lists.
+// descriptors resident in HBM; the claim / ratio / rotation-histogram logic is then replayed over the
+// per-query (index, distance) lists: by k_resolve2 for the tracking stages, on the host (matcher_replay.cpp) elsewhere.
 // The all-pairs matrix (asd_dist_matrix) uses the same exact summation, tiled through LDS.
 #include <algorithm>
 #include <chrono>
@@ -24,7 +25,7 @@
 #include <functional>
 #include <memory>
 
-#include "ctx.h"
+#include "matcher.h"
 #include "resolve2.h"
 
 namespace {
@@ -32,8 +33,6 @@ namespace {
 // (TH_HIGH, TH_LOW, HISTO, kTop: resolve2.h)
 constexpr int GC = ASD_GRID_COLS, GR = ASD_GRID_ROWS;
 
-// A window query = one GetFeaturesInArea call + the descriptor it is matched against.
-using WinQuery = AsdWinQuery;   // (ctx.h: the solver's tail makes queries too)
 struct GridDev {
   const float4* kp;        // (x, y, octave as int bits, angle) per keypoint
   const int* cell_start;   // [64*48+1], cell = ix*48 + iy
@@ -293,7 +292,6 @@ __global__ __launch_bounds__(64 * kSearchWaves) void k_window_search(GridDev G, 
 // Node-restricted search (BoW-guided matchers): query q is matched against the explicit candidate list
 // cand[cbeg[q] .. cend[q]) (the frame-2 members of the query's vocabulary node); distances land at
 // out[ooff[q] + t] in list order.  One wave per query, lanes over candidates.
-struct ListQuery { int qrow, cbeg, cend, ooff; };
 __global__ __launch_bounds__(256) void k_list_dist(const ListQuery* __restrict__ queries, int nq,
                                                    const int* __restrict__ cand, const float* __restrict__ qdesc,
                                                    const float* __restrict__ cdesc, float* __restrict__ out) {
@@ -566,106 +564,6 @@ __global__ __launch_bounds__(256) void k_project_queries(ProjectArgs a) {
 
 // (k_between's body lives in ctx.h: asd_between_body -- it runs as the tail of the motion-model stage's k_pose_opt)
 // ---- host helpers -------------------------------------------------------------------------
-inline void three_maxima(const int* cnt, int& ind1, int& ind2, int& ind3) {  // ORBmatcher.cc:1584-1625
-  int max1 = 0, max2 = 0, max3 = 0;
-  ind1 = ind2 = ind3 = -1;
-  for (int i = 0; i < HISTO; i++) {
-    const int s = cnt[i];
-    if (s > max1) { max3 = max2; max2 = max1; max1 = s; ind3 = ind2; ind2 = ind1; ind1 = i; }
-    else if (s > max2) { max3 = max2; max2 = s; ind3 = ind2; ind2 = i; }
-    else if (s > max3) { max3 = s; ind3 = i; }
-  }
-  if (max2 < 0.1f * (float)max1) { ind2 = -1; ind3 = -1; }
-  else if (max3 < 0.1f * (float)max1) { ind3 = -1; }
-}
-
-inline int rot_bin(float a1, float a2) {  // :1419-1425
-  float rot = a1 - a2;
-  if (rot < 0.0) rot += 360.0f;
-  int bin = (int)std::round(rot * (1.0f / HISTO));
-  if (bin == HISTO) bin = 0;
-  return bin;
-}
-
-// Frame::GetFeaturesInArea (Frame.cc:219-274) on the host CSR mirror (asd_frame_features_in_area only)
-void features_in_area(const AsdFrameSlot& F, float x, float y, float r, int minLevel, int maxLevel, std::vector<int>& out) {
-  const int nMinCellX = std::max(0, (int)std::floor((x - F.min_x - r) * F.inv_w));
-  if (nMinCellX >= GC) return;
-  const int nMaxCellX = std::min(GC - 1, (int)std::ceil((x - F.min_x + r) * F.inv_w));
-  if (nMaxCellX < 0) return;
-  const int nMinCellY = std::max(0, (int)std::floor((y - F.min_y - r) * F.inv_h));
-  if (nMinCellY >= GR) return;
-  const int nMaxCellY = std::min(GR - 1, (int)std::ceil((y - F.min_y + r) * F.inv_h));
-  if (nMaxCellY < 0) return;
-  const bool check = (minLevel > 0) || (maxLevel >= 0);
-  for (int ix = nMinCellX; ix <= nMaxCellX; ix++) {
-    const int b = F.cell_start[ix * GR + nMinCellY], e = F.cell_start[ix * GR + nMaxCellY + 1];
-    for (int t = b; t < e; ++t) {
-      const int idx = F.cell_items[t];
-      const asd_keypoint& kp = F.kps[idx];
-      if (check) {
-        if (kp.octave < minLevel) continue;
-        if (maxLevel >= 0 && kp.octave > maxLevel) continue;
-      }
-      const float dx = kp.x - x, dy = kp.y - y;
-      if (std::fabs(dx) < r && std::fabs(dy) < r) out.push_back(idx);
-    }
-  }
-}
-
-// cv::Mat Rcw*x + tcw (gemm 3x3*3x1 small-matrix path, A*B+C folded): left-to-right f32 dot, then + t
-inline void transform(const float* T, const float* X, float* out) {
-  for (int r = 0; r < 3; ++r) {
-    const float t0 = T[r * 4 + 0] * X[0] + T[r * 4 + 1] * X[1] + T[r * 4 + 2] * X[2];
-    out[r] = (float)((double)t0 + (double)T[r * 4 + 3]);
-  }
-}
-
-struct MatcherState {
-  int q_cap = 0, cand_cap = 0, h_cand_cap = 0, qdesc_cap = 0;   // cand_cap: device candidate buffers; h_cand_cap: their pinned host twins (host replay only)
-  int last_total[4] = {1 << 15, 1 << 15, 1 << 15, 1 << 15};  // candidates the previous search of each kind produced
-  WinQuery *d_queries = nullptr, *h_queries = nullptr;   // h_* pinned
-  int *d_q_off = nullptr, *d_q_cnt = nullptr, *d_total = nullptr, *d_idx = nullptr;
-  float* d_dist = nullptr;
-  int *h_q = nullptr;      // [2*q_cap + 1]: off, cnt, total
-  int* h_idx = nullptr;
-  float* h_dist = nullptr;
-  float *d_qdesc = nullptr, *h_qdesc = nullptr;
-  float* d_bank = nullptr;  // device-resident descriptor bank (MapPoint::mDescriptor rows)
-  int bank_cap = 0;
-  // map-point attribute bank, same row ids: [row][8] = mWorldPos, mNormalVector, mfMinDistance, mfMaxDistance (asd_mpbank_put)
-  float* d_attr = nullptr;
-  int attr_cap = 0;
-  float* d_cxw = nullptr;     // asd_track_local_points_rows: the candidates' positions as k_frustum_queries read them from the bank (the solver's table)
-  size_t cxw_cap = 0;
-  float* h_attr[2] = {nullptr, nullptr};   // pinned staging, used alternately
-  size_t h_attr_cap[2] = {0, 0};
-  hipEvent_t ev_attr[2] = {nullptr, nullptr};
-  int attr_turn = 0;
-  bool replay_host = false;  // ASD_MATCH_REPLAY=host at asd_ctx_create
-};
-
-MatcherState* mstate(asd_ctx* ctx) {
-  if (!ctx->matcher) {
-    MatcherState* m = new MatcherState();
-    m->replay_host = ctx->match_replay_host;
-    ctx->matcher = m;
-  }
-  return static_cast<MatcherState*>(ctx->matcher);
-}
-
-int ensure_queries(asd_ctx* ctx, MatcherState* m, int nq) {
-  if (nq <= m->q_cap) return ASD_OK;
-  const int cap = std::max(nq * 3 / 2, 8192);
-  if (m->d_queries) { (void)hipFree(m->d_queries); (void)hipHostFree(m->h_queries); (void)hipFree(m->d_q_off); (void)hipHostFree(m->h_q); }
-  m->q_cap = 0;
-  ASD_HIP_CHECK(ctx, hipMalloc(&m->d_queries, (size_t)cap * sizeof(WinQuery)));
-  ASD_HIP_CHECK(ctx, hipHostMalloc(&m->h_queries, (size_t)cap * sizeof(WinQuery)));
-  ASD_HIP_CHECK(ctx, hipMalloc(&m->d_q_off, ((size_t)2 * cap + 4) * sizeof(int)));  // off | cnt | total
-  ASD_HIP_CHECK(ctx, hipHostMalloc(&m->h_q, ((size_t)2 * cap + 4) * sizeof(int)));
-  m->q_cap = cap;
-  return ASD_OK;
-}
 // device candidate buffers (k_window_search's output, k_resolve2's input): 8 B per candidate, twice over
 int ensure_cands_dev(asd_ctx* ctx, MatcherState* m, size_t n) {
   if (n <= (size_t)m->cand_cap) return ASD_OK;
@@ -680,7 +578,7 @@ int ensure_cands_dev(asd_ctx* ctx, MatcherState* m, size_t n) {
   m->cand_cap = (int)std::min(cap, (size_t)0x7fffffff);
   return ASD_OK;
 }
-// ... and their pinned host twins, which only the host replay (window_search) reads
+// ... and their pinned host twins, which only the host replay (matcher_window_search) reads
 int ensure_cands(asd_ctx* ctx, MatcherState* m, int n) {
   int rc = ensure_cands_dev(ctx, m, (size_t)n);
   if (rc != ASD_OK) return rc;
@@ -693,7 +591,31 @@ int ensure_cands(asd_ctx* ctx, MatcherState* m, int n) {
   m->h_cand_cap = m->cand_cap;
   return ASD_OK;
 }
-int ensure_qdesc(asd_ctx* ctx, MatcherState* m, int n) {
+}  // namespace
+
+// ---- what matcher_replay.cpp and matcher_banks.cpp call (matcher.h) -----------------------------------------------------------------
+MatcherState* matcher_state(asd_ctx* ctx) {
+  if (!ctx->matcher) {
+    MatcherState* m = new MatcherState();
+    m->replay_host = ctx->match_replay_host;
+    ctx->matcher = m;
+  }
+  return static_cast<MatcherState*>(ctx->matcher);
+}
+
+int matcher_ensure_queries(asd_ctx* ctx, MatcherState* m, int nq) {
+  if (nq <= m->q_cap) return ASD_OK;
+  const int cap = std::max(nq * 3 / 2, 8192);
+  if (m->d_queries) { (void)hipFree(m->d_queries); (void)hipHostFree(m->h_queries); (void)hipFree(m->d_q_off); (void)hipHostFree(m->h_q); }
+  m->q_cap = 0;
+  ASD_HIP_CHECK(ctx, hipMalloc(&m->d_queries, (size_t)cap * sizeof(WinQuery)));
+  ASD_HIP_CHECK(ctx, hipHostMalloc(&m->h_queries, (size_t)cap * sizeof(WinQuery)));
+  ASD_HIP_CHECK(ctx, hipMalloc(&m->d_q_off, ((size_t)2 * cap + 4) * sizeof(int)));  // off | cnt | total
+  ASD_HIP_CHECK(ctx, hipHostMalloc(&m->h_q, ((size_t)2 * cap + 4) * sizeof(int)));
+  m->q_cap = cap;
+  return ASD_OK;
+}
+int matcher_ensure_qdesc(asd_ctx* ctx, MatcherState* m, int n) {
   if (n <= m->qdesc_cap) return ASD_OK;
   const int cap = std::max(n * 3 / 2, 8192);
   if (m->d_qdesc) { (void)hipFree(m->d_qdesc); (void)hipHostFree(m->h_qdesc); }
@@ -704,44 +626,20 @@ int ensure_qdesc(asd_ctx* ctx, MatcherState* m, int n) {
   return ASD_OK;
 }
 
-// rows [first_row, first_row + n) of a bank (first_row >= 0, n >= 0), summed in 64 bits: *end = first_row + n, or ASD_ERR_CAPACITY beyond
-// ASD_BANK_MAX_ROWS.  Called before anything is allocated or enqueued.
-int bank_range(asd_ctx* ctx, const char* who, int32_t first_row, int32_t n, int64_t* end) {
-  *end = (int64_t)first_row + (int64_t)n;
-  if (*end <= (int64_t)ASD_BANK_MAX_ROWS) return ASD_OK;
-  ctx->set_error("%s: rows [%d, %lld) lie beyond ASD_BANK_MAX_ROWS (%d)", who, first_row, (long long)*end, (int)ASD_BANK_MAX_ROWS);
-  return ASD_ERR_CAPACITY;
-}
-// capacity a bank grows to when `rows` (<= ASD_BANK_MAX_ROWS) are asked for
-size_t bank_grown_cap(int64_t rows) {
-  return std::min(std::max((size_t)rows + (size_t)rows / 2, (size_t)16384), (size_t)ASD_BANK_MAX_ROWS);
-}
-
-int ensure_bank(asd_ctx* ctx, MatcherState* m, int64_t rows) {   // rows <= ASD_BANK_MAX_ROWS (bank_range)
-  if (rows <= (int64_t)m->bank_cap) return ASD_OK;
-  const size_t cap = bank_grown_cap(rows);
-  float* nb = nullptr;
-  ASD_HIP_CHECK(ctx, hipMalloc(&nb, cap * 512));
-  if (m->d_bank) {
-    // growth is rare: everything that reads or writes the old bank has finished before it is snapshotted -- on EVERY stream of the
-    // context (inside an asd_prep_async bracket the puts go to the second stream), as asd_mpbank_put's growth does it
-    ASD_HIP_CHECK(ctx, hipDeviceSynchronize());
-    ASD_HIP_CHECK(ctx, hipMemcpyAsync(nb, m->d_bank, (size_t)m->bank_cap * 512, hipMemcpyDeviceToDevice, ctx->stream));
-    ASD_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
-    (void)hipFree(m->d_bank);
-  }
-  m->d_bank = nb;
-  m->bank_cap = (int)cap;
+int matcher_upload_qdesc(asd_ctx* ctx, MatcherState* m, const float* desc, int n) {
+  int rc = matcher_ensure_qdesc(ctx, m, n);
+  if (rc != ASD_OK) return rc;
+  memcpy(m->h_qdesc, desc, (size_t)n * 512);
+  ASD_HIP_CHECK(ctx, hipMemcpyAsync(m->d_qdesc, m->h_qdesc, (size_t)n * 512, hipMemcpyHostToDevice, ctx->stream));
   return ASD_OK;
 }
 
-// result of one batched window search: per query q the candidates idx[off[q] .. off[q]+cnt[q]) in
-// Frame::GetFeaturesInArea order with their DescriptorDistance to the query's descriptor
-struct SearchResult { const int* off; const int* cnt; const int* idx; const float* dist; };
+AsdFrameSlot* matcher_slot(asd_ctx* ctx, int s) {
+  if (!ctx || s < 0 || s >= ASD_MAX_FRAMES) return nullptr;
+  return &ctx->frames[s];
+}
 
-// queries are already in m->h_queries[0..nq); d_q = query descriptor table on the device
-// kind: 0 frame-to-frame, 1 local map, 2 fuse, 3 other -- only sizes the speculative read-back
-int window_search(asd_ctx* ctx, MatcherState* m, const AsdFrameSlot& F, int nq, const float* d_q, SearchResult* res, int kind = 3) {
+int matcher_window_search(asd_ctx* ctx, MatcherState* m, const AsdFrameSlot& F, int nq, const float* d_q, SearchResult* res, int kind) {
   if (asd_track_busy(ctx, "matcher call")) return ASD_ERR_INVALID;
   static const bool timing = getenv("ASD_TIMING") != nullptr;   // per-kind host-side split, printed every 200 searches
   static double tacc[4][3]; static long tcalls[4];
@@ -799,7 +697,7 @@ int window_search(asd_ctx* ctx, MatcherState* m, const AsdFrameSlot& F, int nq, 
   return ASD_OK;
 }
 
-
+namespace {
 // where the claim / ratio / histogram replay runs: on the device (k_resolve2, default) or on the host over the copied-back
 // candidate lists (ASD_MATCH_REPLAY=host in the environment of asd_ctx_create; also taken when the tables would
 // not fit the workgroup's LDS or there are more than 4096 queries)
@@ -812,17 +710,6 @@ bool replay_on_device(const MatcherState* m, int kind, int n_cur, int nq) {
   // replayed in chunks (resolve2.h), so the count of candidates is bounded only by the compaction's rounds and the 16-bit indices
   const int max_q = kind == 0 ? kResolve2Threads * 4 : std::min(kResolve2MaxRounds * 512, 65535);
   return !m->replay_host && n_cur > 0 && n_cur < 65536 && nq <= max_q && resolve_lds_bytes(kind, n_cur, nq) <= 96 * 1024;
-}
-
-// bank rows named by a caller: rows[i] for every i (or every i with used[i]) inside the descriptor bank and, with `attr_too`, inside the
-// attribute bank as well
-int check_bank_rows(asd_ctx* ctx, const MatcherState* m, const int32_t* rows, const uint8_t* used, int n, bool attr_too) {
-  for (int i = 0; i < n; ++i) {
-    if (used && !used[i]) continue;
-    if (rows[i] < 0 || rows[i] >= m->bank_cap) { ctx->set_error("bank row %d out of range (descriptor bank: %d rows)", rows[i], m->bank_cap); return ASD_ERR_INVALID; }
-    if (attr_too && rows[i] >= m->attr_cap) { ctx->set_error("bank row %d out of range (attribute bank: %d rows)", rows[i], m->attr_cap); return ASD_ERR_INVALID; }
-  }
-  return ASD_OK;
 }
 
 // ---- one tracking stage ------------------------------------------------------------------------------------------------------------
@@ -891,11 +778,7 @@ FrustumArgs frustum_args(const asd_ctx* ctx, const AsdFrameSlot& F, int n, const
   fa.n = n; fa.n_levels = ctx->cfg.n_levels; fa.bfactor = th != 1.0;
   if (Tcw) {
     memcpy(fa.T, Tcw, sizeof fa.T);
-    for (int i = 0; i < 3; ++i) {  // mOw = -mRcw.t()*mtcw (Frame.cc:157): transposed gemm accumulates in double
-      double sum = 0;
-      for (int k = 0; k < 3; ++k) sum += (double)Tcw[k * 4 + i] * (double)Tcw[k * 4 + 3];
-      fa.Ow[i] = (float)(-1.0 * sum);
-    }
+    matcher_camera_centre(Tcw, 4, Tcw + 3, 4, fa.Ow);
   }
   fa.T_dev = T_dev;
   fa.fx = K[0]; fa.fy = K[1]; fa.cx = K[2]; fa.cy = K[3];
@@ -1180,19 +1063,6 @@ int search_and_resolve(asd_ctx* ctx, MatcherState* m, const AsdFrameSlot& F, con
   return complete();
 }
 
-// query descriptors: host table -> pinned staging -> device (one async copy)
-int upload_qdesc(asd_ctx* ctx, MatcherState* m, const float* desc, int n) {
-  int rc = ensure_qdesc(ctx, m, n);
-  if (rc != ASD_OK) return rc;
-  memcpy(m->h_qdesc, desc, (size_t)n * 512);
-  ASD_HIP_CHECK(ctx, hipMemcpyAsync(m->d_qdesc, m->h_qdesc, (size_t)n * 512, hipMemcpyHostToDevice, ctx->stream));
-  return ASD_OK;
-}
-
-AsdFrameSlot* slot_of(asd_ctx* ctx, int s) {
-  if (!ctx || s < 0 || s >= ASD_MAX_FRAMES) return nullptr;
-  return &ctx->frames[s];
-}
 }  // namespace
 
 hipError_t asd_copy_rows(hipStream_t st, void* dst, const void* src, size_t bytes) { return copy_rows(st, dst, src, bytes); }
@@ -1238,7 +1108,7 @@ int asd_frame_set_from_ctx(asd_ctx* ctx, int32_t slot, const asd_keypoint* kps, 
 }
 static int frame_set_impl(asd_ctx* ctx, int32_t slot, const asd_keypoint* kps, const float* desc, int32_t n, float min_x,
                           float max_x, float min_y, float max_y, asd_ctx* src) {
-  AsdFrameSlot* F = slot_of(ctx, slot);
+  AsdFrameSlot* F = matcher_slot(ctx, slot);
   if (!F || n < 0 || (n > 0 && !kps) || !(max_x > min_x) || !(max_y > min_y)) return ASD_ERR_INVALID;
   if (n > ctx->cfg.max_patches) { ctx->set_error("frame has %d keypoints, capacity %d", n, ctx->cfg.max_patches); return ASD_ERR_CAPACITY; }
   if (!desc && !src->d_desc_last) { ctx->set_error("desc == NULL: no extraction has completed on the source context yet"); return ASD_ERR_INVALID; }
@@ -1314,31 +1184,6 @@ static int frame_set_impl(asd_ctx* ctx, int32_t slot, const asd_keypoint* kps, c
   } else {
     ASD_HIP_CHECK(ctx, hipStreamSynchronize(st));
   }
-  return ASD_OK;
-}
-
-int asd_frame_features_in_area(asd_ctx* ctx, int32_t slot, float x, float y, float r, int32_t min_level,
-                               int32_t max_level, int32_t capacity, int32_t* idx_out, int32_t* n_out) {
-  AsdFrameSlot* F = slot_of(ctx, slot);
-  if (!F || !idx_out || !n_out) return ASD_ERR_INVALID;
-  // single query through the same kernel the matchers use (so the test of this entry point is a
-  // test of the device grid walk); the host mirror cross-checks it
-  MatcherState* m = mstate(ctx);
-  int rc = ensure_queries(ctx, m, 1);
-  if (rc != ASD_OK) return rc;
-  if (F->n == 0) { *n_out = 0; return ASD_OK; }
-  m->h_queries[0] = WinQuery{x, y, r, min_level, max_level, 0};
-  SearchResult res;
-  if ((rc = window_search(ctx, m, *F, 1, F->d_desc, &res)) != ASD_OK) return rc;
-  std::vector<int> host;
-  features_in_area(*F, x, y, r, min_level, max_level, host);
-  if ((int)host.size() != res.cnt[0] || !std::equal(host.begin(), host.end(), res.idx + res.off[0])) {
-    ctx->set_error("device grid walk disagrees with the host mirror");
-    return ASD_ERR_HIP;
-  }
-  const int n = std::min(res.cnt[0], capacity);
-  for (int i = 0; i < n; ++i) idx_out[i] = res.idx[res.off[0] + i];
-  *n_out = n;
   return ASD_OK;
 }
 
@@ -1443,38 +1288,35 @@ static int match_project_frame_impl(asd_ctx* ctx, int32_t slot_cur, int32_t slot
                             StageInputs* chain = nullptr, const double** solver_io = nullptr, std::function<int()>* defer = nullptr) {
   // chain: what asd_track_motion_model adds to the stage (query kernel, solver); *solver_io stays null when the stage was not chained --
   // nothing to search, or the replay ran on the host
-  AsdFrameSlot *C = slot_of(ctx, slot_cur), *L = slot_of(ctx, slot_last);
+  AsdFrameSlot *C = matcher_slot(ctx, slot_cur), *L = matcher_slot(ctx, slot_last);
   if (!C || !L || !has_mp || !Xw || (!mp_desc && !mp_rows) || !Tcw || !K || !match_cur || !n_matches) return ASD_ERR_INVALID;
   (void)hipSetDevice(ctx->cfg.device);
-  MatcherState* m = mstate(ctx);
+  MatcherState* m = matcher_state(ctx);
   std::fill(match_cur, match_cur + C->n, -1);
   *n_matches = 0;
   if (L->n == 0 || C->n == 0) return ASD_OK;
-  int rc = ensure_queries(ctx, m, L->n);
+  int rc = matcher_ensure_queries(ctx, m, L->n);
   if (rc != ASD_OK) return rc;
-  if (mp_desc) { if ((rc = upload_qdesc(ctx, m, mp_desc, L->n)) != ASD_OK) return rc; }
-  else if ((rc = check_bank_rows(ctx, m, mp_rows, has_mp, L->n, false)) != ASD_OK) return rc;
-  static const bool timing = getenv("ASD_TIMING") != nullptr;
-  static double tacc[3]; static long tcalls;
+  if (mp_desc) { if ((rc = matcher_upload_qdesc(ctx, m, mp_desc, L->n)) != ASD_OK) return rc; }
+  else if ((rc = matcher_check_bank_rows(ctx, m, mp_rows, has_mp, L->n, false)) != ASD_OK) return rc;
   const auto tm0 = std::chrono::steady_clock::now();
   const float fx = K[0], fy = K[1], cx = K[2], cy = K[3];
   const bool on_device = replay_on_device(m, 0, C->n, L->n);
-  if (!(on_device && chain && chain->source == kQueriesProject))   // (else: k_project_queries writes them on the device, asd_track_motion_model)
-  for (int i = 0; i < L->n; ++i) {  // projection, ORBmatcher.cc:1343-1368
-    WinQuery& Q = m->h_queries[i];
-    Q = WinQuery{0.f, 0.f, 0.f, 0, 0, -1};
-    if (!has_mp[i]) continue;
+  auto project = [&](int i, WinQuery& Q) {  // projection, ORBmatcher.cc:1343-1368
+    if (!has_mp[i]) return;
     float Xc[3];
-    transform(Tcw, Xw + 3 * i, Xc);
+    matcher_transform(Tcw, Xw + 3 * i, Xc);
     const float invzc = 1.0 / Xc[2];  // double division, rounded to float (:1352)
-    if (invzc < 0) continue;
+    if (invzc < 0) return;
     const float u = fx * Xc[0] * invzc + cx;
     const float v = fy * Xc[1] * invzc + cy;
-    if (u < C->min_x || u > C->max_x) continue;
-    if (v < C->min_y || v > C->max_y) continue;
+    if (u < C->min_x || u > C->max_x) return;
+    if (v < C->min_y || v > C->max_y) return;
     const int oct = L->kps[i].octave;
     Q = WinQuery{u, v, th * ctx->scale[oct], oct - 1, oct + 1, mp_desc ? i : mp_rows[i]};
-  }
+  };
+  // (on the device with a chain's query kernel: k_project_queries writes them there, asd_track_motion_model)
+  if (!(on_device && chain && chain->source == kQueriesProject) && (rc = matcher_fill_queries(ctx, m, L->n, project)) != ASD_OK) return rc;
   if (on_device)   // search + claims + rotation histogram on the device, one synchronisation, 4 B per keypoint back
   {
     StageInputs plain;
@@ -1484,100 +1326,35 @@ static int match_project_frame_impl(asd_ctx* ctx, int32_t slot_cur, int32_t slot
     in.obs_pos = obs_pos; in.check_ori = check_orientation;
     return search_and_resolve(ctx, m, *C, in, match_cur, n_matches, solver_io, defer);
   }
-  SearchResult R;
-  const auto tm1 = std::chrono::steady_clock::now();
-  if ((rc = window_search(ctx, m, *C, L->n, mp_desc ? m->d_qdesc : m->d_bank, &R, 0)) != ASD_OK) return rc;
-  const auto tm2 = std::chrono::steady_clock::now();
-  int nmatches = 0;
-  // rotation histogram (ORBmatcher.cc:1419-1425, 1437-1450) without per-bin vectors: a current keypoint is matched at most
-  // once, so its bin is kept per keypoint and the bins only need their counts
-  static thread_local std::vector<int8_t> bin_of;
-  // with map points that have no observations a keypoint can be written -- and enter the histogram -- more than once
-  // (ORBmatcher.cc:1392-1395): those calls keep the reference's per-write entries (keypoint, bin)
-  static thread_local std::vector<std::pair<int, int8_t>> writes;
-  if (obs_pos) writes.clear();
-  int cnt[HISTO];
-  for (int b = 0; b < HISTO; ++b) cnt[b] = 0;
-  if (check_orientation) bin_of.assign(C->n, -1);
-  constexpr int kAhead = 12;  // the lists were just written by DMA: every line is a DRAM miss, and segments sit in launch order, not query order
-  for (int i = 0; i < L->n; ++i) {
-    if (i + kAhead < L->n && R.cnt[i + kAhead] > 0) {
-      __builtin_prefetch(R.idx + R.off[i + kAhead]);
-      __builtin_prefetch(R.dist + R.off[i + kAhead]);
-    }
-    if (R.cnt[i] == 0) continue;
-    float best = 100;
-    int best_idx = -1;
-    const int* idx = R.idx + R.off[i];
-    const float* dist = R.dist + R.off[i];
-    for (int t = 0, e = R.cnt[i]; t < e; ++t) {
-      const int j = idx[t];
-      if (match_cur[j] >= 0 && (!obs_pos || obs_pos[match_cur[j]])) continue;  // holds a map point with Observations() > 0
-      if (dist[t] < best) { best = dist[t]; best_idx = j; }
-    }
-    if (best <= TH_HIGH) {
-      match_cur[best_idx] = i;
-      nmatches++;
-      if (check_orientation) {
-        const int b = rot_bin(L->kps[i].angle, C->kps[best_idx].angle);
-        if (obs_pos) writes.emplace_back(best_idx, (int8_t)b);
-        else bin_of[best_idx] = (int8_t)b;
-        ++cnt[b];
-      }
-    }
-  }
-  if (check_orientation) {
-    int i1, i2, i3;
-    three_maxima(cnt, i1, i2, i3);
-    if (obs_pos) {
-      for (const auto& w : writes)
-        if (w.second != i1 && w.second != i2 && w.second != i3) { match_cur[w.first] = -1; nmatches--; }
-    } else {
-      for (int j = 0; j < C->n; ++j) {
-        const int b = bin_of[j];
-        if (b >= 0 && b != i1 && b != i2 && b != i3) { match_cur[j] = -1; nmatches--; }
-      }
-    }
-  }
-  *n_matches = nmatches;
-  if (timing) {
-    const auto tm3 = std::chrono::steady_clock::now();
-    auto ms = [](auto a, auto b) { return std::chrono::duration<double, std::milli>(b - a).count(); };
-    tacc[0] += ms(tm0, tm1); tacc[1] += ms(tm1, tm2); tacc[2] += ms(tm2, tm3);
-    if (++tcalls % 200 == 0)
-      fprintf(stderr, "[match_project_frame] project %.3f search %.3f select %.3f ms\n", tacc[0] / tcalls, tacc[1] / tcalls, tacc[2] / tcalls);
-  }
-  return ASD_OK;
+  return matcher_replay_frame(ctx, m, *C, *L, mp_desc ? m->d_qdesc : m->d_bank, obs_pos, check_orientation, match_cur, n_matches, tm0);
 }
 
 static int match_project_points_impl(asd_ctx* ctx, int32_t slot_cur, int32_t n_mp, const uint8_t* in_view, const float* proj,
                              const int32_t* level, const float* view_cos, const float* desc, const int32_t* rows,
                              const uint8_t* occupied, float th, float nn_ratio, int32_t* match_cur, int32_t* n_matches,
                              const uint8_t* obs_pos, StageInputs* chain = nullptr, const double** solver_io = nullptr, std::function<int()>* defer = nullptr) {
-  AsdFrameSlot* F = slot_of(ctx, slot_cur);
+  AsdFrameSlot* F = matcher_slot(ctx, slot_cur);
   if (!F || n_mp < 0 || !match_cur || !n_matches || (n_mp > 0 && (!in_view || !proj || !level || !view_cos || (!desc && !rows))) ||
       (F->n > 0 && !occupied))
     return ASD_ERR_INVALID;
   (void)hipSetDevice(ctx->cfg.device);
-  MatcherState* m = mstate(ctx);
+  MatcherState* m = matcher_state(ctx);
   std::fill(match_cur, match_cur + F->n, -1);
   *n_matches = 0;
   if (n_mp == 0 || F->n == 0) return ASD_OK;
-  int rc = ensure_queries(ctx, m, n_mp);
-  if (rc != ASD_OK) return rc;
   const bool bFactor = th != 1.0;
-  for (int q = 0; q < n_mp; ++q) {
-    WinQuery& Q = m->h_queries[q];
-    Q = WinQuery{0.f, 0.f, 0.f, 0, 0, -1};
-    if (!in_view[q]) continue;
+  int bad = ASD_OK;   // the first map point the table cannot take ends the call
+  int rc = matcher_fill_queries(ctx, m, n_mp, [&](int q, WinQuery& Q) {
+    if (bad != ASD_OK || !in_view[q]) return;
     const int lvl = level[q];
-    if (lvl < 0 || lvl >= ctx->cfg.n_levels) { ctx->set_error("map point %d: level %d out of range", q, lvl); return ASD_ERR_INVALID; }
+    if (lvl < 0 || lvl >= ctx->cfg.n_levels) { ctx->set_error("map point %d: level %d out of range", q, lvl); bad = ASD_ERR_INVALID; return; }
     float r = view_cos[q] > 0.998 ? 2.5f : 4.0f;  // RadiusByViewingCos (:126-132)
     if (bFactor) r *= th;
-    if (!desc && (rc = check_bank_rows(ctx, m, rows + q, nullptr, 1, false)) != ASD_OK) return rc;
+    if (!desc && (bad = matcher_check_bank_rows(ctx, m, rows + q, nullptr, 1, false)) != ASD_OK) return;
     Q = WinQuery{proj[2 * q], proj[2 * q + 1], r * ctx->scale[lvl], lvl - 1, lvl, desc ? q : rows[q]};
-  }
-  if (desc && (rc = upload_qdesc(ctx, m, desc, n_mp)) != ASD_OK) return rc;
+  });
+  if (rc != ASD_OK || (rc = bad) != ASD_OK) return rc;
+  if (desc && (rc = matcher_upload_qdesc(ctx, m, desc, n_mp)) != ASD_OK) return rc;
   if (replay_on_device(m, 1, F->n, n_mp)) {
     StageInputs plain;
     StageInputs& in = chain ? *chain : plain;
@@ -1586,34 +1363,7 @@ static int match_project_points_impl(asd_ctx* ctx, int32_t slot_cur, int32_t n_m
     in.obs_pos = obs_pos; in.occupied = occupied; in.nn_ratio = nn_ratio;
     return search_and_resolve(ctx, m, *F, in, match_cur, n_matches, solver_io, defer);
   }
-  SearchResult R;
-  if ((rc = window_search(ctx, m, *F, n_mp, desc ? m->d_qdesc : m->d_bank, &R, 1)) != ASD_OK) return rc;
-  int nmatches = 0;
-  for (int q = 0; q < n_mp; ++q) {
-    if (R.cnt[q] == 0) continue;
-    float best = 256, best2 = 256;
-    int best_lvl = -1, best_lvl2 = -1, best_idx = -1;
-    for (int t = R.off[q]; t < R.off[q] + R.cnt[q]; ++t) {
-      const int j = R.idx[t];
-      if (occupied[j] || (match_cur[j] >= 0 && (!obs_pos || obs_pos[match_cur[j]]))) continue;
-      const float d = R.dist[t];
-      if (d < best) {
-        best2 = best; best = d;
-        best_lvl2 = best_lvl; best_lvl = F->kps[j].octave;
-        best_idx = j;
-      } else if (d < best2) {
-        best_lvl2 = F->kps[j].octave;
-        best2 = d;
-      }
-    }
-    if (best <= TH_HIGH) {
-      if (best_lvl == best_lvl2 && best > nn_ratio * best2) continue;
-      match_cur[best_idx] = q;
-      nmatches += 2;  // the reference increments twice per match (ORBmatcher.cc:116-117)
-    }
-  }
-  *n_matches = nmatches;
-  return ASD_OK;
+  return matcher_replay_points(ctx, m, *F, n_mp, desc ? m->d_qdesc : m->d_bank, occupied, obs_pos, nn_ratio, match_cur, n_matches);
 }
 
 extern "C" {
@@ -1711,7 +1461,7 @@ int track_motion_model_impl(asd_ctx* ctx, int32_t slot_cur, int32_t slot_last, c
                             const int32_t* mp_rows, const float* Tcw, const float* K, float th, int32_t check_orientation,
                             const uint8_t* mp_obs_positive, double* pose7, int32_t* match_cur, int32_t* n_matches, uint8_t* outlier,
                             int32_t* n_inliers, std::function<int()>* defer) {
-  AsdFrameSlot *C = slot_of(ctx, slot_cur), *L = slot_of(ctx, slot_last);
+  AsdFrameSlot *C = matcher_slot(ctx, slot_cur), *L = matcher_slot(ctx, slot_last);
   if (!C || !L || !pose7 || !outlier || !n_inliers || !K) return ASD_ERR_INVALID;
   StageInputs in;
   chain_solver_inputs(&in, pose7, K);
@@ -1734,7 +1484,7 @@ int track_local_map_impl(asd_ctx* ctx, int32_t slot_cur, int32_t n_mp, const uin
                          const float* view_cos, const float* desc, const int32_t* rows, const float* mp_Xw, const uint8_t* occupied,
                          const float* cur_Xw, float th, float nn_ratio, const uint8_t* mp_obs_positive, const float* K, double* pose7,
                          int32_t* match_cur, int32_t* n_matches, uint8_t* outlier, int32_t* n_inliers, std::function<int()>* defer) {
-  AsdFrameSlot* F = slot_of(ctx, slot_cur);
+  AsdFrameSlot* F = matcher_slot(ctx, slot_cur);
   if (!F || !pose7 || !outlier || !n_inliers || !K || (n_mp > 0 && !mp_Xw) || (F->n > 0 && (!occupied || !cur_Xw))) return ASD_ERR_INVALID;
   StageInputs in;
   chain_solver_inputs(&in, pose7, K);
@@ -1757,12 +1507,12 @@ int track_local_points_impl(asd_ctx* ctx, int32_t slot_cur, int32_t n_mp, const 
                             const uint8_t* occupied, const float* cur_Xw, float th, float nn_ratio, const uint8_t* mp_obs_positive,
                             double* pose7, int32_t* match_cur, int32_t* n_matches, uint8_t* outlier, int32_t* n_inliers,
                             std::function<int()>* defer) {
-  AsdFrameSlot* F = slot_of(ctx, slot_cur);
+  AsdFrameSlot* F = matcher_slot(ctx, slot_cur);
   if (!F || n_mp < 0 || !Tcw || !K || !pose7 || !match_cur || !n_matches || !outlier || !n_inliers ||
       (n_mp > 0 && (!Xw || !normal || !min_dist || !max_dist || (!desc && !rows))) || (F->n > 0 && (!occupied || !cur_Xw)))
     return ASD_ERR_INVALID;
   (void)hipSetDevice(ctx->cfg.device);
-  MatcherState* m = mstate(ctx);
+  MatcherState* m = matcher_state(ctx);
   if (n_mp == 0 || F->n == 0 || !replay_on_device(m, 1, F->n, n_mp)) {
     // host frustum + the chain on its outputs (also the fallback for very large maps)
     std::vector<uint8_t> in_view(std::max(n_mp, 1));
@@ -1775,10 +1525,10 @@ int track_local_points_impl(asd_ctx* ctx, int32_t slot_cur, int32_t n_mp, const 
   }
   std::fill(match_cur, match_cur + F->n, -1);
   *n_matches = 0;
-  int rc = ensure_queries(ctx, m, n_mp);
+  int rc = matcher_ensure_queries(ctx, m, n_mp);
   if (rc != ASD_OK) return rc;
-  if (!desc && (rc = check_bank_rows(ctx, m, rows, nullptr, n_mp, false)) != ASD_OK) return rc;
-  if (desc && (rc = upload_qdesc(ctx, m, desc, n_mp)) != ASD_OK) return rc;
+  if (!desc && (rc = matcher_check_bank_rows(ctx, m, rows, nullptr, n_mp, false)) != ASD_OK) return rc;
+  if (desc && (rc = matcher_upload_qdesc(ctx, m, desc, n_mp)) != ASD_OK) return rc;
   StageInputs in;
   in.kind = 1; in.nq = n_mp;
   in.d_qdesc = desc ? m->d_qdesc : m->d_bank;
@@ -1804,19 +1554,19 @@ int track_local_points_rows_impl(asd_ctx* ctx, int32_t slot_cur, int32_t n_mp, c
                                  const uint8_t* occupied, const float* cur_Xw, float th, float nn_ratio, const uint8_t* mp_obs_positive,
                                  double* pose7, int32_t* match_cur, int32_t* n_matches, uint8_t* outlier, int32_t* n_inliers, std::function<int()>* defer,
                                  const int32_t* d_rows = nullptr) {
-  AsdFrameSlot* F = slot_of(ctx, slot_cur);
+  AsdFrameSlot* F = matcher_slot(ctx, slot_cur);
   if (!F || n_mp < 1 || !rows || !Tcw || !K || !pose7 || !match_cur || !n_matches || !outlier || !n_inliers || F->n < 1 || !occupied || !cur_Xw) return ASD_ERR_INVALID;
   (void)hipSetDevice(ctx->cfg.device);
-  MatcherState* m = mstate(ctx);
+  MatcherState* m = matcher_state(ctx);
   if (!replay_on_device(m, 1, F->n, n_mp)) {
     ctx->set_error("asd_track_local_points_rows: %d map points / %d keypoints are outside the device replay (use asd_track_local_points_bank)", n_mp, F->n);
     return ASD_ERR_CAPACITY;
   }
-  int rc = check_bank_rows(ctx, m, rows, nullptr, n_mp, true);
+  int rc = matcher_check_bank_rows(ctx, m, rows, nullptr, n_mp, true);
   if (rc != ASD_OK) return rc;
   std::fill(match_cur, match_cur + F->n, -1);
   *n_matches = 0;
-  if ((rc = ensure_queries(ctx, m, n_mp)) != ASD_OK) return rc;
+  if ((rc = matcher_ensure_queries(ctx, m, n_mp)) != ASD_OK) return rc;
   if (m->cxw_cap < (size_t)n_mp * 3) {
     if (m->d_cxw) { ASD_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream)); (void)hipFree(m->d_cxw); m->d_cxw = nullptr; m->cxw_cap = 0; }
     const size_t want = (size_t)n_mp * 3 + (size_t)n_mp / 2 * 3 + 3072;
@@ -1937,14 +1687,14 @@ int asd_track_local_points_map(asd_ctx* ctx, int32_t slot_cur, const float* Tcw,
 
 namespace {
 int track_frame_impl(asd_ctx* ctx, const asd_track_frame_args& A, std::function<int()>* defer) {
-  AsdFrameSlot *C = slot_of(ctx, A.slot_cur), *L = slot_of(ctx, A.slot_last);
+  AsdFrameSlot *C = matcher_slot(ctx, A.slot_cur), *L = matcher_slot(ctx, A.slot_last);
   if (!C || !L || !A.has_mp || !A.Xw_last || !A.last_rows || !A.Tcw || !A.K || !A.cand_rows || A.n_cand < 1 || !A.pose7 || !A.pose1 || !A.match1 ||
       !A.n_matches1 || !A.outlier1 || !A.n_inliers1 || !A.match2 || !A.n_matches2 || !A.outlier2 || !A.n_inliers2)
     return ASD_ERR_INVALID;
   if (asd_track_busy(ctx, "asd_track_frame")) return ASD_ERR_INVALID;
   static const bool timing = getenv("ASD_TIMING") != nullptr;
   (void)hipSetDevice(ctx->cfg.device);
-  MatcherState* m = mstate(ctx);
+  MatcherState* m = matcher_state(ctx);
   const int nl = L->n, nc = C->n, ncand = A.n_cand;
   if (nl < 1 || nc < 1 || !replay_on_device(m, 0, nc, nl) || !replay_on_device(m, 1, nc, ncand) || !pose_chain_lds_form(ctx, nc)) {
     ctx->set_error("asd_track_frame: %d / %d keypoints, %d candidates are outside what the one-submission form handles (empty frame, more than "
@@ -1953,7 +1703,7 @@ int track_frame_impl(asd_ctx* ctx, const asd_track_frame_args& A, std::function<
     return ASD_ERR_CAPACITY;
   }
   int rc;
-  if ((rc = check_bank_rows(ctx, m, A.last_rows, A.has_mp, nl, false)) != ASD_OK || (rc = check_bank_rows(ctx, m, A.cand_rows, nullptr, ncand, true)) != ASD_OK) return rc;
+  if ((rc = matcher_check_bank_rows(ctx, m, A.last_rows, A.has_mp, nl, false)) != ASD_OK || (rc = matcher_check_bank_rows(ctx, m, A.cand_rows, nullptr, ncand, true)) != ASD_OK) return rc;
   // nothing is searched twice here: the candidate buffers take the worst case up front (a list holds at most every keypoint)
   if ((rc = ensure_cands_dev(ctx, m, (size_t)std::max(nl, ncand) * (size_t)nc)) != ASD_OK) return rc;
   hipStream_t st = ctx->stream;
@@ -2103,74 +1853,6 @@ int asd_track_finish(asd_ctx* ctx) {
   return fin();
 }
 
-// ORBmatcher::Fuse, search half (ORBmatcher.cc:825-936): the Replace / AddObservation side effects
-// (:938-956) do not feed back into the search, so every map point is an independent window query.
-int asd_fuse_search(asd_ctx* ctx, int32_t slot_kf, int32_t n_mp, const uint8_t* valid, const float* Xw, const float* normal,
-                    const float* min_dist, const float* max_dist, const float* desc, const float* Tcw, const float* K,
-                    float th, int32_t* best_idx, float* best_dist) {
-  AsdFrameSlot* KF = slot_of(ctx, slot_kf);
-  if (!KF || n_mp < 0 || !Tcw || !K || (n_mp > 0 && (!valid || !Xw || !normal || !min_dist || !max_dist || !desc || !best_idx || !best_dist)))
-    return ASD_ERR_INVALID;
-  (void)hipSetDevice(ctx->cfg.device);
-  MatcherState* m = mstate(ctx);
-  for (int i = 0; i < n_mp; ++i) { best_idx[i] = -1; best_dist[i] = 256.f; }
-  if (n_mp == 0 || KF->n == 0) return ASD_OK;
-  int rc = ensure_queries(ctx, m, n_mp);
-  if (rc != ASD_OK) return rc;
-  const float fx = K[0], fy = K[1], cx = K[2], cy = K[3];
-  const float log_scale = std::log(ctx->cfg.scale_factor);
-  float Ow[3];  // KeyFrame::SetPose: Ow = -Rwc*tcw with Rwc materialised (gemm small-matrix path, f32 sums)
-  for (int i = 0; i < 3; ++i) {
-    const float t0 = Tcw[0 * 4 + i] * Tcw[3] + Tcw[1 * 4 + i] * Tcw[7] + Tcw[2 * 4 + i] * Tcw[11];
-    Ow[i] = (float)((double)t0 * -1.0);
-  }
-  std::vector<int> pred(n_mp, 0);
-  std::vector<float> pu(n_mp), pv(n_mp);
-  for (int i = 0; i < n_mp; ++i) {
-    WinQuery& Q = m->h_queries[i];
-    Q = WinQuery{0.f, 0.f, 0.f, 0, 0, -1};
-    if (!valid[i]) continue;
-    const float* P = Xw + 3 * i;
-    float Pc[3];
-    transform(Tcw, P, Pc);
-    if (Pc[2] < 0.0f) continue;
-    const float invz = 1 / Pc[2];
-    const float u = fx * (Pc[0] * invz) + cx, v = fy * (Pc[1] * invz) + cy;
-    if (!(u >= KF->min_x && u < KF->max_x && v >= KF->min_y && v < KF->max_y)) continue;  // KeyFrame::IsInImage
-    const float maxD = 1.2f * max_dist[i], minD = 0.8f * min_dist[i];
-    const float PO[3] = {P[0] - Ow[0], P[1] - Ow[1], P[2] - Ow[2]};
-    const double nn = (double)PO[0] * PO[0] + (double)PO[1] * PO[1] + (double)PO[2] * PO[2];
-    const float dist3D = (float)std::sqrt(nn);
-    if (dist3D < minD || dist3D > maxD) continue;
-    const float* Pn = normal + 3 * i;
-    const double dot = (double)PO[0] * Pn[0] + (double)PO[1] * Pn[1] + (double)PO[2] * Pn[2];
-    if (dot < 0.5 * dist3D) continue;
-    int lvl = (int)std::ceil(std::log(max_dist[i] / dist3D) / log_scale);
-    if (lvl < 0) lvl = 0;
-    else if (lvl >= ctx->cfg.n_levels) lvl = ctx->cfg.n_levels - 1;
-    pred[i] = lvl; pu[i] = u; pv[i] = v;
-    Q = WinQuery{u, v, th * ctx->scale[lvl], -1, -1, i};  // KeyFrame::GetFeaturesInArea: no level filter
-  }
-  if ((rc = upload_qdesc(ctx, m, desc, n_mp)) != ASD_OK) return rc;
-  SearchResult R;
-  if ((rc = window_search(ctx, m, *KF, n_mp, m->d_qdesc, &R, 2)) != ASD_OK) return rc;
-  for (int i = 0; i < n_mp; ++i) {
-    if (R.cnt[i] == 0) continue;
-    float best = 256;
-    int bi = -1;
-    for (int t = R.off[i]; t < R.off[i] + R.cnt[i]; ++t) {
-      const asd_keypoint& kp = KF->kps[R.idx[t]];
-      if (kp.octave < pred[i] - 1 || kp.octave > pred[i]) continue;
-      const float ex = pu[i] - kp.x, ey = pv[i] - kp.y;
-      const float e2 = ex * ex + ey * ey;
-      if (e2 * ctx->inv_sigma2[kp.octave] > 5.99) continue;
-      if (R.dist[t] < best) { best = R.dist[t]; bi = R.idx[t]; }
-    }
-    if (best <= TH_LOW) { best_idx[i] = bi; best_dist[i] = best; }
-  }
-  return ASD_OK;
-}
-
 // ---- asd_fuse_search_batch: every (keyframe, map point list) pair of SearchInNeighbors in one launch ------------------------------
 // One wave per candidate map point.  The gates of ORBmatcher::Fuse (ORBmatcher.cc:850-895) are evaluated by the wave (uniformly: every
 // lane the same f32 / f64 operations asd_fuse_search's host loop performs, -ffp-contract=off; the predicted level from the thresholds the
@@ -2299,17 +1981,14 @@ int asd_fuse_search_batch(asd_ctx* ctx, int32_t n_calls, const asd_fuse_call* ca
   std::vector<int> call_of(n_total, -1);
   for (int c = 0; c < n_calls; ++c) {
     const asd_fuse_call& A = calls[c];
-    AsdFrameSlot* KF = slot_of(ctx, A.slot_kf);
+    AsdFrameSlot* KF = matcher_slot(ctx, A.slot_kf);
     if (!KF || !KF->d_kp || A.first < 0 || A.n < 0 || A.first + A.n > n_total) { ctx->set_error("asd_fuse_search_batch: call %d: slot %d / rows [%d, %d) of %d", c, A.slot_kf, A.first, A.first + A.n, n_total); return ASD_ERR_INVALID; }
     if (KF->n >= 65536) { ctx->set_error("asd_fuse_search_batch: keyframe of %d keypoints", KF->n); return ASD_ERR_CAPACITY; }
     FuseCallDev& D = cd[c];
     D.G = GridDev{KF->d_kp, KF->d_cell_start, KF->d_cell_items, KF->min_x, KF->min_y, KF->inv_w, KF->inv_h};
     D.desc = KF->d_desc;
     memcpy(D.T, A.Tcw, sizeof D.T);
-    for (int i = 0; i < 3; ++i) {  // KeyFrame::SetPose: Ow = -Rwc*tcw with Rwc materialised (gemm small-matrix path, f32 sums) -- as asd_fuse_search
-      const float t0 = A.Tcw[0 * 4 + i] * A.Tcw[3] + A.Tcw[1 * 4 + i] * A.Tcw[7] + A.Tcw[2 * 4 + i] * A.Tcw[11];
-      D.Ow[i] = (float)((double)t0 * -1.0);
-    }
+    matcher_keyframe_centre(A.Tcw, D.Ow);   // (as asd_fuse_search)
     memcpy(D.K, A.K, sizeof D.K);
     D.min_x = KF->min_x; D.max_x = KF->max_x; D.min_y = KF->min_y; D.max_y = KF->max_y;
     D.first = A.first; D.n = A.n;
@@ -2320,7 +1999,7 @@ int asd_fuse_search_batch(asd_ctx* ctx, int32_t n_calls, const asd_fuse_call* ca
   }
   std::vector<uint8_t> val(valid, valid + n_total);
   for (int i = 0; i < n_total; ++i) if (call_of[i] < 0) { val[i] = 0; call_of[i] = 0; }   // rows no call covers: nothing to search
-  MatcherState* mst = mstate(ctx);
+  MatcherState* mst = matcher_state(ctx);
   if (!desc)
     for (int i = 0; i < n_total; ++i)
       if (val[i] && (desc_rows[i] < 0 || desc_rows[i] >= mst->bank_cap)) { ctx->set_error("asd_fuse_search_batch: bank row %d out of range", desc_rows[i]); return ASD_ERR_INVALID; }
@@ -2357,423 +2036,6 @@ int asd_fuse_search_batch(asd_ctx* ctx, int32_t n_calls, const asd_fuse_call* ca
   return ASD_OK;
 }
 
-// ---- relocalisation / loop-closing variants of the projection searches -----------------------
-// Same split as M1 / M2: the host evaluates the per-point gates in the reference's f32 arithmetic, k_window_search
-// walks the keyframe grid and evaluates the candidates' distances, the host replays best / claim / histogram logic.
-namespace {
-// -Rcw.t()*tcw: gemm with the transpose flag = general path, double accumulation (as Frame.cc:157)
-void centre_gemm_t(const float* R, const float* t, float* Ow) {
-  for (int i = 0; i < 3; ++i) {
-    double s = 0;
-    for (int k = 0; k < 3; ++k) s += (double)R[k * 3 + i] * (double)t[k];
-    Ow[i] = (float)(-1.0 * s);
-  }
-}
-// Scw -> Rcw = sRcw / scw, tcw = Scw.col(3) / scw (ORBmatcher.cc:310-313; Mat / scalar = convertTo with a float scale)
-void decompose_sim3(const float* Scw, float* Rcw, float* tcw) {
-  double d = 0;
-  for (int k = 0; k < 3; ++k) d += (double)Scw[k] * (double)Scw[k];
-  const float scw = (float)std::sqrt(d);
-  const float inv = (float)(1.0 / (double)scw);
-  for (int r = 0; r < 3; ++r) {
-    for (int c = 0; c < 3; ++c) Rcw[r * 3 + c] = Scw[r * 4 + c] * inv + 0.0f;
-    tcw[r] = Scw[r * 4 + 3] * inv + 0.0f;
-  }
-}
-inline void rot_add(const float* R, const float* t, const float* X, float* out) {
-  for (int r = 0; r < 3; ++r) {
-    const float t0 = R[r * 3 + 0] * X[0] + R[r * 3 + 1] * X[1] + R[r * 3 + 2] * X[2];
-    out[r] = (float)((double)t0 + (double)t[r]);
-  }
-}
-inline float norm3f(const float* p) {
-  return (float)std::sqrt((double)p[0] * p[0] + (double)p[1] * p[1] + (double)p[2] * p[2]);
-}
-inline int predict_scale(const asd_ctx* ctx, float maxd_raw, float dist) {  // MapPoint::PredictScale (MapPoint.cc:438-453)
-  int s = (int)std::ceil(std::log(maxd_raw / dist) / std::log(ctx->cfg.scale_factor));
-  if (s < 0) s = 0;
-  else if (s >= ctx->cfg.n_levels) s = ctx->cfg.n_levels - 1;
-  return s;
-}
-// front half shared by the two Scw searches (:300-366, :963-1010)
-bool sim3_project(const asd_ctx* ctx, const AsdFrameSlot& KF, const float* Rcw, const float* tcw, const float* Ow, const float* K,
-                  const float* P, const float* Pn, float mind_raw, float maxd_raw, bool double_invz, float* u, float* v, int* level) {
-  float Pc[3];
-  rot_add(Rcw, tcw, P, Pc);
-  if (Pc[2] < 0.0f) return false;
-  const float invz = double_invz ? (float)(1.0 / Pc[2]) : 1 / Pc[2];
-  *u = K[0] * (Pc[0] * invz) + K[2];
-  *v = K[1] * (Pc[1] * invz) + K[3];
-  if (!(*u >= KF.min_x && *u < KF.max_x && *v >= KF.min_y && *v < KF.max_y)) return false;
-  const float PO[3] = {P[0] - Ow[0], P[1] - Ow[1], P[2] - Ow[2]};
-  const float dist = norm3f(PO);
-  if (dist < 0.8f * mind_raw || dist > 1.2f * maxd_raw) return false;
-  const double dot = (double)PO[0] * Pn[0] + (double)PO[1] * Pn[1] + (double)PO[2] * Pn[2];
-  if (dot < 0.5 * dist) return false;
-  *level = predict_scale(ctx, maxd_raw, dist);
-  return true;
-}
-}  // namespace
-
-extern "C" {
-
-// ORBmatcher::SearchByProjection(Frame&, KeyFrame*, const set<MapPoint*>&, float th, float ORBdist) (:1455-1582)
-int asd_match_project_keyframe(asd_ctx* ctx, int32_t slot_cur, int32_t n_kf, const uint8_t* valid, const float* Xw, const float* min_dist,
-                               const float* max_dist, const float* desc, const float* kf_angle, const uint8_t* occupied, const float* Tcw,
-                               const float* K, float th, float orb_dist, int32_t check_orientation, int32_t* match_cur,
-                               int32_t* n_matches) {
-  AsdFrameSlot* C = slot_of(ctx, slot_cur);
-  if (!C || n_kf < 0 || !Tcw || !K || !match_cur || !n_matches || (C->n > 0 && !occupied) ||
-      (n_kf > 0 && (!valid || !Xw || !min_dist || !max_dist || !desc || !kf_angle)))
-    return ASD_ERR_INVALID;
-  (void)hipSetDevice(ctx->cfg.device);
-  MatcherState* m = mstate(ctx);
-  std::fill(match_cur, match_cur + C->n, -1);
-  *n_matches = 0;
-  if (n_kf == 0 || C->n == 0) return ASD_OK;
-  int rc = ensure_queries(ctx, m, n_kf);
-  if (rc != ASD_OK) return rc;
-  float Rcw[9], tcw[3], Ow[3];
-  for (int r = 0; r < 3; ++r) { for (int c = 0; c < 3; ++c) Rcw[r * 3 + c] = Tcw[r * 4 + c]; tcw[r] = Tcw[r * 4 + 3]; }
-  centre_gemm_t(Rcw, tcw, Ow);
-  for (int i = 0; i < n_kf; ++i) {
-    WinQuery& Q = m->h_queries[i];
-    Q = WinQuery{0.f, 0.f, 0.f, 0, 0, -1};
-    if (!valid[i]) continue;
-    const float* P = Xw + 3 * i;
-    float Pc[3];
-    rot_add(Rcw, tcw, P, Pc);
-    const float invzc = 1.0 / Pc[2];
-    const float u = K[0] * Pc[0] * invzc + K[2];
-    const float v = K[1] * Pc[1] * invzc + K[3];
-    if (!(u >= C->min_x && u <= C->max_x && v >= C->min_y && v <= C->max_y)) continue;  // also drops NaN (z == 0)
-    const float PO[3] = {P[0] - Ow[0], P[1] - Ow[1], P[2] - Ow[2]};
-    const float dist3D = norm3f(PO);
-    if (dist3D < 0.8f * min_dist[i] || dist3D > 1.2f * max_dist[i]) continue;
-    const int lvl = predict_scale(ctx, max_dist[i], dist3D);
-    Q = WinQuery{u, v, th * ctx->scale[lvl], lvl - 1, lvl + 1, i};
-  }
-  if ((rc = upload_qdesc(ctx, m, desc, n_kf)) != ASD_OK) return rc;
-  SearchResult R;
-  if ((rc = window_search(ctx, m, *C, n_kf, m->d_qdesc, &R)) != ASD_OK) return rc;
-  std::vector<uint8_t> occ(occupied, occupied + C->n);
-  std::vector<int> hist[HISTO];
-  int nmatches = 0;
-  for (int i = 0; i < n_kf; ++i) {
-    if (R.cnt[i] == 0) continue;
-    float best = 256;
-    int best_idx = -1;
-    for (int t = R.off[i]; t < R.off[i] + R.cnt[i]; ++t) {
-      const int j = R.idx[t];
-      if (occ[j]) continue;
-      if (R.dist[t] < best) { best = R.dist[t]; best_idx = j; }
-    }
-    if (best <= orb_dist) {
-      occ[best_idx] = 1;
-      match_cur[best_idx] = i;
-      nmatches++;
-      if (check_orientation) hist[rot_bin(kf_angle[i], C->kps[best_idx].angle)].push_back(best_idx);
-    }
-  }
-  if (check_orientation) {
-    int cnt[HISTO], i1, i2, i3;
-    for (int b = 0; b < HISTO; ++b) cnt[b] = (int)hist[b].size();
-    three_maxima(cnt, i1, i2, i3);
-    for (int b = 0; b < HISTO; ++b)
-      if (b != i1 && b != i2 && b != i3)
-        for (int j : hist[b]) { match_cur[j] = -1; nmatches--; }
-  }
-  *n_matches = nmatches;
-  return ASD_OK;
-}
-
-// ORBmatcher::SearchByProjection(KeyFrame*, cv::Mat Scw, const vector<MapPoint*>&, vector<MapPoint*>& vpMatched, int th) (:300-413)
-int asd_match_project_sim3(asd_ctx* ctx, int32_t slot_kf, const float* Scw, int32_t n_mp, const uint8_t* valid, const float* Xw,
-                           const float* normal, const float* min_dist, const float* max_dist, const float* desc, const float* K,
-                           int32_t th, int32_t* matched_kp, int32_t* n_matches) {
-  AsdFrameSlot* KF = slot_of(ctx, slot_kf);
-  if (!KF || !Scw || n_mp < 0 || !K || !n_matches || (KF->n > 0 && !matched_kp) ||
-      (n_mp > 0 && (!valid || !Xw || !normal || !min_dist || !max_dist || !desc)))
-    return ASD_ERR_INVALID;
-  (void)hipSetDevice(ctx->cfg.device);
-  MatcherState* m = mstate(ctx);
-  *n_matches = 0;
-  if (n_mp == 0 || KF->n == 0) return ASD_OK;
-  int rc = ensure_queries(ctx, m, n_mp);
-  if (rc != ASD_OK) return rc;
-  float Rcw[9], tcw[3], Ow[3];
-  decompose_sim3(Scw, Rcw, tcw);
-  centre_gemm_t(Rcw, tcw, Ow);
-  std::vector<int> pred(n_mp, 0);
-  for (int i = 0; i < n_mp; ++i) {
-    WinQuery& Q = m->h_queries[i];
-    Q = WinQuery{0.f, 0.f, 0.f, 0, 0, -1};
-    if (!valid[i]) continue;
-    float u, v;
-    if (!sim3_project(ctx, *KF, Rcw, tcw, Ow, K, Xw + 3 * i, normal + 3 * i, min_dist[i], max_dist[i], false, &u, &v, &pred[i])) continue;
-    Q = WinQuery{u, v, (float)th * ctx->scale[pred[i]], -1, -1, i};
-  }
-  if ((rc = upload_qdesc(ctx, m, desc, n_mp)) != ASD_OK) return rc;
-  SearchResult R;
-  if ((rc = window_search(ctx, m, *KF, n_mp, m->d_qdesc, &R)) != ASD_OK) return rc;
-  int nmatches = 0;
-  for (int i = 0; i < n_mp; ++i) {
-    if (R.cnt[i] == 0) continue;
-    float best = 256;
-    int best_idx = -1;
-    for (int t = R.off[i]; t < R.off[i] + R.cnt[i]; ++t) {
-      const int j = R.idx[t];
-      if (matched_kp[j] != -1) continue;  // vpMatched[idx] already holds a map point
-      const int lv = KF->kps[j].octave;
-      if (lv < pred[i] - 1 || lv > pred[i]) continue;
-      if (R.dist[t] < best) { best = R.dist[t]; best_idx = j; }
-    }
-    if (best <= TH_LOW) { matched_kp[best_idx] = i; nmatches++; }
-  }
-  *n_matches = nmatches;
-  return ASD_OK;
-}
-
-// ORBmatcher::Fuse(KeyFrame*, cv::Mat Scw, const vector<MapPoint*>&, float th, vector<MapPoint*>& vpReplacePoint) (:963-1086)
-int asd_fuse_search_sim3(asd_ctx* ctx, int32_t slot_kf, const float* Scw, int32_t n_mp, const uint8_t* valid, const float* Xw,
-                         const float* normal, const float* min_dist, const float* max_dist, const float* desc, const float* K, float th,
-                         int32_t* best_idx, float* best_dist) {
-  AsdFrameSlot* KF = slot_of(ctx, slot_kf);
-  if (!KF || !Scw || n_mp < 0 || !K || (n_mp > 0 && (!valid || !Xw || !normal || !min_dist || !max_dist || !desc || !best_idx || !best_dist)))
-    return ASD_ERR_INVALID;
-  (void)hipSetDevice(ctx->cfg.device);
-  MatcherState* m = mstate(ctx);
-  for (int i = 0; i < n_mp; ++i) { best_idx[i] = -1; best_dist[i] = 100.f; }
-  if (n_mp == 0 || KF->n == 0) return ASD_OK;
-  int rc = ensure_queries(ctx, m, n_mp);
-  if (rc != ASD_OK) return rc;
-  float Rcw[9], tcw[3], Ow[3];
-  decompose_sim3(Scw, Rcw, tcw);
-  centre_gemm_t(Rcw, tcw, Ow);
-  std::vector<int> pred(n_mp, 0);
-  for (int i = 0; i < n_mp; ++i) {
-    WinQuery& Q = m->h_queries[i];
-    Q = WinQuery{0.f, 0.f, 0.f, 0, 0, -1};
-    if (!valid[i]) continue;
-    float u, v;
-    if (!sim3_project(ctx, *KF, Rcw, tcw, Ow, K, Xw + 3 * i, normal + 3 * i, min_dist[i], max_dist[i], true, &u, &v, &pred[i])) continue;
-    Q = WinQuery{u, v, th * ctx->scale[pred[i]], -1, -1, i};
-  }
-  if ((rc = upload_qdesc(ctx, m, desc, n_mp)) != ASD_OK) return rc;
-  SearchResult R;
-  if ((rc = window_search(ctx, m, *KF, n_mp, m->d_qdesc, &R, 2)) != ASD_OK) return rc;
-  for (int i = 0; i < n_mp; ++i) {
-    if (R.cnt[i] == 0) continue;
-    float best = 100;
-    int bi = -1;
-    for (int t = R.off[i]; t < R.off[i] + R.cnt[i]; ++t) {
-      const int lv = KF->kps[R.idx[t]].octave;
-      if (lv < pred[i] - 1 || lv > pred[i]) continue;
-      if (R.dist[t] < best) { best = R.dist[t]; bi = R.idx[t]; }
-    }
-    if (best <= TH_LOW) { best_idx[i] = bi; best_dist[i] = best; }
-  }
-  return ASD_OK;
-}
-
-// ORBmatcher::SearchBySim3 (:1090-1314)
-int asd_match_sim3(asd_ctx* ctx, int32_t slot1, int32_t slot2, const uint8_t* has1, const uint8_t* has2, const float* Xw1, const float* Xw2,
-                   const float* min_dist1, const float* max_dist1, const float* min_dist2, const float* max_dist2, const float* desc1,
-                   const float* desc2, const float* T1w, const float* T2w, float s12, const float* R12, const float* t12, const float* K,
-                   float th, int32_t* match12, int32_t* n_matches) {
-  AsdFrameSlot *KF1 = slot_of(ctx, slot1), *KF2 = slot_of(ctx, slot2);
-  if (!KF1 || !KF2 || !T1w || !T2w || !R12 || !t12 || !K || !n_matches || (KF1->n > 0 && (!has1 || !Xw1 || !min_dist1 || !max_dist1 || !desc1 || !match12)) ||
-      (KF2->n > 0 && (!has2 || !Xw2 || !min_dist2 || !max_dist2 || !desc2)))
-    return ASD_ERR_INVALID;
-  (void)hipSetDevice(ctx->cfg.device);
-  MatcherState* m = mstate(ctx);
-  *n_matches = 0;
-  std::fill(match12, match12 + KF1->n, -1);
-  if (KF1->n == 0 || KF2->n == 0) return ASD_OK;
-  float R1w[9], t1w[3], R2w[9], t2w[3], sR12[9], sR21[9], t21[3];
-  for (int r = 0; r < 3; ++r) {
-    for (int c = 0; c < 3; ++c) { R1w[r * 3 + c] = T1w[r * 4 + c]; R2w[r * 3 + c] = T2w[r * 4 + c]; }
-    t1w[r] = T1w[r * 4 + 3]; t2w[r] = T2w[r * 4 + 3];
-  }
-  const float a12 = (float)(double)s12, a21 = (float)(1.0 / (double)s12);  // scaled Mat = convertTo with a float scale
-  for (int r = 0; r < 3; ++r)
-    for (int c = 0; c < 3; ++c) { sR12[r * 3 + c] = R12[r * 3 + c] * a12 + 0.0f; sR21[r * 3 + c] = R12[c * 3 + r] * a21 + 0.0f; }
-  for (int r = 0; r < 3; ++r) {
-    const float t0 = sR21[r * 3 + 0] * t12[0] + sR21[r * 3 + 1] * t12[1] + sR21[r * 3 + 2] * t12[2];
-    t21[r] = (float)((double)t0 * -1.0);
-  }
-  auto one_way = [&](AsdFrameSlot& A, AsdFrameSlot& B, const uint8_t* has, const float* Xw, const float* mind, const float* maxd,
-                     const float* desc, const float* Raw, const float* taw, const float* sRba, const float* tba, std::vector<int>& out) -> int {
-    int rc = ensure_queries(ctx, m, A.n);
-    if (rc != ASD_OK) return rc;
-    std::vector<int> pred(A.n, 0);
-    for (int i = 0; i < A.n; ++i) {
-      WinQuery& Q = m->h_queries[i];
-      Q = WinQuery{0.f, 0.f, 0.f, 0, 0, -1};
-      if (!has[i]) continue;
-      float pA[3], pB[3];
-      rot_add(Raw, taw, Xw + 3 * i, pA);
-      rot_add(sRba, tba, pA, pB);
-      if (pB[2] < 0.0) continue;
-      const float invz = 1.0 / pB[2];
-      const float u = K[0] * (pB[0] * invz) + K[2], v = K[1] * (pB[1] * invz) + K[3];
-      if (!(u >= B.min_x && u < B.max_x && v >= B.min_y && v < B.max_y)) continue;
-      const float dist3D = norm3f(pB);
-      if (dist3D < 0.8f * mind[i] || dist3D > 1.2f * maxd[i]) continue;
-      pred[i] = predict_scale(ctx, maxd[i], dist3D);
-      Q = WinQuery{u, v, th * ctx->scale[pred[i]], -1, -1, i};
-    }
-    if ((rc = upload_qdesc(ctx, m, desc, A.n)) != ASD_OK) return rc;
-    SearchResult R;
-    if ((rc = window_search(ctx, m, B, A.n, m->d_qdesc, &R)) != ASD_OK) return rc;
-    out.assign(A.n, -1);
-    for (int i = 0; i < A.n; ++i) {
-      if (R.cnt[i] == 0) continue;
-      float best = 100;
-      int bi = -1;
-      for (int t = R.off[i]; t < R.off[i] + R.cnt[i]; ++t) {
-        const int lv = B.kps[R.idx[t]].octave;
-        if (lv < pred[i] - 1 || lv > pred[i]) continue;
-        if (R.dist[t] < best) { best = R.dist[t]; bi = R.idx[t]; }
-      }
-      if (best <= TH_HIGH) out[i] = bi;
-    }
-    return ASD_OK;
-  };
-  std::vector<int> m1, m2;
-  int rc = one_way(*KF1, *KF2, has1, Xw1, min_dist1, max_dist1, desc1, R1w, t1w, sR21, t21, m1);
-  if (rc != ASD_OK) return rc;
-  if ((rc = one_way(*KF2, *KF1, has2, Xw2, min_dist2, max_dist2, desc2, R2w, t2w, sR12, t12, m2)) != ASD_OK) return rc;
-  int found = 0;
-  for (int i1 = 0; i1 < KF1->n; ++i1) {
-    const int i2 = m1[i1];
-    if (i2 >= 0 && m2[i2] == i1) { match12[i1] = i2; ++found; }
-  }
-  *n_matches = found;
-  return ASD_OK;
-}
-
-}  // extern "C"
-
-// MapPoint::mDescriptor rows kept on the device: written when a map point's descriptor changes
-// (MapPoint::ComputeDistinctiveDescriptors, once per keyframe), read by the matchers every frame.
-int asd_bank_put(asd_ctx* ctx, int32_t first_row, int32_t n, const float* desc) {
-  if (!ctx || first_row < 0 || n < 0 || (n > 0 && !desc)) return ASD_ERR_INVALID;
-  int64_t end;
-  int rc = bank_range(ctx, "asd_bank_put", first_row, n, &end);
-  if (rc != ASD_OK) return rc;
-  (void)hipSetDevice(ctx->cfg.device);
-  MatcherState* m = mstate(ctx);
-  rc = ensure_bank(ctx, m, end);
-  if (rc != ASD_OK || n == 0) return rc;
-  // the pinned staging block is upload_qdesc's too: an armed asd_track_* stage of the descriptor form may still have its copy out of it
-  // pending, so the stream drains BEFORE the block is rewritten (or freed by ensure_qdesc) -- the wait this call makes anyway, moved up
-  ASD_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
-  if ((rc = ensure_qdesc(ctx, m, n)) != ASD_OK) return rc;
-  memcpy(m->h_qdesc, desc, (size_t)n * 512);
-  ASD_HIP_CHECK(ctx, hipMemcpyAsync(m->d_bank + (size_t)first_row * 128, m->h_qdesc, (size_t)n * 512, hipMemcpyHostToDevice, ctx->stream));
-  ASD_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
-  return ASD_OK;
-}
-
-// bank[first_row + i] = descriptor of keypoint i of frame `slot` (device to device), i in [0, n)
-int asd_bank_put_from_frame(asd_ctx* ctx, int32_t slot, int32_t first_row, int32_t n) {
-  AsdFrameSlot* F = slot_of(ctx, slot);
-  if (!F || first_row < 0 || n < 0 || n > F->n) return ASD_ERR_INVALID;
-  int64_t end;
-  int rc = bank_range(ctx, "asd_bank_put_from_frame", first_row, n, &end);
-  if (rc != ASD_OK) return rc;
-  (void)hipSetDevice(ctx->cfg.device);
-  MatcherState* m = mstate(ctx);
-  rc = ensure_bank(ctx, m, end);
-  if (rc != ASD_OK || n == 0) return rc;
-  ASD_HIP_CHECK(ctx, copy_rows(asd_prep_stream(ctx), m->d_bank + (size_t)first_row * 128, F->d_desc, (size_t)n * 512));
-  return ASD_OK;
-}
-
-// MapPoint::{mWorldPos, mNormalVector, mfMinDistance, mfMaxDistance} of rows [first_row, first_row + n) of the bank
-int asd_mpbank_put(asd_ctx* ctx, int32_t first_row, int32_t n, const float* Xw, const float* normal, const float* min_dist, const float* max_dist) {
-  if (!ctx || first_row < 0 || n < 0 || (n > 0 && (!Xw || !normal || !min_dist || !max_dist))) return ASD_ERR_INVALID;
-  int64_t end;
-  const int rc = bank_range(ctx, "asd_mpbank_put", first_row, n, &end);
-  if (rc != ASD_OK) return rc;
-  (void)hipSetDevice(ctx->cfg.device);
-  MatcherState* m = mstate(ctx);
-  if (end > (int64_t)m->attr_cap) {
-    const size_t cap = bank_grown_cap(end);
-    float* nb = nullptr;
-    ASD_HIP_CHECK(ctx, hipMalloc(&nb, cap * 32));
-    ASD_HIP_CHECK(ctx, hipDeviceSynchronize());   // (growth is rare: everything that reads or writes the old table has finished)
-    if (m->d_attr) { ASD_HIP_CHECK(ctx, hipMemcpy(nb, m->d_attr, (size_t)m->attr_cap * 32, hipMemcpyDeviceToDevice)); (void)hipFree(m->d_attr); }
-    m->d_attr = nb;
-    m->attr_cap = (int)cap;
-  }
-  if (n == 0) return ASD_OK;
-  const int k = m->attr_turn ^= 1;
-  if (!m->ev_attr[k]) ASD_HIP_CHECK(ctx, hipEventCreateWithFlags(&m->ev_attr[k], hipEventDisableTiming));
-  else ASD_HIP_CHECK(ctx, hipEventSynchronize(m->ev_attr[k]));   // this staging buffer's previous upload has left it
-  if (m->h_attr_cap[k] < (size_t)n * 32) {
-    if (m->h_attr[k]) (void)hipHostFree(m->h_attr[k]);
-    m->h_attr[k] = nullptr; m->h_attr_cap[k] = 0;
-    ASD_HIP_CHECK(ctx, hipHostMalloc(&m->h_attr[k], (size_t)n * 48));
-    m->h_attr_cap[k] = (size_t)n * 48;
-  }
-  float* h = m->h_attr[k];
-  for (int i = 0; i < n; ++i) {
-    float* r = h + 8 * (size_t)i;
-    r[0] = Xw[3 * i]; r[1] = Xw[3 * i + 1]; r[2] = Xw[3 * i + 2];
-    r[3] = normal[3 * i]; r[4] = normal[3 * i + 1]; r[5] = normal[3 * i + 2];
-    r[6] = min_dist[i]; r[7] = max_dist[i];
-  }
-  hipStream_t st = asd_prep_stream(ctx);
-  ASD_HIP_CHECK(ctx, copy_rows(st, m->d_attr + 8 * (size_t)first_row, h, (size_t)n * 32));
-  ASD_HIP_CHECK(ctx, hipEventRecord(m->ev_attr[k], st));
-  return ASD_OK;
-}
-
-// Test aid: rows [first_row, first_row + n) of the two banks as a consumer would read them -- copies enqueued on the context's stream, that
-// stream alone waited for.  It does NOT wait for the second stream: a bracket that failed to order its writes must show here.
-int32_t asd_debug_bank_get(asd_ctx* ctx, int32_t first_row, int32_t n, float* desc, float* attr) {
-  if (!ctx) return ASD_ERR_INVALID;
-  if (first_row < 0 || n < 0) { ctx->set_error("asd_debug_bank_get: first_row %d, n %d", first_row, n); return ASD_ERR_INVALID; }
-  if (ctx->prep_on) { ctx->set_error("asd_debug_bank_get: an asd_prep_async bracket is open"); return ASD_ERR_INVALID; }
-  if (asd_track_busy(ctx, "asd_debug_bank_get")) return ASD_ERR_INVALID;
-  MatcherState* m = mstate(ctx);
-  const int64_t end = (int64_t)first_row + (int64_t)n;
-  if (desc && end > (int64_t)m->bank_cap) { ctx->set_error("asd_debug_bank_get: rows [%d, %lld) outside the descriptor bank (%d rows)", first_row, (long long)end, m->bank_cap); return ASD_ERR_INVALID; }
-  if (attr && end > (int64_t)m->attr_cap) { ctx->set_error("asd_debug_bank_get: rows [%d, %lld) outside the attribute bank (%d rows)", first_row, (long long)end, m->attr_cap); return ASD_ERR_INVALID; }
-  if (n == 0 || (!desc && !attr)) return ASD_OK;
-  (void)hipSetDevice(ctx->cfg.device);
-  if (desc) ASD_HIP_CHECK(ctx, hipMemcpyAsync(desc, m->d_bank + (size_t)first_row * 128, (size_t)n * 512, hipMemcpyDeviceToHost, ctx->stream));
-  if (attr) ASD_HIP_CHECK(ctx, hipMemcpyAsync(attr, m->d_attr + (size_t)first_row * 8, (size_t)n * 32, hipMemcpyDeviceToHost, ctx->stream));
-  ASD_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
-  return ASD_OK;
-}
-
-// Frame construction beside the stages in flight: between asd_prep_async(ctx, 1) and asd_prep_async(ctx, 0) the device work of
-// asd_frame_set, asd_bank_put_from_frame and asd_mpbank_put goes to a second stream of the context instead of queueing behind the
-// outstanding asd_track_* stage; closing the bracket makes everything enqueued on the context's stream AFTERWARDS wait for it.
-int asd_prep_async(asd_ctx* ctx, int32_t on) {
-  if (!ctx) return ASD_ERR_INVALID;
-  (void)hipSetDevice(ctx->cfg.device);
-  if (on) {
-    if (!ctx->stream_prep) {
-      int lo = 0, hi = 0;
-      (void)hipDeviceGetStreamPriorityRange(&lo, &hi);
-      // highest priority, like the main stream
-      ASD_HIP_CHECK(ctx, hipStreamCreateWithPriority(&ctx->stream_prep, hipStreamNonBlocking, hi));
-      ASD_HIP_CHECK(ctx, hipEventCreateWithFlags(&ctx->ev_prep, hipEventDisableTiming));
-    }
-    ctx->prep_on = true;
-    return ASD_OK;
-  }
-  if (!ctx->prep_on) return ASD_OK;
-  ctx->prep_on = false;
-  ASD_HIP_CHECK(ctx, hipEventRecord(ctx->ev_prep, ctx->stream_prep));
-  ASD_HIP_CHECK(ctx, hipStreamWaitEvent(ctx->stream, ctx->ev_prep, 0));
-  return ASD_OK;
-}
-
 }  // extern "C"
 
 // merge-join of two DBoW2 feature vectors (std::map iteration + lower_bound, ORBmatcher.cc:183-278):
@@ -2788,22 +2050,8 @@ static void node_join(const asd_feature_vector* A, const asd_feature_vector* B, 
   }
 }
 
-static bool fv_valid(const asd_feature_vector* fv, int n) {
-  if (!fv || fv->n_nodes < 0 || (fv->n_nodes > 0 && (!fv->node_id || !fv->start || !fv->idx))) return false;
-  for (int i = 0; i < fv->n_nodes; ++i) {
-    if (i > 0 && fv->node_id[i] <= fv->node_id[i - 1]) return false;
-    if (fv->start[i + 1] < fv->start[i]) return false;
-  }
-  for (int t = fv->n_nodes ? fv->start[0] : 0; t < (fv->n_nodes ? fv->start[fv->n_nodes] : 0); ++t)
-    if (fv->idx[t] < 0 || fv->idx[t] >= n) return false;
-  return true;
-}
-
-// distances of every (query keypoint of A, same-node keypoint of B) pair; queries in reference visiting order.
-// On return lq[k] describes query k (qrow = keypoint in A, candidates fvB->idx[cbeg..cend), distances at dist[ooff..]).
-static int list_search(asd_ctx* ctx, MatcherState* m, const AsdFrameSlot& A, const AsdFrameSlot& B,
-                       const asd_feature_vector* fvA, const asd_feature_vector* fvB, const uint8_t* skipA, bool skip_if_set,
-                       std::vector<ListQuery>& lq, const float** dist_out) {
+int matcher_list_search(asd_ctx* ctx, MatcherState* m, const AsdFrameSlot& A, const AsdFrameSlot& B, const asd_feature_vector* fvA,
+                        const asd_feature_vector* fvB, const uint8_t* skipA, bool skip_if_set, std::vector<ListQuery>& lq, const float** dist_out) {
   lq.clear();
   int total = 0;
   node_join(fvA, fvB, [&](int a, int b) {
@@ -2819,7 +2067,7 @@ static int list_search(asd_ctx* ctx, MatcherState* m, const AsdFrameSlot& A, con
   if (lq.empty() || total == 0) return ASD_OK;
   int rc;
   if ((rc = ensure_cands(ctx, m, std::max(total, fvB->start[fvB->n_nodes]))) != ASD_OK) return rc;
-  if ((rc = ensure_queries(ctx, m, (int)lq.size())) != ASD_OK) return rc;
+  if ((rc = matcher_ensure_queries(ctx, m, (int)lq.size())) != ASD_OK) return rc;
   static_assert(sizeof(ListQuery) <= sizeof(WinQuery), "query staging is shared");
   hipStream_t st = ctx->stream;
   memcpy(m->h_queries, lq.data(), lq.size() * sizeof(ListQuery));
@@ -2838,262 +2086,3 @@ static int list_search(asd_ctx* ctx, MatcherState* m, const AsdFrameSlot& A, con
   *dist_out = m->h_dist;
   return ASD_OK;
 }
-
-extern "C" {
-
-int asd_match_bow(asd_ctx* ctx, int32_t slot_kf, int32_t slot_f, const asd_feature_vector* fv_kf,
-                  const asd_feature_vector* fv_f, const uint8_t* has_mp_kf, float nn_ratio, int32_t check_orientation,
-                  int32_t* match_f, int32_t* n_matches) {
-  AsdFrameSlot *KF = slot_of(ctx, slot_kf), *F = slot_of(ctx, slot_f);
-  if (!KF || !F || !has_mp_kf || !match_f || !n_matches || !fv_valid(fv_kf, KF->n) || !fv_valid(fv_f, F->n)) return ASD_ERR_INVALID;
-  (void)hipSetDevice(ctx->cfg.device);
-  MatcherState* m = mstate(ctx);
-  std::fill(match_f, match_f + F->n, -1);
-  *n_matches = 0;
-  std::vector<ListQuery> lq;
-  const float* dist = nullptr;
-  int rc = list_search(ctx, m, *KF, *F, fv_kf, fv_f, has_mp_kf, /*skip_if_set=*/false, lq, &dist);
-  if (rc != ASD_OK) return rc;
-  int nmatches = 0;
-  std::vector<int> hist[HISTO];
-  for (const ListQuery& Q : lq) {  // reference order: node by node, KF keypoints of the node in order (:194-262)
-    float best1 = 256, best2 = 256;
-    int best_idx = -1;
-    for (int t = Q.cbeg; t < Q.cend; ++t) {
-      const int j = fv_f->idx[t];
-      if (match_f[j] >= 0) continue;
-      const float d = dist[Q.ooff + (t - Q.cbeg)];
-      if (d < best1) { best2 = best1; best1 = d; best_idx = j; }
-      else if (d < best2) best2 = d;
-    }
-    if (best1 <= TH_LOW && best1 < nn_ratio * best2) {
-      match_f[best_idx] = Q.qrow;
-      if (check_orientation) hist[rot_bin(KF->kps[Q.qrow].angle, F->kps[best_idx].angle)].push_back(best_idx);
-      nmatches++;
-    }
-  }
-  if (check_orientation) {
-    int cnt[HISTO], a, b, c;
-    for (int k = 0; k < HISTO; ++k) cnt[k] = (int)hist[k].size();
-    three_maxima(cnt, a, b, c);
-    for (int k = 0; k < HISTO; ++k) {
-      if (k == a || k == b || k == c) continue;
-      for (int j : hist[k]) { match_f[j] = -1; nmatches--; }
-    }
-  }
-  *n_matches = nmatches;
-  return ASD_OK;
-}
-
-// SearchByBoW(KeyFrame*, KeyFrame*, ...) (ORBmatcher.cc:533-666): the same list search, another replay.  A candidate of keyframe 2
-// needs a map point and must not have been taken (vbMatched2, :587), the claim is on keyframe 2's index, the threshold is strict
-// (:609) and the histogram holds idx1 (:625).
-int asd_match_bow_kf(asd_ctx* ctx, int32_t slot1, int32_t slot2, const asd_feature_vector* fv1, const asd_feature_vector* fv2,
-                     const uint8_t* has_mp1, const uint8_t* has_mp2, float nn_ratio, int32_t check_orientation,
-                     int32_t* match12, int32_t* n_matches) {
-  AsdFrameSlot *K1 = slot_of(ctx, slot1), *K2 = slot_of(ctx, slot2);
-  if (!K1 || !K2 || !has_mp1 || !has_mp2 || !match12 || !n_matches || !fv_valid(fv1, K1->n) || !fv_valid(fv2, K2->n)) return ASD_ERR_INVALID;
-  (void)hipSetDevice(ctx->cfg.device);
-  MatcherState* m = mstate(ctx);
-  std::fill(match12, match12 + K1->n, -1);
-  *n_matches = 0;
-  std::vector<ListQuery> lq;
-  const float* dist = nullptr;
-  int rc = list_search(ctx, m, *K1, *K2, fv1, fv2, has_mp1, /*skip_if_set=*/false, lq, &dist);
-  if (rc != ASD_OK) return rc;
-  int nmatches = 0;
-  std::vector<uint8_t> matched2((size_t)K2->n, 0);
-  std::vector<int> hist[HISTO];
-  for (const ListQuery& Q : lq) {  // reference order: node by node, keyframe 1's keypoints of the node in order (:561-634)
-    float best1 = 256, best2 = 256;
-    int best_idx = -1;
-    for (int t = Q.cbeg; t < Q.cend; ++t) {
-      const int j = fv2->idx[t];
-      if (matched2[j] || !has_mp2[j]) continue;
-      const float d = dist[Q.ooff + (t - Q.cbeg)];
-      if (d < best1) { best2 = best1; best1 = d; best_idx = j; }
-      else if (d < best2) best2 = d;
-    }
-    if (best1 < TH_LOW && best1 < nn_ratio * best2) {
-      match12[Q.qrow] = best_idx;
-      matched2[best_idx] = 1;
-      if (check_orientation) hist[rot_bin(K1->kps[Q.qrow].angle, K2->kps[best_idx].angle)].push_back(Q.qrow);
-      nmatches++;
-    }
-  }
-  if (check_orientation) {
-    int cnt[HISTO], a, b, c;
-    for (int k = 0; k < HISTO; ++k) cnt[k] = (int)hist[k].size();
-    three_maxima(cnt, a, b, c);
-    for (int k = 0; k < HISTO; ++k) {
-      if (k == a || k == b || k == c) continue;
-      for (int i1 : hist[k]) { match12[i1] = -1; nmatches--; }
-    }
-  }
-  *n_matches = nmatches;
-  return ASD_OK;
-}
-
-int asd_match_triangulate(asd_ctx* ctx, int32_t slot1, int32_t slot2, const asd_feature_vector* fv1,
-                          const asd_feature_vector* fv2, const uint8_t* has_mp1, const uint8_t* has_mp2, const float* F12,
-                          float ex, float ey, int32_t check_orientation, int32_t* matches12, int32_t* n_matches) {
-  AsdFrameSlot *K1 = slot_of(ctx, slot1), *K2 = slot_of(ctx, slot2);
-  if (!K1 || !K2 || !has_mp1 || !has_mp2 || !F12 || !matches12 || !n_matches || !fv_valid(fv1, K1->n) || !fv_valid(fv2, K2->n))
-    return ASD_ERR_INVALID;
-  (void)hipSetDevice(ctx->cfg.device);
-  MatcherState* m = mstate(ctx);
-  std::fill(matches12, matches12 + K1->n, -1);
-  *n_matches = 0;
-  std::vector<ListQuery> lq;
-  const float* dist = nullptr;
-  int rc = list_search(ctx, m, *K1, *K2, fv1, fv2, has_mp1, /*skip_if_set=*/true, lq, &dist);
-  if (rc != ASD_OK) return rc;
-  int nmatches = 0;
-  std::vector<int> hist[HISTO];
-  for (const ListQuery& Q : lq) {
-    const asd_keypoint& kp1 = K1->kps[Q.qrow];
-    // epipolar line of kp1 in image 2 (CheckDistEpipolarLine, ORBmatcher.cc:136-153)
-    const float la = kp1.x * F12[0] + kp1.y * F12[3] + F12[6];
-    const float lb = kp1.x * F12[1] + kp1.y * F12[4] + F12[7];
-    const float lc = kp1.x * F12[2] + kp1.y * F12[5] + F12[8];
-    const float den = la * la + lb * lb;
-    float best = TH_LOW;
-    int best_idx = -1;
-    for (int t = Q.cbeg; t < Q.cend; ++t) {
-      const int idx2 = fv2->idx[t];
-      if (has_mp2[idx2]) continue;  // vbMatched2 is never set by the reference (:688, :729)
-      const float d = dist[Q.ooff + (t - Q.cbeg)];
-      if (d > TH_LOW || d > best) continue;
-      const asd_keypoint& kp2 = K2->kps[idx2];
-      const float dex = ex - kp2.x, dey = ey - kp2.y;
-      if (dex * dex + dey * dey < 100 * ctx->scale[kp2.octave]) continue;
-      const float num = la * kp2.x + lb * kp2.y + lc;
-      if (den == 0) continue;
-      const float dsqr = num * num / den;
-      if (dsqr < 3.84 * ctx->sigma2[kp2.octave]) { best_idx = idx2; best = d; }
-    }
-    if (best_idx >= 0) {
-      matches12[Q.qrow] = best_idx;
-      nmatches++;
-      if (check_orientation) hist[rot_bin(kp1.angle, K2->kps[best_idx].angle)].push_back(Q.qrow);
-    }
-  }
-  if (check_orientation) {
-    int cnt[HISTO], a, b, c;
-    for (int k = 0; k < HISTO; ++k) cnt[k] = (int)hist[k].size();
-    three_maxima(cnt, a, b, c);
-    for (int k = 0; k < HISTO; ++k) {
-      if (k == a || k == b || k == c) continue;
-      for (int i1 : hist[k]) { matches12[i1] = -1; nmatches--; }
-    }
-  }
-  *n_matches = nmatches;
-  return ASD_OK;
-}
-
-int asd_frustum(asd_ctx* ctx, int32_t slot_cur, int32_t n, const float* Xw, const float* normal, const float* min_dist,
-                const float* max_dist, const float* Tcw, const float* K, float cos_limit, uint8_t* in_view,
-                float* proj, int32_t* level, float* view_cos) {
-  AsdFrameSlot* F = slot_of(ctx, slot_cur);
-  if (!F || n < 0 || !Tcw || !K || (n > 0 && (!Xw || !normal || !min_dist || !max_dist || !in_view || !proj || !level || !view_cos)))
-    return ASD_ERR_INVALID;
-  const float fx = K[0], fy = K[1], cx = K[2], cy = K[3];
-  const float log_scale = std::log(ctx->cfg.scale_factor);  // Frame.cc:74 (float log)
-  float Ow[3];  // mOw = -mRcw.t()*mtcw (Frame.cc:157): transposed gemm accumulates in double
-  for (int i = 0; i < 3; ++i) {
-    double s = 0;
-    for (int k = 0; k < 3; ++k) s += (double)Tcw[k * 4 + i] * (double)Tcw[k * 4 + 3];
-    Ow[i] = (float)(-1.0 * s);
-  }
-  for (int q = 0; q < n; ++q) {
-    in_view[q] = 0; proj[2 * q] = proj[2 * q + 1] = 0.f; level[q] = 0; view_cos[q] = 0.f;
-    const float* P = Xw + 3 * q;
-    float Pc[3];
-    transform(Tcw, P, Pc);
-    if (Pc[2] < 0.0f) continue;
-    const float invz = 1.0f / Pc[2];
-    const float u = fx * Pc[0] * invz + cx, v = fy * Pc[1] * invz + cy;
-    if (u < F->min_x || u > F->max_x || v < F->min_y || v > F->max_y) continue;
-    const float maxD = 1.2f * max_dist[q], minD = 0.8f * min_dist[q];  // MapPoint.cc:409-419
-    const float PO[3] = {P[0] - Ow[0], P[1] - Ow[1], P[2] - Ow[2]};
-    const double nn = (double)PO[0] * PO[0] + (double)PO[1] * PO[1] + (double)PO[2] * PO[2];
-    const float dist = (float)std::sqrt(nn);
-    if (dist < minD || dist > maxD) continue;
-    const float* Pn = normal + 3 * q;
-    const double dot = (double)PO[0] * Pn[0] + (double)PO[1] * Pn[1] + (double)PO[2] * Pn[2];
-    const float vc = (float)(dot / dist);
-    if (vc < cos_limit) continue;
-    const float ratio = max_dist[q] / dist;  // MapPoint::PredictScale (MapPoint.cc:438-453)
-    int s = (int)std::ceil(std::log(ratio) / log_scale);
-    if (s < 0) s = 0;
-    else if (s >= ctx->cfg.n_levels) s = ctx->cfg.n_levels - 1;
-    in_view[q] = 1;
-    proj[2 * q] = u; proj[2 * q + 1] = v;
-    level[q] = s;
-    view_cos[q] = vc;
-  }
-  return ASD_OK;
-}
-
-int asd_match_init(asd_ctx* ctx, int32_t slot1, int32_t slot2, float* prev_matched, int32_t window, float nn_ratio,
-                   int32_t check_orientation, int32_t* matches12, int32_t* n_matches) {
-  AsdFrameSlot *F1 = slot_of(ctx, slot1), *F2 = slot_of(ctx, slot2);
-  if (!F1 || !F2 || !prev_matched || !matches12 || !n_matches) return ASD_ERR_INVALID;
-  (void)hipSetDevice(ctx->cfg.device);
-  MatcherState* m = mstate(ctx);
-  std::fill(matches12, matches12 + F1->n, -1);
-  *n_matches = 0;
-  if (F1->n == 0 || F2->n == 0) return ASD_OK;
-  int rc = ensure_queries(ctx, m, F1->n);
-  if (rc != ASD_OK) return rc;
-  for (int i1 = 0; i1 < F1->n; ++i1) {
-    m->h_queries[i1] = WinQuery{0.f, 0.f, 0.f, 0, 0, -1};
-    if (F1->kps[i1].octave > 0) continue;  // :434-436
-    m->h_queries[i1] = WinQuery{prev_matched[2 * i1], prev_matched[2 * i1 + 1], (float)window, 0, 0, i1};
-  }
-  SearchResult R;
-  if ((rc = window_search(ctx, m, *F2, F1->n, F1->d_desc, &R)) != ASD_OK) return rc;  // query descriptors: frame 1's, resident
-  std::vector<float> matched_dist(F2->n, 100.f);
-  std::vector<int> matches21(F2->n, -1);
-  std::vector<int> hist[HISTO];
-  int nmatches = 0;
-  for (int i1 = 0; i1 < F1->n; ++i1) {
-    if (R.cnt[i1] == 0) continue;
-    float best = 100.f, best2 = 100.f;
-    int best_idx = -1;
-    for (int t = R.off[i1]; t < R.off[i1] + R.cnt[i1]; ++t) {
-      const int i2 = R.idx[t];
-      const float d = R.dist[t];
-      if (matched_dist[i2] <= d) continue;
-      if (d < best) { best2 = best; best = d; best_idx = i2; }
-      else if (d < best2) best2 = d;
-    }
-    if (best <= TH_LOW && best < best2 * nn_ratio) {
-      if (matches21[best_idx] >= 0) { matches12[matches21[best_idx]] = -1; nmatches--; }
-      matches12[i1] = best_idx;
-      matches21[best_idx] = i1;
-      matched_dist[best_idx] = best;
-      nmatches++;
-      if (check_orientation) hist[rot_bin(F1->kps[i1].angle, F2->kps[best_idx].angle)].push_back(i1);
-    }
-  }
-  if (check_orientation) {
-    int cnt[HISTO], a, b, c;
-    for (int k = 0; k < HISTO; ++k) cnt[k] = (int)hist[k].size();
-    three_maxima(cnt, a, b, c);
-    for (int k = 0; k < HISTO; ++k) {
-      if (k == a || k == b || k == c) continue;
-      for (int idx1 : hist[k])
-        if (matches12[idx1] >= 0) { matches12[idx1] = -1; nmatches--; }
-    }
-  }
-  for (int i1 = 0; i1 < F1->n; ++i1)
-    if (matches12[i1] >= 0) {
-      prev_matched[2 * i1] = F2->kps[matches12[i1]].x;
-      prev_matched[2 * i1 + 1] = F2->kps[matches12[i1]].y;
-    }
-  *n_matches = nmatches;
-  return ASD_OK;
-}
-
-}  // extern "C"
