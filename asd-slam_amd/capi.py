@@ -84,6 +84,11 @@ class asd_kf_culling_args(C.Structure):
                 ("n_mps", C.c_void_p), ("n_redundant", C.c_void_p), ("bad_capacity", C.c_int32), ("bad_rows", C.c_void_p), ("n_bad", C.c_int32)]
 
 
+class asd_normal_depth_args(C.Structure):
+    _fields_ = [("n", C.c_int32), ("rows", C.c_void_p), ("ref_kf", C.c_void_p), ("Xw", C.c_void_p), ("normal", C.c_void_p),
+                ("min_dist", C.c_void_p), ("max_dist", C.c_void_p), ("status", C.c_void_p)]
+
+
 class asd_ba_problem(C.Structure):
     _fields_ = [("n_poses", C.c_int32), ("n_points", C.c_int32), ("n_edges", C.c_int32),
                 ("poses", C.c_void_p), ("fixed", C.c_void_p), ("points", C.c_void_p),
@@ -232,6 +237,20 @@ def initializer_normalize(keys):
     if rc != 0:
         raise AsdError(rc, "asd_initializer_normalize: invalid arguments")
     return pts, T.reshape(3, 3)
+
+
+def normal_and_depth_point(Ow, ref, Pos, scale_level, scale_top):
+    """asd_normal_and_depth_point: the rule of asd_update_normal_and_depth for one point (host only, no context).  Ow [n_obs][3] = the
+    observers' centres in walk order, ref = the reference keyframe's index among them -> (normal [3] f32, min_dist, max_dist as np.float32)"""
+    lib = load_library()
+    Ow, Pos = _c(Ow, np.float32).reshape(-1, 3), _c(Pos, np.float32)
+    normal = np.empty(3, np.float32)
+    mn, mx = C.c_float(0.0), C.c_float(0.0)
+    rc = lib.asd_normal_and_depth_point(C.c_int32(len(Ow)), _p(Ow), C.c_int32(ref), _p(Pos), C.c_float(scale_level), C.c_float(scale_top), _p(normal),
+                                        C.byref(mn), C.byref(mx))
+    if rc != 0:
+        raise AsdError(rc, "asd_normal_and_depth_point: invalid arguments")
+    return normal, np.float32(mn.value), np.float32(mx.value)
 
 
 # asd_debug_prim: op -> (name, doubles in, doubles out), in the order of the enum in include/asd_slam.h
@@ -1006,6 +1025,35 @@ class AsdHip:
         counts = np.full(max(len(rows), 1), -7, np.int32)
         self._chk(self.lib.asd_map_observations(self.ctx, len(rows), _p(rows), _p(counts)))
         return counts[:len(rows)].copy()
+
+    def map_kf_centers(self, kfs, Ow):
+        """KeyFrame::GetCameraCenter() of keyframes in the table (Ow [n][3] f32)"""
+        kfs, Ow = _c(kfs, np.int32), _c(Ow, np.float32).reshape(-1, 3)
+        assert len(kfs) == len(Ow)
+        self._chk(self.lib.asd_map_kf_centers(self.ctx, len(kfs), _p(kfs), _p(Ow)))
+
+    def update_normal_and_depth_raw(self, rows, ref_kf, Xw=None):
+        """asd_update_normal_and_depth -> (rc, dict(normal, min_dist, max_dist, status)); the dict is filled only when rc == 0"""
+        rows, ref_kf = _c(rows, np.int32), _c(ref_kf, np.int32)
+        n = len(rows)
+        assert len(ref_kf) == n
+        xw = None if Xw is None else _c(Xw, np.float32).reshape(n, 3)
+        normal, mn, mx = np.full((max(n, 1), 3), -7, np.float32), np.full(max(n, 1), -7, np.float32), np.full(max(n, 1), -7, np.float32)
+        status = np.full(max(n, 1), 9, np.uint8)
+        a = asd_normal_depth_args()
+        a.n, a.rows, a.ref_kf, a.Xw = n, rows.ctypes.data, ref_kf.ctypes.data, None if xw is None else xw.ctypes.data
+        a.normal, a.min_dist, a.max_dist, a.status = normal.ctypes.data, mn.ctypes.data, mx.ctypes.data, status.ctypes.data
+        rc = self.lib.asd_update_normal_and_depth(self.ctx, C.byref(a))
+        out = {}
+        if rc == 0:
+            out.update(normal=normal[:n].copy(), min_dist=mn[:n].copy(), max_dist=mx[:n].copy(), status=status[:n].copy())
+        return rc, out
+
+    def update_normal_and_depth(self, rows, ref_kf, Xw=None):
+        """MapPoint::UpdateNormalAndDepth over the tables (with Xw: SetWorldPos first) -> dict(normal, min_dist, max_dist, status)"""
+        rc, out = self.update_normal_and_depth_raw(rows, ref_kf, Xw)
+        self._chk(rc)
+        return out
 
     def map_debug(self):
         """(live keyframes, live entries, slot capacity, arena capacity, row-table capacity, slot / arena / row-table growths)"""

@@ -6,6 +6,7 @@
 #include <new>
 
 #include "ctx.h"
+#include "normal_depth.h"
 
 int frontend_alloc(asd_ctx* ctx);
 void frontend_free(asd_ctx* ctx);
@@ -457,6 +458,21 @@ int asd_pose7_to_tcw(const double* p, float* T) {
   }
   T[12] = T[13] = T[14] = 0.f;
   T[15] = 1.f;
+  return ASD_OK;
+}
+
+// MapPoint::UpdateNormalAndDepth's arithmetic for one point (normal_depth.h: the kernel's own functions), without a context
+int asd_normal_and_depth_point(int32_t n_obs, const float* Ow, int32_t ref, const float* Pos, float scale_level, float scale_top, float normal[3],
+                               float* min_dist, float* max_dist) {
+  if (n_obs < 1 || !Ow || ref < 0 || ref >= n_obs || !Pos || !normal || !min_dist || !max_dist) return ASD_ERR_INVALID;
+  float sum[3] = {0.f, 0.f, 0.f}, unit[3];
+  double nrm_ref = 0.0;
+  for (int32_t k = 0; k < n_obs; ++k) {
+    const double nrm = asd_nd_unit(Pos, Ow + 3 * (size_t)k, unit);
+    asd_nd_add(sum, unit);
+    if (k == ref) nrm_ref = nrm;
+  }
+  asd_nd_finish(sum, n_obs, nrm_ref, scale_level, scale_top, normal, min_dist, max_dist);
   return ASD_OK;
 }
 

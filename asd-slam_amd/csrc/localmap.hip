@@ -31,6 +31,15 @@
 // the entries of the points that turned bad; k_cull_finish undoes the marks either way.  asd_map_observations is the same marking and the
 // same pass with one counter per point.
 //
+// UpdateNormalAndDepth.  MapPoint::UpdateNormalAndDepth (reference src/vslam/src/MapPoint.cc:361-407) for many points at once, over this
+// table, a camera centre per slot (d_center, beside d_table) and the matcher's attribute bank, which it rewrites in place.  The mean
+// viewing direction is an f32 sum whose order is part of the result, so nothing is added atomically: k_nd_mark writes the points'
+// positions into the mark table, k_cull_count counts their observers (ONE pass over the live rows, integer atomics), k_nd_scan gives
+// every point a segment, k_nd_fill (the second pass) drops (keyframe id, slot) into the segments through an integer cursor, k_nd_order
+// ranks every segment by keyframe id, and k_nd_point -- one wave per point -- adds the unit vectors one after the other in that order.
+// The arithmetic itself is normal_depth.h, shared with the host function asd_normal_and_depth_point.  Nothing is sized by a typical
+// observer count: the host reads the total between scan and fill and sizes the segments by it.
+//
 // Streams.  Every copy into these tables and every kernel that reads them is enqueued on ctx->stream, every entry point returns with that
 // stream drained, and all of them are refused while an armed asd_track_* call is unfinished (asd_track_local_points_map reads the search
 // list on that stream).  A growth therefore orders itself against the only stream that can hold a write to the old storage: the copy
@@ -42,7 +51,8 @@
 #include <unordered_map>
 #include <vector>
 
-#include "ctx.h"
+#include "matcher.h"
+#include "normal_depth.h"
 
 namespace {
 
@@ -61,6 +71,8 @@ constexpr int kTile = 1024;               // entries per workgroup of the compac
 constexpr int kLevels = ASD_MAX_LEVELS;   // counters per point of asd_keyframe_culling
 constexpr int kMaxCand = 4096;
 constexpr long long kMaxCullEntries = 1ll << 26;   // entries of the candidates' rows together: 16 counters each stay below 2^31 words
+constexpr int kMaxNdPoints = 1 << 20;              // points of one asd_update_normal_and_depth
+constexpr long long kMaxNdEntries = 1ll << 30;     // their observations together: the segment offsets are int32
 
 struct LmSlotDev { long long off; int n; int id; int bad; int n_cov; int parent; int pad; int cov[kMaxCov]; int pad2[2]; };   // n < 0: free slot
 struct LmMove { long long from, to; int n; int pad; };
@@ -515,12 +527,137 @@ __global__ __launch_bounds__(256) void k_obs_unmark(const int* __restrict__ rows
   if (i < n && rows[i] < row_cap) mark[rows[i]] = 0;
 }
 
+// ---- MapPoint::UpdateNormalAndDepth
+struct LmNdArgs {
+  const LmSlotDev* table; int n_slots; const int* rows; const uint8_t* oct; const uint8_t* pbad; const int* mark; int row_cap;
+  const float* center;         // [slots][3]
+  const int* req; const int* ref_slot; const float* xw; int n;   // the call's points: bank row, slot of mpRefKF (-1: not in the table; k_nd_mark), new position or null
+  const int* cnt; int* cursor; const int* seg_off;                // per point: observers, fill cursor, start of its segment
+  int* lvl;                    // per point: the octave of ref_kf's entry, -1 = its row does not name the point
+  int2* seg;                   // (keyframe id, slot) per observation, segment by segment, in the order the fill met them
+  int* ord;                    // the slots of a segment in ascending keyframe id
+  float* attr;                 // the attribute bank
+  float* res;                  // out [n][6], pinned host memory: normal, min, max, status (as int bits)
+  float scale[kLevels]; float scale_top;
+};
+
+// the requested rows get their position (+ 1) in the mark table (distinct rows; a row beyond the row tables has no entry and stays unmarked)
+// and mpRefKF's id becomes its slot, or -1 (the ascending id list of refresh_lists)
+__global__ __launch_bounds__(256) void k_nd_mark(const int* __restrict__ req, int n, int row_cap, int* __restrict__ mark, int* __restrict__ cnt,
+                                                 int* __restrict__ cursor, int* __restrict__ lvl, const int* __restrict__ ref_id,
+                                                 const int* __restrict__ sorted_id, const int* __restrict__ sorted_slot, int n_live, int* __restrict__ ref_slot) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  cnt[i] = 0; cursor[i] = 0; lvl[i] = -1;
+  ref_slot[i] = lm_lookup(sorted_id, sorted_slot, n_live, ref_id[i]);
+  if (req[i] < row_cap) mark[req[i]] = i + 1;
+}
+// exclusive prefix of the counts in ONE workgroup, 16 consecutive points per thread and round; head[12..13] = the total (64 bit)
+__global__ __launch_bounds__(256) void k_nd_scan(const int* __restrict__ cnt, int n, int* __restrict__ seg_off, int* __restrict__ head) {
+  __shared__ int s_scan[256];
+  long long run = 0;
+  for (int base = 0; base < n; base += 4096) {
+    const int i0 = base + threadIdx.x * 16;
+    int v[16], mine = 0;
+    for (int k = 0; k < 16; ++k) { v[k] = i0 + k < n ? cnt[i0 + k] : 0; mine += v[k]; }
+    int total;
+    int ex = lm_block_scan(mine, s_scan, &total);
+    for (int k = 0; k < 16; ++k) {
+      if (i0 + k < n) seg_off[i0 + k] = (int)(run + ex);   // (meaningless beyond kMaxNdEntries: the host reads the total first)
+      ex += v[k];
+    }
+    run += total;
+  }
+  if (threadIdx.x == 0) { seg_off[n] = (int)run; head[12] = (int)(unsigned)(run & 0xffffffffll); head[13] = (int)(run >> 32); }   // (head: pinned host memory)
+}
+// the second pass over the table, one wave per slot: every entry that names a marked point drops (id, slot) into the point's segment
+// through an integer cursor; the entry of mpRefKF leaves its octave.  The order inside a segment is whatever the scheduling made it:
+// k_nd_order undoes that.
+__global__ __launch_bounds__(256) void k_nd_fill(LmNdArgs a) {
+  const int lane = threadIdx.x & 63;
+  const int slot = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (slot >= a.n_slots) return;
+  const long long off = a.table[slot].off;
+  const int n = a.table[slot].n, id = a.table[slot].id;
+  for (int i = lane; i < n; i += 64) {
+    const int r = a.rows[off + i];
+    if (r < 0) continue;
+    const int m = a.mark[r];
+    if (m <= 0) continue;
+    const int p = atomicAdd(&a.cursor[m - 1], 1);
+    if (p < a.cnt[m - 1]) a.seg[(size_t)a.seg_off[m - 1] + p] = make_int2(id, slot);   // (the count pass saw the same table: p is always inside)
+    if (slot == a.ref_slot[m - 1]) a.lvl[m - 1] = a.oct[off + i] & (kLevels - 1);
+  }
+}
+// one wave per point: the rank of every observer by comparison (the ids of a segment are distinct: a point occurs once per row), the slots
+// written in that order.  Lanes read the same id together, so a segment costs len^2 / 64 broadcast loads.
+__global__ __launch_bounds__(256) void k_nd_order(LmNdArgs a) {
+  const int lane = threadIdx.x & 63;
+  const int i = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (i >= a.n) return;
+  const int len = a.cnt[i];
+  const int2* seg = a.seg + a.seg_off[i];
+  int* ord = a.ord + a.seg_off[i];
+  for (int e = lane; e < len; e += 64) {
+    const int2 me = seg[e];
+    int rank = 0;
+    for (int j = 0; j < len; ++j) { const int o = seg[j].x; rank += o < me.x || (o == me.x && j < e); }   // (a table that breaks the precondition still gets a permutation)
+    ord[rank] = me.y;
+  }
+}
+// one wave per point: MapPoint.cc:361-407.  The units of up to 64 observers are computed side by side, then added one after the other in
+// ascending keyframe id -- every lane forms the same f32 sum from the same values, lane 0 stores it.
+__global__ __launch_bounds__(256) void k_nd_point(LmNdArgs a) {
+  const int lane = threadIdx.x & 63;
+  const int i = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (i >= a.n) return;
+  const int r = a.req[i];
+  float* row = a.attr + 8 * (size_t)r;
+  float Pos[3];
+  if (a.xw) { Pos[0] = a.xw[3 * (size_t)i]; Pos[1] = a.xw[3 * (size_t)i + 1]; Pos[2] = a.xw[3 * (size_t)i + 2]; }   // SetWorldPos: no bad test
+  else { Pos[0] = row[0]; Pos[1] = row[1]; Pos[2] = row[2]; }
+  const int len = a.cnt[i], lvl = a.lvl[i];
+  const int status = (r < a.row_cap && a.pbad[r]) ? 1 : len == 0 ? 2 : lvl < 0 ? 3 : 0;
+  float out[5] = {row[3], row[4], row[5], row[6], row[7]};
+  if (status == 0) {
+    const int* ord = a.ord + a.seg_off[i];
+    float sum[3] = {0.f, 0.f, 0.f};
+    for (int base = 0; base < len; base += 64) {
+      const int m = min(64, len - base);
+      float u[3] = {0.f, 0.f, 0.f};
+      if (lane < m) asd_nd_unit(Pos, a.center + 3 * (size_t)ord[base + lane], u);
+      for (int k = 0; k < m; ++k) {
+        const float v[3] = {__shfl(u[0], k, 64), __shfl(u[1], k, 64), __shfl(u[2], k, 64)};
+        asd_nd_add(sum, v);
+      }
+    }
+    float unused[3];
+    const double nrm_ref = asd_nd_unit(Pos, a.center + 3 * (size_t)a.ref_slot[i], unused);
+    asd_nd_finish(sum, len, nrm_ref, a.scale[lvl], a.scale_top, out, out + 3, out + 4);
+  }
+  if (lane == 0) {
+    if (a.xw) { row[0] = Pos[0]; row[1] = Pos[1]; row[2] = Pos[2]; }
+    if (status == 0) for (int k = 0; k < 5; ++k) row[3 + k] = out[k];
+    float* q = a.res + 6 * (size_t)i;
+    for (int k = 0; k < 5; ++k) q[k] = out[k];
+    q[5] = __int_as_float(status);
+  }
+}
+// asd_map_kf_centers: distinct slots
+__global__ __launch_bounds__(256) void k_nd_set_centers(float* __restrict__ center, const int* __restrict__ slot, const float* __restrict__ val, int n) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  float* c = center + 3 * (size_t)slot[i];
+  c[0] = val[3 * i]; c[1] = val[3 * i + 1]; c[2] = val[3 * i + 2];
+}
+
 struct LmSlot {
   int kf = -1;   // -1: free slot
   int n = -1;
   long long off = 0;
   bool bad = false;
   bool has_oct = false;   // asd_map_put_octaves has filled the octave plane of this row
+  bool has_center = false;   // asd_map_kf_centers has set this slot's camera centre
   int n_cov = 0, cov[kMaxCov] = {};
   int parent = -1;
   std::vector<int> children;
@@ -536,6 +673,8 @@ struct LocalMapState {
   int* d_rows = nullptr; long long entry_cap = 0, entry_used = 0;
   uint8_t* d_oct = nullptr;   // the octave plane of the arena: same offsets, same capacity
   int live_without_oct = 0;   // live keyframes whose row has no octaves (asd_keyframe_culling refuses unless 0)
+  float* d_center = nullptr; size_t center_cap = 0;   // KeyFrame::GetCameraCenter() per slot [3], beside d_table: grows with it
+  int live_without_center = 0;   // live keyframes without a centre (asd_update_normal_and_depth refuses unless 0)
   uint8_t* d_pbad = nullptr; int* d_mark = nullptr; int* d_claim = nullptr; size_t row_cap = 0;
   bool tables_dirty = false;  // a query failed between marking and undoing
   int* d_sorted = nullptr; size_t sorted_cap = 0; bool sorted_dirty = true;   // ids [live] | slots [live]
@@ -551,6 +690,8 @@ struct LocalMapState {
   int* d_search = nullptr; size_t search_cap = 0;
   int* d_cull = nullptr; size_t cull_cap = 0;           // scratch of asd_keyframe_culling / asd_map_observations
   int* d_culled = nullptr; size_t culled_cap = 0;       // [slots]
+  int* d_nd = nullptr; size_t nd_cap = 0;               // asd_update_normal_and_depth: the observers' segments (id, slot) | the ordered slots
+  std::vector<uint32_t> nd_stamp; uint32_t nd_call = 0; // its duplicate test: the call that named a bank row last
   AsdXfer up, down;
   int growths[3] = {0, 0, 0};   // slot table, arena, row tables
   // what the last asd_update_local_map left for asd_track_local_points_map
@@ -586,11 +727,12 @@ int lm_reserve(asd_ctx* ctx, T** p, size_t* cap, size_t need, size_t keep, int f
 
 void release_device(LocalMapState* S) {
   void* dev[] = {S->d_table, S->d_rows, S->d_pbad, S->d_mark, S->d_claim, S->d_sorted, S->d_child, S->d_cnt, S->d_list, S->d_list_base, S->d_head,
-                 S->d_tile, S->d_local, S->d_search, S->d_oct, S->d_cull, S->d_culled};
+                 S->d_tile, S->d_local, S->d_search, S->d_oct, S->d_cull, S->d_culled, S->d_center, S->d_nd};
   for (void* p : dev) if (p) (void)hipFree(p);
   S->d_table = nullptr; S->d_rows = nullptr; S->d_pbad = nullptr; S->d_mark = nullptr; S->d_claim = nullptr; S->d_sorted = nullptr; S->d_child = nullptr;
   S->d_cnt = nullptr; S->d_list = nullptr; S->d_list_base = nullptr; S->d_head = nullptr; S->d_tile = nullptr; S->d_local = nullptr; S->d_search = nullptr;
   S->d_oct = nullptr; S->d_cull = nullptr; S->d_culled = nullptr; S->cull_cap = S->culled_cap = 0;
+  S->d_center = nullptr; S->d_nd = nullptr; S->center_cap = S->nd_cap = 0;
   S->table_cap = S->row_cap = S->sorted_cap = S->child_cap = S->cnt_cap = S->list_cap = S->list_base_cap = S->head_cap = S->tile_cap = S->local_cap = S->search_cap = 0;
   S->entry_cap = S->entry_used = 0;
 }
@@ -635,7 +777,9 @@ int upload_entry(asd_ctx* ctx, LocalMapState* S, int slot) {
 }
 
 int grow_table(asd_ctx* ctx, LocalMapState* S, size_t need) {
-  return lm_reserve(ctx, &S->d_table, &S->table_cap, need, S->table_cap, 0xff, kInitSlots, &S->growths[0]);   // (0xff: n = -1, a free slot)
+  const int rc = lm_reserve(ctx, &S->d_table, &S->table_cap, need, S->table_cap, 0xff, kInitSlots, &S->growths[0]);   // (0xff: n = -1, a free slot)
+  if (rc != ASD_OK) return rc;
+  return lm_reserve(ctx, &S->d_center, &S->center_cap, 3 * S->table_cap, S->center_cap, 0, 3 * S->table_cap);   // the centres follow their slots
 }
 
 // room for `need` more entries behind entry_used: a new arena of twice the live entries, the live rows moved into it back to back in slot
@@ -774,6 +918,7 @@ int asd_map_clear(asd_ctx* ctx) {
   S->slots.clear(); S->free_slots.clear(); S->by_kf.clear();
   S->live_entries = 0;
   S->live_without_oct = 0;
+  S->live_without_center = 0;
   S->sorted_dirty = S->child_dirty = true; S->child_off_words = 0; S->tables_dirty = false;
   S->growths[0] = S->growths[1] = S->growths[2] = 0;
   S->last_valid = false; S->last_search.clear();
@@ -813,7 +958,7 @@ int asd_map_put(asd_ctx* ctx, int32_t kf, int32_t n, const int32_t* rows) {
   } else {
     S->live_entries += n - old_n;
   }
-  if (fresh) { L = LmSlot(); L.kf = kf; S->by_kf[kf] = slot; S->sorted_dirty = true; S->child_dirty = true; ++S->live_without_oct; }
+  if (fresh) { L = LmSlot(); L.kf = kf; S->by_kf[kf] = slot; S->sorted_dirty = true; S->child_dirty = true; ++S->live_without_oct; ++S->live_without_center; }
   else if (n != old_n && L.has_oct) { L.has_oct = false; ++S->live_without_oct; }   // the octaves are the keypoints': another n is another set of keypoints
   L.n = n; L.off = off;
   ++S->version;
@@ -873,6 +1018,7 @@ int asd_map_erase(asd_ctx* ctx, int32_t kf) {
   const int slot = it->second;
   S->live_entries -= S->slots[slot].n;
   if (!S->slots[slot].has_oct) --S->live_without_oct;
+  if (!S->slots[slot].has_center) --S->live_without_center;
   S->slots[slot] = LmSlot();   // its row stays in the arena until the next growth compacts it
   S->free_slots.push_back(slot);
   S->by_kf.erase(it);
@@ -1291,6 +1437,141 @@ int asd_map_observations(asd_ctx* ctx, int32_t n, const int32_t* rows, int32_t* 
   ASD_HIP_CHECK(ctx, hipStreamSynchronize(st));
   S->tables_dirty = false;
   memcpy(counts, S->down.h + o_res, (size_t)n * sizeof(int));
+  return ASD_OK;
+}
+
+int asd_map_kf_centers(asd_ctx* ctx, int32_t n, const int32_t* kfs, const float* Ow) {
+  if (!ctx) return ASD_ERR_INVALID;
+  if (refuse(ctx, "asd_map_kf_centers")) return ASD_ERR_INVALID;
+  if (n < 0 || (n > 0 && (!kfs || !Ow))) { ctx->set_error("asd_map_kf_centers: invalid argument (%d keyframes)", n); return ASD_ERR_INVALID; }
+  LocalMapState* S = lstate(ctx);
+  std::unordered_map<int, int> last;   // slot -> the last position that names it
+  for (int i = 0; i < n; ++i) {
+    int slot;
+    if (!find_kf(ctx, S, "asd_map_kf_centers", kfs[i], &slot)) return ASD_ERR_INVALID;
+    last[slot] = i;
+  }
+  if (n == 0) return ASD_OK;
+  (void)hipSetDevice(ctx->cfg.device);
+  std::vector<int> vs;
+  std::vector<float> vc;
+  for (const auto& kv : last) { vs.push_back(kv.first); for (int k = 0; k < 3; ++k) vc.push_back(Ow[3 * (size_t)kv.second + k]); }
+  const int m = (int)vs.size();
+  hipStream_t st = ctx->stream;
+  ASD_HIP_CHECK(ctx, S->up.begin(st, (size_t)m * 16 + 1024));
+  const size_t o_s = S->up.add(vs.data(), (size_t)m * sizeof(int)), o_c = S->up.add(vc.data(), (size_t)m * 3 * sizeof(float));
+  ASD_HIP_CHECK(ctx, S->up.upload(st));
+  hipLaunchKernelGGL(k_nd_set_centers, dim3((m + 255) / 256), dim3(256), 0, st, S->d_center, S->up.dev<int>(o_s), S->up.dev<float>(o_c), m);
+  ASD_HIP_CHECK(ctx, hipGetLastError());
+  ASD_HIP_CHECK(ctx, hipStreamSynchronize(st));
+  for (const int slot : vs) if (!S->slots[slot].has_center) { S->slots[slot].has_center = true; --S->live_without_center; }
+  return ASD_OK;   // (the search list of the last asd_update_local_map stays: nothing it was built from has changed)
+}
+
+int asd_update_normal_and_depth(asd_ctx* ctx, asd_normal_depth_args* A) {
+  if (!ctx) return ASD_ERR_INVALID;
+  if (!A || A->n < 0 || (A->n > 0 && (!A->rows || !A->ref_kf))) { ctx->set_error("asd_update_normal_and_depth: invalid argument"); return ASD_ERR_INVALID; }
+  if (ctx->prep_on) { ctx->set_error("asd_update_normal_and_depth: an asd_prep_async bracket is open"); return ASD_ERR_INVALID; }
+  if (refuse(ctx, "asd_update_normal_and_depth")) return ASD_ERR_INVALID;
+  const int n = A->n;
+  if (n > kMaxNdPoints) { ctx->set_error("asd_update_normal_and_depth: %d points exceed the %d one call takes", n, kMaxNdPoints); return ASD_ERR_CAPACITY; }
+  if (n == 0) return ASD_OK;
+  LocalMapState* S = lstate(ctx);
+  MatcherState* M = matcher_state(ctx);
+  for (int i = 0; i < n; ++i)
+    if (A->rows[i] < 0 || A->rows[i] >= M->attr_cap) {
+      ctx->set_error("asd_update_normal_and_depth: bank row %d at %d lies outside the attribute bank (%d rows): its position was never put", A->rows[i], i, M->attr_cap);
+      return ASD_ERR_INVALID;
+    }
+  if (S->nd_stamp.size() < (size_t)M->attr_cap || S->nd_call == 0xffffffffu) { S->nd_stamp.assign((size_t)M->attr_cap, 0u); S->nd_call = 0; }
+  ++S->nd_call;
+  for (int i = 0; i < n; ++i) {
+    uint32_t& stamp = S->nd_stamp[A->rows[i]];
+    if (stamp == S->nd_call) { ctx->set_error("asd_update_normal_and_depth: bank row %d occurs twice", A->rows[i]); return ASD_ERR_INVALID; }
+    stamp = S->nd_call;
+  }
+  if (S->live_without_oct > 0 || S->live_without_center > 0) {
+    for (const auto& kv : S->by_kf) {
+      const LmSlot& L = S->slots[kv.second];
+      if (!L.has_oct) { ctx->set_error("asd_update_normal_and_depth: keyframe %d has no octaves (asd_map_put_octaves); %d live keyframes have none", kv.first, S->live_without_oct); break; }
+      if (!L.has_center) { ctx->set_error("asd_update_normal_and_depth: keyframe %d has no camera centre (asd_map_kf_centers); %d live keyframes have none", kv.first, S->live_without_center); break; }
+    }
+    return ASD_ERR_INVALID;
+  }
+  (void)hipSetDevice(ctx->cfg.device);
+  hipStream_t st = ctx->stream;
+  const int n_slots = (int)S->slots.size(), n_live = (int)S->by_kf.size();
+  const int row_cap = (int)S->row_cap;   // (at most 2^28)
+  int rc;
+  if ((rc = refresh_lists(ctx, S)) != ASD_OK) return rc;
+  if ((rc = clean_tables(ctx, S)) != ASD_OK) return rc;
+  // counts | cursors | levels | segment offsets [n + 1] | slots of mpRefKF
+  const size_t N = ((size_t)n + 4) / 4 * 4;
+  if ((rc = lm_reserve(ctx, &S->d_cull, &S->cull_cap, 5 * N, 0, -1, 65536)) != ASD_OK) return rc;
+  int* const d_cnt = S->d_cull; int* const d_cursor = d_cnt + N; int* const d_lvl = d_cursor + N; int* const d_off = d_lvl + N;
+  int* const d_ref = d_off + N;
+  if (!S->h_head) ASD_HIP_CHECK(ctx, hipHostMalloc(&S->h_head, 16 * sizeof(int)));
+  ASD_HIP_CHECK(ctx, S->up.begin(st, (size_t)n * (A->Xw ? 20 : 8) + 1024));
+  const size_t o_rows = S->up.add(A->rows, (size_t)n * sizeof(int)), o_ref = S->up.add(A->ref_kf, (size_t)n * sizeof(int));
+  const size_t o_xw = A->Xw ? S->up.add(A->Xw, (size_t)n * 3 * sizeof(float)) : 0;
+  ASD_HIP_CHECK(ctx, S->up.upload(st));
+  ASD_HIP_CHECK(ctx, S->down.begin(st, (size_t)n * 6 * sizeof(float)));
+  const size_t o_res = S->down.reserve((size_t)n * 6 * sizeof(float));
+  const dim3 per_point((n + 255) / 256), per_wave((n + 3) / 4), per_slot((n_slots + 3) / 4);
+  S->tables_dirty = true;
+  hipLaunchKernelGGL(k_nd_mark, per_point, dim3(256), 0, st, S->up.dev<int>(o_rows), n, row_cap, S->d_mark, d_cnt, d_cursor, d_lvl, S->up.dev<int>(o_ref),
+                     S->d_sorted, S->d_sorted ? S->d_sorted + n_live : nullptr, n_live, d_ref);
+  ASD_HIP_CHECK(ctx, hipGetLastError());
+  if (n_slots > 0 && row_cap > 0) {
+    hipLaunchKernelGGL(k_cull_count, per_slot, dim3(256), 0, st, S->d_table, n_slots, S->d_rows, S->d_oct, S->d_mark, d_cnt, 1);
+    ASD_HIP_CHECK(ctx, hipGetLastError());
+  }
+  int* const head = S->h_head;   // (pinned: the kernels store the total and the results there themselves, no copy commands in the call)
+  hipLaunchKernelGGL(k_nd_scan, dim3(1), dim3(256), 0, st, d_cnt, n, d_off, head);
+  ASD_HIP_CHECK(ctx, hipGetLastError());
+  ASD_HIP_CHECK(ctx, hipStreamSynchronize(st));
+  const long long entries = ((long long)head[13] << 32) | (unsigned)head[12];
+  auto unmark = [&]() -> int {
+    hipLaunchKernelGGL(k_obs_unmark, per_point, dim3(256), 0, st, S->up.dev<int>(o_rows), n, row_cap, S->d_mark);
+    ASD_HIP_CHECK(ctx, hipGetLastError());
+    return ASD_OK;
+  };
+  if (entries > kMaxNdEntries) {   // nothing has been written but the marks
+    if ((rc = unmark()) != ASD_OK) return rc;
+    ASD_HIP_CHECK(ctx, hipStreamSynchronize(st));
+    S->tables_dirty = false;
+    ctx->set_error("asd_update_normal_and_depth: the %d points have %lld observations, more than one call takes (%lld)", n, entries, kMaxNdEntries);
+    return ASD_ERR_CAPACITY;
+  }
+  if ((rc = lm_reserve(ctx, &S->d_nd, &S->nd_cap, 3 * (size_t)entries + 4, 0, -1, 65536)) != ASD_OK) return rc;
+  LmNdArgs na{};
+  na.table = S->d_table; na.n_slots = n_slots; na.rows = S->d_rows; na.oct = S->d_oct; na.pbad = S->d_pbad; na.mark = S->d_mark; na.row_cap = row_cap;
+  na.center = S->d_center;
+  na.req = S->up.dev<int>(o_rows); na.ref_slot = d_ref; na.xw = A->Xw ? S->up.dev<float>(o_xw) : nullptr; na.n = n;
+  na.cnt = d_cnt; na.cursor = d_cursor; na.seg_off = d_off; na.lvl = d_lvl;
+  na.seg = reinterpret_cast<int2*>(S->d_nd); na.ord = S->d_nd + 2 * (size_t)entries;
+  na.attr = M->d_attr; na.res = S->down.host<float>(o_res);
+  for (int l = 0; l < kLevels; ++l) na.scale[l] = l < ctx->cfg.n_levels ? ctx->scale[l] : 0.f;
+  na.scale_top = ctx->scale[ctx->cfg.n_levels - 1];
+  if (entries > 0) {
+    hipLaunchKernelGGL(k_nd_fill, per_slot, dim3(256), 0, st, na);
+    ASD_HIP_CHECK(ctx, hipGetLastError());
+    hipLaunchKernelGGL(k_nd_order, per_wave, dim3(256), 0, st, na);
+    ASD_HIP_CHECK(ctx, hipGetLastError());
+  }
+  hipLaunchKernelGGL(k_nd_point, per_wave, dim3(256), 0, st, na);
+  ASD_HIP_CHECK(ctx, hipGetLastError());
+  if ((rc = unmark()) != ASD_OK) return rc;
+  ASD_HIP_CHECK(ctx, hipStreamSynchronize(st));
+  S->tables_dirty = false;
+  const float* res = S->down.host<float>(o_res);
+  for (int i = 0; i < n; ++i) {
+    const float* q = res + 6 * (size_t)i;
+    if (A->normal) { A->normal[3 * (size_t)i] = q[0]; A->normal[3 * (size_t)i + 1] = q[1]; A->normal[3 * (size_t)i + 2] = q[2]; }
+    if (A->min_dist) A->min_dist[i] = q[3];
+    if (A->max_dist) A->max_dist[i] = q[4];
+    if (A->status) { int s; memcpy(&s, q + 5, sizeof s); A->status[i] = (uint8_t)s; }
+  }
   return ASD_OK;
 }
 

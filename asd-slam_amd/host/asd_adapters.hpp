@@ -571,7 +571,7 @@ struct Optimizer {
     std::vector<double> sim3;        // [keyframes][8], in the caller's order: the optimised CorrectedSiw
     std::vector<float> Tcw;          // [keyframes][16]: what pKFi->SetPose gets (:963-965)
     std::vector<uint8_t> mp_written; // map point i is not bad
-    std::vector<float> Xw;           // [points][3]: what pMP->SetWorldPos gets (:995-996); UpdateNormalAndDepth stays the caller's
+    std::vector<float> Xw;           // [points][3]: what pMP->SetWorldPos gets (:995-996); Optimizer::WriteBack hands it to the bank with UpdateNormalAndDepth (:998)
   };
   // The vertices and edges of :765-939, without a device: vScw (CorrectedSim3 where present, else (Rcw, tcw, 1)), pLoopKF fixed, then
   // the LoopConnections edges (minFeat = 100 with the pCurKF <-> pLoopKF exemption of :819) and per keyframe -- in the vector's order --
@@ -686,6 +686,23 @@ struct Optimizer {
   static int LocalBundleAdjustment(Context& c, asd_ba_problem* problem, asd_ba_result* result, const bool* pbStopFlag = nullptr) {
     if (pbStopFlag && *pbStopFlag) return 0;  // :595-597
     return asd_local_ba(c.get(), problem, result);
+  }
+
+  // The write-back of LocalBundleAdjustment (Optimizer.cc:718-732), BundleAdjustment (:196-228) and OptimizeEssentialGraph (:960-999) over the
+  // resident tables: pKF->SetPose for the keyframes (their new camera centres, asd_map_kf_centers), then pMP->SetWorldPos and
+  // pMP->UpdateNormalAndDepth for the points (asd_update_normal_and_depth with Xw) -- two calls, and the attribute bank is current.  Ow
+  // [kfIds][3] = KeyFrame::GetCameraCenter() after SetPose, Xw [rows][3], refKFs = mpRefKF->mnId per point.  status (may be null): per
+  // point 0 updated, 1 bad, 2 no observations, 3 mpRefKF does not observe it (include/asd_slam.h).
+  static int WriteBack(Context& c, const std::vector<int32_t>& kfIds, const std::vector<float>& Ow, const std::vector<int32_t>& rows,
+                       const std::vector<int32_t>& refKFs, const std::vector<float>& Xw, std::vector<uint8_t>* status = nullptr) {
+    if (Ow.size() != 3 * kfIds.size() || refKFs.size() != rows.size() || Xw.size() != 3 * rows.size()) return ASD_ERR_INVALID;
+    const int rc = asd_map_kf_centers(c.get(), (int32_t)kfIds.size(), kfIds.data(), Ow.data());
+    if (rc != ASD_OK) return rc;
+    if (status) status->assign(rows.size(), 0);
+    asd_normal_depth_args a{};
+    a.n = (int32_t)rows.size(); a.rows = rows.data(); a.ref_kf = refKFs.data(); a.Xw = Xw.data();
+    a.status = status ? status->data() : nullptr;
+    return asd_update_normal_and_depth(c.get(), &a);
   }
 };
 
@@ -880,6 +897,37 @@ struct KeyFrame {
     if (vPairs.empty()) vPairs.emplace_back(R.nmax, R.pKFmax);
     std::sort(vPairs.begin(), vPairs.end());
     for (size_t i = vPairs.size(); i-- > 0;) { R.mvpOrderedConnectedKeyFrames.push_back(vPairs[i].second); R.mvOrderedWeights.push_back(vPairs[i].first); }
+    return R;
+  }
+
+  // void KeyFrame::SetPose(const cv::Mat& Tcw) (KeyFrame.cc:221-235), the part the resident tables keep: Ow = GetCameraCenter() of the
+  // keyframes `ids` as the caller's own SetPose computed them ([ids][3], f32).  Batched: LocalBA, GBA and the essential graph rewrite many poses.
+  static int SetPose(Context& c, const std::vector<int32_t>& ids, const std::vector<float>& Ow) {
+    if (Ow.size() != 3 * ids.size()) return ASD_ERR_INVALID;
+    return asd_map_kf_centers(c.get(), (int32_t)ids.size(), ids.data(), Ow.data());
+  }
+};
+
+// ---- MapPoint (MapPoint.h; src/vslam/src/MapPoint.cc) ---------------------------------------------
+struct MapPoint {
+  struct NormalAndDepth {
+    int rc = ASD_OK;
+    std::vector<float> mNormalVector, mfMinDistance, mfMaxDistance;   // [rows][3], [rows], [rows]: what the attribute bank now holds
+    std::vector<uint8_t> status;                                      // 0 updated, 1 bad, 2 no observations, 3 mpRefKF does not observe the point
+  };
+  // void MapPoint::UpdateNormalAndDepth() (MapPoint.cc:361-407) for the points `rows` (bank rows, distinct) with refKFs = mpRefKF->mnId,
+  // over the observation table, the keyframes' centres (KeyFrame::SetPose above) and octaves, and the attribute bank, which is rewritten in
+  // place.  Xw (null or [rows][3]): MapPoint::SetWorldPos directly in front, as the optimizers' write-backs have it.
+  static NormalAndDepth UpdateNormalAndDepth(Context& c, const std::vector<int32_t>& rows, const std::vector<int32_t>& refKFs,
+                                             const std::vector<float>* Xw = nullptr) {
+    NormalAndDepth R;
+    if (refKFs.size() != rows.size() || (Xw && Xw->size() != 3 * rows.size())) { R.rc = ASD_ERR_INVALID; return R; }
+    const size_t n = rows.size();
+    R.mNormalVector.assign(3 * n, 0.f); R.mfMinDistance.assign(n, 0.f); R.mfMaxDistance.assign(n, 0.f); R.status.assign(n, 0);
+    asd_normal_depth_args a{};
+    a.n = (int32_t)n; a.rows = rows.data(); a.ref_kf = refKFs.data(); a.Xw = Xw ? Xw->data() : nullptr;
+    a.normal = R.mNormalVector.data(); a.min_dist = R.mfMinDistance.data(); a.max_dist = R.mfMaxDistance.data(); a.status = R.status.data();
+    R.rc = asd_update_normal_and_depth(c.get(), &a);
     return R;
   }
 };

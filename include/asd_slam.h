@@ -1444,6 +1444,61 @@ int asd_keyframe_culling(asd_ctx* ctx, asd_kf_culling_args* args);
  * bad byte is not consulted; a row never named gives 0.  Changes neither the table nor the search list. */
 int asd_map_observations(asd_ctx* ctx, int32_t n, const int32_t* rows, int32_t* counts);
 
+/* ---- MapPoint::UpdateNormalAndDepth over the tables ----
+ * asd_map_kf_centers sets KeyFrame::GetCameraCenter() (Ow, f32, as KeyFrame::SetPose leaves it, KeyFrame.cc:221-235) for n keyframes
+ * that are in the table.  The library does not recompute it from Tcw.  An unknown keyframe is ASD_ERR_INVALID and nothing is written; a
+ * keyframe named twice takes the last value.  The centre belongs to the keyframe's slot: it follows table growth, an asd_map_put that
+ * replaces the row keeps it (whatever n), asd_map_erase and asd_map_clear drop it.  Setting centres does not invalidate the search list of
+ * asd_track_local_points_map. */
+int asd_map_kf_centers(asd_ctx* ctx, int32_t n, const int32_t* kfs, const float* Ow /*[n][3]*/);
+
+/* MapPoint::UpdateNormalAndDepth (MapPoint.cc:361-407) for n points at once, over the observation table, the centres above, the octaves of
+ * asd_map_put_octaves and the attribute bank, whose rows it rewrites in place -- the caller uploads no normals and no ranges.
+ * Xw non-NULL is the write-back form, MapPoint::SetWorldPos directly in front of the update (Optimizer.cc:728-731, :225-227, :995-998,
+ * LoopClosing.cc:518-520): Xw[i] becomes the row's position first, whatever the point's status (SetWorldPos has no bad test either).
+ * Per point, with Pos = the row's position in the attribute bank (f32):
+ *   status 0  updated: the row's normal, min_dist and max_dist are rewritten;
+ *          1  the point is flagged bad (asd_map_point_bad; :369): normal and range untouched;
+ *          2  no table entry names the row (:381) -- a row beyond the row tables included: untouched;
+ *          3  ref_kf[i] is not in the table, or its row does not name the point: untouched.  The reference cannot reach this state
+ *             (MapPoint::EraseObservation re-seats mpRefKF); what it would do there -- std::map::operator[] inserting index 0 and reading
+ *             keypoint 0's octave (:397) -- is NOT restated.
+ * The tests apply in this order.  The observers of a point are ALL table entries that name it, no bad-keyframe test, as mObservations is
+ * walked (:386-393), in ASCENDING KEYFRAME ID (the section's standing rule for pointer-order walks).  level = the octave of ref_kf's entry
+ * for the point; scaleFactor[] and nLevels are the context's own (asd_get_scale_tables); an octave >= nLevels (the reference would read
+ * past mvScaleFactors) takes the factor 0.  The reference leaves the arithmetic to OpenCV; the library's rule is
+ *   d      = Pos - Ow_kf                                              f32, per component
+ *   nrm    = sqrt(((double)dx*dx + (double)dy*dy) + (double)dz*dz)    f64 (the products are exact)
+ *   unit_k = (float)((double)d_k * (1.0 / nrm))
+ *   normal = normal + unit                                            f32, one observer after the other in ascending keyframe id, from zero
+ *   mNormalVector_k = (float)((double)normal_k * (1.0 / (double)n_obs))
+ *   dist          = (float)nrm  with kf = ref_kf
+ *   mfMaxDistance = dist * scaleFactor[level]                         one f32 product
+ *   mfMinDistance = mfMaxDistance / scaleFactor[nLevels - 1]          one correctly rounded f32 division
+ * A point that sits on a camera centre follows IEEE arithmetic (inf / NaN), as the reference would; it is not an error.
+ * normal / min_dist / max_dist (each may be NULL) return what the bank holds for the rows after the call, for every status.
+ * ASD_ERR_INVALID (asd_last_error names the culprit): a row < 0 or beyond the attribute bank's capacity (its position was never put);
+ * a row named twice; any live keyframe without octaves or without a centre; an open asd_prep_async bracket or an unfinished call armed with
+ * asd_track_async (the attribute bank may be written on the second stream: asd_debug_bank_get's conditions).  ASD_ERR_CAPACITY: more than
+ * 2^20 points per call, or more than 2^30 observations of the requested points together.  n == 0 is ASD_OK.  On any error neither bank nor
+ * table is changed.  The call runs on the context's stream and returns drained; results are identical from run to run; it changes neither
+ * the table nor its version: the search list of asd_track_local_points_map stays valid and the next stage reads the new attributes. */
+typedef struct asd_normal_depth_args {
+  int32_t n; const int32_t* rows;      /* bank rows of the points, distinct                                   */
+  const int32_t* ref_kf;               /* [n] mpRefKF->mnId                                                   */
+  const float* Xw;                     /* [n][3] or NULL: MapPoint::SetWorldPos in front of the update        */
+  float* normal; float* min_dist; float* max_dist;   /* [n][3], [n], [n], each may be NULL: what the bank now holds */
+  uint8_t* status;                     /* [n] or NULL                                                         */
+} asd_normal_depth_args;
+int asd_update_normal_and_depth(asd_ctx* ctx, asd_normal_depth_args* args);
+
+/* The rule above for ONE point on the host, without a context or a device (the kernel's own functions, csrc/normal_depth.h): Ow[n_obs][3]
+ * = the observers' centres in walk order, ref = the index of the reference keyframe among them, scale_level = scaleFactor[level],
+ * scale_top = scaleFactor[nLevels - 1].  ASD_ERR_INVALID for n_obs < 1, ref outside [0, n_obs) or a NULL pointer.  It also gives a caller
+ * the MapPoint constructor's normal (MapPoint.cc:60-77) for free. */
+int asd_normal_and_depth_point(int32_t n_obs, const float* Ow /*[n_obs][3], in walk order*/, int32_t ref /*index into Ow*/,
+                               const float* Pos, float scale_level, float scale_top, float normal[3], float* min_dist, float* max_dist);
+
 /* Test aid: out = {live keyframes, live entries, slot capacity, arena capacity, row-table capacity, growths of the slot table, of the arena,
  * of the row tables}. */
 int32_t asd_debug_map(asd_ctx* ctx, int64_t out[8]);
