@@ -89,6 +89,20 @@ class asd_normal_depth_args(C.Structure):
                 ("min_dist", C.c_void_p), ("max_dist", C.c_void_p), ("status", C.c_void_p)]
 
 
+class asd_ba_graph_args(C.Structure):
+    _fields_ = [("kf", C.c_int32), ("n_neigh", C.c_int32), ("neigh", C.c_void_p), ("kf_capacity", C.c_int32), ("local_kfs", C.c_void_p),
+                ("n_local_kfs", C.c_int32), ("point_capacity", C.c_int32), ("local_rows", C.c_void_p), ("point_rank", C.c_void_p),
+                ("n_points", C.c_int32), ("fixed_capacity", C.c_int32), ("fixed_kfs", C.c_void_p), ("n_fixed", C.c_int32),
+                ("pose_capacity", C.c_int32), ("pose_kfs", C.c_void_p), ("pose_fixed", C.c_void_p), ("n_poses", C.c_int32),
+                ("edge_capacity", C.c_int32), ("e_point", C.c_void_p), ("e_pose", C.c_void_p), ("e_kf", C.c_void_p), ("e_idx", C.c_void_p),
+                ("e_octave", C.c_void_p), ("n_edges", C.c_int32), ("Xw", C.c_void_p)]
+
+
+class asd_ba_apply_args(C.Structure):
+    _fields_ = [("n_edges", C.c_int32), ("erase", C.c_void_p), ("apply", C.c_int32), ("n_erased", C.c_int32), ("bad_capacity", C.c_int32),
+                ("bad_rows", C.c_void_p), ("n_bad", C.c_int32), ("n_points", C.c_int32), ("new_ref", C.c_void_p)]
+
+
 class asd_ba_problem(C.Structure):
     _fields_ = [("n_poses", C.c_int32), ("n_points", C.c_int32), ("n_edges", C.c_int32),
                 ("poses", C.c_void_p), ("fixed", C.c_void_p), ("points", C.c_void_p),
@@ -1052,6 +1066,65 @@ class AsdHip:
     def update_normal_and_depth(self, rows, ref_kf, Xw=None):
         """MapPoint::UpdateNormalAndDepth over the tables (with Xw: SetWorldPos first) -> dict(normal, min_dist, max_dist, status)"""
         rc, out = self.update_normal_and_depth_raw(rows, ref_kf, Xw)
+        self._chk(rc)
+        return out
+
+    def local_ba_graph_raw(self, kf, neigh, caps, want_Xw=False):
+        """asd_local_ba_graph with the caller's capacities caps = (kfs, points, fixed, poses, edges) -> (rc, dict); the dict always holds
+        the five counts, the lists (cut to the counts) only when rc == 0"""
+        neigh = _c(neigh, np.int32)
+        ck, cp, cf, cq, ce = (int(c) for c in caps)
+        i32 = lambda c: np.full(max(c, 1), -7, np.int32)
+        kfs, rows, rank, fixed, pose = i32(ck), i32(cp), i32(cp), i32(cf), i32(cq)
+        pfix, e_point, e_pose, e_kf, e_idx = np.full(max(cq, 1), 9, np.uint8), i32(ce), i32(ce), i32(ce), i32(ce)
+        e_oct = np.full(max(ce, 1), 99, np.uint8)
+        xw = np.full((max(cp, 1), 3), np.nan) if want_Xw else None
+        a = asd_ba_graph_args()
+        a.kf, a.n_neigh, a.neigh = int(kf), len(neigh), neigh.ctypes.data
+        a.kf_capacity, a.local_kfs = ck, kfs.ctypes.data
+        a.point_capacity, a.local_rows, a.point_rank = cp, rows.ctypes.data, rank.ctypes.data
+        a.fixed_capacity, a.fixed_kfs = cf, fixed.ctypes.data
+        a.pose_capacity, a.pose_kfs, a.pose_fixed = cq, pose.ctypes.data, pfix.ctypes.data
+        a.edge_capacity, a.e_point, a.e_pose, a.e_kf, a.e_idx, a.e_octave = ce, e_point.ctypes.data, e_pose.ctypes.data, e_kf.ctypes.data, e_idx.ctypes.data, e_oct.ctypes.data
+        a.Xw = None if xw is None else xw.ctypes.data
+        a.n_local_kfs = a.n_points = a.n_fixed = a.n_poses = a.n_edges = -1
+        rc = self.lib.asd_local_ba_graph(self.ctx, C.byref(a))
+        out = dict(n_local_kfs=a.n_local_kfs, n_points=a.n_points, n_fixed=a.n_fixed, n_poses=a.n_poses, n_edges=a.n_edges)
+        if rc == 0:
+            out.update(local_kfs=kfs[:a.n_local_kfs].copy(), local_rows=rows[:a.n_points].copy(), point_rank=rank[:a.n_points].copy(),
+                       fixed_kfs=fixed[:a.n_fixed].copy(), pose_kfs=pose[:a.n_poses].copy(), pose_fixed=pfix[:a.n_poses].copy(),
+                       e_point=e_point[:a.n_edges].copy(), e_pose=e_pose[:a.n_edges].copy(), e_kf=e_kf[:a.n_edges].copy(),
+                       e_idx=e_idx[:a.n_edges].copy(), e_octave=e_oct[:a.n_edges].copy())
+            if want_Xw:
+                out["Xw"] = xw[:a.n_points].copy()
+        return rc, out
+
+    def local_ba_graph(self, kf, neigh, want_Xw=False, caps=(64, 4096, 64, 128, 16384)):
+        """Optimizer::LocalBundleAdjustment's lists and edges over the table; repeats once with the counts the library asked for"""
+        rc, out = self.local_ba_graph_raw(kf, neigh, caps, want_Xw)
+        if rc == -5 and out["n_local_kfs"] > 0:   # ASD_ERR_CAPACITY with the counts set
+            rc, out = self.local_ba_graph_raw(kf, neigh, (out["n_local_kfs"], out["n_points"], out["n_fixed"], out["n_poses"], out["n_edges"]), want_Xw)
+        self._chk(rc)
+        return out
+
+    def local_ba_apply_raw(self, erase, n_points, apply, bad_capacity):
+        """asd_local_ba_apply -> (rc, dict(n_erased, n_bad[, bad_rows, new_ref]))"""
+        erase = _c(erase, np.uint8)
+        bad, ref = np.full(max(int(bad_capacity), 1), -7, np.int32), np.full(max(int(n_points), 1), -7, np.int32)
+        a = asd_ba_apply_args()
+        a.n_edges, a.erase, a.apply, a.n_erased = len(erase), erase.ctypes.data, int(bool(apply)), -1
+        a.bad_capacity, a.bad_rows, a.n_bad, a.n_points, a.new_ref = int(bad_capacity), bad.ctypes.data, -1, int(n_points), ref.ctypes.data
+        rc = self.lib.asd_local_ba_apply(self.ctx, C.byref(a))
+        out = dict(n_erased=a.n_erased, n_bad=a.n_bad)
+        if rc == 0:
+            out.update(bad_rows=bad[:a.n_bad].copy(), new_ref=ref[:int(n_points)].copy())
+        return rc, out
+
+    def local_ba_apply(self, erase, n_points, apply=False, bad_capacity=64):
+        """the erase policy of Optimizer.cc:652-697 over the resident graph; repeats once with the capacity the library asked for"""
+        rc, out = self.local_ba_apply_raw(erase, n_points, apply, bad_capacity)
+        if rc == -5 and out["n_bad"] > bad_capacity:
+            rc, out = self.local_ba_apply_raw(erase, n_points, apply, out["n_bad"])
         self._chk(rc)
         return out
 

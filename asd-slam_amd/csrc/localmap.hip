@@ -40,6 +40,15 @@
 // The arithmetic itself is normal_depth.h, shared with the host function asd_normal_and_depth_point.  Nothing is sized by a typical
 // observer count: the host reads the total between scan and fill and sizes the segments by it.
 //
+// LocalBundleAdjustment.  asd_local_ba_graph is Optimizer.cc:418-467 with the structure of :484-593: the local keyframes' rows go through
+// the claim / count / tile-scan / scatter compaction (lLocalMapPoints), k_cull_count and k_nd_scan give every point its Observations() and
+// a segment, k_bg_fill / k_bg_order lay (keyframe id, slot, keypoint index, octave) into it in ascending id.  An entry's position in the
+// ordered segments is the moment the reference's walk meets it, so lFixedCameras is one more ordered de-duplication (a claim word per slot,
+// atomicMin of the position) and one more count / tile-scan / scatter, which numbers the edges at the same time; point_rank is a scan over
+// the marked rows of the row tables.  The segments and the edge -> entry map stay resident (d_bg*: storage of their own) for
+// asd_local_ba_apply, which evaluates the erase policy of :652-697 per point in closed form and, with apply = 1, empties the erased
+// entries THROUGH the segments, without another pass over the table.
+//
 // Streams.  Every copy into these tables and every kernel that reads them is enqueued on ctx->stream, every entry point returns with that
 // stream drained, and all of them are refused while an armed asd_track_* call is unfinished (asd_track_local_points_map reads the search
 // list on that stream).  A growth therefore orders itself against the only stream that can hold a write to the old storage: the copy
@@ -651,6 +660,201 @@ __global__ __launch_bounds__(256) void k_nd_set_centers(float* __restrict__ cent
   c[0] = val[3 * i]; c[1] = val[3 * i + 1]; c[2] = val[3 * i + 2];
 }
 
+// ---- Optimizer::LocalBundleAdjustment: the graph (Optimizer.cc:418-467, :534-593) and the erase policy (:652-697)
+struct LmBgArgs {
+  const LmSlotDev* table; const int* rows; const uint8_t* oct; const int* mark; int n_slots;
+  const int* pts; int n;                          // lLocalMapPoints (the compaction's list) and their number
+  const int* cnt; int* cursor; const int* seg_off;   // per point: Observations(), fill cursor, start of its segment
+  int4* useg; int4* oseg;                         // (keyframe id, slot, keypoint index | octave << 16, point) as the fill met them / in ascending id
+  const uint8_t* local;                           // [slots] 1 = member of lLocalKeyFrames
+  int* kf_claim;                                  // [slots] the first position in the ordered segments that names a not-local, not-bad keyframe
+  long long total;                                // entries of all segments
+  int* tile_cnt; const int* tile_off;             // [tiles][2]: fixed keyframes first met in the tile, edges of the tile
+  int* fixed; int* e_ent;                         // out: lFixedCameras as ids; edge -> position in the ordered segments
+};
+struct LmBgEdgeArgs {
+  const int4* oseg; const int* e_ent; const int* rank; const int* pose_idx; int n_edges; int cap;
+  int* e_point; int* e_pose; int* e_kf; int* e_idx; uint8_t* e_oct;   // pinned host memory, as far as the caller's capacity goes
+};
+struct LmBaArgs {
+  LmSlotDev* table; int* rows; uint8_t* pbad;
+  const int* pts; int n; const int* cnt; const int* seg_off; const int4* oseg;
+  const uint8_t* flagged;      // per segment entry: its edge is in vToErase
+  int* gone; const int* boff;  // per point: turned bad; its place in bad_rows
+  int* new_ref; int* bad_rows; int bad_cap;   // pinned host memory
+  int* head;                   // head[14] += observations erased
+  int apply;
+};
+
+// the compacted points get their position (+ 1) in the mark table, a clean counter and a clean cursor
+__global__ __launch_bounds__(256) void k_bg_index(const int* __restrict__ pts, int n, int* __restrict__ mark, int* __restrict__ cnt, int* __restrict__ cursor) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  mark[pts[i]] = i + 1;
+  cnt[i] = 0; cursor[i] = 0;
+}
+// point_rank: the marked rows counted in row order -- tiles of the row tables, then k_lm_tilescan, then the ranks
+__global__ __launch_bounds__(256) void k_bg_rank_count(const int* __restrict__ mark, int row_cap, int* __restrict__ tile_cnt) {
+  __shared__ int s_wave[4];
+  int c = 0;
+  for (int k = 0; k < 4; ++k) {
+    const long long r = (long long)blockIdx.x * kTile + k * 256 + threadIdx.x;
+    c += r < row_cap && mark[r] > 0;
+  }
+  for (int s = 32; s > 0; s >>= 1) c += __shfl_xor(c, s, 64);
+  if ((threadIdx.x & 63) == 0) s_wave[threadIdx.x >> 6] = c;
+  asd_syncthreads();
+  if (threadIdx.x == 0) { tile_cnt[2 * blockIdx.x] = s_wave[0] + s_wave[1] + s_wave[2] + s_wave[3]; tile_cnt[2 * blockIdx.x + 1] = 0; }
+}
+__global__ __launch_bounds__(256) void k_bg_rank_scatter(const int* __restrict__ mark, int row_cap, const int* __restrict__ tile_off, int* __restrict__ rank) {
+  __shared__ int s_wave[4];
+  int o = tile_off[2 * blockIdx.x];
+  for (int k = 0; k < 4; ++k) {
+    const long long r = (long long)blockIdx.x * kTile + k * 256 + threadIdx.x;
+    const int m = r < row_cap ? mark[r] : 0;
+    int total;
+    const int p = lm_block_scan_flag(m > 0, s_wave, &total);
+    if (m > 0) rank[m - 1] = o + p;
+    o += total;
+  }
+}
+// k_nd_fill with the keypoint index and the octave kept: one wave per slot, every entry that names a marked point drops into the point's
+// segment through an integer cursor
+__global__ __launch_bounds__(256) void k_bg_fill(LmBgArgs a) {
+  const int lane = threadIdx.x & 63;
+  const int slot = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (slot >= a.n_slots) return;
+  const long long off = a.table[slot].off;
+  const int n = a.table[slot].n, id = a.table[slot].id;
+  for (int i = lane; i < n; i += 64) {
+    const int r = a.rows[off + i];
+    if (r < 0) continue;
+    const int m = a.mark[r];
+    if (m <= 0) continue;
+    const int p = atomicAdd(&a.cursor[m - 1], 1);
+    if (p < a.cnt[m - 1]) a.useg[(size_t)a.seg_off[m - 1] + p] = make_int4(id, slot, i | ((a.oct[off + i] & (kLevels - 1)) << 16), m - 1);
+  }
+}
+// k_nd_order with the whole entry moved: one wave per point ranks its observers by keyframe id.  The position of an entry in the ordered
+// segments is the moment the walk of :453-467 meets it: a keyframe that is neither local nor bad is claimed by the smallest one.
+__global__ __launch_bounds__(256) void k_bg_order(LmBgArgs a) {
+  const int lane = threadIdx.x & 63;
+  const int i = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (i >= a.n) return;
+  const int len = a.cnt[i], base = a.seg_off[i];
+  const int4* seg = a.useg + base;
+  for (int e = lane; e < len; e += 64) {
+    const int4 me = seg[e];
+    int rank = 0;
+    for (int j = 0; j < len; ++j) { const int o = seg[j].x; rank += o < me.x || (o == me.x && j < e); }
+    a.oseg[base + rank] = me;
+    if (!a.local[me.y] && !a.table[me.y].bad) atomicMin(&a.kf_claim[me.y], base + rank);
+  }
+}
+// the ordered segments as one array in tiles of 1024: the claimants are lFixedCameras in order, the entries of not-bad keyframes the edges
+__device__ inline void bg_entry(const LmBgArgs& a, int k, bool* win, bool* edge, long long* pos, int* id) {
+  *pos = (long long)blockIdx.x * kTile + k * 256 + threadIdx.x;
+  *win = false; *edge = false; *id = -1;
+  if (*pos >= a.total) return;
+  const int4 s = a.oseg[*pos];
+  *win = a.kf_claim[s.y] == (int)*pos;
+  *edge = !a.table[s.y].bad;
+  *id = s.x;
+}
+__global__ __launch_bounds__(256) void k_bg_count(LmBgArgs a) {
+  __shared__ int s_wave[4];
+  int nf = 0, ne = 0;
+  for (int k = 0; k < 4; ++k) {
+    bool win, edge; long long pos; int id;
+    bg_entry(a, k, &win, &edge, &pos, &id);
+    nf += win; ne += edge;
+  }
+  int packed = nf | (ne << 12);
+  for (int s = 32; s > 0; s >>= 1) packed += __shfl_xor(packed, s, 64);
+  if ((threadIdx.x & 63) == 0) s_wave[threadIdx.x >> 6] = packed;
+  asd_syncthreads();
+  if (threadIdx.x == 0) {
+    const int sum = s_wave[0] + s_wave[1] + s_wave[2] + s_wave[3];
+    a.tile_cnt[2 * blockIdx.x] = sum & 0xfff;
+    a.tile_cnt[2 * blockIdx.x + 1] = sum >> 12;
+  }
+}
+__global__ __launch_bounds__(256) void k_bg_scatter(LmBgArgs a) {
+  __shared__ int s_wave[4];
+  int of = a.tile_off[2 * blockIdx.x], oe = a.tile_off[2 * blockIdx.x + 1];
+  for (int k = 0; k < 4; ++k) {
+    bool win, edge; long long pos; int id;
+    bg_entry(a, k, &win, &edge, &pos, &id);
+    int tf, te;
+    const int pf = lm_block_scan_flag(win, s_wave, &tf);
+    const int pe = lm_block_scan_flag(edge, s_wave, &te);
+    if (win) a.fixed[of + pf] = id;
+    if (edge) a.e_ent[oe + pe] = (int)pos;
+    of += tf; oe += te;
+  }
+}
+__global__ __launch_bounds__(256) void k_bg_edges(LmBgEdgeArgs a) {
+  const int e = blockIdx.x * 256 + threadIdx.x;
+  if (e >= a.n_edges || e >= a.cap) return;
+  const int4 s = a.oseg[a.e_ent[e]];
+  a.e_point[e] = a.rank[s.w];
+  a.e_pose[e] = a.pose_idx[s.y];
+  a.e_kf[e] = s.x;
+  a.e_idx[e] = s.z & 0xffff;
+  a.e_oct[e] = (uint8_t)(s.z >> 16);
+}
+// Converter::toVector3d of the points' positions, in point_rank order; a row outside the attribute bank is reported, not read
+__global__ __launch_bounds__(256) void k_bg_xw(const int* __restrict__ pts, const int* __restrict__ rank, int n, const float* __restrict__ attr, int attr_cap,
+                                               double* __restrict__ xw, int* __restrict__ head) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  const int r = pts[i];
+  if (r >= attr_cap) { atomicMax(&head[15], r + 1); return; }
+  double* q = xw + 3 * (size_t)rank[i];
+  for (int k = 0; k < 3; ++k) q[k] = (double)attr[8 * (size_t)r + k];
+}
+__global__ __launch_bounds__(256) void k_ba_flag(const uint8_t* __restrict__ erase, const int* __restrict__ e_ent, int n_edges, uint8_t* __restrict__ flagged) {
+  const int e = blockIdx.x * 256 + threadIdx.x;
+  if (e < n_edges && erase[e]) flagged[e_ent[e]] = 1;
+}
+// one wave per point, the closed form of the sequential erasure: left = Observations() - flagged edges; the point turns bad when it has
+// a flagged edge and left <= 2; otherwise mpRefKF's candidate is the lowest id left
+__global__ __launch_bounds__(256) void k_ba_point(LmBaArgs a) {
+  const int lane = threadIdx.x & 63;
+  const int i = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (i >= a.n) return;
+  const int len = a.cnt[i], base = a.seg_off[i];
+  int nflag = 0, first = INT_MAX;
+  for (int e = lane; e < len; e += 64) {
+    if (a.flagged[base + e]) ++nflag; else first = min(first, e);
+  }
+  for (int s = 32; s > 0; s >>= 1) { nflag += __shfl_xor(nflag, s, 64); first = min(first, __shfl_xor(first, s, 64)); }
+  if (lane) return;
+  const bool bad = nflag > 0 && len - nflag <= 2;
+  a.gone[i] = bad;
+  a.new_ref[i] = nflag > 0 && !bad ? a.oseg[base + first].x : -1;
+  const int erased = nflag == 0 ? 0 : bad ? max(1, len - 2) : nflag;   // the pairs behind the one that turned the point bad are no-ops
+  if (erased) atomicAdd(&a.head[14], erased);
+}
+// bad_rows in lLocalMapPoints order; with apply the flagged entries and every entry of a point that turned bad become -1, through the segments
+__global__ __launch_bounds__(256) void k_ba_write(LmBaArgs a) {
+  const int lane = threadIdx.x & 63;
+  const int i = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (i >= a.n) return;
+  const int len = a.cnt[i], base = a.seg_off[i];
+  const bool g = a.gone[i] != 0;
+  if (g && lane == 0) {
+    if (a.boff[i] < a.bad_cap) a.bad_rows[a.boff[i]] = a.pts[i];
+    if (a.apply) a.pbad[a.pts[i]] = 1;
+  }
+  if (!a.apply) return;
+  for (int e = lane; e < len; e += 64) {
+    if (!g && !a.flagged[base + e]) continue;
+    const int4 s = a.oseg[base + e];
+    a.rows[a.table[s.y].off + (s.z & 0xffff)] = -1;
+  }
+}
+
 struct LmSlot {
   int kf = -1;   // -1: free slot
   int n = -1;
@@ -692,6 +896,15 @@ struct LocalMapState {
   int* d_culled = nullptr; size_t culled_cap = 0;       // [slots]
   int* d_nd = nullptr; size_t nd_cap = 0;               // asd_update_normal_and_depth: the observers' segments (id, slot) | the ordered slots
   std::vector<uint32_t> nd_stamp; uint32_t nd_call = 0; // its duplicate test: the call that named a bank row last
+  // asd_local_ba_graph: its own storage, because what it leaves is resident for asd_local_ba_apply
+  int* d_bgp = nullptr; size_t bgp_cap = 0;             // lLocalMapPoints | the compaction's second list
+  int* d_bgn = nullptr; size_t bgn_cap = 0;             // per point: Observations() | cursor | segment offsets | point_rank | gone | place in bad_rows
+  int4* d_bgs = nullptr; size_t bgs_cap = 0;            // the segments as filled | in ascending keyframe id
+  int* d_bge = nullptr; size_t bge_cap = 0;             // edge -> segment entry
+  int* d_bgk = nullptr; size_t bgk_cap = 0;             // [slots] claim | lFixedCameras
+  uint8_t* d_bgf = nullptr; size_t bgf_cap = 0;         // per segment entry: flagged by asd_local_ba_apply
+  bool bg_valid = false; uint64_t bg_version = 0;       // the resident graph and the table version it was built from
+  int bg_points = 0, bg_edges = 0; long long bg_total = 0; size_t bg_N = 0;
   AsdXfer up, down;
   int growths[3] = {0, 0, 0};   // slot table, arena, row tables
   // what the last asd_update_local_map left for asd_track_local_points_map
@@ -727,12 +940,14 @@ int lm_reserve(asd_ctx* ctx, T** p, size_t* cap, size_t need, size_t keep, int f
 
 void release_device(LocalMapState* S) {
   void* dev[] = {S->d_table, S->d_rows, S->d_pbad, S->d_mark, S->d_claim, S->d_sorted, S->d_child, S->d_cnt, S->d_list, S->d_list_base, S->d_head,
-                 S->d_tile, S->d_local, S->d_search, S->d_oct, S->d_cull, S->d_culled, S->d_center, S->d_nd};
+                 S->d_tile, S->d_local, S->d_search, S->d_oct, S->d_cull, S->d_culled, S->d_center, S->d_nd, S->d_bgp, S->d_bgn, S->d_bgs, S->d_bge, S->d_bgk, S->d_bgf};
   for (void* p : dev) if (p) (void)hipFree(p);
   S->d_table = nullptr; S->d_rows = nullptr; S->d_pbad = nullptr; S->d_mark = nullptr; S->d_claim = nullptr; S->d_sorted = nullptr; S->d_child = nullptr;
   S->d_cnt = nullptr; S->d_list = nullptr; S->d_list_base = nullptr; S->d_head = nullptr; S->d_tile = nullptr; S->d_local = nullptr; S->d_search = nullptr;
   S->d_oct = nullptr; S->d_cull = nullptr; S->d_culled = nullptr; S->cull_cap = S->culled_cap = 0;
   S->d_center = nullptr; S->d_nd = nullptr; S->center_cap = S->nd_cap = 0;
+  S->d_bgp = nullptr; S->d_bgn = nullptr; S->d_bgs = nullptr; S->d_bge = nullptr; S->d_bgk = nullptr; S->d_bgf = nullptr;
+  S->bgp_cap = S->bgn_cap = S->bgs_cap = S->bge_cap = S->bgk_cap = S->bgf_cap = 0; S->bg_valid = false;
   S->table_cap = S->row_cap = S->sorted_cap = S->child_cap = S->cnt_cap = S->list_cap = S->list_base_cap = S->head_cap = S->tile_cap = S->local_cap = S->search_cap = 0;
   S->entry_cap = S->entry_used = 0;
 }
@@ -1572,6 +1787,306 @@ int asd_update_normal_and_depth(asd_ctx* ctx, asd_normal_depth_args* A) {
     if (A->max_dist) A->max_dist[i] = q[4];
     if (A->status) { int s; memcpy(&s, q + 5, sizeof s); A->status[i] = (uint8_t)s; }
   }
+  return ASD_OK;
+}
+
+static_assert(sizeof(asd_ba_graph_args) == 160 && offsetof(asd_ba_graph_args, local_kfs) == 24 && offsetof(asd_ba_graph_args, n_points) == 56 &&
+              offsetof(asd_ba_graph_args, pose_fixed) == 88 && offsetof(asd_ba_graph_args, e_octave) == 136 && offsetof(asd_ba_graph_args, Xw) == 152,
+              "asd_ba_graph_args: the layout the bindings restate");
+static_assert(sizeof(asd_ba_apply_args) == 56 && offsetof(asd_ba_apply_args, bad_rows) == 32 && offsetof(asd_ba_apply_args, new_ref) == 48,
+              "asd_ba_apply_args: the layout the bindings restate");
+
+int asd_local_ba_graph(asd_ctx* ctx, asd_ba_graph_args* A) {
+  if (!ctx) return ASD_ERR_INVALID;
+  if (!A || A->kf < 0 || A->n_neigh < 0 || (A->n_neigh > 0 && !A->neigh) || A->kf_capacity < 0 || A->point_capacity < 0 || A->fixed_capacity < 0 ||
+      A->pose_capacity < 0 || A->edge_capacity < 0 || (A->kf_capacity > 0 && !A->local_kfs) || (A->point_capacity > 0 && (!A->local_rows || !A->point_rank)) ||
+      (A->fixed_capacity > 0 && !A->fixed_kfs) || (A->pose_capacity > 0 && (!A->pose_kfs || !A->pose_fixed)) ||
+      (A->edge_capacity > 0 && (!A->e_point || !A->e_pose || !A->e_kf || !A->e_idx || !A->e_octave))) {
+    ctx->set_error("asd_local_ba_graph: invalid argument");
+    return ASD_ERR_INVALID;
+  }
+  if (A->Xw && ctx->prep_on) { ctx->set_error("asd_local_ba_graph: an asd_prep_async bracket is open"); return ASD_ERR_INVALID; }
+  if (refuse(ctx, "asd_local_ba_graph")) return ASD_ERR_INVALID;
+  A->n_local_kfs = 0; A->n_points = 0; A->n_fixed = 0; A->n_poses = 0; A->n_edges = 0;
+  if (A->n_neigh > kMaxCand) { ctx->set_error("asd_local_ba_graph: %d neighbours exceed %d", A->n_neigh, kMaxCand); return ASD_ERR_CAPACITY; }
+  LocalMapState* S = lstate(ctx);
+  int kf_slot;
+  if (!find_kf(ctx, S, "asd_local_ba_graph", A->kf, &kf_slot)) return ASD_ERR_INVALID;
+  {
+    std::vector<int> seen(A->neigh, A->neigh + A->n_neigh);
+    seen.push_back(A->kf);
+    std::sort(seen.begin(), seen.end());
+    if (seen[0] < 0) { ctx->set_error("asd_local_ba_graph: keyframe id %d among the neighbours", seen[0]); return ASD_ERR_INVALID; }
+    for (size_t i = 1; i < seen.size(); ++i)
+      if (seen[i] == seen[i - 1]) { ctx->set_error("asd_local_ba_graph: keyframe %d occurs twice among the keyframe and its neighbours", seen[i]); return ASD_ERR_INVALID; }
+  }
+  if (S->live_without_oct > 0) {
+    for (const auto& kv : S->by_kf)
+      if (!S->slots[kv.second].has_oct) { ctx->set_error("asd_local_ba_graph: keyframe %d has no octaves (asd_map_put_octaves); %d live keyframes have none", kv.first, S->live_without_oct); break; }
+    return ASD_ERR_INVALID;
+  }
+  // lLocalKeyFrames (:420-431): the slot table's host mirror knows isBad(); an id that is not in the table is not bad and has no row
+  const int n_slots = (int)S->slots.size();
+  std::vector<int> list_id, list_slot;
+  std::vector<long long> base;
+  std::vector<uint8_t> local(n_slots, 0);
+  long long entries = 0;
+  int maxn = 0;
+  for (int i = -1; i < A->n_neigh; ++i) {
+    const int id = i < 0 ? A->kf : A->neigh[i];
+    const auto it = S->by_kf.find(id);
+    const int sl = it == S->by_kf.end() ? -1 : it->second;
+    if (sl >= 0 && S->slots[sl].bad && i >= 0) continue;
+    list_id.push_back(id); list_slot.push_back(sl); base.push_back(entries);
+    if (sl >= 0) { local[sl] = 1; entries += S->slots[sl].n; maxn = std::max(maxn, S->slots[sl].n); }
+  }
+  const int n_list = (int)list_id.size();
+  if (entries >= kMaxEntriesPerQuery) {
+    ctx->set_error("asd_local_ba_graph: the %d local keyframes hold %lld table entries, more than one call collects (%lld)", n_list, entries, kMaxEntriesPerQuery);
+    return ASD_ERR_CAPACITY;
+  }
+  (void)hipSetDevice(ctx->cfg.device);
+  hipStream_t st = ctx->stream;
+  MatcherState* M = A->Xw ? matcher_state(ctx) : nullptr;
+  const int row_cap = (int)S->row_cap;
+  S->bg_valid = false;
+  int rc;
+  if ((rc = clean_tables(ctx, S)) != ASD_OK) return rc;
+  if ((rc = lm_reserve(ctx, &S->d_head, &S->head_cap, 16, 0, 0, 16)) != ASD_OK) return rc;
+  if (!S->h_head) ASD_HIP_CHECK(ctx, hipHostMalloc(&S->h_head, 16 * sizeof(int)));
+  int* const head = S->h_head;
+  const size_t E = (size_t)entries + 4;
+  if ((rc = lm_reserve(ctx, &S->d_bgp, &S->bgp_cap, 2 * E, 0, -1, 65536)) != ASD_OK) return rc;
+  if ((rc = lm_reserve(ctx, &S->d_bgk, &S->bgk_cap, 2 * (size_t)n_slots + 2, 0, -1, 2 * kInitSlots)) != ASD_OK) return rc;
+  int* const d_pts = S->d_bgp; int* const d_second = d_pts + E;
+  int* const d_kfclaim = S->d_bgk; int* const d_fixed = d_kfclaim + n_slots + 1;
+  ASD_HIP_CHECK(ctx, S->up.begin(st, (size_t)n_list * 12 + (size_t)n_slots * 5 + 2048));
+  const size_t o_slot = S->up.add(list_slot.data(), (size_t)n_list * sizeof(int)), o_base = S->up.add(base.data(), (size_t)n_list * sizeof(long long));
+  const size_t o_loc = S->up.add(local.data(), (size_t)n_slots);
+  ASD_HIP_CHECK(ctx, S->up.upload(st));
+  const size_t o_pose = S->up.reserve((size_t)n_slots * sizeof(int));   // filled and sent further down
+  ASD_HIP_CHECK(ctx, hipMemsetAsync(S->d_head, 0, 16 * sizeof(int), st));
+  S->tables_dirty = true;
+  if (entries > 0) {   // lLocalMapPoints (:435-449): the compaction of asd_update_local_map over these rows
+    const int tiles_per_kf = (maxn + kTile - 1) / kTile;
+    const size_t n_tiles = (size_t)tiles_per_kf * n_list;
+    if ((rc = lm_reserve(ctx, &S->d_tile, &S->tile_cap, 4 * n_tiles, 0, -1, 4096)) != ASD_OK) return rc;
+    LmPointArgs pa{};
+    pa.table = S->d_table; pa.rows = S->d_rows; pa.list_slot = S->up.dev<int>(o_slot); pa.list_base = S->up.dev<long long>(o_base); pa.tiles_per_kf = tiles_per_kf;
+    pa.pbad = S->d_pbad; pa.mark = S->d_mark; pa.claim = S->d_claim;
+    pa.tile_cnt = S->d_tile; pa.tile_off = S->d_tile + 2 * n_tiles;
+    pa.d_local = d_pts; pa.d_search = d_second;   // (not the resident search list: that one stays as it is)
+    const dim3 grid((unsigned)n_list, (unsigned)tiles_per_kf);
+    hipLaunchKernelGGL(k_lm_claim, grid, dim3(256), 0, st, pa);
+    ASD_HIP_CHECK(ctx, hipGetLastError());
+    hipLaunchKernelGGL(k_lm_count, grid, dim3(256), 0, st, pa);
+    ASD_HIP_CHECK(ctx, hipGetLastError());
+    hipLaunchKernelGGL(k_lm_tilescan, dim3(1), dim3(256), 0, st, S->d_tile, S->d_tile + 2 * n_tiles, (int)n_tiles, S->d_head);
+    ASD_HIP_CHECK(ctx, hipGetLastError());
+    hipLaunchKernelGGL(k_lm_scatter, grid, dim3(256), 0, st, pa);
+    ASD_HIP_CHECK(ctx, hipGetLastError());
+  }
+  ASD_HIP_CHECK(ctx, hipMemcpyAsync(head, S->d_head, 16 * sizeof(int), hipMemcpyDeviceToHost, st));
+  ASD_HIP_CHECK(ctx, hipStreamSynchronize(st));
+  const int n = head[8];
+  if (n > kMaxNdPoints) {   // (the claims are reset by the scatter; no mark has been set yet)
+    S->tables_dirty = false;
+    ctx->set_error("asd_local_ba_graph: %d local points exceed the %d one call takes", n, kMaxNdPoints);
+    return ASD_ERR_CAPACITY;
+  }
+  // Observations() of every local point, its segment, point_rank
+  const size_t N = ((size_t)n + 4) / 4 * 4;
+  if ((rc = lm_reserve(ctx, &S->d_bgn, &S->bgn_cap, 7 * N, 0, -1, 65536)) != ASD_OK) return rc;
+  int* const d_cnt = S->d_bgn; int* const d_cursor = d_cnt + N; int* const d_off = d_cursor + N; int* const d_rank = d_off + N;
+  const dim3 per_point((n + 255) / 256), per_wave((n + 3) / 4), per_slot((n_slots + 3) / 4);
+  auto unmark = [&]() -> int {
+    if (n > 0) { hipLaunchKernelGGL(k_obs_unmark, per_point, dim3(256), 0, st, d_pts, n, row_cap, S->d_mark); ASD_HIP_CHECK(ctx, hipGetLastError()); }
+    return ASD_OK;
+  };
+  long long total = 0;
+  if (n > 0) {
+    hipLaunchKernelGGL(k_bg_index, per_point, dim3(256), 0, st, d_pts, n, S->d_mark, d_cnt, d_cursor);
+    ASD_HIP_CHECK(ctx, hipGetLastError());
+    hipLaunchKernelGGL(k_cull_count, per_slot, dim3(256), 0, st, S->d_table, n_slots, S->d_rows, S->d_oct, S->d_mark, d_cnt, 1);
+    ASD_HIP_CHECK(ctx, hipGetLastError());
+    hipLaunchKernelGGL(k_nd_scan, dim3(1), dim3(256), 0, st, d_cnt, n, d_off, head);   // (head: pinned, the kernel stores the total there)
+    ASD_HIP_CHECK(ctx, hipGetLastError());
+    const size_t r_tiles = ((size_t)row_cap + kTile - 1) / kTile;
+    if ((rc = lm_reserve(ctx, &S->d_tile, &S->tile_cap, 4 * r_tiles, 0, -1, 4096)) != ASD_OK) return rc;
+    hipLaunchKernelGGL(k_bg_rank_count, dim3((unsigned)r_tiles), dim3(256), 0, st, S->d_mark, row_cap, S->d_tile);
+    ASD_HIP_CHECK(ctx, hipGetLastError());
+    hipLaunchKernelGGL(k_lm_tilescan, dim3(1), dim3(256), 0, st, S->d_tile, S->d_tile + 2 * r_tiles, (int)r_tiles, S->d_head + 2);   // (its totals land in head[10..11], unused)
+    ASD_HIP_CHECK(ctx, hipGetLastError());
+    hipLaunchKernelGGL(k_bg_rank_scatter, dim3((unsigned)r_tiles), dim3(256), 0, st, S->d_mark, row_cap, S->d_tile + 2 * r_tiles, d_rank);
+    ASD_HIP_CHECK(ctx, hipGetLastError());
+    ASD_HIP_CHECK(ctx, hipStreamSynchronize(st));
+    total = ((long long)head[13] << 32) | (unsigned)head[12];
+  }
+  if (total > kMaxNdEntries) {
+    if ((rc = unmark()) != ASD_OK) return rc;
+    ASD_HIP_CHECK(ctx, hipStreamSynchronize(st));
+    S->tables_dirty = false;
+    ctx->set_error("asd_local_ba_graph: the %d local points have %lld observations, more than one call takes (%lld)", n, total, kMaxNdEntries);
+    return ASD_ERR_CAPACITY;
+  }
+  const size_t T = (size_t)total + 4;
+  const size_t n_tiles = ((size_t)total + kTile - 1) / kTile;
+  if ((rc = lm_reserve(ctx, &S->d_bgs, &S->bgs_cap, 2 * T, 0, -1, 65536)) != ASD_OK) return rc;
+  if ((rc = lm_reserve(ctx, &S->d_bge, &S->bge_cap, T, 0, -1, 65536)) != ASD_OK) return rc;
+  if ((rc = lm_reserve(ctx, &S->d_tile, &S->tile_cap, 4 * n_tiles + 4, 0, -1, 4096)) != ASD_OK) return rc;
+  LmBgArgs ga{};
+  ga.table = S->d_table; ga.rows = S->d_rows; ga.oct = S->d_oct; ga.mark = S->d_mark; ga.n_slots = n_slots;
+  ga.pts = d_pts; ga.n = n; ga.cnt = d_cnt; ga.cursor = d_cursor; ga.seg_off = d_off;
+  ga.useg = S->d_bgs; ga.oseg = S->d_bgs + T; ga.local = S->up.dev<uint8_t>(o_loc); ga.kf_claim = d_kfclaim; ga.total = total;
+  ga.tile_cnt = S->d_tile; ga.tile_off = S->d_tile + 2 * n_tiles; ga.fixed = d_fixed; ga.e_ent = S->d_bge;
+  ASD_HIP_CHECK(ctx, hipMemsetAsync(S->d_head, 0, 16 * sizeof(int), st));
+  if (total > 0) {
+    ASD_HIP_CHECK(ctx, hipMemsetAsync(d_kfclaim, 0x7f, ((size_t)n_slots + 1) * sizeof(int), st));
+    hipLaunchKernelGGL(k_bg_fill, per_slot, dim3(256), 0, st, ga);
+    ASD_HIP_CHECK(ctx, hipGetLastError());
+    hipLaunchKernelGGL(k_bg_order, per_wave, dim3(256), 0, st, ga);
+    ASD_HIP_CHECK(ctx, hipGetLastError());
+    hipLaunchKernelGGL(k_bg_count, dim3((unsigned)n_tiles), dim3(256), 0, st, ga);
+    ASD_HIP_CHECK(ctx, hipGetLastError());
+    hipLaunchKernelGGL(k_lm_tilescan, dim3(1), dim3(256), 0, st, S->d_tile, S->d_tile + 2 * n_tiles, (int)n_tiles, S->d_head);
+    ASD_HIP_CHECK(ctx, hipGetLastError());
+    hipLaunchKernelGGL(k_bg_scatter, dim3((unsigned)n_tiles), dim3(256), 0, st, ga);
+    ASD_HIP_CHECK(ctx, hipGetLastError());
+  }
+  if ((rc = unmark()) != ASD_OK) return rc;
+  const size_t give_p = std::min((size_t)A->point_capacity, (size_t)n), give_e = std::min((size_t)A->edge_capacity, (size_t)total);
+  ASD_HIP_CHECK(ctx, S->down.begin(st, ((size_t)n_slots + 2 * give_p + 4 * give_e) * sizeof(int) + give_e + (A->Xw ? (size_t)n * 24 : 0) + 4096));
+  const size_t o_fix = S->down.reserve(((size_t)n_slots + 1) * sizeof(int)), o_pts = S->down.reserve(give_p * sizeof(int)), o_rank = S->down.reserve(give_p * sizeof(int));
+  const size_t o_ep = S->down.reserve(give_e * sizeof(int)), o_eq = S->down.reserve(give_e * sizeof(int)), o_ek = S->down.reserve(give_e * sizeof(int));
+  const size_t o_ei = S->down.reserve(give_e * sizeof(int)), o_eo = S->down.reserve(give_e), o_xw = A->Xw ? S->down.reserve((size_t)n * 24) : 0;
+  ASD_HIP_CHECK(ctx, hipMemcpyAsync(head, S->d_head, 16 * sizeof(int), hipMemcpyDeviceToHost, st));
+  if (total > 0 && n_slots > 0) ASD_HIP_CHECK(ctx, hipMemcpyAsync(S->down.h + o_fix, d_fixed, (size_t)n_slots * sizeof(int), hipMemcpyDeviceToHost, st));
+  ASD_HIP_CHECK(ctx, hipStreamSynchronize(st));
+  S->tables_dirty = false;
+  const int n_fixed = head[8], n_edges = head[9];
+  // the pose order of asd_ba_problem: local and fixed keyframes together in ascending id
+  const int* fixed_ids = S->down.host<int>(o_fix);
+  std::vector<std::pair<int, int>> poses;   // (id, fixed)
+  for (int i = 0; i < n_list; ++i) poses.emplace_back(list_id[i], 0);
+  for (int i = 0; i < n_fixed; ++i) poses.emplace_back(fixed_ids[i], 1);
+  std::sort(poses.begin(), poses.end());
+  const int n_poses = (int)poses.size();
+  int* pose_idx = S->up.host<int>(o_pose);
+  for (int s = 0; s < n_slots; ++s) pose_idx[s] = -1;
+  for (int i = 0; i < n_poses; ++i) { const auto it = S->by_kf.find(poses[i].first); if (it != S->by_kf.end()) pose_idx[it->second] = i; }
+  if (n_slots > 0) ASD_HIP_CHECK(ctx, hipMemcpyAsync(S->up.d + o_pose, S->up.h + o_pose, (size_t)n_slots * sizeof(int), hipMemcpyHostToDevice, st));
+  if (n_edges > 0 && give_e > 0) {
+    LmBgEdgeArgs ea{};
+    ea.oseg = ga.oseg; ea.e_ent = S->d_bge; ea.rank = d_rank; ea.pose_idx = S->up.dev<int>(o_pose); ea.n_edges = n_edges; ea.cap = (int)give_e;
+    ea.e_point = S->down.host<int>(o_ep); ea.e_pose = S->down.host<int>(o_eq); ea.e_kf = S->down.host<int>(o_ek); ea.e_idx = S->down.host<int>(o_ei);
+    ea.e_oct = S->down.host<uint8_t>(o_eo);
+    hipLaunchKernelGGL(k_bg_edges, dim3((n_edges + 255) / 256), dim3(256), 0, st, ea);
+    ASD_HIP_CHECK(ctx, hipGetLastError());
+  }
+  if (A->Xw && n > 0) {
+    hipLaunchKernelGGL(k_bg_xw, per_point, dim3(256), 0, st, d_pts, d_rank, n, M->d_attr, (int)M->attr_cap, S->down.host<double>(o_xw), S->d_head);
+    ASD_HIP_CHECK(ctx, hipGetLastError());
+    ASD_HIP_CHECK(ctx, hipMemcpyAsync(head, S->d_head, 16 * sizeof(int), hipMemcpyDeviceToHost, st));
+  }
+  if (give_p) {
+    ASD_HIP_CHECK(ctx, hipMemcpyAsync(S->down.h + o_pts, d_pts, give_p * sizeof(int), hipMemcpyDeviceToHost, st));
+    ASD_HIP_CHECK(ctx, hipMemcpyAsync(S->down.h + o_rank, d_rank, give_p * sizeof(int), hipMemcpyDeviceToHost, st));
+  }
+  ASD_HIP_CHECK(ctx, hipStreamSynchronize(st));
+  if (A->Xw && n > 0 && head[15] > 0) {
+    ctx->set_error("asd_local_ba_graph: bank row %d lies outside the attribute bank (%d rows): its position was never put", head[15] - 1, (int)M->attr_cap);
+    return ASD_ERR_INVALID;
+  }
+  A->n_local_kfs = n_list; A->n_points = n; A->n_fixed = n_fixed; A->n_poses = n_poses; A->n_edges = n_edges;
+  if (n_list > A->kf_capacity || n > A->point_capacity || n_fixed > A->fixed_capacity || n_poses > A->pose_capacity || n_edges > A->edge_capacity) {
+    ctx->set_error("asd_local_ba_graph: %d local keyframes, %d points, %d fixed keyframes, %d poses, %d edges exceed the capacities %d, %d, %d, %d, %d", n_list, n,
+                   n_fixed, n_poses, n_edges, A->kf_capacity, A->point_capacity, A->fixed_capacity, A->pose_capacity, A->edge_capacity);
+    return ASD_ERR_CAPACITY;
+  }
+  memcpy(A->local_kfs, list_id.data(), (size_t)n_list * sizeof(int));
+  if (n) { memcpy(A->local_rows, S->down.h + o_pts, (size_t)n * sizeof(int)); memcpy(A->point_rank, S->down.h + o_rank, (size_t)n * sizeof(int)); }
+  if (n_fixed) memcpy(A->fixed_kfs, fixed_ids, (size_t)n_fixed * sizeof(int));
+  for (int i = 0; i < n_poses; ++i) { A->pose_kfs[i] = poses[i].first; A->pose_fixed[i] = (uint8_t)poses[i].second; }
+  if (n_edges) {
+    memcpy(A->e_point, S->down.h + o_ep, (size_t)n_edges * sizeof(int)); memcpy(A->e_pose, S->down.h + o_eq, (size_t)n_edges * sizeof(int));
+    memcpy(A->e_kf, S->down.h + o_ek, (size_t)n_edges * sizeof(int)); memcpy(A->e_idx, S->down.h + o_ei, (size_t)n_edges * sizeof(int));
+    memcpy(A->e_octave, S->down.h + o_eo, (size_t)n_edges);
+  }
+  if (A->Xw && n) memcpy(A->Xw, S->down.h + o_xw, (size_t)n * 24);
+  S->bg_valid = true; S->bg_version = S->version; S->bg_points = n; S->bg_edges = n_edges; S->bg_total = total; S->bg_N = N;
+  return ASD_OK;
+}
+
+int asd_local_ba_apply(asd_ctx* ctx, asd_ba_apply_args* A) {
+  if (!ctx) return ASD_ERR_INVALID;
+  if (!A || A->n_edges < 0 || (A->n_edges > 0 && !A->erase) || A->bad_capacity < 0 || (A->bad_capacity > 0 && !A->bad_rows) || A->n_points < 0 ||
+      (A->n_points > 0 && !A->new_ref)) {
+    ctx->set_error("asd_local_ba_apply: invalid argument");
+    return ASD_ERR_INVALID;
+  }
+  if (refuse(ctx, "asd_local_ba_apply")) return ASD_ERR_INVALID;
+  A->n_erased = 0; A->n_bad = 0;
+  LocalMapState* S = lstate(ctx);
+  if (!S->bg_valid) { ctx->set_error("asd_local_ba_apply: no asd_local_ba_graph of this context has left a graph"); return ASD_ERR_INVALID; }
+  if (S->bg_version != S->version) { ctx->set_error("asd_local_ba_apply: the observation table has changed since the last asd_local_ba_graph"); return ASD_ERR_INVALID; }
+  if (A->n_edges != S->bg_edges || A->n_points != S->bg_points) {
+    ctx->set_error("asd_local_ba_apply: %d edges and %d points, the resident graph has %d and %d", A->n_edges, A->n_points, S->bg_edges, S->bg_points);
+    return ASD_ERR_INVALID;
+  }
+  const int n = S->bg_points, n_edges = S->bg_edges;
+  const long long total = S->bg_total;
+  bool any = false;
+  for (int e = 0; e < n_edges; ++e) any = any || A->erase[e];
+  if (n == 0 || !any) {   // nothing is flagged: nothing changes, the version stays
+    for (int i = 0; i < n; ++i) A->new_ref[i] = -1;
+    if (A->apply) S->bg_valid = false;
+    return ASD_OK;
+  }
+  (void)hipSetDevice(ctx->cfg.device);
+  hipStream_t st = ctx->stream;
+  const size_t N = S->bg_N, T = (size_t)total + 4;
+  int rc;
+  if ((rc = lm_reserve(ctx, &S->d_bgf, &S->bgf_cap, T, 0, -1, 65536)) != ASD_OK) return rc;
+  if (!S->h_head) ASD_HIP_CHECK(ctx, hipHostMalloc(&S->h_head, 16 * sizeof(int)));
+  int* const head = S->h_head;
+  int* const d_cnt = S->d_bgn; int* const d_off = d_cnt + 2 * N; int* const d_gone = d_cnt + 4 * N; int* const d_boff = d_cnt + 5 * N;   // (d_boff: n + 1 words of 2 N)
+  ASD_HIP_CHECK(ctx, S->up.begin(st, (size_t)n_edges + 1024));
+  const size_t o_er = S->up.add(A->erase, (size_t)n_edges);
+  ASD_HIP_CHECK(ctx, S->up.upload(st));
+  const size_t give_bad = std::min((size_t)A->bad_capacity, (size_t)n);
+  ASD_HIP_CHECK(ctx, S->down.begin(st, ((size_t)n + give_bad + 16) * sizeof(int) + 1024));
+  const size_t o_ref = S->down.reserve((size_t)n * sizeof(int)), o_bad = S->down.reserve(give_bad * sizeof(int)), o_hd = S->down.reserve(16 * sizeof(int));
+  ASD_HIP_CHECK(ctx, hipMemsetAsync(S->d_head, 0, 16 * sizeof(int), st));
+  ASD_HIP_CHECK(ctx, hipMemsetAsync(S->d_bgf, 0, T, st));
+  LmBaArgs ba{};
+  ba.table = S->d_table; ba.rows = S->d_rows; ba.pbad = S->d_pbad;
+  ba.pts = S->d_bgp; ba.n = n; ba.cnt = d_cnt; ba.seg_off = d_off; ba.oseg = S->d_bgs + T; ba.flagged = S->d_bgf;
+  ba.gone = d_gone; ba.boff = d_boff; ba.new_ref = S->down.host<int>(o_ref); ba.bad_rows = S->down.host<int>(o_bad); ba.bad_cap = (int)give_bad;
+  ba.head = S->d_head; ba.apply = 0;
+  const dim3 per_wave((n + 3) / 4);
+  hipLaunchKernelGGL(k_ba_flag, dim3((n_edges + 255) / 256), dim3(256), 0, st, S->up.dev<uint8_t>(o_er), S->d_bge, n_edges, S->d_bgf);
+  ASD_HIP_CHECK(ctx, hipGetLastError());
+  hipLaunchKernelGGL(k_ba_point, per_wave, dim3(256), 0, st, ba);
+  ASD_HIP_CHECK(ctx, hipGetLastError());
+  hipLaunchKernelGGL(k_nd_scan, dim3(1), dim3(256), 0, st, d_gone, n, d_boff, head);   // (head[12]: the points that turned bad)
+  ASD_HIP_CHECK(ctx, hipGetLastError());
+  ASD_HIP_CHECK(ctx, hipMemcpyAsync(S->down.h + o_hd, S->d_head, 16 * sizeof(int), hipMemcpyDeviceToHost, st));
+  ASD_HIP_CHECK(ctx, hipStreamSynchronize(st));
+  const int n_bad = head[12];
+  A->n_erased = S->down.host<int>(o_hd)[14]; A->n_bad = n_bad;
+  if (n_bad > A->bad_capacity) {   // nothing has been written but this call's scratch
+    ctx->set_error("asd_local_ba_apply: %d points turn bad, bad_capacity is %d", n_bad, A->bad_capacity);
+    return ASD_ERR_CAPACITY;
+  }
+  ba.apply = A->apply ? 1 : 0;
+  if (n_bad > 0 || ba.apply) {
+    hipLaunchKernelGGL(k_ba_write, per_wave, dim3(256), 0, st, ba);
+    ASD_HIP_CHECK(ctx, hipGetLastError());
+    ASD_HIP_CHECK(ctx, hipStreamSynchronize(st));
+  }
+  memcpy(A->new_ref, S->down.h + o_ref, (size_t)n * sizeof(int));
+  if (n_bad) memcpy(A->bad_rows, S->down.h + o_bad, (size_t)n_bad * sizeof(int));
+  if (ba.apply) { ++S->version; S->bg_valid = false; }
   return ASD_OK;
 }
 

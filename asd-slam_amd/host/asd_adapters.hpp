@@ -704,6 +704,169 @@ struct Optimizer {
     a.status = status ? status->data() : nullptr;
     return asd_update_normal_and_depth(c.get(), &a);
   }
+
+  // The lists and edges of LocalBundleAdjustment (Optimizer.cc:418-467, :484-593) over the resident observation table -- the caller keeps
+  // no mObservations for it.  kf = pKF->mnId, neigh = pKF->GetVectorCovisibleKeyFrames() as ids in its order.
+  struct LocalBAGraph {
+    int rc = ASD_OK;
+    std::vector<int32_t> lLocalKeyFrames, lLocalMapPoints, lFixedCameras;   // ids, bank rows, ids
+    std::vector<int32_t> pose_kfs, point_rank;                              // asd_ba_problem's pose order; per local point its index in the point order
+    std::vector<uint8_t> pose_fixed;                                        // 1 = member of lFixedCameras
+    std::vector<int32_t> e_point, e_pose, e_kf, e_idx;                      // the edges in insertion order (:534-593)
+    std::vector<uint8_t> e_octave;
+    std::vector<double> Xw;                                                 // [points][3] in point order (with wantXw)
+  };
+  static LocalBAGraph LocalBundleAdjustmentGraph(Context& c, int32_t kf, const std::vector<int32_t>& neigh, bool wantXw = false) {
+    LocalBAGraph G;
+    int32_t cap[5] = {(int32_t)neigh.size() + 1, 4096, 64, (int32_t)neigh.size() + 65, 16384};
+    for (int attempt = 0; attempt < 2; ++attempt) {   // repeated once with the counts the library asked for
+      G.lLocalKeyFrames.assign(cap[0], 0); G.lLocalMapPoints.assign(cap[1], 0); G.point_rank.assign(cap[1], 0); G.lFixedCameras.assign(cap[2], 0);
+      G.pose_kfs.assign(cap[3], 0); G.pose_fixed.assign(cap[3], 0);
+      G.e_point.assign(cap[4], 0); G.e_pose.assign(cap[4], 0); G.e_kf.assign(cap[4], 0); G.e_idx.assign(cap[4], 0); G.e_octave.assign(cap[4], 0);
+      G.Xw.assign(wantXw ? 3 * (size_t)cap[1] + 1 : 0, 0.0);
+      asd_ba_graph_args a{};
+      a.kf = kf; a.n_neigh = (int32_t)neigh.size(); a.neigh = neigh.data();
+      a.kf_capacity = cap[0]; a.local_kfs = G.lLocalKeyFrames.data();
+      a.point_capacity = cap[1]; a.local_rows = G.lLocalMapPoints.data(); a.point_rank = G.point_rank.data();
+      a.fixed_capacity = cap[2]; a.fixed_kfs = G.lFixedCameras.data();
+      a.pose_capacity = cap[3]; a.pose_kfs = G.pose_kfs.data(); a.pose_fixed = G.pose_fixed.data();
+      a.edge_capacity = cap[4]; a.e_point = G.e_point.data(); a.e_pose = G.e_pose.data(); a.e_kf = G.e_kf.data(); a.e_idx = G.e_idx.data();
+      a.e_octave = G.e_octave.data();
+      a.Xw = wantXw ? G.Xw.data() : nullptr;
+      G.rc = asd_local_ba_graph(c.get(), &a);
+      const int32_t need[5] = {a.n_local_kfs, a.n_points, a.n_fixed, a.n_poses, a.n_edges};
+      if (G.rc == ASD_ERR_CAPACITY && attempt == 0 && need[0] > 0) { for (int k = 0; k < 5; ++k) cap[k] = need[k]; continue; }
+      if (G.rc != ASD_OK) for (int k = 0; k < 5; ++k) cap[k] = 0;
+      else for (int k = 0; k < 5; ++k) cap[k] = need[k];
+      break;
+    }
+    G.lLocalKeyFrames.resize(cap[0]); G.lLocalMapPoints.resize(cap[1]); G.point_rank.resize(cap[1]); G.lFixedCameras.resize(cap[2]);
+    G.pose_kfs.resize(cap[3]); G.pose_fixed.resize(cap[3]);
+    G.e_point.resize(cap[4]); G.e_pose.resize(cap[4]); G.e_kf.resize(cap[4]); G.e_idx.resize(cap[4]); G.e_octave.resize(cap[4]);
+    G.Xw.resize(wantXw ? 3 * (size_t)cap[1] : 0);
+    return G;
+  }
+
+  // What LocalBundleAdjustment leaves behind, for the caller's own objects: the local keyframes' poses, the points' positions and seats.
+  struct LocalBAResult {
+    int rc = ASD_OK;
+    bool stopped = false;             // pbStopFlag was set at :597: nothing was optimised and nothing written
+    bool second_round = true;         // false: pbStopFlag was set at :606 (bDoMore = false)
+    LocalBAGraph graph;
+    std::vector<uint8_t> erase;       // per edge: chi2 > 5.991 || !isDepthPositive (:664)
+    int32_t n_erased = 0;
+    std::vector<int32_t> bad_rows;    // the points EraseObservation turned bad, in the order it happened
+    std::vector<float> Tcw, Ow;       // [lLocalKeyFrames][16], [..][3]: pKF->SetPose(Converter::toCvMat(SE3quat)) (:701-707)
+    std::vector<int32_t> rows, mpRefKF;   // the points written back (:712-732: not GetGlobalMapFlag()), their seats after the erasures
+    std::vector<float> Xw;            // [rows][3]: pMP->SetWorldPos
+    std::vector<uint8_t> status;      // asd_update_normal_and_depth's: 1 for a point that just turned bad
+    asd_ba_result ba{};
+  };
+  // void static LocalBundleAdjustment(KeyFrame* pKF, bool* pbStopFlag, Map* pMap)  (Optimizer.cc:415-734) over the resident tables: graph ->
+  // asd_ba_problem -> asd_local_ba -> erase policy (asd_local_ba_apply) -> WriteBack.  `view` is the caller's map:
+  //   const float* Tcw(int32_t kf)      pKFi->GetPose(), 16 floats           bool fixed(int32_t kf)     pKFi->GetGlobalMapFlag() (:490)
+  //   const float* keysUn(int32_t kf)   mvKeysUn[i].pt as [N][2]            const float* K()           fx, fy, cx, cy (:581-584)
+  //   bool global(int32_t row)          pMP->GetGlobalMapFlag()              int32_t refKF(int32_t row) mpRefKF->mnId
+  //   bool inTable(int32_t kf)          the caller has put the keyframe into the observation table (a neighbour it has not is legal)
+  // The stop flag is read where the reference reads it: at :597 in front of the optimisation, and at :606 behind the first round -- for
+  // that the two rounds run as two asd_local_ba calls (5 + 0 and 0 + 10 iterations: a round without iterations leaves the estimate as it
+  // is), which is done only when a flag is given.  The caller assigns Tcw, Xw, mpRefKF and the bad flags of bad_rows to its own objects.
+  template <class View>
+  static LocalBAResult LocalBundleAdjustment(Context& c, int32_t kf, const std::vector<int32_t>& neigh, const View& view, const bool* pbStopFlag = nullptr) {
+    LocalBAResult R;
+    R.graph = LocalBundleAdjustmentGraph(c, kf, neigh, true);
+    const LocalBAGraph& G = R.graph;
+    if ((R.rc = G.rc) != ASD_OK) return R;
+    const size_t P = G.pose_kfs.size(), L = G.lLocalMapPoints.size(), E = G.e_kf.size();
+    float scale[ASD_MAX_LEVELS], inv_scale[ASD_MAX_LEVELS], sigma2[ASD_MAX_LEVELS], inv_sigma2[ASD_MAX_LEVELS];
+    int32_t per_level[ASD_MAX_LEVELS];
+    if ((R.rc = asd_get_scale_tables(c.get(), scale, inv_scale, sigma2, inv_sigma2, per_level)) != ASD_OK) return R;
+    std::vector<double> poses(7 * P + 1), points(G.Xw), e_obs(2 * E + 1), e_info(E + 1), chi2(E + 1);
+    std::vector<uint8_t> fixed(P + 1), dpos(E + 1), out1(E + 1);
+    std::vector<int32_t> row_of_rank(L + 1);
+    for (size_t i = 0; i < L; ++i) row_of_rank[G.point_rank[i]] = G.lLocalMapPoints[i];
+    for (size_t i = 0; i < P; ++i) {
+      asd_tcw_to_pose7(view.Tcw(G.pose_kfs[i]), poses.data() + 7 * i);                                           // :488, :501
+      fixed[i] = G.pose_fixed[i] || G.pose_kfs[i] == 0 || view.fixed(G.pose_kfs[i]);                             // :490, :503
+    }
+    for (size_t e = 0; e < E; ++e) {
+      const float* pt = view.keysUn(G.e_kf[e]) + 2 * (size_t)G.e_idx[e];
+      e_obs[2 * e] = pt[0]; e_obs[2 * e + 1] = pt[1];                                                            // :563
+      const float invSigma2 = inv_sigma2[G.e_octave[e]];
+      e_info[e] = view.global(row_of_rank[G.e_point[e]]) ? 10.0 * (double)invSigma2 : (double)invSigma2;         // :570-575
+    }
+    if (pbStopFlag && *pbStopFlag) { R.stopped = true; return R; }                                               // :597-599
+    asd_ba_problem pr{};
+    pr.n_poses = (int32_t)P; pr.n_points = (int32_t)L; pr.n_edges = (int32_t)E;
+    pr.poses = poses.data(); pr.fixed = fixed.data(); pr.points = points.data();
+    pr.e_point = G.e_point.data(); pr.e_pose = G.e_pose.data(); pr.e_obs = e_obs.data(); pr.e_info = e_info.data();
+    for (int k = 0; k < 4; ++k) pr.K[k] = view.K()[k];
+    R.ba.edge_chi2 = chi2.data(); R.ba.edge_depth_pos = dpos.data(); R.ba.edge_outlier1 = out1.data();
+    if (!pbStopFlag) {
+      pr.its_first = 5; pr.its_second = 10;                                                                      // :602, :648
+      if ((R.rc = asd_local_ba(c.get(), &pr, &R.ba)) != ASD_OK) return R;
+    } else {
+      pr.its_first = 5; pr.its_second = 0;
+      if ((R.rc = asd_local_ba(c.get(), &pr, &R.ba)) != ASD_OK) return R;
+      if (*pbStopFlag) R.second_round = false;                                                                   // :606-608
+      else {
+        const double chi2_first = R.ba.chi2_first;
+        const int32_t iters_first = R.ba.iters_first;
+        pr.its_first = 0; pr.its_second = 10;
+        if ((R.rc = asd_local_ba(c.get(), &pr, &R.ba)) != ASD_OK) return R;
+        R.ba.chi2_first = chi2_first; R.ba.iters_first = iters_first;
+      }
+    }
+    R.ba.edge_chi2 = nullptr; R.ba.edge_depth_pos = nullptr; R.ba.edge_outlier1 = nullptr;   // (they pointed into this function's vectors)
+    R.erase.assign(E, 0);
+    for (size_t e = 0; e < E; ++e) R.erase[e] = chi2[e] > 5.991 || !dpos[e];                                     // :664
+    std::vector<int32_t> new_ref(L + 1), bad(65);
+    asd_ba_apply_args ap{};
+    ap.n_edges = (int32_t)E; ap.erase = R.erase.data(); ap.apply = 1; ap.n_points = (int32_t)L; ap.new_ref = new_ref.data();
+    ap.bad_capacity = 64; ap.bad_rows = bad.data();
+    R.rc = asd_local_ba_apply(c.get(), &ap);
+    if (R.rc == ASD_ERR_CAPACITY && ap.n_bad > ap.bad_capacity) {
+      bad.assign((size_t)ap.n_bad + 1, 0);
+      ap.bad_capacity = ap.n_bad; ap.bad_rows = bad.data();
+      R.rc = asd_local_ba_apply(c.get(), &ap);
+    }
+    if (R.rc != ASD_OK) return R;
+    R.n_erased = ap.n_erased;
+    R.bad_rows.assign(bad.begin(), bad.begin() + ap.n_bad);
+    // mpRefKF is re-seated when its own observation was erased (MapPoint.cc:131-132): then it ends at the lowest id left
+    std::vector<int32_t> seat(L);
+    for (size_t i = 0; i < L; ++i) seat[i] = view.refKF(G.lLocalMapPoints[i]);
+    std::vector<int32_t> local_of_rank(L + 1);
+    for (size_t i = 0; i < L; ++i) local_of_rank[G.point_rank[i]] = (int32_t)i;
+    std::vector<uint8_t> seat_erased(L + 1, 0);
+    for (size_t e = 0; e < E; ++e)
+      if (R.erase[e] && G.e_kf[e] == seat[local_of_rank[G.e_point[e]]]) seat_erased[local_of_rank[G.e_point[e]]] = 1;
+    for (size_t i = 0; i < L; ++i) if (seat_erased[i] && new_ref[i] >= 0) seat[i] = new_ref[i];
+    // :701-707, then :712-732
+    const size_t nLocal = G.lLocalKeyFrames.size();
+    R.Tcw.assign(16 * nLocal, 0.f); R.Ow.assign(3 * nLocal, 0.f);
+    for (size_t k = 0; k < nLocal; ++k) {
+      const size_t i = std::lower_bound(G.pose_kfs.begin(), G.pose_kfs.end(), G.lLocalKeyFrames[k]) - G.pose_kfs.begin();
+      float* T = R.Tcw.data() + 16 * k;
+      asd_pose7_to_tcw(poses.data() + 7 * i, T);
+      for (int r = 0; r < 3; ++r) R.Ow[3 * k + r] = -(T[r] * T[3] + T[4 + r] * T[7] + T[8 + r] * T[11]);   // Ow = -Rcw.t() * tcw, in f32 (KeyFrame.cc:228-230)
+    }
+    std::vector<int32_t> table_kfs;   // the centres go to the keyframes the table holds
+    std::vector<float> table_Ow;
+    for (size_t k = 0; k < nLocal; ++k) {
+      if (!view.inTable(G.lLocalKeyFrames[k])) continue;
+      table_kfs.push_back(G.lLocalKeyFrames[k]);
+      table_Ow.insert(table_Ow.end(), R.Ow.begin() + 3 * k, R.Ow.begin() + 3 * k + 3);
+    }
+    for (size_t i = 0; i < L; ++i) {
+      const int32_t row = G.lLocalMapPoints[i];
+      if (view.global(row)) continue;                                                                            // :715-716
+      R.rows.push_back(row); R.mpRefKF.push_back(seat[i]);
+      for (int k = 0; k < 3; ++k) R.Xw.push_back((float)points[3 * (size_t)G.point_rank[i] + k]);                // Converter::toCvMat(Vector3d): CV_32F
+    }
+    R.rc = WriteBack(c, table_kfs, table_Ow, R.rows, R.mpRefKF, R.Xw, &R.status);
+    return R;
+  }
 };
 
 // ---- Tracking (Tracking.cc): the two per-frame stages as one submission each ------------------------------------------------

@@ -1499,6 +1499,73 @@ int asd_update_normal_and_depth(asd_ctx* ctx, asd_normal_depth_args* args);
 int asd_normal_and_depth_point(int32_t n_obs, const float* Ow /*[n_obs][3], in walk order*/, int32_t ref /*index into Ow*/,
                                const float* Pos, float scale_level, float scale_top, float normal[3], float* min_dist, float* max_dist);
 
+/* ---- Optimizer::LocalBundleAdjustment over the table: the graph and the erase policy ----
+ * asd_local_ba_graph is Optimizer.cc:418-467 and the structure of :484-593 for keyframe kf (which must be in the table) and
+ * neigh[n_neigh <= 4096] = GetVectorCovisibleKeyFrames() as ids in its order (the full vector: the table's 10 links do not hold it).  An id
+ * that is not in the table is legal: it counts as not bad and contributes no points.  Every walk over mObservations is in ASCENDING
+ * KEYFRAME ID (the section's standing rule); an observer of a point is any table entry that names it.
+ *   local_kfs / n_local_kfs   lLocalKeyFrames: kf, then the neighbours that are not bad, in the order given (:420-431)
+ *   local_rows / n_points     lLocalMapPoints: the local keyframes in list order, their entries in ascending keypoint index, a point taken
+ *                             at its first occurrence unless it is -1 or flagged bad (:435-449)
+ *   fixed_kfs / n_fixed       lFixedCameras: local_rows in order, each point's observers in ascending id, an observer taken at its first
+ *                             occurrence when it is neither local nor bad (:453-467)
+ *   pose_kfs, pose_fixed / n_poses   local and fixed keyframes together in ascending id -- asd_ba_problem's pose order; pose_fixed = 1 for
+ *                             the members of lFixedCameras (the caller ORs in mnId == 0 || GetGlobalMapFlag(), :490).  A local keyframe
+ *                             without any edge is listed all the same: asd_local_ba accepts idle vertices.
+ *   point_rank[n_points]      the index of local_rows[i] among the local rows sorted ascending -- asd_ba_problem's point order.  It equals
+ *                             ascending mnId when the caller hands out bank rows in creation order; a caller that does not renumbers.
+ *   e_* / n_edges             the edges in the reference's insertion order (:534-593): the points in local_rows order, each point's observers
+ *                             in ascending id, bad keyframes skipped (:556).  e_point = the point's point_rank, e_pose = the index into
+ *                             pose_kfs, e_kf = the keyframe id, e_idx = the keypoint index (mit->second), e_octave = mvKeysUn[e_idx].octave
+ *                             from the octave plane.  e_obs (mvKeysUn[e_idx].pt) and e_info (inv_sigma2[e_octave], x 10 for a global-map
+ *                             point) are the caller's to fill.
+ *   Xw[n_points][3]           optional (NULL = skip): the points' positions from the attribute bank in point_rank order, widened to f64
+ *                             (Converter::toVector3d).  When asked for, the bank conditions of asd_update_normal_and_depth apply: the rows lie
+ *                             inside the bank's capacity, no asd_prep_async bracket is open.
+ * Capacities are the caller's.  When one is too small the call returns ASD_ERR_CAPACITY with ALL counts set to what is needed; it changes
+ * nothing and may simply be repeated.  ASD_ERR_INVALID: kf not in the table; a duplicate id, a negative id or kf itself in neigh; any
+ * live keyframe without octaves.  ASD_ERR_CAPACITY also when the local keyframes' rows together exceed asd_update_local_map's bound, or
+ * the local points (2^20) or their observations together (2^30) asd_update_normal_and_depth's.  The call runs on the context's stream,
+ * returns drained and undoes every mark it set; it changes neither the table nor its version (the search list stays valid); results
+ * are identical from run to run.  After ASD_OK the graph stays resident for asd_local_ba_apply -- the points' observer segments and the
+ * edge -> entry map -- until any asd_map_* call changes the table. */
+typedef struct asd_ba_graph_args {
+  int32_t kf; int32_t n_neigh; const int32_t* neigh;
+  int32_t kf_capacity;    int32_t* local_kfs;  int32_t n_local_kfs;
+  int32_t point_capacity; int32_t* local_rows; int32_t* point_rank; int32_t n_points;
+  int32_t fixed_capacity; int32_t* fixed_kfs;  int32_t n_fixed;
+  int32_t pose_capacity;  int32_t* pose_kfs;   uint8_t* pose_fixed; int32_t n_poses;
+  int32_t edge_capacity;  int32_t* e_point; int32_t* e_pose; int32_t* e_kf; int32_t* e_idx; uint8_t* e_octave; int32_t n_edges;
+  double* Xw;
+} asd_ba_graph_args;
+int asd_local_ba_graph(asd_ctx* ctx, asd_ba_graph_args* args);
+
+/* The erase policy of Optimizer.cc:652-697 over the resident graph: erase[n_edges] = one byte per edge of the last asd_local_ba_graph,
+ * chi2 > 5.991 || !isDepthPositive as the caller read it from asd_ba_result; n_points = that graph's.  The reference erases one pair after
+ * the other (KeyFrame::EraseMapPointMatch + MapPoint::EraseObservation, MapPoint.cc:119-142): a point whose nObs reaches <= 2 turns bad on
+ * the spot and loses ALL its entries (SetBadFlag, :180-197), later pairs of that point are no-ops.  The edges are grouped by point, so
+ * this has a closed form, which is what the device evaluates: left = Observations(r) - flagged edges of r, where Observations counts
+ * every table entry that names r, the bad keyframes' included; the point turns bad exactly when it has a flagged edge and left <= 2.
+ *   n_erased              the observations EraseObservation itself removed (the pairs that were not no-ops)
+ *   bad_rows / n_bad      the points that turned bad, in local_rows order (= the order it happened); bad_capacity too small is
+ *                         ASD_ERR_CAPACITY with n_bad and n_erased set, nothing changed, and the call may be repeated
+ *   new_ref[n_points]     in local_rows order: the lowest remaining observer id for a point that lost an observation and did not turn
+ *                         bad, -1 otherwise.  mpRefKF is re-seated only when its own observation goes and ends at the lowest id among the
+ *                         observers finally left: the caller assigns new_ref when the point's mpRefKF was among its erased keyframes.
+ * apply = 1 leaves the table as the reference leaves the map: every flagged edge's entry -1, every entry of a point that turned bad -1 in
+ * every row (through the resident segments), that point's bad byte set.  When a flagged edge exists the table's version is bumped and the
+ * search list of asd_track_local_points_map is invalid; without one nothing changes.  apply = 1 consumes the graph either way; apply = 0
+ * changes nothing and keeps it.  ASD_ERR_INVALID, the table untouched: no resident graph; the table has changed since the graph call;
+ * n_edges or n_points differ from the graph's; an unfinished call armed with asd_track_async. */
+typedef struct asd_ba_apply_args {
+  int32_t n_edges; const uint8_t* erase;
+  int32_t apply;
+  int32_t n_erased;
+  int32_t bad_capacity; int32_t* bad_rows; int32_t n_bad;
+  int32_t n_points; int32_t* new_ref;
+} asd_ba_apply_args;
+int asd_local_ba_apply(asd_ctx* ctx, asd_ba_apply_args* args);
+
 /* Test aid: out = {live keyframes, live entries, slot capacity, arena capacity, row-table capacity, growths of the slot table, of the arena,
  * of the row tables}. */
 int32_t asd_debug_map(asd_ctx* ctx, int64_t out[8]);
