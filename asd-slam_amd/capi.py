@@ -103,6 +103,12 @@ class asd_ba_apply_args(C.Structure):
                 ("bad_rows", C.c_void_p), ("n_bad", C.c_int32), ("n_points", C.c_int32), ("new_ref", C.c_void_p)]
 
 
+class asd_fuse_apply_args(C.Structure):
+    _fields_ = [("kf", C.c_int32), ("mode", C.c_int32), ("n", C.c_int32), ("cand", C.c_void_p), ("best_idx", C.c_void_p), ("apply", C.c_int32),
+                ("action", C.c_void_p), ("other", C.c_void_p), ("obs_cand", C.c_void_p), ("obs_other", C.c_void_p), ("n_moved", C.c_void_p),
+                ("n_dropped", C.c_void_p), ("n_fused", C.c_int32)]
+
+
 class asd_ba_problem(C.Structure):
     _fields_ = [("n_poses", C.c_int32), ("n_points", C.c_int32), ("n_edges", C.c_int32),
                 ("poses", C.c_void_p), ("fixed", C.c_void_p), ("points", C.c_void_p),
@@ -1127,6 +1133,57 @@ class AsdHip:
             rc, out = self.local_ba_apply_raw(erase, n_points, apply, out["n_bad"])
         self._chk(rc)
         return out
+
+    def fuse_apply_raw(self, kf, cand, best_idx, mode=0, apply=False):
+        """asd_fuse_apply -> (rc, dict(action, other, obs_cand, obs_other, n_moved, n_dropped, n_fused)); the dict is filled only when rc == 0"""
+        cand, best = _c(cand, np.int32), _c(best_idx, np.int32)
+        n = len(cand)
+        assert len(best) == n
+        act = np.full(max(n, 1), 99, np.uint8)
+        oth, oc, oo, mv, dr = (np.full(max(n, 1), -7, np.int32) for _ in range(5))
+        a = asd_fuse_apply_args()
+        a.kf, a.mode, a.n, a.cand, a.best_idx, a.apply = int(kf), int(mode), n, cand.ctypes.data, best.ctypes.data, int(bool(apply))
+        a.action, a.other, a.obs_cand, a.obs_other = act.ctypes.data, oth.ctypes.data, oc.ctypes.data, oo.ctypes.data
+        a.n_moved, a.n_dropped, a.n_fused = mv.ctypes.data, dr.ctypes.data, -1
+        rc = self.lib.asd_fuse_apply(self.ctx, C.byref(a))
+        out = {}
+        if rc == 0:
+            out.update(action=act[:n].copy(), other=oth[:n].copy(), obs_cand=oc[:n].copy(), obs_other=oo[:n].copy(), n_moved=mv[:n].copy(),
+                       n_dropped=dr[:n].copy(), n_fused=int(a.n_fused))
+        return rc, out
+
+    def fuse_apply(self, kf, cand, best_idx, mode=0, apply=False):
+        """the side effects of ORBmatcher::Fuse (mode 0), Fuse with Scw + SearchAndFuse's loop (1), CorrectLoop's loop fusion (2) over the table"""
+        rc, out = self.fuse_apply_raw(kf, cand, best_idx, mode, apply)
+        self._chk(rc)
+        return out
+
+    def map_get_raw(self, kf, capacity):
+        rows, n = np.full(max(int(capacity), 1), -7, np.int32), C.c_int32(-1)
+        rc = self.lib.asd_map_get(self.ctx, int(kf), int(capacity), _p(rows), C.byref(n))
+        return rc, n.value, (rows[:n.value].copy() if rc == 0 else None)
+
+    def map_get(self, kf, capacity=2048):
+        """KeyFrame::GetMapPointMatches(): the keyframe's row as it stands; repeats once with the length the library asked for"""
+        rc, n, rows = self.map_get_raw(kf, capacity)
+        if rc == -5:   # ASD_ERR_CAPACITY
+            rc, n, rows = self.map_get_raw(kf, n)
+        self._chk(rc)
+        return rows
+
+    def map_points_raw(self, kfs, capacity):
+        kfs = _c(kfs, np.int32)
+        rows, n = np.full(max(int(capacity), 1), -7, np.int32), C.c_int32(-1)
+        rc = self.lib.asd_map_points(self.ctx, len(kfs), _p(kfs), int(capacity), _p(rows), C.byref(n))
+        return rc, n.value, (rows[:n.value].copy() if rc == 0 else None)
+
+    def map_points(self, kfs, capacity=65536):
+        """the distinct not-bad points of the keyframes' rows in order (UpdateLocalPoints' rule); repeats once with the count asked for"""
+        rc, n, rows = self.map_points_raw(kfs, capacity)
+        if rc == -5:   # ASD_ERR_CAPACITY
+            rc, n, rows = self.map_points_raw(kfs, n)
+        self._chk(rc)
+        return rows
 
     def map_debug(self):
         """(live keyframes, live entries, slot capacity, arena capacity, row-table capacity, slot / arena / row-table growths)"""

@@ -49,6 +49,13 @@
 // asd_local_ba_apply, which evaluates the erase policy of :652-697 per point in closed form and, with apply = 1, empties the erased
 // entries THROUGH the segments, without another pass over the table.
 //
+// Fuse's side effects.  asd_fuse_apply is what ORBmatcher::Fuse does with bestIdx (ORBmatcher.cc:939-955, :1065-1079), the Replace loops of
+// LoopClosing (LoopClosing.cc:540-555, :619-627) and MapPoint::Replace (MapPoint.cc:206-244), in the reference's order.  The points that can
+// take part -- the candidates with a best_idx and what kf's row holds there -- are marked, k_cull_count counts their observers, k_nd_scan
+// gives them segments, k_fa_fill lays (slot, keypoint index, point, owner) into them; k_fa_walk is ONE workgroup: thread 0 takes the
+// candidates in order and stops at every Replace, which all threads do together over the two points' chains of segments.  With apply = 1
+// k_fa_write rewrites the rows THROUGH the segments, without another pass over the table.
+//
 // Streams.  Every copy into these tables and every kernel that reads them is enqueued on ctx->stream, every entry point returns with that
 // stream drained, and all of them are refused while an armed asd_track_* call is unfinished (asd_track_local_points_map reads the search
 // list on that stream).  A growth therefore orders itself against the only stream that can hold a write to the old storage: the copy
@@ -58,6 +65,7 @@
 #include <climits>
 #include <map>
 #include <unordered_map>
+#include <unordered_set>
 #include <vector>
 
 #include "matcher.h"
@@ -855,6 +863,189 @@ __global__ __launch_bounds__(256) void k_ba_write(LmBaArgs a) {
   }
 }
 
+// ---- ORBmatcher::Fuse's side effects (ORBmatcher.cc:939-955, :1065-1079; LoopClosing.cc:540-555, :619-627) and MapPoint::Replace
+// (MapPoint.cc:206-244).  The points that can take part are known at entry: the candidates that carry a best_idx (the hits; point index
+// j = their place among the hits) and what kf's row holds at those keypoints (point index nh + j for the hit that claims the point).
+struct LmFaArgs {
+  const LmSlotDev* table; int* rows; uint8_t* pbad; int* mark; int n_slots;
+  int kf_slot; long long kf_off; int mode;
+  const int* cand; const int* best; int nh; int P;   // the hits: bank row and keypoint of kf; P = 2 nh points
+  int* cnt; int* cursor; int* seg_off;               // per point: Observations() as the walk proceeds, fill cursor, start of its segment [P + 1]
+  int* pt_row; int* gone; int* head; int* tail;      // per point: bank row (-1: unused index), replaced in this call, its chain of segments
+  int* inkf; int* inkf0;                             // per point: the keypoint of kf that names it, now / at entry (-1: none)
+  int* next;                                         // per segment [P + nh]: the next one of the chain; segment P + j is the spare entry of hit j
+  int* oidx;                                         // per hit: pMPinKF as a point index
+  int4* ent; int total;                              // (slot, keypoint index, the point the fill found there, the point that owns it now or -1)
+  int* krow;                                         // kf's row as point indices, valid at the hits' keypoints
+  int* stamp;                                        // [slots] the Replace that met a live entry of the winner in that keyframe last
+  int* out;                                          // [6][nh]: action, other (bank row), obs_cand, obs_other, n_moved, n_dropped
+  int apply;
+};
+
+__global__ __launch_bounds__(256) void k_fa_mark_cand(const int* __restrict__ cand, int nh, int* __restrict__ mark) {
+  const int j = blockIdx.x * 256 + threadIdx.x;
+  if (j < nh) mark[cand[j]] = j + 1;   // (distinct rows)
+}
+// what kf's row holds at the hits' keypoints: a point that is no candidate belongs to the largest hit that meets it, whatever the scheduling
+__global__ __launch_bounds__(256) void k_fa_mark_other(LmFaArgs a) {
+  const int j = blockIdx.x * 256 + threadIdx.x;
+  if (j >= a.nh) return;
+  const int q = a.rows[a.kf_off + a.best[j]];
+  if (q < 0) return;
+  const int m = a.mark[q];
+  if (m == 0 || m > a.nh) atomicMax(&a.mark[q], a.nh + j + 1);
+}
+__global__ __launch_bounds__(256) void k_fa_index(LmFaArgs a) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= a.P) return;
+  a.cnt[i] = 0; a.cursor[i] = 0; a.gone[i] = 0; a.inkf[i] = -1; a.inkf0[i] = -1;
+  const int j = i < a.nh ? i : i - a.nh;
+  const int q = a.rows[a.kf_off + a.best[j]];
+  if (i < a.nh) {
+    a.pt_row[i] = a.cand[i];
+    a.krow[a.best[j]] = q >= 0 ? a.mark[q] - 1 : -1;   // (hits that share a keypoint store the same value)
+  } else {
+    a.pt_row[i] = q >= 0 && a.mark[q] == i + 1 ? q : -1;
+  }
+}
+// k_bg_fill without the octave plane; the entry of kf leaves its keypoint with the point
+__global__ __launch_bounds__(256) void k_fa_fill(LmFaArgs a) {
+  const int lane = threadIdx.x & 63;
+  const int slot = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (slot >= a.n_slots) return;
+  const long long off = a.table[slot].off;
+  const int n = a.table[slot].n;
+  for (int i = lane; i < n; i += 64) {
+    const int r = a.rows[off + i];
+    if (r < 0) continue;
+    const int m = a.mark[r];
+    if (m <= 0) continue;
+    const int p = atomicAdd(&a.cursor[m - 1], 1);
+    if (p < a.seg_off[m] - a.seg_off[m - 1]) a.ent[(size_t)a.seg_off[m - 1] + p] = make_int4(slot, i, m - 1, m - 1);   // (the count pass saw the same table)
+    if (slot == a.kf_slot) { a.inkf[m - 1] = i; a.inkf0[m - 1] = i; }
+  }
+}
+__device__ inline void fa_seg(const LmFaArgs& a, int s, int* base, int* len) {
+  if (s < a.P) { *base = a.seg_off[s]; *len = a.seg_off[s + 1] - *base; }
+  else { *base = a.total + (s - a.P); *len = 1; }
+}
+// The ordered walk as ONE workgroup.  Thread 0 takes the hits one after the other -- gate, empty entry, bad entry, the comparison of the
+// two Observations() -- and stops at a Replace(L -> W), which all threads do together: the live entries of W's chain stamp their keyframes,
+// the live entries of L's chain are re-seated on W or dropped by that stamp, L's chain is appended to W's.  The keyframes of one point are
+// distinct, so the threads of a round touch different stamps and the counts are sums: nothing depends on the order inside a segment.
+__global__ __launch_bounds__(256) void k_fa_walk(LmFaArgs a) {
+  __shared__ int s_dec[4], s_red[4][2];
+  const int t = threadIdx.x, lane = t & 63, w = t >> 6;
+  for (int p = t; p < a.P; p += 256) { const int h = a.cnt[p] > 0 ? p : -1; a.head[p] = h; a.tail[p] = h; }
+  for (int s = t; s < a.P + a.nh; s += 256) a.next[s] = -1;
+  for (int j = t; j < a.nh; j += 256) a.ent[(size_t)a.total + j] = make_int4(a.kf_slot, a.best[j], j, -1);
+  asd_syncthreads();
+  int* const o_act = a.out; int* const o_oth = a.out + a.nh; int* const o_oc = a.out + 2 * a.nh; int* const o_oo = a.out + 3 * a.nh;
+  int* const o_mv = a.out + 4 * a.nh; int* const o_dr = a.out + 5 * a.nh;
+  const int last = a.mode == 1 ? 2 * a.nh : a.nh;   // mode 1: the hits once more for SearchAndFuse's loop (LoopClosing.cc:619-627)
+  int pos = 0, step = 0;                            // pos: thread 0's place in the walk
+  while (true) {
+    if (t == 0) {
+      int kind = 0, L = -1, W = -1, hit = -1;
+      for (; pos < last && !kind; ++pos) {
+        const int j = pos < a.nh ? pos : pos - a.nh;
+        if (pos >= a.nh) {   // pass 2: vpReplacePoint[i]->Replace(vpPoints[i]), no test at all
+          if (o_act[j] != 3) continue;
+          L = a.oidx[j]; W = j; hit = j; kind = 1;
+          o_oc[j] = a.cnt[W]; o_oo[j] = a.cnt[L];
+          continue;
+        }
+        const int b = a.best[j], q = a.krow[b];
+        const bool cbad = a.pbad[a.pt_row[j]] || a.gone[j];
+        int act, oth = -1, oc = 0, oo = 0;
+        if (a.mode == 0 && (cbad || a.inkf[j] >= 0)) act = 7;         // :849, at the candidate's turn
+        else if (a.mode == 1 && (cbad || a.inkf0[j] >= 0)) act = 7;   // :979, :992: spAlreadyFound is a snapshot
+        else if (q < 0) {
+          oc = a.cnt[j];
+          if (a.mode == 2 && a.inkf[j] >= 0) act = 6;                 // not restated: the table holds a point once per row
+          else {                                                      // AddObservation + AddMapPoint
+            act = 1;
+            a.krow[b] = j; a.inkf[j] = b; a.cnt[j] = oc + 1;
+            reinterpret_cast<int*>(a.ent + (size_t)a.total + j)[3] = j;
+            if (a.head[j] < 0) a.head[j] = a.P + j; else a.next[a.tail[j]] = a.P + j;
+            a.tail[j] = a.P + j;
+          }
+        } else {
+          oth = a.pt_row[q]; oc = a.cnt[j]; oo = a.cnt[q];
+          a.oidx[j] = q;
+          if (q == j) act = 5;
+          else if (a.mode != 2 && (a.pbad[oth] || a.gone[q])) act = 4;
+          else if (a.mode == 1) { act = 3; oc = 0; oo = 0; }          // noted; pass 2 fills the counts when it acts
+          else if (a.mode == 0 && oo > oc) { act = 2; kind = 1; L = j; W = q; hit = j; }
+          else { act = 3; kind = 1; L = q; W = j; hit = j; }
+        }
+        o_act[j] = act; o_oth[j] = oth; o_oc[j] = oc; o_oo[j] = oo; o_mv[j] = 0; o_dr[j] = 0;
+      }
+      s_dec[0] = kind; s_dec[1] = L; s_dec[2] = W; s_dec[3] = hit;
+    }
+    asd_syncthreads();
+    if (!s_dec[0]) break;   // (the same for every thread)
+    const int L = s_dec[1], W = s_dec[2], hit = s_dec[3];
+    ++step;
+    for (int s = a.head[W]; s >= 0; s = a.next[s]) {
+      int base, len;
+      fa_seg(a, s, &base, &len);
+      for (int e = t; e < len; e += 256) { const int4 x = a.ent[(size_t)base + e]; if (x.w >= 0) a.stamp[x.x] = step; }
+    }
+    asd_syncthreads();
+    int mv = 0, dr = 0;
+    for (int s = a.head[L]; s >= 0; s = a.next[s]) {
+      int base, len;
+      fa_seg(a, s, &base, &len);
+      for (int e = t; e < len; e += 256) {
+        const int4 x = a.ent[(size_t)base + e];
+        if (x.w < 0) continue;
+        const bool in_w = a.stamp[x.x] == step;   // pMP->IsInKeyFrame(pKF)
+        reinterpret_cast<int*>(a.ent + (size_t)base + e)[3] = in_w ? -1 : W;
+        if (in_w) ++dr; else ++mv;
+        if (x.x == a.kf_slot) { a.krow[x.y] = in_w ? -1 : W; if (!in_w) a.inkf[W] = x.y; }
+      }
+    }
+    for (int s = 32; s > 0; s >>= 1) { mv += __shfl_xor(mv, s, 64); dr += __shfl_xor(dr, s, 64); }
+    if (lane == 0) { s_red[w][0] = mv; s_red[w][1] = dr; }
+    asd_syncthreads();
+    if (t == 0) {
+      mv = s_red[0][0] + s_red[1][0] + s_red[2][0] + s_red[3][0];
+      dr = s_red[0][1] + s_red[1][1] + s_red[2][1] + s_red[3][1];
+      o_mv[hit] = mv; o_dr[hit] = dr;
+      a.cnt[W] += mv; a.cnt[L] = 0; a.gone[L] = 1; a.inkf[L] = -1;
+      const int h = a.head[L];
+      if (h >= 0) {
+        if (a.head[W] < 0) a.head[W] = h; else a.next[a.tail[W]] = h;
+        a.tail[W] = a.tail[L];
+        a.head[L] = -1; a.tail[L] = -1;
+      }
+    }
+    // (thread 0 goes on with the walk; everybody else waits for it at the barrier above)
+  }
+}
+// apply = 1, THROUGH the segments: an entry of another keyframe whose owner changed is rewritten; kf's own row is written from the walk's
+// view of it (its keypoints can be emptied and taken again, so several segment entries may stand for one of them)
+__global__ __launch_bounds__(256) void k_fa_write(LmFaArgs a) {
+  const long long e = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (e < a.total) {
+    const int4 x = a.ent[e];
+    if (x.x != a.kf_slot && x.w != x.z) a.rows[a.table[x.x].off + x.y] = x.w < 0 ? -1 : a.pt_row[x.w];
+  } else if (e < (long long)a.total + a.nh) {
+    const int b = a.best[e - a.total], v = a.krow[b];
+    a.rows[a.kf_off + b] = v < 0 ? -1 : a.pt_row[v];
+  }
+}
+// the marks are undone; with apply the losers get their bad byte
+__global__ __launch_bounds__(256) void k_fa_finish(LmFaArgs a) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= a.P) return;
+  const int r = a.pt_row[i];
+  if (r < 0) return;
+  a.mark[r] = 0;
+  if (a.apply && a.gone[i]) a.pbad[r] = 1;
+}
+
 struct LmSlot {
   int kf = -1;   // -1: free slot
   int n = -1;
@@ -903,6 +1094,8 @@ struct LocalMapState {
   int* d_bge = nullptr; size_t bge_cap = 0;             // edge -> segment entry
   int* d_bgk = nullptr; size_t bgk_cap = 0;             // [slots] claim | lFixedCameras
   uint8_t* d_bgf = nullptr; size_t bgf_cap = 0;         // per segment entry: flagged by asd_local_ba_apply
+  int* d_fa = nullptr; size_t fa_cap = 0;               // asd_fuse_apply: per point, per segment and per hit words | kf's row | stamps
+  int4* d_fas = nullptr; size_t fas_cap = 0;            // its segments
   bool bg_valid = false; uint64_t bg_version = 0;       // the resident graph and the table version it was built from
   int bg_points = 0, bg_edges = 0; long long bg_total = 0; size_t bg_N = 0;
   AsdXfer up, down;
@@ -940,13 +1133,14 @@ int lm_reserve(asd_ctx* ctx, T** p, size_t* cap, size_t need, size_t keep, int f
 
 void release_device(LocalMapState* S) {
   void* dev[] = {S->d_table, S->d_rows, S->d_pbad, S->d_mark, S->d_claim, S->d_sorted, S->d_child, S->d_cnt, S->d_list, S->d_list_base, S->d_head,
-                 S->d_tile, S->d_local, S->d_search, S->d_oct, S->d_cull, S->d_culled, S->d_center, S->d_nd, S->d_bgp, S->d_bgn, S->d_bgs, S->d_bge, S->d_bgk, S->d_bgf};
+                 S->d_tile, S->d_local, S->d_search, S->d_oct, S->d_cull, S->d_culled, S->d_center, S->d_nd, S->d_bgp, S->d_bgn, S->d_bgs, S->d_bge, S->d_bgk, S->d_bgf, S->d_fa, S->d_fas};
   for (void* p : dev) if (p) (void)hipFree(p);
   S->d_table = nullptr; S->d_rows = nullptr; S->d_pbad = nullptr; S->d_mark = nullptr; S->d_claim = nullptr; S->d_sorted = nullptr; S->d_child = nullptr;
   S->d_cnt = nullptr; S->d_list = nullptr; S->d_list_base = nullptr; S->d_head = nullptr; S->d_tile = nullptr; S->d_local = nullptr; S->d_search = nullptr;
   S->d_oct = nullptr; S->d_cull = nullptr; S->d_culled = nullptr; S->cull_cap = S->culled_cap = 0;
   S->d_center = nullptr; S->d_nd = nullptr; S->center_cap = S->nd_cap = 0;
   S->d_bgp = nullptr; S->d_bgn = nullptr; S->d_bgs = nullptr; S->d_bge = nullptr; S->d_bgk = nullptr; S->d_bgf = nullptr;
+  S->d_fa = nullptr; S->d_fas = nullptr; S->fa_cap = S->fas_cap = 0;
   S->bgp_cap = S->bgn_cap = S->bgs_cap = S->bge_cap = S->bgk_cap = S->bgf_cap = 0; S->bg_valid = false;
   S->table_cap = S->row_cap = S->sorted_cap = S->child_cap = S->cnt_cap = S->list_cap = S->list_base_cap = S->head_cap = S->tile_cap = S->local_cap = S->search_cap = 0;
   S->entry_cap = S->entry_used = 0;
@@ -2087,6 +2281,217 @@ int asd_local_ba_apply(asd_ctx* ctx, asd_ba_apply_args* A) {
   memcpy(A->new_ref, S->down.h + o_ref, (size_t)n * sizeof(int));
   if (n_bad) memcpy(A->bad_rows, S->down.h + o_bad, (size_t)n_bad * sizeof(int));
   if (ba.apply) { ++S->version; S->bg_valid = false; }
+  return ASD_OK;
+}
+
+static_assert(sizeof(asd_fuse_apply_args) == 96 && offsetof(asd_fuse_apply_args, cand) == 16 && offsetof(asd_fuse_apply_args, apply) == 32 &&
+              offsetof(asd_fuse_apply_args, action) == 40 && offsetof(asd_fuse_apply_args, n_dropped) == 80 && offsetof(asd_fuse_apply_args, n_fused) == 88,
+              "asd_fuse_apply_args: the layout the bindings restate");
+
+int asd_fuse_apply(asd_ctx* ctx, asd_fuse_apply_args* A) {
+  if (!ctx) return ASD_ERR_INVALID;
+  if (!A || A->n < 0 || (A->n > 0 && (!A->cand || !A->best_idx || !A->action || !A->other || !A->obs_cand || !A->obs_other || !A->n_moved || !A->n_dropped))) {
+    ctx->set_error("asd_fuse_apply: invalid argument");
+    return ASD_ERR_INVALID;
+  }
+  if (refuse(ctx, "asd_fuse_apply")) return ASD_ERR_INVALID;
+  if (A->mode < 0 || A->mode > 2) { ctx->set_error("asd_fuse_apply: mode %d (0 Fuse, 1 Fuse with Scw + SearchAndFuse's loop, 2 the loop fusion of CorrectLoop)", A->mode); return ASD_ERR_INVALID; }
+  const int n = A->n;
+  if (n > kMaxNdPoints) { ctx->set_error("asd_fuse_apply: %d candidates exceed the %d one call takes", n, kMaxNdPoints); return ASD_ERR_CAPACITY; }
+  LocalMapState* S = lstate(ctx);
+  int kf_slot;
+  const LmSlot* K = find_kf(ctx, S, "asd_fuse_apply", A->kf, &kf_slot);
+  if (!K) return ASD_ERR_INVALID;
+  std::vector<int> h_cand, h_best, h_pos;   // the hits: candidates that take a step, in list order
+  int max_row = -1;
+  {
+    std::unordered_set<int> seen;   // the candidate rows >= 0 met so far
+    seen.reserve((size_t)n);
+    for (int i = 0; i < n; ++i) {
+      const int c = A->cand[i], b = A->best_idx[i];
+      if (c < -1 || c >= kMaxRow) { ctx->set_error("asd_fuse_apply: bank row %d at candidate %d (rows are -1 or 0 .. %d)", c, i, kMaxRow - 1); return ASD_ERR_INVALID; }
+      if (b < -1 || b >= K->n) { ctx->set_error("asd_fuse_apply: best_idx %d at candidate %d, the row of keyframe %d has %d entries", b, i, A->kf, K->n); return ASD_ERR_INVALID; }
+      if (c < 0) continue;
+      if (!seen.insert(c).second) { ctx->set_error("asd_fuse_apply: bank row %d occurs twice among the candidates", c); return ASD_ERR_INVALID; }
+      if (b >= 0) { h_cand.push_back(c); h_best.push_back(b); h_pos.push_back(i); max_row = std::max(max_row, c); }
+    }
+  }
+  A->n_fused = 0;   // (every check has passed: from here on the caller's arrays are written)
+  for (int i = 0; i < n; ++i) { A->action[i] = 0; A->other[i] = -1; A->obs_cand[i] = 0; A->obs_other[i] = 0; A->n_moved[i] = 0; A->n_dropped[i] = 0; }
+  const int nh = (int)h_cand.size();
+  if (nh == 0) return ASD_OK;   // no candidate takes a step: nothing is launched
+  (void)hipSetDevice(ctx->cfg.device);
+  hipStream_t st = ctx->stream;
+  const int n_slots = (int)S->slots.size();
+  const int P = 2 * nh;
+  int rc;
+  if ((rc = ensure_rows(ctx, S, (size_t)max_row + 1)) != ASD_OK) return rc;   // a candidate created this keyframe may lie beyond the row tables
+  if ((rc = clean_tables(ctx, S)) != ASD_OK) return rc;
+  const size_t N = ((size_t)P + 8) / 4 * 4;
+  if ((rc = lm_reserve(ctx, &S->d_fa, &S->fa_cap, 18 * N + (size_t)K->n + (size_t)n_slots + 16, 0, -1, 65536)) != ASD_OK) return rc;
+  if (!S->h_head) ASD_HIP_CHECK(ctx, hipHostMalloc(&S->h_head, 16 * sizeof(int)));
+  int* const head = S->h_head;
+  LmFaArgs fa{};
+  fa.table = S->d_table; fa.rows = S->d_rows; fa.pbad = S->d_pbad; fa.mark = S->d_mark; fa.n_slots = n_slots;
+  fa.kf_slot = kf_slot; fa.kf_off = K->off; fa.mode = A->mode; fa.nh = nh; fa.P = P;
+  fa.cnt = S->d_fa; fa.cursor = fa.cnt + N; fa.seg_off = fa.cursor + N; fa.pt_row = fa.seg_off + N; fa.gone = fa.pt_row + N; fa.head = fa.gone + N;
+  fa.tail = fa.head + N; fa.inkf = fa.tail + N; fa.inkf0 = fa.inkf + N; fa.next = fa.inkf0 + N; fa.oidx = fa.next + 2 * N; fa.out = fa.oidx + N;
+  fa.krow = fa.out + 6 * N; fa.stamp = fa.krow + K->n;
+  ASD_HIP_CHECK(ctx, S->up.begin(st, (size_t)nh * 8 + 1024));
+  const size_t o_cand = S->up.add(h_cand.data(), (size_t)nh * sizeof(int)), o_best = S->up.add(h_best.data(), (size_t)nh * sizeof(int));
+  ASD_HIP_CHECK(ctx, S->up.upload(st));
+  fa.cand = S->up.dev<int>(o_cand); fa.best = S->up.dev<int>(o_best);
+  ASD_HIP_CHECK(ctx, hipMemsetAsync(fa.krow, 0xff, (size_t)K->n * sizeof(int), st));
+  ASD_HIP_CHECK(ctx, hipMemsetAsync(fa.stamp, 0, ((size_t)n_slots + 1) * sizeof(int), st));
+  const dim3 per_hit((nh + 255) / 256), per_point((P + 255) / 256), per_slot((n_slots + 3) / 4);
+  S->tables_dirty = true;
+  hipLaunchKernelGGL(k_fa_mark_cand, per_hit, dim3(256), 0, st, fa.cand, nh, S->d_mark);
+  ASD_HIP_CHECK(ctx, hipGetLastError());
+  hipLaunchKernelGGL(k_fa_mark_other, per_hit, dim3(256), 0, st, fa);
+  ASD_HIP_CHECK(ctx, hipGetLastError());
+  hipLaunchKernelGGL(k_fa_index, per_point, dim3(256), 0, st, fa);
+  ASD_HIP_CHECK(ctx, hipGetLastError());
+  hipLaunchKernelGGL(k_cull_count, per_slot, dim3(256), 0, st, S->d_table, n_slots, S->d_rows, S->d_oct, S->d_mark, fa.cnt, 1);
+  ASD_HIP_CHECK(ctx, hipGetLastError());
+  hipLaunchKernelGGL(k_nd_scan, dim3(1), dim3(256), 0, st, fa.cnt, P, fa.seg_off, head);   // (head: pinned, the kernel stores the total there)
+  ASD_HIP_CHECK(ctx, hipGetLastError());
+  ASD_HIP_CHECK(ctx, hipStreamSynchronize(st));
+  const long long total = ((long long)head[13] << 32) | (unsigned)head[12];
+  auto finish = [&](int apply) -> int {
+    fa.apply = apply;
+    hipLaunchKernelGGL(k_fa_finish, per_point, dim3(256), 0, st, fa);
+    ASD_HIP_CHECK(ctx, hipGetLastError());
+    ASD_HIP_CHECK(ctx, hipStreamSynchronize(st));
+    S->tables_dirty = false;
+    return ASD_OK;
+  };
+  if (total > kMaxNdEntries) {   // nothing has been written but the marks
+    if ((rc = finish(0)) != ASD_OK) return rc;
+    ctx->set_error("asd_fuse_apply: the points involved have %lld observations, more than one call takes (%lld)", total, kMaxNdEntries);
+    return ASD_ERR_CAPACITY;
+  }
+  if ((rc = lm_reserve(ctx, &S->d_fas, &S->fas_cap, (size_t)total + nh + 4, 0, -1, 65536)) != ASD_OK) return rc;
+  fa.ent = S->d_fas; fa.total = (int)total;
+  if (total > 0) {
+    hipLaunchKernelGGL(k_fa_fill, per_slot, dim3(256), 0, st, fa);
+    ASD_HIP_CHECK(ctx, hipGetLastError());
+  }
+  hipLaunchKernelGGL(k_fa_walk, dim3(1), dim3(256), 0, st, fa);
+  ASD_HIP_CHECK(ctx, hipGetLastError());
+  ASD_HIP_CHECK(ctx, S->down.begin(st, 6 * (size_t)nh * sizeof(int) + 1024));
+  const size_t o_out = S->down.reserve(6 * (size_t)nh * sizeof(int));
+  ASD_HIP_CHECK(ctx, hipMemcpyAsync(S->down.h + o_out, fa.out, 6 * (size_t)nh * sizeof(int), hipMemcpyDeviceToHost, st));
+  ASD_HIP_CHECK(ctx, hipStreamSynchronize(st));
+  const int* out = S->down.host<int>(o_out);
+  bool changed = false;
+  int n_fused = 0;
+  for (int j = 0; j < nh; ++j) {
+    const int act = out[j];
+    changed = changed || (act >= 1 && act <= 3);
+    n_fused += act >= 1 && act <= 5;
+  }
+  const bool write = A->apply && changed;
+  if (write) {
+    hipLaunchKernelGGL(k_fa_write, dim3((unsigned)((total + nh + 255) / 256)), dim3(256), 0, st, fa);
+    ASD_HIP_CHECK(ctx, hipGetLastError());
+  }
+  if ((rc = finish(write ? 1 : 0)) != ASD_OK) return rc;
+  for (int j = 0; j < nh; ++j) {
+    const int i = h_pos[j];
+    A->action[i] = (uint8_t)out[j]; A->other[i] = out[nh + j]; A->obs_cand[i] = out[2 * nh + j]; A->obs_other[i] = out[3 * nh + j];
+    A->n_moved[i] = out[4 * nh + j]; A->n_dropped[i] = out[5 * nh + j];
+  }
+  A->n_fused = n_fused;
+  if (write) ++S->version;
+  return ASD_OK;
+}
+
+int asd_map_get(asd_ctx* ctx, int32_t kf, int32_t capacity, int32_t* rows, int32_t* n) {
+  if (!ctx) return ASD_ERR_INVALID;
+  if (!n || capacity < 0 || (capacity > 0 && !rows)) { ctx->set_error("asd_map_get: invalid argument"); return ASD_ERR_INVALID; }
+  if (refuse(ctx, "asd_map_get")) return ASD_ERR_INVALID;
+  LocalMapState* S = lstate(ctx);
+  int slot;
+  const LmSlot* L = find_kf(ctx, S, "asd_map_get", kf, &slot);
+  if (!L) return ASD_ERR_INVALID;
+  *n = L->n;
+  if (L->n > capacity) { ctx->set_error("asd_map_get: the row of keyframe %d has %d entries, the capacity is %d", kf, L->n, capacity); return ASD_ERR_CAPACITY; }
+  if (L->n == 0) return ASD_OK;
+  (void)hipSetDevice(ctx->cfg.device);
+  hipStream_t st = ctx->stream;
+  ASD_HIP_CHECK(ctx, S->down.begin(st, (size_t)L->n * sizeof(int)));
+  const size_t o = S->down.reserve((size_t)L->n * sizeof(int));
+  ASD_HIP_CHECK(ctx, hipMemcpyAsync(S->down.h + o, S->d_rows + L->off, (size_t)L->n * sizeof(int), hipMemcpyDeviceToHost, st));
+  ASD_HIP_CHECK(ctx, hipStreamSynchronize(st));
+  memcpy(rows, S->down.h + o, (size_t)L->n * sizeof(int));
+  return ASD_OK;
+}
+
+int asd_map_points(asd_ctx* ctx, int32_t n_kfs, const int32_t* kfs, int32_t capacity, int32_t* rows, int32_t* n) {
+  if (!ctx) return ASD_ERR_INVALID;
+  if (!n || n_kfs < 0 || (n_kfs > 0 && !kfs) || capacity < 0 || (capacity > 0 && !rows)) { ctx->set_error("asd_map_points: invalid argument"); return ASD_ERR_INVALID; }
+  if (refuse(ctx, "asd_map_points")) return ASD_ERR_INVALID;
+  *n = 0;
+  if (n_kfs > kMaxSlots) { ctx->set_error("asd_map_points: %d keyframes exceed the %d the table holds", n_kfs, kMaxSlots); return ASD_ERR_CAPACITY; }
+  LocalMapState* S = lstate(ctx);
+  {
+    std::vector<int> seen(kfs, kfs + n_kfs);
+    std::sort(seen.begin(), seen.end());
+    for (int i = 1; i < n_kfs; ++i) if (seen[i] == seen[i - 1]) { ctx->set_error("asd_map_points: keyframe %d occurs twice", seen[i]); return ASD_ERR_INVALID; }
+  }
+  std::vector<int> list_slot(n_kfs);
+  std::vector<long long> base(n_kfs);
+  long long entries = 0;
+  int maxn = 0;
+  for (int i = 0; i < n_kfs; ++i) {   // an id that is not in the table contributes nothing
+    const auto it = S->by_kf.find(kfs[i]);
+    list_slot[i] = it == S->by_kf.end() ? -1 : it->second;
+    base[i] = entries;
+    if (list_slot[i] >= 0) { entries += S->slots[list_slot[i]].n; maxn = std::max(maxn, S->slots[list_slot[i]].n); }
+  }
+  if (entries >= kMaxEntriesPerQuery) { ctx->set_error("asd_map_points: the %d keyframes hold %lld table entries, more than one call collects (%lld)", n_kfs, entries, kMaxEntriesPerQuery); return ASD_ERR_CAPACITY; }
+  if (entries == 0) return ASD_OK;
+  (void)hipSetDevice(ctx->cfg.device);
+  hipStream_t st = ctx->stream;
+  int rc;
+  if ((rc = clean_tables(ctx, S)) != ASD_OK) return rc;
+  if ((rc = lm_reserve(ctx, &S->d_head, &S->head_cap, 16, 0, 0, 16)) != ASD_OK) return rc;
+  if (!S->h_head) ASD_HIP_CHECK(ctx, hipHostMalloc(&S->h_head, 16 * sizeof(int)));
+  const size_t E = (size_t)entries + 4;
+  if ((rc = lm_reserve(ctx, &S->d_cull, &S->cull_cap, 2 * E, 0, -1, 65536)) != ASD_OK) return rc;
+  const int tiles_per_kf = (maxn + kTile - 1) / kTile;
+  const size_t n_tiles = (size_t)tiles_per_kf * n_kfs;
+  if ((rc = lm_reserve(ctx, &S->d_tile, &S->tile_cap, 4 * n_tiles, 0, -1, 4096)) != ASD_OK) return rc;
+  ASD_HIP_CHECK(ctx, S->up.begin(st, (size_t)n_kfs * 12 + 1024));
+  const size_t o_slot = S->up.add(list_slot.data(), (size_t)n_kfs * sizeof(int)), o_base = S->up.add(base.data(), (size_t)n_kfs * sizeof(long long));
+  ASD_HIP_CHECK(ctx, S->up.upload(st));
+  const size_t give = std::min((size_t)capacity, (size_t)entries);
+  ASD_HIP_CHECK(ctx, S->down.begin(st, give * sizeof(int) + 1024));
+  const size_t o_pts = S->down.reserve(give * sizeof(int));
+  ASD_HIP_CHECK(ctx, hipMemsetAsync(S->d_head, 0, 16 * sizeof(int), st));
+  LmPointArgs pa{};
+  pa.table = S->d_table; pa.rows = S->d_rows; pa.list_slot = S->up.dev<int>(o_slot); pa.list_base = S->up.dev<long long>(o_base); pa.tiles_per_kf = tiles_per_kf;
+  pa.pbad = S->d_pbad; pa.mark = S->d_mark; pa.claim = S->d_claim;
+  pa.tile_cnt = S->d_tile; pa.tile_off = S->d_tile + 2 * n_tiles;
+  pa.d_local = S->d_cull; pa.d_search = S->d_cull + E;   // (not the resident search list: that one stays as it is)
+  pa.h_local = S->down.host<int>(o_pts); pa.cap_local = (int)give; pa.h_search = nullptr; pa.cap_search = 0;
+  const dim3 grid((unsigned)n_kfs, (unsigned)tiles_per_kf);
+  S->tables_dirty = true;
+  hipLaunchKernelGGL(k_lm_claim, grid, dim3(256), 0, st, pa);
+  ASD_HIP_CHECK(ctx, hipGetLastError());
+  hipLaunchKernelGGL(k_lm_count, grid, dim3(256), 0, st, pa);
+  ASD_HIP_CHECK(ctx, hipGetLastError());
+  hipLaunchKernelGGL(k_lm_tilescan, dim3(1), dim3(256), 0, st, S->d_tile, S->d_tile + 2 * n_tiles, (int)n_tiles, S->d_head);
+  ASD_HIP_CHECK(ctx, hipGetLastError());
+  hipLaunchKernelGGL(k_lm_scatter, grid, dim3(256), 0, st, pa);
+  ASD_HIP_CHECK(ctx, hipGetLastError());
+  int* const head = S->h_head;
+  ASD_HIP_CHECK(ctx, hipMemcpyAsync(head, S->d_head, 16 * sizeof(int), hipMemcpyDeviceToHost, st));
+  ASD_HIP_CHECK(ctx, hipStreamSynchronize(st));
+  S->tables_dirty = false;   // (the scatter has reset every claim; no mark was set)
+  *n = head[8];
+  if (*n > capacity) { ctx->set_error("asd_map_points: %d points exceed the capacity %d", *n, capacity); return ASD_ERR_CAPACITY; }
+  if (*n) memcpy(rows, S->down.h + o_pts, (size_t)*n * sizeof(int));
   return ASD_OK;
 }
 

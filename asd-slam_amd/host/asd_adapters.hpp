@@ -278,8 +278,9 @@ class ORBmatcher {
   }
 
   // int Fuse(KeyFrame* pKF, const vector<MapPoint*>& vpMapPoints, float th)  (:825): search half.  bestIdx[i] = keypoint
-  // of pKF that map point i should be fused into (-1 = none); the caller then runs the Replace / AddObservation loop
-  // (:938-956).  valid[i] = pMP && !pMP->isBad() && !pMP->IsInKeyFrame(pKF).
+  // of pKF that map point i should be fused into (-1 = none); the Replace / AddObservation loop (:938-956) is asd::FuseApply(c,
+  // kfId, 0, rows, bestIdx) over the observation table, and the static Fuse(c, kfId, ...) below is both halves as one call
+  // (host/fuse_apply.hpp for a caller that keeps its own lists).  valid[i] = pMP && !pMP->isBad() && !pMP->IsInKeyFrame(pKF).
   int Fuse(const FrameView& KF, const std::vector<MapPointView>& vpMapPoints, const std::vector<uint8_t>& valid, const Camera& K,
            std::vector<int32_t>& bestIdx, float th = 3.f) {
     const int n = (int)vpMapPoints.size();
@@ -298,6 +299,18 @@ class ORBmatcher {
     for (int m = 0; m < n; ++m) nFused += bestIdx[m] >= 0;
     return nFused;
   }
+
+  // what both Fuse searches read, from the caller's views and the table: valid[i] = rows[i] names a point that kfId's row does not hold
+  // (pMP && !IsInKeyFrame(pKF) / !spAlreadyFound.count(pMP), from asd_map_get); isBad() is left to asd_fuse_apply's gate, which tests it
+  // at the candidate's turn -- a bad point costs a search and takes no step
+  static int FuseSearchInput(Context& c, int32_t kfId, const std::vector<MapPointView>& points, const std::vector<int32_t>& rows,
+                             std::vector<uint8_t>& valid, std::vector<float>& Xw, std::vector<float>& nrm, std::vector<float>& mind,
+                             std::vector<float>& maxd, std::vector<float>& desc);
+  // int Fuse(KeyFrame* pKF, const vector<MapPoint*>& vpMapPoints, float th)  (:825-960) as the reference's ONE call over the observation
+  // table: the search (asd_fuse_search) and the side effects (asd_fuse_apply mode 0).  kfId = pKF->mnId, KF its view (slot, pose);
+  // points[i] = the view of bank row rows[i], ignored where rows[i] < 0.  nFused is the reference's return value.
+  static struct FuseOutcome Fuse(Context& c, int32_t kfId, const FrameView& KF, const std::vector<MapPointView>& points,
+                                 const std::vector<int32_t>& rows, const Camera& K, float th = 3.f);
 
  private:
   Context& c_;
@@ -1095,6 +1108,96 @@ struct MapPoint {
   }
 };
 
+// ---- ORBmatcher::Fuse's side effects and MapPoint::Replace over the observation table (asd_fuse_apply) ----------------------------
+// What the reference does with bestIdx (ORBmatcher.cc:939-955, :1065-1079, LoopClosing.cc:540-555, :619-627; MapPoint.cc:206-244), in its
+// order, on the context's table: the host keeps no observation lists for it.  From action and other follow, in order, the pairs the host
+// owes mpReplaced / IncreaseFound / IncreaseVisible for, and the points whose ComputeDistinctiveDescriptors Replace (and mode 2's
+// AddMapPoint branch) calls.
+struct FuseOutcome {
+  int rc = ASD_OK;
+  std::vector<uint8_t> action;                                   // asd_fuse_apply's codes, per candidate
+  std::vector<int32_t> other, obsCand, obsOther, nMoved, nDropped;
+  int nFused = 0;
+  std::vector<int32_t> bestIdx;                                  // what the search half chose (the search-plus-apply forms fill it)
+  std::vector<std::pair<int32_t, int32_t>> replaced;             // (loser, winner): loser->Replace(winner), in the reference's order
+  std::vector<int32_t> winners;                                  // ComputeDistinctiveDescriptors is due for these, in order
+  bool Changed() const { for (const uint8_t a : action) if (a >= 1 && a <= 3) return true; return false; }
+};
+inline FuseOutcome FuseApply(Context& c, int32_t kfId, int mode, const std::vector<int32_t>& rows, const std::vector<int32_t>& bestIdx, bool apply = true) {
+  FuseOutcome R;
+  if (rows.size() != bestIdx.size()) { R.rc = ASD_ERR_INVALID; return R; }
+  const size_t n = rows.size();
+  R.action.assign(n, 0); R.other.assign(n, -1); R.obsCand.assign(n, 0); R.obsOther.assign(n, 0); R.nMoved.assign(n, 0); R.nDropped.assign(n, 0);
+  asd_fuse_apply_args a{};
+  a.kf = kfId; a.mode = mode; a.n = (int32_t)n; a.cand = rows.data(); a.best_idx = bestIdx.data(); a.apply = apply ? 1 : 0;
+  a.action = R.action.data(); a.other = R.other.data(); a.obs_cand = R.obsCand.data(); a.obs_other = R.obsOther.data();
+  a.n_moved = R.nMoved.data(); a.n_dropped = R.nDropped.data();
+  R.rc = asd_fuse_apply(c.get(), &a);
+  if (R.rc != ASD_OK) return R;
+  R.nFused = a.n_fused;
+  for (size_t i = 0; i < n; ++i) {
+    if (R.action[i] == 2) { R.replaced.emplace_back(rows[i], R.other[i]); R.winners.push_back(R.other[i]); }
+    else if (R.action[i] == 3) { R.replaced.emplace_back(R.other[i], rows[i]); R.winners.push_back(rows[i]); }
+    else if (R.action[i] == 1 && mode == 2) R.winners.push_back(rows[i]);   // LoopClosing.cc:552
+  }
+  return R;
+}
+// KeyFrame::GetMapPointMatches() from the table (asd_map_get)
+inline int GetMapPointMatches(Context& c, int32_t kfId, std::vector<int32_t>& rows) {
+  int32_t n = 0;
+  rows.resize(2048);
+  int rc = asd_map_get(c.get(), kfId, (int32_t)rows.size(), rows.data(), &n);
+  if (rc == ASD_ERR_CAPACITY && n > (int32_t)rows.size()) { rows.resize(n); rc = asd_map_get(c.get(), kfId, n, rows.data(), &n); }
+  rows.resize(rc == ASD_OK ? n : 0);
+  return rc;
+}
+// the distinct not-bad points of the keyframes' rows in order (asd_map_points): vpFuseCandidates, the gathering loop of mvpLoopMapPoints
+inline int GetMapPointsOf(Context& c, const std::vector<int32_t>& kfs, std::vector<int32_t>& rows) {
+  int32_t n = 0;
+  rows.resize(65536);
+  int rc = asd_map_points(c.get(), (int32_t)kfs.size(), kfs.data(), (int32_t)rows.size(), rows.data(), &n);
+  if (rc == ASD_ERR_CAPACITY && n > (int32_t)rows.size()) { rows.resize(n); rc = asd_map_points(c.get(), (int32_t)kfs.size(), kfs.data(), n, rows.data(), &n); }
+  rows.resize(rc == ASD_OK ? n : 0);
+  return rc;
+}
+
+inline int ORBmatcher::FuseSearchInput(Context& c, int32_t kfId, const std::vector<MapPointView>& points, const std::vector<int32_t>& rows,
+                                       std::vector<uint8_t>& valid, std::vector<float>& Xw, std::vector<float>& nrm, std::vector<float>& mind,
+                                       std::vector<float>& maxd, std::vector<float>& desc) {
+  if (points.size() != rows.size()) return ASD_ERR_INVALID;
+  std::vector<int32_t> inKF;
+  const int rc = GetMapPointMatches(c, kfId, inKF);
+  if (rc != ASD_OK) return rc;
+  std::sort(inKF.begin(), inKF.end());
+  const size_t n = rows.size();
+  valid.assign(n, 0); Xw.assign(3 * n, 0.f); nrm.assign(3 * n, 0.f); mind.assign(n, 0.f); maxd.assign(n, 0.f); desc.assign(n * ASD_DESC_DIM, 0.f);
+  for (size_t i = 0; i < n; ++i) {
+    if (rows[i] < 0 || std::binary_search(inKF.begin(), inKF.end(), rows[i]) || !points[i].descriptor) continue;
+    valid[i] = 1;
+    for (int k = 0; k < 3; ++k) { Xw[3 * i + k] = points[i].Xw[k]; nrm[3 * i + k] = points[i].normal[k]; }
+    mind[i] = points[i].mfMinDistance; maxd[i] = points[i].mfMaxDistance;
+    for (int k = 0; k < ASD_DESC_DIM; ++k) desc[i * ASD_DESC_DIM + k] = points[i].descriptor[k];
+  }
+  return ASD_OK;
+}
+inline FuseOutcome ORBmatcher::Fuse(Context& c, int32_t kfId, const FrameView& KF, const std::vector<MapPointView>& points,
+                                    const std::vector<int32_t>& rows, const Camera& K, float th) {
+  FuseOutcome R;
+  std::vector<uint8_t> valid;
+  std::vector<float> Xw, nrm, mind, maxd, desc;
+  if ((R.rc = FuseSearchInput(c, kfId, points, rows, valid, Xw, nrm, mind, maxd, desc)) != ASD_OK) return R;
+  const int n = (int)rows.size();
+  std::vector<int32_t> bestIdx(n, -1);
+  std::vector<float> bd(n);
+  const float Kv[4] = {K.fx, K.fy, K.cx, K.cy};
+  if (n > 0 && (R.rc = asd_fuse_search(c.get(), KF.slot, n, valid.data(), Xw.data(), nrm.data(), mind.data(), maxd.data(), desc.data(), KF.mTcw, Kv, th,
+                                       bestIdx.data(), bd.data())) != ASD_OK)
+    return R;
+  R = FuseApply(c, kfId, 0, rows, bestIdx, true);
+  R.bestIdx = bestIdx;
+  return R;
+}
+
 // OPTIONAL: Optimizer::LocalBundleAdjustment on the library's lane.  The reference calls it IN LINE (Tracking.cc:797 ->
 // LocalMapping::DoMapping, LocalMapping.cc:89; no mapping thread exists in this fork) -- that is asd::Optimizer::LocalBundleAdjustment /
 // asd_local_ba.  Submit returns at once (problem / result stay owned by the library), Tracking goes on against the PRE-BA map, Wait
@@ -1142,6 +1245,42 @@ struct LocalMapping {
     const int rc = asd_map_observations(c.get(), (int32_t)rows.size(), rows.data(), obs.data());
     if (rc != ASD_OK) { MapPointCullingResult R; R.rc = rc; R.recent = recent; return R; }
     return MapPointCullingRule(recent, obs, nCurrentKFid, 2);
+  }
+
+  // void LocalMapping::SearchInNeighbors() (:557-636), the part between vpTargetKFs and the tail, in the reference's per-call order
+  // (:587-617): vpMapPointMatches from the table once (asd_map_get); per target ORBmatcher::Fuse = search + apply; vpFuseCandidates from
+  // the table as those applies left it (asd_map_points); ORBmatcher::Fuse into the current keyframe.  `view` is the caller's map:
+  // view.KF(mnId) -> const FrameView& (slot, pose) and view.MP(row) -> MapPointView of a bank row, read anew for every search.
+  // onReplaced(winners) is called after every apply that replaced or added something and before the next search, so the caller can
+  // refresh the descriptors MapPoint::Replace recomputes.  vpTargetKFs (:563-582) is the caller's: the table's ten links do not hold
+  // GetBestCovisibilityKeyFrames(20).  The tail (:620-635) is ComputeDistinctiveDescriptors, asd::MapPoint::UpdateNormalAndDepth and
+  // asd::KeyFrame::UpdateConnections.
+  struct Neighbors {
+    int rc = ASD_OK;
+    std::vector<int32_t> vpMapPointMatches, vpFuseCandidates;
+    std::vector<FuseOutcome> perTarget;
+    FuseOutcome intoCurrent;
+  };
+  template <class MapView, class ReplacedFn>
+  static Neighbors SearchInNeighbors(Context& c, int32_t currentKfId, const std::vector<int32_t>& vpTargetKFs, const MapView& view, ReplacedFn onReplaced,
+                                     const Camera& K, float th = 3.f) {
+    Neighbors R;
+    if ((R.rc = GetMapPointMatches(c, currentKfId, R.vpMapPointMatches)) != ASD_OK) return R;
+    auto points_of = [&](const std::vector<int32_t>& rows) {
+      std::vector<MapPointView> pts(rows.size(), MapPointView{});
+      for (size_t i = 0; i < rows.size(); ++i) if (rows[i] >= 0) pts[i] = view.MP(rows[i]);
+      return pts;
+    };
+    for (const int32_t kf : vpTargetKFs) {                                                   // :588-593
+      R.perTarget.push_back(ORBmatcher::Fuse(c, kf, view.KF(kf), points_of(R.vpMapPointMatches), R.vpMapPointMatches, K, th));
+      if ((R.rc = R.perTarget.back().rc) != ASD_OK) return R;
+      if (!R.perTarget.back().winners.empty()) onReplaced(R.perTarget.back().winners);
+    }
+    if ((R.rc = GetMapPointsOf(c, vpTargetKFs, R.vpFuseCandidates)) != ASD_OK) return R;    // :599-615
+    R.intoCurrent = ORBmatcher::Fuse(c, currentKfId, view.KF(currentKfId), points_of(R.vpFuseCandidates), R.vpFuseCandidates, K, th);   // :617
+    R.rc = R.intoCurrent.rc;
+    if (R.rc == ASD_OK && !R.intoCurrent.winners.empty()) onReplaced(R.intoCurrent.winners);
+    return R;
   }
 };
 
@@ -1647,6 +1786,35 @@ int Tracking::RelocalizationRound(Context& c, std::vector<PnPsolver*>& vpPnPsolv
 // ComputeSim3 over the candidate list with asd::Sim3Solver (:291-377), and ComputeSim3Candidate, the numeric body for ONE candidate with
 // the Sim3 handed in by a callback (a caller that keeps a solver of its own).  Both end in the same tail (Sim3Tail: :359-375, :415).
 struct LoopClosing {
+  // LoopClosing::SearchAndFuse (LoopClosing.cc:603-629) for ONE keyframe of CorrectedPosesMap: ORBmatcher::Fuse(pKF, cvScw,
+  // mvpLoopMapPoints, 4, vpReplacePoints) -- its search half is asd_fuse_search_sim3, with valid[i] = "a point, and not in spAlreadyFound"
+  // from the keyframe's row in the table; a bad point is dropped by the apply's gate -- then its own additions and the Replace loop of
+  // :619-627 (asd_fuse_apply mode 1).  points[i] is the view of bank row rows[i] (ignored where rows[i] < 0); Scw row-major 4x4.
+  static FuseOutcome SearchAndFuse(Context& c, int32_t kfId, const FrameView& KF, const float Scw[16], const std::vector<MapPointView>& points,
+                                   const std::vector<int32_t>& rows, const Camera& K, float th = 4.f) {
+    FuseOutcome R;
+    std::vector<uint8_t> valid;
+    std::vector<float> Xw, nrm, mind, maxd, desc;
+    if ((R.rc = ORBmatcher::FuseSearchInput(c, kfId, points, rows, valid, Xw, nrm, mind, maxd, desc)) != ASD_OK) return R;
+    const int n = (int)rows.size();
+    std::vector<int32_t> bestIdx(n, -1);
+    std::vector<float> bd(n);
+    const float Kv[4] = {K.fx, K.fy, K.cx, K.cy};
+    if (n > 0 && (R.rc = asd_fuse_search_sim3(c.get(), KF.slot, Scw, n, valid.data(), Xw.data(), nrm.data(), mind.data(), maxd.data(), desc.data(), Kv, th,
+                                              bestIdx.data(), bd.data())) != ASD_OK)
+      return R;
+    R = FuseApply(c, kfId, 1, rows, bestIdx, true);
+    R.bestIdx = bestIdx;
+    return R;
+  }
+  // the loop-fusion block of CorrectLoop (LoopClosing.cc:540-555): vpCurrentMatchedPoints[i] = mvpCurrentMatchedPoints[i] as a bank row,
+  // -1 = NULL
+  static FuseOutcome FuseMatchedPoints(Context& c, int32_t currentKfId, const std::vector<int32_t>& vpCurrentMatchedPoints) {
+    std::vector<int32_t> bestIdx(vpCurrentMatchedPoints.size());
+    for (size_t i = 0; i < bestIdx.size(); ++i) bestIdx[i] = vpCurrentMatchedPoints[i] >= 0 ? (int32_t)i : -1;
+    return FuseApply(c, currentKfId, 2, vpCurrentMatchedPoints, bestIdx, true);
+  }
+
   // LoopClosing::DetectLoop's lowest score to a connected keyframe (LoopClosing.cc:154-168): vConnected = the ids of
   // mpCurrentKF->GetVectorCovisibleKeyFrames() that are not bad (all of them must be in the database); 1 when there is none.
   // The result is DetectLoopCandidates' minScore (:171).

@@ -532,8 +532,10 @@ int asd_match_triangulate(asd_ctx* ctx, int32_t slot1, int32_t slot2, const asd_
  * search half: for every candidate map point (valid[i] = pMP && !isBad() && !IsInKeyFrame(pKF)) project into
  * the keyframe, apply the depth / viewing-angle / scale gates, search the window and return the keypoint
  * with the smallest descriptor distance among those passing the level and 5.99-chi2 gates.  best_idx[i] = -1
- * when nothing qualifies (bestDist > TH_LOW).  The caller performs the pointer-graph side effects
- * (Replace / AddObservation / AddMapPoint, :938-956) in map point order; they do not influence the search.
+ * when nothing qualifies (bestDist > TH_LOW).  The side effects (Replace / AddObservation / AddMapPoint,
+ * :938-956) are asd_fuse_apply over the resident observation table, which takes best_idx as it is returned
+ * here (this call, asd_fuse_search_batch, asd_fuse_search_sim3); a caller that keeps its own observation
+ * lists performs them itself in map point order (host/fuse_apply.hpp).  They do not influence the search.
  * min_dist / max_dist are the raw mfMinDistance / mfMaxDistance like asd_frustum. */
 int asd_fuse_search(asd_ctx* ctx, int32_t slot_kf, int32_t n_mp, const uint8_t* valid, const float* Xw,
                     const float* normal, const float* min_dist, const float* max_dist, const float* desc,
@@ -1565,6 +1567,74 @@ typedef struct asd_ba_apply_args {
   int32_t n_points; int32_t* new_ref;
 } asd_ba_apply_args;
 int asd_local_ba_apply(asd_ctx* ctx, asd_ba_apply_args* args);
+
+/* ---- ORBmatcher::Fuse's side effects and MapPoint::Replace over the table ----
+ * asd_fuse_apply is the half of Fuse that asd_fuse_search* leave out: what the reference does with bestIdx, in its order, with every
+ * Replace seen by the candidates behind it.  cand[n] are the candidates as bank rows in the caller's list order (-1 = null pointer),
+ * best_idx[n] the keypoint of kf the search chose (-1 = bestDist > TH_LOW or not searched).  A candidate with cand < 0 or best_idx < 0
+ * takes no step (action 0).  Observations(r) = the number of table entries that name r (the section's standing precondition: a point at
+ * most once per row); a row no entry has ever named counts 0 -- a point created this keyframe.
+ *   mode 0  Fuse(pKF, vpMapPoints, th), ORBmatcher.cc:842-957: at its turn a candidate that is flagged bad or that kf's row names AT THAT
+ *           MOMENT is skipped (:849, action 7); then :939-955 literally -- an empty entry takes the candidate (AddObservation + AddMapPoint),
+ *           an entry whose point is flagged bad does nothing, otherwise Observations(pMPinKF) > Observations(pMP) (strict) decides who is
+ *           replaced.
+ *   mode 1  Fuse(pKF, Scw, vpPoints, th, vpReplacePoint) :986-1083 followed by SearchAndFuse's loop, LoopClosing.cc:619-627.  Pass 1, in
+ *           order: the gate is "flagged bad, or named by kf's row AT ENTRY" (spAlreadyFound is a snapshot); an empty entry takes the
+ *           candidate; an occupied entry whose point is not bad is noted as vpReplacePoint[i] (it may be a candidate pass 1 put there).
+ *           Pass 2, in order: vpReplacePoint[i]->Replace(vpPoints[i]) with no test at all.  A point noted twice goes through Replace
+ *           twice; the second time its observations are gone (n_moved = n_dropped = 0) and it is reported with action 3 all the same: the
+ *           host owes mpReplaced and the found / visible transfer for it.
+ *   mode 2  the loop fusion of CorrectLoop, LoopClosing.cc:540-555: cand[i] = mvpCurrentMatchedPoints[i], best_idx[i] = i.  An occupied
+ *           entry gives pCurMP->Replace(pLoopMP) with no bad test and no comparison, an empty entry takes the point.
+ * MapPoint::Replace(L -> W), MapPoint.cc:206-244: L == W is a no-op; otherwise L is flagged bad and loses every entry: for each of L's
+ * observations (k, idx), the entry becomes W when no entry of keyframe k names W (Observations(W) grows by one), and -1 otherwise.  The
+ * keyframes of one point are distinct, so the result does not depend on the order of that walk and no ordering rule is needed.  W may be a
+ * point that is itself flagged bad (modes 1 and 2 have no test): it receives the entries all the same, as in the reference.
+ *   action  0 no step;  1 observation added at an empty entry;  2 the candidate was replaced by the keyframe's point (mode 0);
+ *           3 the keyframe's point was replaced by the candidate;  4 the entry's point is flagged bad: nothing happens, nFused still counts
+ *           (:942, :1073);  5 Replace of a point by itself (mode 2);  6 mode 2 only: the entry is empty but the candidate already observes
+ *           kf elsewhere -- the reference's AddObservation is a no-op there while AddMapPoint would write a second entry; the table cannot
+ *           hold that state and it is NOT restated: the step is skipped;  7 skipped at its turn by the gate.
+ *   other   pMPinKF as the walk met it (bank row), -1 = the entry was empty / no step
+ *   obs_cand, obs_other   Observations() of the two directly in front of the step (mode 1, action 3: in front of pass 2's Replace); 0
+ *           where there is no step (actions 0 and 7) and for the missing side of actions 1 and 6
+ *   n_moved, n_dropped    Replace: observations re-seated on the winner / erased because the winner is already in that keyframe
+ *   n_fused the number of actions 1 .. 5 in every mode.  Modes 0 and 1: nFused as the reference counts it (:956, :1080).  Mode 2: the steps
+ *           the loop of :540-555 took, the self-Replace of action 5 INCLUDED (the reference calls Replace there, which returns at once);
+ *           the skipped step of action 6 is not counted.  Written only when the call returns ASD_OK.
+ * From action and other the host derives, in order, the (loser, winner) pairs for mpReplaced / IncreaseFound / IncreaseVisible and the
+ * winners whose ComputeDistinctiveDescriptors is due.
+ * apply = 1 leaves the table as the reference leaves the map: every moved, dropped or added entry rewritten, every loser's bad byte set,
+ * and -- when an action 1, 2 or 3 occurred -- the version bumped, so the search list of asd_track_local_points_map is invalid.  Without
+ * such an action the table keeps its version.  apply = 0 changes nothing.  Results are identical from run to run.
+ * ASD_ERR_INVALID (asd_last_error names the culprit): kf is not in the table; a best_idx outside kf's row; a candidate row >= 0 named
+ * twice; a row >= 2^28 or < -1; an unknown mode; an unfinished call armed with asd_track_async.  ASD_ERR_CAPACITY: n > 2^20, or more than
+ * 2^30 observations of the involved points together.  On any error the table is untouched.  Neither octaves nor centres are needed.  The
+ * call runs on the context's stream and returns drained. */
+typedef struct asd_fuse_apply_args {
+  int32_t kf;                      /* pKF: must be in the table                                                          */
+  int32_t mode;                    /* 0, 1, 2: above                                                                     */
+  int32_t n; const int32_t* cand;  /* the candidates as bank rows, in the caller's list order; -1 = null pointer         */
+  const int32_t* best_idx;         /* [n] keypoint of kf the search chose, -1 = none                                     */
+  int32_t apply;                   /* 0: outcomes only, the table is left as it was                                      */
+  uint8_t* action;                 /* [n] outcome codes above                                                            */
+  int32_t* other;                  /* [n] pMPinKF as the walk met it (bank row), -1 = the entry was empty / no step      */
+  int32_t* obs_cand; int32_t* obs_other;   /* [n] Observations() of the two in front of the step                         */
+  int32_t* n_moved; int32_t* n_dropped;    /* [n] Replace: observations re-seated on the winner / erased                 */
+  int32_t n_fused;                 /* out: nFused as the reference counts it                                             */
+} asd_fuse_apply_args;
+int asd_fuse_apply(asd_ctx* ctx, asd_fuse_apply_args* args);
+
+/* KeyFrame::GetMapPointMatches(): the row of keyframe kf as it stands, rows[*n].  ASD_ERR_CAPACITY with *n = the row's length when
+ * `capacity` is too small, ASD_ERR_INVALID for an unknown kf.  Changes neither the table nor its version. */
+int asd_map_get(asd_ctx* ctx, int32_t kf, int32_t capacity, int32_t* rows, int32_t* n);
+
+/* The points of n_kfs keyframes: the keyframes in the order given, their entries in ascending keypoint index, a point taken at its first
+ * occurrence unless it is -1 or flagged bad -- the rule of UpdateLocalPoints, i.e. vpFuseCandidates of SearchInNeighbors (LocalMapping.cc:
+ * 599-615) and the gathering loop of mvpLoopMapPoints in ComputeSim3.  An id that is not in the table contributes nothing; an id named
+ * twice is ASD_ERR_INVALID; ASD_ERR_CAPACITY with *n = the count needed when `capacity` is too small.  Changes neither the table nor its
+ * version. */
+int asd_map_points(asd_ctx* ctx, int32_t n_kfs, const int32_t* kfs, int32_t capacity, int32_t* rows, int32_t* n);
 
 /* Test aid: out = {live keyframes, live entries, slot capacity, arena capacity, row-table capacity, growths of the slot table, of the arena,
  * of the row tables}. */
